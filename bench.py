@@ -16,7 +16,10 @@ configs[2] (ResNeXt-50 full MaskLab, 8 images per GPU; N GPUs process 8*N images
 Weights are random-init of that architecture (no network for checkpoints), with the class logits widened x8 for the
 TIMED batch so that the NMS and mask head carry their full load (100 RoIs / image).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the K steps,
+writes the last timed step's outputs if --dump-outputs DIR is given, and prints the line; `value` / `ms_per_step` are
+that timing.  With --full it measures and checks everything else too, and the line carries these extra objects (each
+can still be switched off by its --no-* option; without --full they are null):
   roofline     -- the dominant kernel (MFMA implicit-GEMM conv, 128x128 tile): algorithmic FLOP of all its launches
                   in one step / their summed duration, timed with HIP events on the launch stream in an instrumented
                   step; peak = 157.3 TFLOP/s (fp32 MFMA).  `traffic` comes from a committed PMC pass only when that
@@ -28,6 +31,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   parity       -- image 0 of ONE full-batch GPU forward (the launch shapes that are timed) vs the oracle at full size on an
                   UN-saturated score fixture (oracle/fixtures.py): float outputs within 1e-3, (anchor, class) rows and
                   their ORDER exact.  The oracle is parity-UNPINNED against TensorFlow.
+  f32x3        -- the same workload timed once more under the split-operand conv math (one GPU, fp32 workloads).
+  other_configs -- short timings of the other BASELINE configs' shapes (default workload, one GPU).
+  kernels      -- per-kernel time, FLOP and bytes of the instrumented step (with `roofline`).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the output list of its LAST timed step (what a caller of the
+forward receives; with N>1 also the merged detections) as DIR/<name>.npy, float32 (float64 for integer outputs), at
+most DUMP_BUDGET_BYTES in all: an output that does not fit its share is replaced by a fixed, seeded sample of its
+elements.  Inputs and weights are seeded, so two builds run with the same arguments can be compared output by output.
 """
 import argparse
 import hashlib
@@ -89,6 +100,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="resnext50_full_b8_1024", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: roofline / per-kernel step, f32x3 leg, cpu_baseline + parity, "
+                         "other configs (the --no-* options below switch single parts off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, sampled to fit "
+                         "DUMP_BUDGET_BYTES)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--quick-cpu-baseline", action="store_true",
                     help="one oracle forward only (parity + a single timing), no repeats / 1-thread / 512^2 legs")
@@ -96,12 +113,20 @@ def parse_args():
     ap.add_argument("--no-f32x3", action="store_true", help="skip the extra timed leg under the split-operand conv math")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short timings of the other BASELINE configs' shapes (default workload, one GPU)")
-    ap.add_argument("--dump-launches", default=None, help="write one line per profiled launch to this file")
+    ap.add_argument("--dump-launches", default=None,
+                    help="write one line per profiled launch to this file (the roofline step: needs --full)")
     ap.add_argument("--host-inputs", action="store_true",
                     help="every step starts from pinned HOST uint8 images (PCIe-inclusive rate; not the headline)")
     ap.add_argument("--graph", action="store_true",
                     help="replay stage 1 of the forward from a hipGraph (launch-bound small batches)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_launches and not (args.full and not args.no_roofline):
+        ap.error("--dump-launches writes the launches of the roofline step: it needs --full (and no --no-roofline)")
+    return args
 
 
 def spawn_ranks(args):
@@ -135,6 +160,45 @@ def csrc_hash():
             h.update(open(os.path.join(d, name), "rb").read())
     h.update(open(os.path.join(ROOT, "include", "masklab_hip.h"), "rb").read())
     return h.hexdigest()
+
+
+DUMP_BUDGET_BYTES = 60 << 20          # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(named, out_dir, budget=DUMP_BUDGET_BYTES):
+    """[(name, tensor)] -> out_dir/<name>.npy.  Floating outputs are written as float32 (float64 stays float64), integer
+    and bool outputs as float64, which holds them exactly.  Smallest first, every output gets an equal share of what the
+    budget has left; one larger than its share is written as a fixed sample instead: `share` distinct flat indices,
+    sorted, drawn by a generator seeded with the output's element count -- the same elements on every run and build.
+    -> {name: {"shape": [...], "sampled": number of elements written or None when whole}}"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def np_dtype(t):
+        return np.float32 if t.is_floating_point() and t.dtype != torch.float64 else np.float64
+
+    _TORCH_OF = {np.float32: torch.float32, np.float64: torch.float64}
+
+    items = sorted(named, key=lambda nt: nt[1].numel() * np.dtype(np_dtype(nt[1])).itemsize)
+    left, info = budget, {}
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        dt = np_dtype(t)
+        share = left // (len(items) - i)
+        n = t.numel()
+        if n * np.dtype(dt).itemsize <= share:
+            a = t.to(_TORCH_OF[dt]).cpu().numpy()
+            sampled = None
+        else:
+            k = share // np.dtype(dt).itemsize
+            idx = np.sort(np.random.default_rng(n).choice(n, size=k, replace=False, shuffle=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(_TORCH_OF[dt]).cpu().numpy()
+            sampled = int(k)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        left -= a.nbytes
+        info[name] = {"shape": list(t.shape), "sampled": sampled}
+    return info
 
 
 # bench.py kernel label -> substring of the demangled kernel name in a rocprofv3 pass (a label covers every instantiation
@@ -633,7 +697,7 @@ def main():
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outs = step()
     merged = drain()                       # the last all-gather is inside the timed region too
     torch.cuda.synchronize(device)
     if dist is not None:
@@ -653,9 +717,23 @@ def main():
         if err:
             raise SystemExit(f"bench.py: rank {rank}: merged detections are wrong: {err}")
 
+    # how loaded NMS / mask head were: read from the LAST timed step (same batch, same weights as every timed step),
+    # before anything below runs another forward and overwrites what it returned
+    n_det = n_cand = []
+    dumped = None
+    if rank == 0:
+        det = model.last_detections
+        n_det = det["counts"].cpu().tolist() if det else []
+        n_cand = (outs[0] >= cfg.detection.min_confidence).sum(dim=(1, 2)).cpu().tolist() if det else []
+        if args.dump_outputs:
+            named = list(zip(model.output_names, outs))
+            if merged is not None:
+                named += [("gathered_proposals", merged[0]), ("gathered_counts", merged[1])]
+            dumped = dump_outputs(named, args.dump_outputs)
+
     roofline = None
     per_kernel = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         ops.PROFILE = []
         step(collective=False)          # rank 0 only: the other ranks are not in this step, so no collective
         torch.cuda.synchronize(device)
@@ -745,19 +823,12 @@ def main():
                 roofline.pop("peak_measured", None)
                 roofline.pop("frac_of_measured", None)
 
-    n_det = n_cand = []
-    if rank == 0:
-        outs = model(images)                    # the full bench batch once more: how loaded NMS / mask head were
-        det = model.last_detections
-        n_det = det["counts"].cpu().tolist() if det else []
-        n_cand = (outs[0] >= cfg.detection.min_confidence).sum(dim=(1, 2)).cpu().tolist() if det else []
-
     # ---- the same workload once more under "f32x3" (fp32 tensors; every product of the dense convs = three f16 MFMAs
     # on operands split into two halves, fp32 accumulation -- tests/test_gpu_f32x3.py holds it to the fp32 bars and shows
     # its error against fp64 is not above the fp32 MFMA path's).  Reported BESIDE `value`, never as `value`: the headline
     # stays the exact-product fp32 path.  One GPU, the fp32 workloads only.
     alt = None
-    want_alt = world == 1 and not f16 and not args.workload.endswith("_x3") and not args.no_f32x3
+    want_alt = args.full and world == 1 and not f16 and not args.workload.endswith("_x3") and not args.no_f32x3
     if want_alt:
         ops.set_conv_math("f32x3")
         try:
@@ -779,7 +850,7 @@ def main():
             ops.set_conv_math("f32")
 
     cpu = parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, parity, extra = cpu_baseline_and_parity(cfg, model, weights, hot_weights, backbone, images,
                                                      device, f16, args.quick_cpu_baseline,
                                                      extra_modes=("f32x3",) if alt is not None else ())
@@ -791,7 +862,7 @@ def main():
     # not raised): configs[4]'s shard (ResNeXt-101, 16 x 1280^2, fp16 MFMA path with fp16 storage) and configs[0]
     # (MobileNet, 1 x 512^2; whole-forward hipGraph), the latter under both fp32-tensor conv maths.
     others = None
-    if rank == 0 and world == 1 and args.workload == "resnext50_full_b8_1024" and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.workload == "resnext50_full_b8_1024" and args.full and not args.no_other_configs:
         others = {}
         for key, wl, math, graph in (("resnext101_full_b16_1280_f16", "resnext101_full_b16_1280_f16", "f16s", False),
                                      ("mobilenet_full_b1_512_graph", "mobilenet_full_b1_512", "f32", True),
@@ -819,8 +890,10 @@ def main():
                                       f"({'gloo rehearsal' if rehearsal else 'RCCL'}), merged batch {gathered_images}")
                        if world > 1 else None,
                        "detections_per_image_rank0": n_det, "nms_candidates_per_image_rank0": n_cand},
+            "full": bool(args.full),
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "f32x3": alt, "other_configs": others,
             "kernels": per_kernel,
+            "dumped_outputs": None if dumped is None else {"dir": args.dump_outputs, "arrays": dumped},
             # the ONE native library the product path loaded (masklab_hip/_lib.py: no override), and its sources' hash
             "library": {"path": os.path.relpath(_lib.LIB_PATH, ROOT), "abi_version": int(_lib.load().ml_version()),
                         "kernel_sources_sha256": csrc_hash()},

@@ -11,7 +11,7 @@ WL=${2:-resnext50_full_b8_1024}
 OUT=gpurun_out/prof_${TAG}
 mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline --no-f32x3 --no-other-configs"
+BENCH="python3 bench.py --workload $WL --steps 5 --warmup 2 --full --no-cpu-baseline --no-f32x3 --no-other-configs"
 # (1a) kernels ALONE on the GPU (auxiliary streams off), like bench.py's instrumented roofline step: these average
 #      durations are the ones `roofline.avg_launch_us` must agree with
 export MASKLAB_SIDE_STREAM=0

@@ -31,11 +31,12 @@ def test_bench_json_contract_single_rank():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    # (--quick-cpu-baseline: one timed oracle forward per way instead of the repeated / per-thread-count legs, which at
-    # this size only cost minutes; the driver's default run takes the full legs)
+    # (--full: roofline, cpu_baseline, parity and the f32x3 leg are measured only when asked for; --quick-cpu-baseline:
+    # one timed oracle forward per way instead of the repeated / per-thread-count legs, which at this size only cost
+    # minutes; a plain --full run takes the full legs)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "resnext50_full_b2_256",
-                        "--steps", "2", "--warmup", "1", "--quick-cpu-baseline"], capture_output=True, text=True, env=env,
-                       timeout=900)
+                        "--steps", "2", "--warmup", "1", "--full", "--quick-cpu-baseline"], capture_output=True, text=True,
+                       env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -65,6 +66,38 @@ def test_bench_json_contract_single_rank():
     assert x3["value"] > 0 and x3["steps"] == 2 and x3["warmup"] == 1 and x3["unit"] == "images/sec"
     assert x3["parity"]["ok"] is True and x3["parity"]["order_exact"] is True and x3["parity"]["rows_exact"] is True
     assert d["dtype"] == "f32" and "f16 MFMA" in x3["dtype"]
+
+
+def test_bench_plain_run_times_only_and_dumps_outputs(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps and the line: none of the extra legs.  --steps sets the
+    number of timed steps; --dump-outputs writes the last timed step's outputs, and a second run with the same
+    arguments writes the same arrays (seeded inputs and weights)."""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    import numpy as np
+    lines, dumps = [], []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "resnext50_full_b2_256",
+                            "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True,
+                           env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_json_line(r.stdout))
+        dumps.append({p.stem: np.load(p) for p in sorted(out.glob("*.npy"))})
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) / d["value"] < 0.01        # 2 images per step
+    for key in ("roofline", "cpu_baseline", "parity", "f32x3", "other_configs", "kernels"):
+        assert d[key] is None, key
+    names = ["cls_pred", "loc_pred", "roi_boxes", "roi_masks", "seg_pred"]
+    assert sorted(dumps[0]) == sorted(names) and sorted(d["dumped_outputs"]["arrays"]) == sorted(names)
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for n in names:
+        a, b = dumps[0][n], dumps[1][n]
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, n
+        assert list(a.shape) == d["dumped_outputs"]["arrays"][n]["shape"], n      # small enough: written whole
+        np.testing.assert_allclose(a, b, rtol=0, atol=1e-5, err_msg=n)
 
 
 def test_bench_refuses_more_gpus_than_visible():
