@@ -85,7 +85,12 @@ typedef struct ml_conv2d_desc {
     int32_t act;            /* ML_ACT_*                                                       */
     int32_t group_cin_step; /* grouped 3x3: input-channel offset per 32-wide N block; else 0  */
     int32_t shuffle2x2;     /* 1: Conv2DTranspose epilogue, column = (a*2+b)*cout_real + o    */
-    int32_t tile;           /* 0 auto, 1 = 128x128, 2 = 128x64, 3 = 128x32, 4 = pipelined 1x1 (128x128), 5 = half 1x1 on 256x256 tiles */
+    int32_t tile;           /* 0 auto, 1 = 128x128, 2 = 128x64, 3 = 128x32, 4 = pipelined 1x1 (128x128), 5 = half 1x1 on 256x256 tiles,
+                               6 = Winograd F(2x2,3x3) (conv_wino.hip; ml_conv2d_wino_eligible problems only, every problem of
+                               the launch): `wgt` then points to the transformed weights U = G g G^T (fp64, rounded once),
+                               [n_pad / 32][span_pad / 8][8 channels][32 outputs][16 positions] floats (packing.py
+                               pack_winograd); never split along K; gn_partials on even maps whose Wo / 2 divides or is a
+                               multiple of 64 with (Ho / 2)(Wo / 2) % 64 == 0 (slot = 32-channel group)            */
     int32_t math;           /* ML_MATH_F32: v_mfma_f32_32x32x2_f32 (exact fp32 products);
                                ML_MATH_F16: operands rounded to fp16 on their way into LDS,
                                v_mfma_f32_32x32x16_f16 with fp32 accumulation (BASELINE config 5);
@@ -117,7 +122,7 @@ typedef struct ml_conv2d_desc {
     const int32_t *live;    /* NULL, or a DEVICE int: the batch is a fixed-capacity RoI batch (the mask head run
                                without a host read of the RoI counts, instance.py:121-134 + MoldBatch misc.py:231-286)
                                in which image i exists iff i % live_period < max(1, *live); tiles that hold only
-                               non-existing images compute and store nothing.  Generic kernel only.        */
+                               non-existing images compute and store nothing.  Generic and Winograd kernels. */
     int32_t live_period;    /* RoI slots per image (B % live_period == 0); ignored when live == NULL      */
     int32_t reserved1;
     double *gn_partials;    /* NULL, or [ceil(M/128)][4][2] DEVICE doubles: the epilogue also writes (sum, sum of squares)
@@ -157,6 +162,10 @@ int ml_conv2d_uses_pipe(const ml_conv2d_desc *d);
  * of a batch may sum K in other pieces than the whole batch does (fp32 rounding; reference DP merge
  * engine/parallel.py:64-107).  splits: n host ints.  For reporting / tests. */
 int ml_conv2d_launch_splits(const ml_conv2d_desc *descs, int32_t n, int64_t workspace_bytes, int32_t *splits);
+/* 1 iff the problem may run on the Winograd F(2x2,3x3) kernel (tile = 6): ML_MATH_F32, 3x3, stride 1, dilation 1, 'same'
+ * padding (pad 1, Ho = H, Wo = W), dense input (no row-span / grouped windows), no shuffle2x2 / residual / half
+ * output, span % 32 == 0, n_pad == 128.  Per-problem geometry and math mode only (never the batch or the launch).    */
+int ml_conv2d_wino_eligible(const ml_conv2d_desc *d);
 /* Smallest launch, in 128 x 128 tiles over all its problems, that ml_conv2d_multi_f32 neither narrows to 128 x 64 / 128 x 32
  * tiles nor cuts along K on the current device: the size from which ml_conv2d_desc.gn_partials may be set. */
 int64_t ml_conv2d_gn_min_launch_tiles(void);

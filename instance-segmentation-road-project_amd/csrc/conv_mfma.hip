@@ -953,6 +953,7 @@ splitk_reduce_kernel(const ReduceArgs args) {
 int pick_tile(int cout, int tile) {
     if (tile == 4 || tile == 5) return 1;   // the pipelined 1x1 kernels (4: 128x128 tiles; 5: the half 256x256 one) pack like tile 1
     if (tile >= 1 && tile <= 3) return tile;
+    if (tile == 6) return 1;                 // Winograd F(2x2,3x3): n_pad = 128 (four 32-channel blocks)
     if (cout <= 32) return 3;
     if (cout <= 64) return 2;
     if (cout <= 96) return 3;
@@ -1171,6 +1172,8 @@ int ml_conv1x1_h256_try(const ml_conv2d_desc &d, hipStream_t s, int *took);     
 int ml_conv1x1_h256_eligible(const ml_conv2d_desc &d);
 // half tensors: where the 256 x 256-tile kernel is preferred over the 128 x 128 pipelined one (per-launch A/B,
 // gpurun_out/r03_h256_ab.txt): K >= 512, or K >= 256 with at least two 256-wide N tiles
+int ml_conv2d_wino_launch(const ml_conv2d_desc *descs, int n, hipStream_t s);          // conv_wino.hip
+
 static bool h256_preferred(const ml_conv2d_desc &d) {
     return d.tile == 5 || (d.tile == 0 && (d.span >= 512 || (d.span >= 256 && d.cout >= 512)));
 }
@@ -1317,6 +1320,15 @@ static bool x3_uses_256_row_tiles(const ml_conv2d_desc *descs, int n, int t) {
 extern "C" int ml_conv2d_multi_f32(const ml_conv2d_desc *descs_in, int32_t n_in, void *workspace, int64_t workspace_bytes,
                                    void *stream) {
     ML_REQUIRE(descs_in != nullptr && n_in >= 1 && n_in <= MAXP, "conv2d: need 1..%d problems", MAXP);
+    if (descs_in[0].tile == 6) {
+        // Winograd F(2x2,3x3) (conv_wino.hip): every problem of the launch asks for it; 64-bit addressing, no image groups
+        for (int i = 0; i < n_in; ++i) {
+            ML_REQUIRE(descs_in[i].tile == 6, "conv2d: all problems of one launch must use the same tile shape");
+            const int rc = validate(descs_in[i]);
+            if (rc != ML_OK) return rc;
+        }
+        return ml_conv2d_wino_launch(descs_in, n_in, reinterpret_cast<hipStream_t>(stream));
+    }
     // the persistent 1x1 kernel has no tensor-size limit: try it before any splitting
     if (n_in == 1 && (descs_in[0].tile == 0 || descs_in[0].tile == 4 || descs_in[0].tile == 5)) {
         const int rc0 = validate(descs_in[0], false);
@@ -1428,6 +1440,7 @@ extern "C" int ml_conv2d_launch_mtile(const ml_conv2d_desc *descs, int32_t n, in
 extern "C" int ml_conv2d_launch_splits(const ml_conv2d_desc *descs, int32_t n, int64_t workspace_bytes, int32_t *splits) {
     ML_REQUIRE(descs && splits && n >= 1 && n <= MAXP, "conv2d_launch_splits: need 1..%d problems", MAXP);
     for (int i = 0; i < n; ++i) splits[i] = 1;
+    if (descs[0].tile == 6) return ML_OK;                  // Winograd: the whole K sum in every block
     if (n == 1 && ml_conv2d_uses_pipe(descs)) return ML_OK;
     const int t0 = pick_tile(descs[0].cout, descs[0].tile);
     long long ref_tiles = -1;

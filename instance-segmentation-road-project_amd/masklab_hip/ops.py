@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .packing import PackedConv, resolve_padding
+from .packing import PackedConv, pack_winograd, resolve_padding
 
 import weakref
 
@@ -131,6 +131,15 @@ class DeviceConv:
         self.bias = None if packed.bias is None else torch.from_numpy(packed.bias).to(device)
         self._wgt_h = None
         self._wgt_x3 = None
+        self._wgt_wino = None
+
+    @property
+    def wgt_wino(self):
+        """The Winograd F(2x2,3x3) weights U = G g G^T (packing.pack_winograd: fp64, rounded once) of a dense 3x3 conv with
+        n_pad = 128 -- what ml_conv2d_desc.tile = 6 reads; made on first use."""
+        if self._wgt_wino is None:
+            self._wgt_wino = torch.from_numpy(pack_winograd(self.p)).to(self.wgt.device)
+        return self._wgt_wino
 
     @property
     def wgt_x3(self):
@@ -276,6 +285,37 @@ def _conv_kernel_name(p, descs=None, n=1, half=False):
                                      "_h" if half else {"f32": "", "f32x3": "_x3"}.get(CONV_MATH, "_f16"))
 
 
+def _wino_select(descs, n, problems):
+    """Move a launch onto the Winograd F(2x2,3x3) kernel (tile = 6) when the conv math is "f32", every problem holds fp32
+    tensors, was packed for the automatic tile choice and passes the library's one eligibility rule
+    (ml_conv2d_wino_eligible); a mixed launch stays on the direct kernel.  -> True if it was moved."""
+    if CONV_MATH != "f32":
+        return False
+    lib = _lib.load()
+    for i, (x, dc) in enumerate(problems):
+        if x.dtype != torch.float32 or dc.p.tile != 0 or not lib.ml_conv2d_wino_eligible(C.byref(descs[i])):
+            return False
+    for i, (x, dc) in enumerate(problems):
+        descs[i].tile = 6
+        descs[i].wgt = dc.wgt_wino.data_ptr()
+    return True
+
+
+def _wino_flops(d):
+    """FLOP the Winograd kernel's MFMAs execute for one problem: 2 x tiles x 16 positions x Cin x Cout."""
+    return 2.0 * d.B * ((d.Ho + 1) // 2) * ((d.Wo + 1) // 2) * 16 * d.span * d.cout
+
+
+def _wino_gn_ok(out_shape):
+    """Host copy of the library's gn_partials rule on the Winograd path (conv_wino.hip ml_conv2d_wino_gn_ok): every
+    64-tile block covers two whole 128-pixel flattened tiles."""
+    _, Ho, Wo = out_shape
+    if Ho % 2 or Wo % 2:
+        return False
+    th, tw = Ho // 2, Wo // 2
+    return (64 % tw == 0 or tw % 64 == 0) and (th * tw) % 64 == 0
+
+
 def gn_fusable(out_shape, C_out, groups, dc, launch_tiles, dtype):
     """Can the GroupNormalization behind this conv take its statistics from the conv's epilogue (ml_conv2d_desc.gn_partials)?
     out_shape = (B, Ho, Wo): whole 128-row tiles per image and per chunk, one 128-wide N tile, fp32, and a launch big
@@ -291,6 +331,10 @@ def gn_fusable(out_shape, C_out, groups, dc, launch_tiles, dtype):
     ok = (math_ok and C_out == 128 and p.cout == 128 and p.n_pad == 128 and
           not p.shuffle2x2 and not p.group_cin_step and hw % 128 == 0 and hw % groups == 0 and (hw // groups) % 128 == 0 and
           launch_tiles >= _gn_min_launch_tiles())
+    # a conv the Winograd kernel may take ("f32", dense 3x3 'same' at stride 1 -- the towers): its blocks must also cover
+    # whole 128-pixel tiles, whichever kernel the launch ends up on
+    if ok and CONV_MATH == "f32" and p.KH == 3 and p.KW == 3 and p.cpp_shift == 30 and p.tile == 0:
+        ok = _wino_gn_ok(out_shape)
     return 4 * ((hw // groups) // 128) if ok else 0
 
 
@@ -327,8 +371,12 @@ def conv2d(x, dc: DeviceConv, stride=1, padding="same", dilation=1, act=_lib.ACT
     d, ret, (flops, nbytes, shape) = _conv_desc(x, dc, stride, padding, dilation, act, residual, out, out_coff,
                                                 in_coff, out_view, out_dtype, gn_partials=gn_partials)
     ws = workspace(lib.ml_conv2d_workspace_bytes(), x.device, "conv")
-    name = _conv_kernel_name(dc.p, C.byref(d), 1, half=x.dtype == torch.float16)
-    if PROFILE is not None:
+    wino = _wino_select([d], 1, [(x, dc)])
+    name = "conv_wino_f32" if wino else _conv_kernel_name(dc.p, C.byref(d), 1, half=x.dtype == torch.float16)
+    if wino:
+        shape += " wino direct_flop=%.0f" % flops
+        flops = _wino_flops(d)
+    elif PROFILE is not None:
         which = lib.ml_conv2d_uses_pipe(C.byref(d))          # 1: the 128 x 128 pipelined kernel, 2: the half 256 x 256 one
         if which:
             name = "conv1x1_h256_h" if which == 2 else (
@@ -363,10 +411,15 @@ def conv2d_multi(problems):
         flops += f
         nbytes += nb
         shapes.append(shape)
-    name = _conv_kernel_name(problems[0]["dc"].p, arr, n, half=problems[0]["x"].dtype == torch.float16)
+    wino = _wino_select(arr, n, [(pr["x"], pr["dc"]) for pr in problems])
+    if wino:
+        name, label = "conv_wino_f32", "multi x%d wino direct_flop=%.0f" % (n, flops)
+        flops = sum(_wino_flops(arr[i]) for i in range(n))
+    else:
+        name, label = _conv_kernel_name(problems[0]["dc"].p, arr, n, half=problems[0]["x"].dtype == torch.float16), f"multi x{n}"
     ws = workspace(int(lib.ml_conv2d_workspace_bytes()), problems[0]["x"].device, "conv")
     _log_launch(arr, n, ws, " | ".join(shapes))
-    with _Prof(name, flops, nbytes, f"multi x{n}"):
+    with _Prof(name, flops, nbytes, label):
         _lib.check(lib.ml_conv2d_multi_f32(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_multi_f32")
     return rets
 

@@ -214,3 +214,27 @@ def pack_depthwise(dw_kernel):
     kh, kw, C, mult = dw_kernel.shape
     assert (kh, kw, mult) == (3, 3, 1)
     return np.ascontiguousarray(dw_kernel.reshape(9, C), np.float32)
+
+
+# Winograd F(2x2,3x3) (Lavin & Gray 2016): Y = A^T [ (G g G^T) .* (B^T d B) ] A on a 4x4 input patch d -> 2x2 outputs.
+WINO_G = np.array([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]])
+WINO_BT = np.array([[1.0, 0.0, -1.0, 0.0], [0.0, 1.0, 1.0, 0.0], [0.0, -1.0, 1.0, 0.0], [0.0, 1.0, 0.0, -1.0]])
+WINO_AT = np.array([[1.0, 1.0, 1.0, 0.0], [0.0, 1.0, -1.0, -1.0]])
+
+
+def winograd_transform(g):
+    """U = G g G^T in fp64 for g [..., 3, 3] -> [..., 4, 4] (float64; the caller rounds once)."""
+    return np.einsum("ai,...ij,bj->...ab", WINO_G, np.asarray(g, np.float64), WINO_G)
+
+
+def pack_winograd(packed: PackedConv):
+    """The weights of the Winograd kernel (ml_conv2d_desc.tile = 6) from a dense 3x3 packing: U = G g G^T in fp64, rounded
+    once to fp32, laid out [n_pad / 32][span_pad / 8][8 channels][32 outputs][16 positions p = 4a + b] -- one contiguous
+    16 KB block per (32-output block, 8-channel chunk), the order conv_wino.hip stages it in."""
+    p = packed
+    if (p.KH, p.KW) != (3, 3) or p.cpp_shift != NO_PIX_SPAN or p.group_cin_step or p.shuffle2x2 or p.n_pad % 32 or p.span_pad % 8:
+        raise ValueError("winograd packing needs a dense 3x3 conv (n_pad % 32 == 0)")
+    g = p.wgt.reshape(p.n_pad, 3, 3, p.span_pad).transpose(0, 3, 1, 2)              # [n][c][3][3]
+    u = winograd_transform(g).reshape(p.n_pad, p.span_pad, 16).astype(np.float32)    # [n][c][p]
+    u = u.reshape(p.n_pad // 32, 32, p.span_pad // 8, 8, 16).transpose(0, 2, 3, 1, 4)  # [nb][chunk][k][n][p]
+    return np.ascontiguousarray(u)
