@@ -50,7 +50,8 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             the size rule of gn_partials asked of the library, not restated by callers)
                                          7: ml_stem7x7s2_pool_f16 / _f32 / _x3; ml_gconv3x3_f16 takes groups of 32 channels;
                                             ML_MATH_F32X3 on the persistent 1x1 kernel (ml_conv2d_uses_pipe);
-                                            ml_mold_levels_dev_f32                                                    */
+                                            ml_mold_levels_dev_f32; (additive, same version) ml_se_desc,
+                                            ml_squeeze_excite_f32 / _f16 / _workspace_bytes, ml_add_f16                */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -339,6 +340,33 @@ int ml_global_mean_f32(const float *in, float *out, int32_t B, int32_t HW, int32
 /* x[b,h,w,c] *= s[b,c]  (SqueezeExcite scale, misc.py:46-47)                                 */
 int ml_scale_channels_f32(float *x, const float *s, int32_t B, int32_t HW, int32_t C, void *stream);
 
+/* SqueezeExcite whole (engine/layers/misc.py:24-54): GlobalAveragePooling2D (:43) -> Dense(Hd, relu, no bias) (:44) ->
+ * Dense(C, sigmoid, no bias) (:45) -> Multiply (:46-47), for up to ML_SE_MAX_PROBLEMS problems (the pyramid / RoI levels
+ * of one tower depth, detection.py:111-125, instance.py:179-193) in ONE launch pair:
+ *   squeeze_excite_pool[_h]  per (sample, 256-pixel chunk) the channel sums, fp64, stored as a slab in the workspace;
+ *   squeeze_excite_scale[_h] per (sample, chunk) the sample's slabs added in chunk order, mean = sum / HW, the two Dense
+ *                            layers in fp32 (w1 [C][Hd], w2 [Hd][C]), then out = x * gate over the chunk.
+ * No atomics: the result is the same bits run to run and under graph replay.  `out` may equal `x`; anything else must
+ * not overlap it.  x / out: NHWC [B,HW,C] float (_f32) or IEEE half (_f16: fp32 weights and gate, one rounding at the
+ * store), 16-byte aligned, C a multiple of 4 (_f32) / 8 (_f16), C <= 1024, 1 <= Hd <= 64.  `live` as in
+ * ml_conv2d_desc: sample n exists iff n % live_period < max(1, *live); nothing of the others is read or written.
+ * Problem i's slabs are workspace[ws_offset, + ml_squeeze_excite_workspace_bytes(B, HW, C)): 16-byte aligned, disjoint,
+ * inside workspace_bytes.                                                                                        */
+typedef struct ml_se_desc {
+    const void *x;
+    void *out;
+    const float *w1;              /* [C][Hd] (Dense 1 kernel, misc.py:34-36) */
+    const float *w2;              /* [Hd][C] (Dense 2 kernel, misc.py:37-40) */
+    int32_t B, HW, C, Hd;
+    const int32_t *live;          /* NULL, or a device int (fixed-capacity RoI batches) */
+    int32_t live_period, reserved;
+    int64_t ws_offset;            /* bytes into the call's workspace */
+} ml_se_desc;
+#define ML_SE_MAX_PROBLEMS 8
+int64_t ml_squeeze_excite_workspace_bytes(int32_t B, int32_t HW, int32_t C);
+int ml_squeeze_excite_f32(const ml_se_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
+int ml_squeeze_excite_f16(const ml_se_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- detection post-process
  * RestoreBoxes (engine/layers/detection.py:325-344): priors int32 [A,4] (cx,cy,w,h) shared by
  * the batch; loc [B,A,4] -> boxes [B,A,4].                                                    */
@@ -410,6 +438,8 @@ int ml_mold_levels_dev_f32(const float *src, float *dst, int32_t B, int32_t L, i
 
 /* x += y over n floats (n % 4 == 0): the `Add` of MobileSeparableConv2D (misc.py:92,105) */
 int ml_add_f32(float *x, const float *y, int64_t n, void *stream);
+/* the same on IEEE half x / y (fp16-storage heads): summed in fp32, rounded once; any n > 0, 16-byte aligned pointers */
+int ml_add_f16(void *x, const void *y, int64_t n, void *stream);
 
 /* fill n floats with v */
 int ml_fill_f32(float *x, float v, int64_t n, void *stream);

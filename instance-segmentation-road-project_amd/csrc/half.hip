@@ -201,6 +201,22 @@ __global__ void cast_f2h_kernel(const float *__restrict__ in, _Float16 *__restri
     *reinterpret_cast<f16x8h *>(out + i * 8) = x;
 }
 
+// x += y (the skip `Add` of MobileSeparableConv2D, engine/layers/misc.py:105): fp32 sum, one rounding.  Thread i < n8 takes
+// 8 halves with 16-byte accesses; thread n8 takes the n % 8 tail one by one.
+__global__ void add_h_kernel(_Float16 *__restrict__ x, const _Float16 *__restrict__ y, long long n8, int tail) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i < n8) {
+        float a[8], b[8];
+        h8_to_f(*reinterpret_cast<const f16x8h *>(x + i * 8), a);
+        h8_to_f(*reinterpret_cast<const f16x8h *>(y + i * 8), b);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] += b[e];
+        *reinterpret_cast<f16x8h *>(x + i * 8) = f_to_h8(a);
+    } else if (i == n8) {
+        for (int e = 0; e < tail; ++e) x[i * 8 + e] = (_Float16)((float)x[i * 8 + e] + (float)y[i * 8 + e]);
+    }
+}
+
 unsigned grid_of(long long total) { return (unsigned)((total + TPB - 1) / TPB); }
 
 }  // namespace
@@ -263,6 +279,17 @@ extern "C" int ml_cast_f32_to_f16(const float *in, void *out, int64_t n, void *s
     hipLaunchKernelGGL(cast_f2h_kernel, dim3(grid_of(n / 8)), dim3(TPB), 0, (hipStream_t)stream, in,
                        reinterpret_cast<_Float16 *>(out), (long long)(n / 8));
     ML_CHECK_LAUNCH("cast_f32_to_f16");
+    return ML_OK;
+}
+
+extern "C" int ml_add_f16(void *x, const void *y, int64_t n, void *stream) {
+    ML_REQUIRE(x && y && n > 0, "add_f16: bad arguments");
+    ML_REQUIRE(ml_aligned16(x) && ml_aligned16(y), "add_f16: pointers must be 16-byte aligned");
+    const long long n8 = n / 8;
+    const int tail = (int)(n % 8);
+    hipLaunchKernelGGL(add_h_kernel, dim3(grid_of(n8 + (tail ? 1 : 0))), dim3(TPB), 0, (hipStream_t)stream,
+                       reinterpret_cast<_Float16 *>(x), reinterpret_cast<const _Float16 *>(y), n8, tail);
+    ML_CHECK_LAUNCH("add_f16");
     return ML_OK;
 }
 

@@ -57,7 +57,15 @@ class DeconvOutProblem(C.Structure):
                 ("out_base", C.c_int64), ("live", C.c_void_p)]
 
 
+class SeDesc(C.Structure):
+    """Mirror of `ml_se_desc` (include/masklab_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p),
+                ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("Hd", C.c_int32),
+                ("live", C.c_void_p), ("live_period", C.c_int32), ("reserved", C.c_int32), ("ws_offset", C.c_int64)]
+
+
 GN_MAX_PROBLEMS = 8
+SE_MAX_PROBLEMS = 8
 DECONV_OUT_MAX_PROBLEMS = 4
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -102,6 +110,9 @@ SIGNATURES = {
     "ml_resize_bilinear_ac_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 12 + [_vp]),
     "ml_global_mean_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ml_scale_channels_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
+    "ml_squeeze_excite_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ml_squeeze_excite_f32": (C.c_int, [C.POINTER(SeDesc), _i32, _vp, _i64, _vp]),
+    "ml_squeeze_excite_f16": (C.c_int, [C.POINTER(SeDesc), _i32, _vp, _i64, _vp]),
     "ml_restore_boxes_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "ml_detection_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ml_detection_proposal_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp]),
@@ -110,6 +121,7 @@ SIGNATURES = {
     "ml_mold_levels_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int32), _vp]),
     "ml_mold_levels_dev_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),
     "ml_add_f32": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "ml_add_f16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "ml_fill_f32": (C.c_int, [_vp, _f32, _i64, _vp]),
     "ml_resize_image_ac": (C.c_int, [_vp, _i32, _vp, _vp, _f32] + [_i32] * 6 + [_vp]),
     "ml_trim_instances_f32": (C.c_int, [_vp] * 5 + [_i32] * 5 + [_vp]),

@@ -127,25 +127,50 @@ class _TowerMixin:
         return x
 
     @staticmethod
+    def _units(block):
+        """The depth units [SqueezeExcite?, Conv2D | MobileSeparableConv2D, GroupNormalization] of a tower block, as
+        (se or None, conv, norm) triples; None when the block is made of anything else."""
+        units, i = [], 0
+        while i < len(block):
+            se = block[i] if isinstance(block[i], SqueezeExcite) else None
+            i += se is not None
+            if i + 1 >= len(block) or not isinstance(block[i], (Conv2D, MobileSeparableConv2D)) or \
+                    not isinstance(block[i + 1], GroupNormalization):
+                return None
+            units.append((se, block[i], block[i + 1]))
+            i += 2
+        return units
+
+    @staticmethod
     def _run_towers_multi(blocks, xs, lives=None):
         """Depth-major execution of several un-shared towers (one per pyramid level / RoI level):
-        the conv of depth i runs for ALL towers in one multi-problem launch, so the few-tile
-        problems of the coarse levels ride along with the fine level instead of each being a
-        latency-bound launch of its own.  Falls back to tower-major order when a tower holds
-        anything but [Conv2D, GroupNormalization] pairs (SqueezeExcite)."""
-        plain = all(len(b) % 2 == 0 and all(isinstance(b[2 * i], Conv2D) and
-                                              isinstance(b[2 * i + 1], GroupNormalization)
-                                              for i in range(len(b) // 2)) for b in blocks)
-        if not plain or len({len(b) for b in blocks}) != 1:
+        the SqueezeExcites of depth i run for ALL towers in one launch pair and their convs in one multi-problem launch,
+        so the few-tile problems of the coarse levels ride along with the fine level instead of each being a
+        latency-bound launch of its own.  Separable units (MobileSeparableConv2D) run level by level within their depth.
+        Falls back to tower-major order when the towers are not made of the same depth units."""
+        units = [_TowerMixin._units(b) for b in blocks]
+        same = (all(u is not None for u in units) and len({len(u) for u in units}) == 1 and
+                all(len({(se is None, type(c)) for se, c, _ in (u[d] for u in units)}) == 1 for d in range(len(units[0]))))
+        if not same:
             if lives is not None:
-                raise NotImplementedError("fixed-capacity RoI batches: plain [Conv2D, GroupNormalization] towers only")
+                raise NotImplementedError("fixed-capacity RoI batches: towers of [SqueezeExcite?, Conv2D | "
+                                          "MobileSeparableConv2D, GroupNormalization] units only")
             return [_TowerMixin._run_tower(b, x) for b, x in zip(blocks, xs)]
+        inputs = list(xs)                  # the caller's tensors: never modified in place
         xs = list(xs)
         lives = lives if lives is not None else [None] * len(xs)
         no_lives = all(lv is None for lv in lives)
-        for i in range(len(blocks[0]) // 2):
-            convs = [b[2 * i] for b in blocks]
-            norms = [b[2 * i + 1] for b in blocks]
+        for d in range(len(units[0])):
+            ses = [u[d][0] for u in units]
+            convs = [u[d][1] for u in units]
+            norms = [u[d][2] for u in units]
+            if ses[0] is not None:
+                xs = SqueezeExcite.call_multi(ses, xs, lives=None if no_lives else lives,
+                                              keep_input=[x is x0 for x, x0 in zip(xs, inputs)])
+            if isinstance(convs[0], MobileSeparableConv2D):
+                xs = [c(x, live=lv) for c, x, lv in zip(convs, xs, lives)]
+                xs = GroupNormalization.call_multi(norms, xs, inplace=True, lives=None if no_lives else lives)
+                continue
             # levels whose GroupNorm chunks are whole conv tiles take their statistics from the conv's epilogue
             parts = [None] * len(xs)
             if no_lives:

@@ -172,9 +172,10 @@ class MaskSubNet(Layer, _TowerMixin):
         return True
 
     def capacity_supported(self, crop_size):
-        """True when the whole head runs in the fixed-capacity form (plain towers + the fused tail kernel)."""
-        plain = all(len(b) >= 2 and all(type(l).__name__ in ("Conv2D", "GroupNormalization") for l in b[:-2]) for b in self.blocks)
-        return plain and getattr(self, "_tail_tables", None) is not None and crop_size[0] * crop_size[1] >= 2
+        """True when the whole head runs in the fixed-capacity form (towers of [SqueezeExcite?, Conv2D |
+        MobileSeparableConv2D, GroupNormalization] units + the fused tail kernel)."""
+        towers = all(len(b) >= 2 and self._units(b[:-2]) is not None for b in self.blocks)
+        return towers and getattr(self, "_tail_tables", None) is not None and crop_size[0] * crop_size[1] >= 2
 
     def call(self, inputs, lives=None, **kwargs):
         """lives (fixed-capacity form, PyramidRoiAlign.crop_capacity): per level (device int32 [1], cap) -- RoI slots past

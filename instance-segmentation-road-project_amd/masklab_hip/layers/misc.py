@@ -6,7 +6,7 @@ IncludeMyRoad :601-626, CalculateInstanceSize :629-727)."""
 import numpy as np
 import torch
 
-from .. import ops
+from .. import _lib, ops
 from ..keras_like import Conv2D, Dense, DepthwiseConv2D, Layer
 from ..normalization import GroupNormalization
 
@@ -54,13 +54,14 @@ class ResizeLike(Layer):
 
 class SqueezeExcite(Layer):
     """SqueezeAndExcite (reference misc.py:24-54): GAP -> Dense(C//ratio, relu, no bias) ->
-    Dense(C, sigmoid, no bias) -> channel scale.  The two Dense layers are 1x1 MFMA convs on the
-    pooled [B,1,1,C] map; the scale is applied in place."""
+    Dense(C, sigmoid, no bias) -> channel scale, all of it one launch pair (ops.squeeze_excite_multi,
+    csrc/squeeze_excite.hip) whose kernels read the two Dense kernels as fp32 matrices packed at load time."""
 
     def __init__(self, ratio=16., **kwargs):
         super().__init__(**kwargs)
         self.ratio = ratio
         self.dense1 = self.dense2 = None
+        self.w1 = self.w2 = None
 
     def build(self, input_shape):
         n_channel = int(input_shape[-1])
@@ -76,11 +77,29 @@ class SqueezeExcite(Layer):
     def children(self):
         return [l for l in (self.dense1, self.dense2) if l is not None]
 
+    def _load_own(self, weights, device):
+        if self.dense1 is None:
+            return
+        self.w1 = torch.from_numpy(np.ascontiguousarray(self.dense1._get(weights, "kernel"))).to(device)   # [C, Hd]
+        self.w2 = torch.from_numpy(np.ascontiguousarray(self.dense2._get(weights, "kernel"))).to(device)   # [Hd, C]
+
+    def _problem(self, x, keep_input, live=None):
+        if self.w1 is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+        # out of place only when x is the caller's tensor (a tower input): no copy of it is made first
+        return dict(x=x, w1=self.w1, w2=self.w2, out=torch.empty_like(x) if keep_input else None, live=live)
+
     def call(self, inputs, **kwargs):
-        se = ops.global_mean(inputs)
-        se = self.dense2(self.dense1(se))
-        out = inputs.clone() if kwargs.get("keep_input", True) else inputs
-        return ops.scale_channels_(out, se)
+        return ops.squeeze_excite_multi([self._problem(inputs, kwargs.get("keep_input", True))])[0]
+
+    @staticmethod
+    def call_multi(layers, xs, lives=None, keep_input=True):
+        """The SqueezeExcites of several levels (one tower depth) in ONE launch pair: results identical to calling each.
+        lives: per input None or (device int32 [1], slots per image) -- fixed-capacity RoI batches, dead slots untouched.
+        keep_input: a bool, or one per input."""
+        lives = lives if lives is not None else [None] * len(xs)
+        keeps = keep_input if isinstance(keep_input, (list, tuple)) else [keep_input] * len(xs)
+        return ops.squeeze_excite_multi([l._problem(x, k, lv) for l, x, k, lv in zip(layers, xs, keeps, lives)])
 
     def get_config(self):
         config = super().get_config()
@@ -133,14 +152,29 @@ class MobileSeparableConv2D(Layer):
         self.built = True
         return self.squeeze_norm.build(s)
 
-    def call(self, inputs, **kwargs):
-        x = self.expand_conv2d(inputs)
-        x = self.expand_norm(x, fuse_relu=True, inplace=True)
-        x = self.depth_conv2d(x)
-        x = self.depth_norm(x, fuse_relu=True, inplace=True)
-        x = self.squeeze_conv2d(x)
-        x = self.squeeze_norm(x, inplace=True)
-        return ops.add_(x, inputs)              # skip_connection (misc.py:105)
+    def call(self, inputs, live=None, **kwargs):
+        """live: None, or (device int32 [1], slots per image) -- a fixed-capacity RoI batch (the mask head at capacity):
+        the 1x1 convs skip the tiles and the GroupNorms the samples of dead slots; the depthwise conv and the skip add run
+        over every slot (what they leave in dead slots is never read back)."""
+        if live is None:
+            x = self.expand_conv2d(inputs)
+            x = self.expand_norm(x, fuse_relu=True, inplace=True)
+            x = self.depth_conv2d(x)
+            x = self.depth_norm(x, fuse_relu=True, inplace=True)
+            x = self.squeeze_conv2d(x)
+            x = self.squeeze_norm(x, inplace=True)
+            return ops.add_(x, inputs)              # skip_connection (misc.py:105)
+
+        def conv(c, x):
+            return ops.conv2d_multi([dict(x=x, dc=c.dev, act=_lib.ACT_BY_NAME[c.activation], live=live)])[0]
+
+        def norm(g, x, relu):
+            return ops.groupnorm_chunk_multi([dict(x=x, gamma=g.gamma, beta=g.beta, groups=g.groups, eps=g.epsilon,
+                                                   relu=relu, out=x, live=live)])[0]
+        x = norm(self.expand_norm, conv(self.expand_conv2d, inputs), True)
+        x = norm(self.depth_norm, self.depth_conv2d(x), True)
+        x = norm(self.squeeze_norm, conv(self.squeeze_conv2d, x), False)
+        return ops.add_(x, inputs)
 
     def get_config(self):
         config = super().get_config()

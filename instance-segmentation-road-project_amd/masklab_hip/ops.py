@@ -753,6 +753,63 @@ def scale_channels_(x, s):
     return x
 
 
+def squeeze_excite_multi(problems):
+    """ml_squeeze_excite_f32 / _f16: whole SqueezeExcites (reference engine/layers/misc.py:24-54) of several problems in ONE
+    launch pair.  problems: dicts x (contiguous NHWC fp32 or fp16, one dtype per call), w1 fp32 [C, Hd], w2 fp32 [Hd, C]
+    (device), out=None (None: in place into x) and live=None ((device int32 [1], slots per image): a fixed-capacity
+    RoI batch whose dead samples are neither read nor written).  -> list of outputs."""
+    lib = _lib.load()
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.SE_MAX_PROBLEMS:
+        return squeeze_excite_multi(problems[:_lib.SE_MAX_PROBLEMS]) + squeeze_excite_multi(problems[_lib.SE_MAX_PROBLEMS:])
+    arr = (_lib.SeDesc * n)()
+    outs, nbytes, ws_bytes = [], 0.0, 0
+    half = problems[0]["x"].dtype == torch.float16
+    for i, pr in enumerate(problems):
+        x, w1, w2 = pr["x"], pr["w1"], pr["w2"]
+        _require_dev(x, "x")
+        _require_dev(w1, "w1")
+        _require_dev(w2, "w2")
+        if x.dtype not in (torch.float32, torch.float16) or (x.dtype == torch.float16) != half:
+            raise ValueError("squeeze_excite: x must be float32 or float16, one dtype per call")
+        out = pr.get("out")
+        if out is None:
+            out = x
+        else:
+            _require_dev(out, "out")
+            if out.shape != x.shape or out.dtype != x.dtype:
+                raise ValueError("squeeze_excite: out must match x")
+        B, Cc = int(x.shape[0]), int(x.shape[-1])
+        HW = x.numel() // (B * Cc)
+        if w1.dtype != torch.float32 or w2.dtype != torch.float32 or w1.dim() != 2 or w1.shape[0] != Cc or \
+                tuple(w2.shape) != (w1.shape[1], Cc):
+            raise ValueError("squeeze_excite: w1 must be fp32 [C, Hd] and w2 fp32 [Hd, C]")
+        d = arr[i]
+        d.x, d.out, d.w1, d.w2 = x.data_ptr(), out.data_ptr(), w1.data_ptr(), w2.data_ptr()
+        d.B, d.HW, d.C, d.Hd = B, HW, Cc, int(w1.shape[1])
+        if pr.get("live") is not None:
+            lv, period = pr["live"]
+            _require_dev(lv, "live")
+            d.live, d.live_period = lv.data_ptr(), int(period)
+        d.ws_offset = ws_bytes
+        ws_bytes += (int(lib.ml_squeeze_excite_workspace_bytes(B, HW, Cc)) + 255) // 256 * 256
+        nbytes += 3 * x.element_size() * x.numel()          # x read twice (pool, scale), out written once
+        outs.append(out)
+    ws = workspace(ws_bytes, problems[0]["x"].device, "se")
+    fn = lib.ml_squeeze_excite_f16 if half else lib.ml_squeeze_excite_f32
+    sfx = "_h" if half else ""
+    # the two kernels are enqueued by ONE library call: the pool record's events bracket both, the scale record counts
+    # the second launch (no time, no bytes of its own)
+    with _Prof("squeeze_excite_pool" + sfx, 0, nbytes, f"multi x{n} (pool + scale timed together)") as prof:
+        _lib.check(fn(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_squeeze_excite")
+    if prof.on:
+        PROFILE.append({"kernel": "squeeze_excite_scale" + sfx, "flops": 0.0, "bytes": 0.0,
+                        "shape": "timed with squeeze_excite_pool" + sfx, "start": prof.rec["end"], "end": prof.rec["end"]})
+    return outs
+
+
 def restore_boxes(loc_pred, priors_i32):
     lib = _lib.load()
     _require_dev(loc_pred, "loc_pred")
@@ -874,8 +931,12 @@ def add_(x, y):
     _require_dev(y, "y")
     if x.shape != y.shape:
         raise ValueError("add_: shape mismatch")
+    if x.dtype == torch.float16 and y.dtype == torch.float16:
+        with _Prof("add_h", 0, 6 * x.numel()):
+            _lib.check(lib.ml_add_f16(_ptr(x), _ptr(y), x.numel(), _stream()), "ml_add_f16")
+        return x
     if x.dtype != torch.float32 or y.dtype != torch.float32:
-        raise NotImplementedError("add_: float32 tensors only (MobileSeparableConv2D is not built for fp16 storage)")
+        raise NotImplementedError("add_: float32 or float16 tensors (one dtype for both)")
     _lib.check(lib.ml_add_f32(_ptr(x), _ptr(y), x.numel(), _stream()), "ml_add_f32")
     return x
 

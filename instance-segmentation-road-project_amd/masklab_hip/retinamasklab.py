@@ -366,7 +366,8 @@ class InferenceModel(K.Layer):
         """Estimate of what ONE fixed-capacity stage 2 holds: per RoI level the crops and every tower / deconv
         intermediate ([B*cap, ch, cw, C] each: under graph capture none of them is recycled), plus masks_cap
         [B, L*cap, 2ch, 2cw, classes] fp32 twice (at capacity, and the buffer its molded form is the front of) and the
-        split-K workspace (per stream)."""
+        split-K workspace (per stream).  A SqueezeExcite tower adds the out-of-place SqueezeExcite output at the tower input
+        and its pooled-sum workspace; a separable tower the expanded (expand_ratio x C) maps of every depth."""
         from . import ops
         ins = self.configuration.instance
         pra, mask = self.instance_networks[2], self.instance_networks[3]
@@ -375,9 +376,17 @@ class InferenceModel(K.Layer):
         ch, cw = pra.crop_size
         es = 2 if ops.half_storage() else 4
         slots = int(batch) * cap
-        per_level = slots * ch * cw * mask.num_features * es * (2 + mask.num_depth)
+        maps = 2 + mask.num_depth                         # crops, tower outputs, deconv output (per level)
+        extra = 0
+        if mask.use_squeeze_excite:
+            maps += 1
+            extra = L * ((int(ops._lib.load().ml_squeeze_excite_workspace_bytes(slots, ch * cw, mask.num_features)) + 255)
+                         // 256 * 256)
+        if mask.use_separable_conv:                       # expand conv output + depthwise output of every depth
+            maps += mask.num_depth * 2 * int(mask.expand_ratio * mask.num_features) / mask.num_features
+        per_level = int(slots * ch * cw * mask.num_features * es * maps)
         masks = slots * L * 4 * ch * cw * mask.num_classes * 4
-        return L * per_level + 2 * masks + 2 * int(ops._lib.load().ml_conv2d_workspace_bytes())   # (masks: at capacity + molded)
+        return L * per_level + 2 * masks + extra + 2 * int(ops._lib.load().ml_conv2d_workspace_bytes())   # (masks: at capacity + molded)
 
     def _capacity_wanted(self, images):
         mode = getattr(self, "device_counts", "auto")
