@@ -146,12 +146,19 @@ int ml_conv2d_multi_f32(const ml_conv2d_desc *descs, int32_t n, void *workspace,
                         void *stream);
 /* N-tile width the auto heuristic picks for `cout` (host packs n_pad from it). */
 int ml_conv2d_ntile(int32_t cout, int32_t tile);
-/* N-tile width (128 / 64 / 32) of the generic implicit-GEMM kernel that ml_conv2d_multi_f32 will run for these
+/* The four reporting entries below read the launch plan of ml_conv2d_multi_f32 -- the one function that decides which
+ * kernel a launch runs, on which tiles and with how many K slices -- for these problems (tensor pointers may be NULL:
+ * nothing is dereferenced).  ml_conv2d_launch_splits checks the descriptors as the launch does: where the launch would
+ * be refused (the Winograd kernel's own checks excepted) it returns the same ML_E_BADARG and message.  The other three
+ * report the kernel and tiles the plan picks without checking the descriptors' arguments, and 0 where no kernel can be
+ * picked (mixed tile shapes or math modes, a `live` problem of >= 2 GiB, ...).
+ * N-tile width (128 / 64 / 32) of the generic implicit-GEMM kernel that ml_conv2d_multi_f32 will run for these
  * problems: launches too small to fill the chip with 128-wide tiles run on narrower ones (bit-identical results:
- * same k-ordered chains, split-K cut at the same k).  For reporting only; 0 on bad arguments. */
+ * same k-ordered chains, split-K cut at the same k).  For reporting only; 0 as above, or when the launch runs
+ * another kernel (Winograd, the persistent 1x1 kernels). */
 int ml_conv2d_launch_ntile(const ml_conv2d_desc *descs, int32_t n, int32_t has_workspace);
 /* M-tile height (128 / 256) of the same launch: ML_MATH_F32X3 launches that fill the chip with 256 x 128 tiles run the
- * 8-wave software-pipelined form of the kernel (bit-identical results).  For reporting only; 0 on bad arguments. */
+ * 8-wave software-pipelined form of the kernel (bit-identical results).  For reporting only; 0 as for the N tile. */
 int ml_conv2d_launch_mtile(const ml_conv2d_desc *descs, int32_t n, int32_t has_workspace);
 /* Which persistent 1x1 kernel ml_conv2d_multi_f32 runs this single problem on: 1 = the tile-pipelined 128 x 128 kernel
  * (conv1x1_pipe.hip: the short-K bottleneck convs of engine/backbone/ResNext.py:199-231; fp32 or half tensors),
@@ -161,7 +168,8 @@ int ml_conv2d_uses_pipe(const ml_conv2d_desc *d);
 /* K slices (1 = not split) of every problem of the launch ml_conv2d_multi_f32 would make for these problems with a
  * workspace of `workspace_bytes` (0 = none): launches of fewer than 192 tiles with a long K are cut along K, so a shard
  * of a batch may sum K in other pieces than the whole batch does (fp32 rounding; reference DP merge
- * engine/parallel.py:64-107).  splits: n host ints.  For reporting / tests. */
+ * engine/parallel.py:64-107).  splits: n host ints, one per problem given (a problem cut into image groups: the most
+ * slices of any of its groups).  For reporting / tests. */
 int ml_conv2d_launch_splits(const ml_conv2d_desc *descs, int32_t n, int64_t workspace_bytes, int32_t *splits);
 /* 1 iff the problem may run on the Winograd F(2x2,3x3) kernel (tile = 6): ML_MATH_F32, 3x3, stride 1, dilation 1, 'same'
  * padding (pad 1, Ho = H, Wo = W), dense input (no row-span / grouped windows), no shuffle2x2 / residual / half

@@ -640,7 +640,10 @@ int ml_conv1x1_pipe_eligible(const ml_conv2d_desc &d) {
     if (d.residual && (d.res_cstride != d.out_cstride || d.res_coff != d.out_coff)) return 0;
     // lane offsets are 32-bit and cover one 128-row tile only
     if ((long long)BM * d.in_cstride * 4 >= (1ll << 31) || (long long)(BM + 32) * d.out_cstride * 4 >= (1ll << 31)) return 0;
-    return 1;
+    // a block walks at most PIPE_MAX_NBG N tiles: some split of them into 2^g groups (ml_conv1x1_pipe_try) must get there
+    int nbg = d.cout / BN;
+    for (int g = 1; g < 8 && nbg > PIPE_MAX_NBG && nbg % 2 == 0 && (1 << g) <= ml_resident_blocks(2); ++g) nbg /= 2;
+    return nbg <= PIPE_MAX_NBG;
 }
 
 // -> ML_OK and *eligible = 1 when the problem was launched on the pipelined kernel; *eligible = 0 when it is not a

@@ -962,7 +962,6 @@ int pick_tile(int cout, int tile) {
 
 // generic = the checks of the implicit-GEMM kernel in this file (the persistent 1x1 kernel has its own eligibility test)
 int validate(const ml_conv2d_desc &d, bool generic = true) {
-    ML_REQUIRE(d.in && d.wgt && d.out, "conv2d: null tensor pointer");
     ML_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Ho > 0 && d.Wo > 0, "conv2d: bad spatial dims");
     ML_REQUIRE(d.KH > 0 && d.KW > 0 && d.stride > 0 && d.dil > 0, "conv2d: bad kernel geometry");
     const bool hs = d.math == ML_MATH_F16S;
@@ -974,7 +973,6 @@ int validate(const ml_conv2d_desc &d, bool generic = true) {
     if (hs)
         ML_REQUIRE(d.cpp_shift == 30 && d.group_cin_step == 0,
                    "conv2d: fp16 storage takes no image (row-span) input and no grouped windows");
-    ML_REQUIRE(ml_aligned16(d.in) && ml_aligned16(d.wgt), "conv2d: in/wgt must be 16-byte aligned");
     ML_REQUIRE(d.cpp_shift >= 0 && d.cpp_shift <= 30, "conv2d: bad cpp_shift");
     ML_REQUIRE(d.cout > 0 && d.out_cstride > 0 && d.out_coff >= 0 && d.out_bstride >= 0, "conv2d: bad output channels");
     ML_REQUIRE((long long)d.B * d.H * d.W < (1ll << 31) / 2, "conv2d: too many input pixels for int32 indexing");
@@ -1015,22 +1013,12 @@ int validate(const ml_conv2d_desc &d, bool generic = true) {
     return ML_OK;
 }
 
-// where the pipelined 1x1 kernel is used by default (per-launch A/B inside the model, gpurun_out/launches_r02a vs r02d:
-// x1.2-1.3 at K = 64-128, x1.05-1.15 at K = 256-512, nothing at K >= 1024; it loses where there are few rows -- no
-// split-K: 64 panels of K = 2048 took 131 us against 50).  The rule looks at ONE image's pixel count, never at the
-// batch: an image's results must not depend on the shard it is computed in (tests/test_gpu_model.py).
-bool pipe_preferred(const ml_conv2d_desc &d) {
-    if (!(d.KH == 1 && d.KW == 1 && d.span <= 512 && (long long)d.H * d.W >= 4096)) return false;
-    // ML_MATH_F32X3 (round 4, gpurun_out/r04x_ab_x3*.txt): x1.3-1.4 where the launch is HBM-bound (K <= 256, or a residual
-    // to read: 5.2-5.5 TB/s against 3.4-3.9), x1.2 at 512 -> 1024 + residual; 512 -> 256 without one is compute-bound in
-    // that mode and 2-8 % faster on the generic 256-row tile
-    if (d.math == ML_MATH_F32X3) return d.span <= 256 || d.residual != nullptr;
-    return true;
-}
+constexpr long long UNSPLIT_TILES = 192;     // launches of this many tiles are never cut along K
+constexpr int NARROW_BLOCKS_PER_CU = 2;      // the resident blocks per CU a small launch's narrow tiles are sized for
 
 // split-K heuristic: few tiles and a long K => slice K so that ~2 blocks per CU are in flight
 int choose_splits(long long tiles, int chunks) {
-    if (tiles >= 192 || chunks < 16) return 1;
+    if (tiles < 1 || tiles >= UNSPLIT_TILES || chunks < 16) return 1;     // (tiles < 1: an unchecked descriptor)
     long long want = (512 + tiles - 1) / tiles;
     int max_by_k = chunks / 8;           // keep >= 8 chunks per slice
     int s = (int)(want < max_by_k ? want : max_by_k);
@@ -1047,43 +1035,58 @@ static bool host_out_vec_ok(const ml_conv2d_desc &p) {
     return ok;
 }
 
-// The K-slice count of every problem of one launch on BM x BN tiles with KC-deep chunks -- THE place the decision is taken
-// (launch_multi and the reporting entry ml_conv2d_launch_splits both call it).  split_tiles >= 0: the tile count the
-// decision is taken on (see narrow_tile_for_small_launch), else this launch's own.  Split-K looks at the whole launch:
-// five pyramid levels of one image are 171 tiles together -- a third of the chip -- and each tile then walks all 36
-// chunks alone (92 us); slicing K fills the other CUs.  Fixed-capacity RoI batches (`live`): an image's RoIs are spread
-// over the launch's RoI levels, so about 1 / levels of the nominal tiles are live -- the decision is taken on that
-// estimate (the host does not know the counts).
-static void plan_splits(const ml_conv2d_desc *descs, int n, int BM, int BN, int KC, bool have_ws, long long ws_bytes,
-                        long long split_tiles, int *splits_out, int *cps_out = nullptr) {
-    long long launch_tiles = 0, ws_off = 0;
+// The launch ml_conv2d_multi_f32 makes for a set of problems.  plan_launch() takes every decision about it once; the
+// launch runs it and the reporting entries (ml_conv2d_uses_pipe, ml_conv2d_launch_ntile / _mtile / _splits) read it.
+enum ConvFamily { CONV_WINO, CONV_H256, CONV_PIPE, CONV_GENERIC };
+
+struct ConvPlan {
+    int family;                    // ConvFamily: Winograd, the half 256 x 256 1x1 kernel, the pipelined 1x1 kernel, the generic one
+    int n;                         // (the generic kernel only from here) problems after image-group splitting
+    ml_conv2d_desc descs[MAXP];
+    int src[MAXP];                 // the input problem each one was cut from
+    int kernel;                    // row of kGenericKernels
+    int BM, BN, KC;                // tile rows, tile columns, K chunk depth
+    long long ref_tiles;           // the tile count the split-K decision is taken on (-1: the launch's own)
+    int splits[MAXP], cps[MAXP];   // K slices, chunks per slice
+    long long slab_off[MAXP];      // workspace offset of the partial sums of a problem cut along K
+    int start[MAXP + 1];           // first block of each problem; start[n] = the grid
+};
+
+// BM x BN tiles of a launch (per problem in `per`).  Fixed-capacity RoI batches (`live`): an image's RoIs are spread over
+// the launch's RoI levels, so about 1 / levels of their tiles are live -- the estimate decisions are taken on.
+static long long launch_tiles(const ml_conv2d_desc *descs, int n, int BM, int BN, long long *per = nullptr) {
     int n_live = 0;
     for (int i = 0; i < n; ++i) n_live += descs[i].live != nullptr;
+    long long total = 0;
     for (int i = 0; i < n; ++i) {
-        const long long M = (long long)descs[i].B * descs[i].Ho * descs[i].Wo;
-        const long long t = ((M + BM - 1) / BM) * (descs[i].n_pad / BN);
-        launch_tiles += descs[i].live ? (t + n_live - 1) / n_live : t;
+        const long long t = ((long long)descs[i].B * descs[i].Ho * descs[i].Wo + BM - 1) / BM * (descs[i].n_pad / BN);
+        const long long est = descs[i].live ? (t + n_live - 1) / n_live : t;
+        if (per) per[i] = est;
+        total += est;
     }
-    if (split_tiles >= 0) launch_tiles = split_tiles;
-    for (int i = 0; i < n; ++i) {
-        const ml_conv2d_desc &d = descs[i];
-        const long long M = (long long)d.B * d.Ho * d.Wo;
-        const long long MB = (M + BM - 1) / BM;
-        const int chunks = d.KH * d.KW * (d.span_pad / KC);
-        int splits = have_ws ? choose_splits(launch_tiles, chunks) : 1;     // (the reduce kernel stores half too)
-        const long long slab_bytes = (long long)splits * MB * BM * d.n_pad * 4;
-        if (splits > 1 && ws_off + slab_bytes > ws_bytes) splits = 1;
-        const int cps = (chunks + splits - 1) / splits;
-        splits = (chunks + cps - 1) / cps;           // drop empty trailing slices
-        if (splits > 1) ws_off += (slab_bytes + 255) / 256 * 256;
-        splits_out[i] = splits;
-        if (cps_out) cps_out[i] = cps;
-    }
+    return total;
+}
+
+// where the pipelined 1x1 kernel is used by default (per-launch A/B inside the model, gpurun_out/launches_r02a vs r02d:
+// x1.2-1.3 at K = 64-128, x1.05-1.15 at K = 256-512, nothing at K >= 1024; it loses where there are few rows -- no
+// split-K: 64 panels of K = 2048 took 131 us against 50).  The rule looks at ONE image's pixel count, never at the
+// batch: an image's results must not depend on the shard it is computed in (tests/test_gpu_model.py).  tile = 4 forces it.
+static bool pipe_preferred(const ml_conv2d_desc &d) {
+    if (d.tile == 4) return true;
+    // fp16 storage: the persistent kernel takes every 1x1 problem it can run, except those the generic kernel would cut
+    // along K (few tiles, long K: the laterals of the coarse pyramid levels, the image-pooling branch) -- it has no split-K.
+    // A residual (the ResNeXt conv3 of every block) is only implemented there.  (Eligible problems: n_pad = cout, no `live`.)
+    if (d.math == ML_MATH_F16S) return d.residual || launch_tiles(&d, 1, 128, 128) >= UNSPLIT_TILES || d.span / 64 < 16;
+    if (!(d.KH == 1 && d.KW == 1 && d.span <= 512 && (long long)d.H * d.W >= 4096)) return false;
+    // ML_MATH_F32X3 (round 4, gpurun_out/r04x_ab_x3*.txt): x1.3-1.4 where the launch is HBM-bound (K <= 256, or a residual
+    // to read: 5.2-5.5 TB/s against 3.4-3.9), x1.2 at 512 -> 1024 + residual; 512 -> 256 without one is compute-bound in
+    // that mode and 2-8 % faster on the generic 256-row tile
+    if (d.math == ML_MATH_F32X3) return d.span <= 256 || d.residual != nullptr;
+    return true;
 }
 
 template <int WAVES_M, int WAVES_N, int TM, int TN, int MATH, bool GNS = false, int NSTAGE = 2>
-int launch_multi(const ml_conv2d_desc *descs, int n, void *workspace, long long ws_bytes, hipStream_t s,
-                 long long split_tiles = -1) {
+int launch_multi(const ConvPlan &plan, void *workspace, hipStream_t s) {
     constexpr int BM = WAVES_M * TM * 32;
     constexpr int BN = WAVES_N * TN * 32;
     constexpr bool F16 = MATH == ML_MATH_F16;
@@ -1092,18 +1095,15 @@ int launch_multi(const ml_conv2d_desc *descs, int n, void *workspace, long long 
     constexpr int STAGE_BYTES = F16 ? 2 * (BM + BN) * LDS_LD_H * 2 : NSTAGE * (BM + BN) * LDS_LD * 4;
     constexpr int EPI_BYTES = BM * (BN + 4) * 4 + (GNS && NT == 512 ? 256 : 0);   // the epilogue's transposed tile re-uses the staging LDS
                                                                                   // (+ 8 waves x 2 halves x 2 doubles of GroupNorm partial sums)
-    constexpr int LDS_BYTES0 = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
-    constexpr int LDS_BYTES = LDS_BYTES0;
+    constexpr int LDS_BYTES = STAGE_BYTES > EPI_BYTES ? STAGE_BYTES : EPI_BYTES;
     auto kern = conv_mfma_kernel<WAVES_M, WAVES_N, TM, TN, MATH, GNS, NSTAGE>;
     static std::atomic<unsigned long long> lds_ok{0};      // per kernel instantiation, one bit per device
     if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), LDS_BYTES, lds_ok, "conv2d")) return rc;
+    const int n = plan.n;
     MultiArgs args;
     args.n = n;
-    long long start = 0, ws_off = 0;
-    int planned[MAXP], planned_cps[MAXP];
-    plan_splits(descs, n, BM, BN, KC, workspace != nullptr, ws_bytes, split_tiles, planned, planned_cps);
     for (int i = 0; i < n; ++i) {
-        const ml_conv2d_desc &d = descs[i];
+        const ml_conv2d_desc &d = plan.descs[i];
         Problem &P = args.p[i];
         P.d = d;
         const long long M = (long long)d.B * d.Ho * d.Wo;
@@ -1116,32 +1116,13 @@ int launch_multi(const ml_conv2d_desc *descs, int n, void *workspace, long long 
         P.div_wo = make_fastdiv((unsigned)d.Wo);
         P.in_bytes = (unsigned)((long long)d.B * d.H * d.W * d.in_cstride * ES);
         P.wgt_bytes = (unsigned)((long long)d.n_pad * P.ktot * ES);
-        const int chunks = d.KH * d.KW * P.ncpt;
         P.blocks_per_split = (P.MB + 7) / 8 * 8 * P.NB;
-        const int splits = planned[i];
-        const long long slab_bytes = (long long)splits * P.MB * BM * d.n_pad * 4;
-        if (d.gn_partials)
-            ML_REQUIRE(GNS && splits == 1 && BN == 128 && d.cout == 128 && d.n_pad == 128 && M % BM == 0 && !d.residual &&
-                           !d.out_bstride && (!d.out_f16 || MATH == ML_MATH_F16S) && !d.shuffle2x2 && d.act != ML_ACT_SIGMOID &&
-                           !d.live && (d.out_f16 || host_out_vec_ok(d)),
-                       "conv2d: gn_partials needs a launch that is neither narrowed nor split along K (ml_conv2d_gn_min_launch_tiles() "
-                       "tiles of 128 x 128), cout = 128, whole 128-row tiles, no residual, and a dense fp32 destination on the "
-                       "vector epilogue (out / bias 16-byte aligned, out_cstride and out_coff multiples of 4)");
-        P.splits = splits;
-        P.cps = planned_cps[i];
-        P.slab = nullptr;
-        if (P.splits > 1) {
-            P.slab = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + ws_off);
-            ws_off += (slab_bytes + 255) / 256 * 256;
-        } else {
-            P.cps = chunks;
-        }
-        args.start[i] = (int)start;
-        start += (long long)P.blocks_per_split * P.splits;
-        ML_REQUIRE(start < (1ll << 31), "conv2d: grid too large");
+        P.splits = plan.splits[i];
+        P.cps = plan.cps[i];
+        P.slab = P.splits > 1 ? reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + plan.slab_off[i]) : nullptr;
     }
-    args.start[n] = (int)start;
-    hipLaunchKernelGGL(kern, dim3((unsigned)start), dim3(NT), LDS_BYTES, s, args);
+    for (int i = 0; i <= n; ++i) args.start[i] = plan.start[i];
+    hipLaunchKernelGGL(kern, dim3((unsigned)plan.start[n]), dim3(NT), LDS_BYTES, s, args);
     ML_CHECK_LAUNCH("conv2d");
     ReduceArgs ra;
     ra.n = 0;
@@ -1165,15 +1146,85 @@ int launch_multi(const ml_conv2d_desc *descs, int n, void *workspace, long long 
     return ML_OK;
 }
 
+// The instantiations of the generic kernel, by (math, gn_partials, tile rows, tile columns).
+struct GenericKernel { int math; bool gns; int BM, BN; int (*launch)(const ConvPlan &, void *, hipStream_t); };
+
+template <int WAVES_M, int WAVES_N, int TM, int TN, int MATH, bool GNS = false, int NSTAGE = 2>
+constexpr GenericKernel generic_kernel() {
+    return {MATH, GNS, WAVES_M * TM * 32, WAVES_N * TN * 32, launch_multi<WAVES_M, WAVES_N, TM, TN, MATH, GNS, NSTAGE>};
+}
+
+// (ML_MATH_F32X3: 4 x 1 waves, a wave = 32 rows x the whole N tile -- ONE wave splits the A fragments: +3-5 % on 3x3 convs)
+const GenericKernel kGenericKernels[] = {
+    generic_kernel<2, 2, 2, 2, ML_MATH_F32>(),
+    generic_kernel<2, 2, 2, 1, ML_MATH_F32>(),
+    generic_kernel<4, 1, 1, 1, ML_MATH_F32>(),
+    generic_kernel<2, 2, 2, 2, ML_MATH_F32, true>(),
+    generic_kernel<2, 2, 2, 2, ML_MATH_F16>(),
+    generic_kernel<2, 2, 2, 1, ML_MATH_F16>(),
+    generic_kernel<4, 1, 1, 1, ML_MATH_F16>(),
+    generic_kernel<2, 2, 2, 2, ML_MATH_F16S>(),
+    generic_kernel<2, 2, 2, 1, ML_MATH_F16S>(),
+    generic_kernel<4, 1, 1, 1, ML_MATH_F16S>(),
+    generic_kernel<2, 2, 2, 2, ML_MATH_F16S, true>(),
+    generic_kernel<4, 1, 1, 4, ML_MATH_F32X3>(),
+    generic_kernel<4, 1, 1, 2, ML_MATH_F32X3>(),
+    generic_kernel<4, 1, 1, 1, ML_MATH_F32X3>(),
+    generic_kernel<4, 1, 1, 4, ML_MATH_F32X3, true>(),
+    generic_kernel<8, 1, 1, 4, ML_MATH_F32X3, false, 3>(),
+    generic_kernel<8, 1, 1, 4, ML_MATH_F32X3, true, 3>(),
+};
+constexpr int N_GENERIC_KERNELS = sizeof(kGenericKernels) / sizeof(kGenericKernels[0]);
+
+// K slices, chunks per slice, workspace slab and first block of every problem of a generic launch, or its refusal.  Split-K
+// looks at the whole launch: five pyramid levels of one image are 171 tiles -- a third of the chip -- and each tile walks all
+// 36 chunks alone (92 us); slicing K fills the other CUs.  A slab that does not fit in the workspace left is not cut (the
+// fit counts slices before empty trailing ones are dropped; the slabs are laid out at the final count).
+static int plan_splits(ConvPlan &p, long long ws_bytes) {
+    const long long tiles = p.ref_tiles >= 0 ? p.ref_tiles : launch_tiles(p.descs, p.n, p.BM, p.BN);
+    const int math = p.descs[0].math;
+    long long reserved = 0, off = 0, start = 0;
+    for (int i = 0; i < p.n; ++i) {
+        const ml_conv2d_desc &d = p.descs[i];
+        const long long M = (long long)d.B * d.Ho * d.Wo, MB = (M + p.BM - 1) / p.BM, rows = MB * p.BM;
+        const int chunks = d.KH * d.KW * (d.span_pad / p.KC);
+        int splits = ws_bytes > 0 ? choose_splits(tiles, chunks) : 1;     // (the reduce kernel stores half too)
+        const long long slab_bytes = (long long)splits * rows * d.n_pad * 4;
+        if (splits > 1 && reserved + slab_bytes > ws_bytes) splits = 1;
+        const int cps = (chunks + splits - 1) / splits;
+        splits = (chunks + cps - 1) / cps;           // drop empty trailing slices
+        p.splits[i] = splits;
+        p.cps[i] = cps;
+        p.slab_off[i] = off;
+        if (splits > 1) {
+            reserved += (slab_bytes + 255) / 256 * 256;
+            off += ((long long)splits * rows * d.n_pad * 4 + 255) / 256 * 256;
+        }
+        if (d.gn_partials)
+            ML_REQUIRE(kGenericKernels[p.kernel].gns && splits == 1 && p.BN == 128 && d.cout == 128 && d.n_pad == 128 &&
+                           M % p.BM == 0 && !d.residual && !d.out_bstride && (!d.out_f16 || math == ML_MATH_F16S) &&
+                           !d.shuffle2x2 && d.act != ML_ACT_SIGMOID && !d.live && (d.out_f16 || host_out_vec_ok(d)),
+                       "conv2d: gn_partials needs a launch that is neither narrowed nor split along K (ml_conv2d_gn_min_launch_tiles() "
+                       "tiles of 128 x 128), cout = 128, whole 128-row tiles, no residual, and a dense fp32 destination on the "
+                       "vector epilogue (out / bias 16-byte aligned, out_cstride and out_coff multiples of 4)");
+        p.start[i] = (int)start;
+        start += (MB + 7) / 8 * 8 * (d.n_pad / p.BN) * splits;
+        ML_REQUIRE(start < (1ll << 31), "conv2d: grid too large");
+    }
+    p.start[p.n] = (int)start;
+    return ML_OK;
+}
+
 }  // namespace
 
 int ml_conv1x1_pipe_try(const ml_conv2d_desc &d, hipStream_t s, int *eligible);     // conv1x1_pipe.hip
+int ml_conv1x1_pipe_eligible(const ml_conv2d_desc &d);
 int ml_conv1x1_h256_try(const ml_conv2d_desc &d, hipStream_t s, int *took);          // conv1x1_h256.hip
 int ml_conv1x1_h256_eligible(const ml_conv2d_desc &d);
-// half tensors: where the 256 x 256-tile kernel is preferred over the 128 x 128 pipelined one (per-launch A/B,
-// gpurun_out/r03_h256_ab.txt): K >= 512, or K >= 256 with at least two 256-wide N tiles
 int ml_conv2d_wino_launch(const ml_conv2d_desc *descs, int n, hipStream_t s);          // conv_wino.hip
 
+// half tensors: where the 256 x 256-tile kernel is preferred over the 128 x 128 pipelined one (per-launch A/B,
+// gpurun_out/r03_h256_ab.txt): K >= 512, or K >= 256 with at least two 256-wide N tiles
 static bool h256_preferred(const ml_conv2d_desc &d) {
     return d.tile == 5 || (d.tile == 0 && (d.span >= 512 || (d.span >= 256 && d.cout >= 512)));
 }
@@ -1185,62 +1236,43 @@ extern "C" int ml_conv2d_ntile(int32_t cout, int32_t tile) {
 
 extern "C" int64_t ml_conv2d_workspace_bytes(void) { return 512ll << 20; }   // (split-K slabs of fixed-capacity RoI batches are sized for every slot)
 
-int ml_conv1x1_pipe_eligible(const ml_conv2d_desc &d);                               // conv1x1_pipe.hip
-// fp16 storage: the persistent kernel takes every 1x1 problem it can run, except those the generic kernel would cut
-// along K (few tiles, long K: the laterals of the coarse pyramid levels, the image-pooling branch) -- it has no split-K.
-// A residual (the ResNeXt conv3 of every block) is only implemented there.
-static bool pipe_preferred_half(const ml_conv2d_desc &d) {
-    if (d.residual || d.tile == 4) return true;
-    const long long M = (long long)d.B * d.Ho * d.Wo;
-    const long long tiles = ((M + 127) / 128) * ((d.cout + 127) / 128);
-    return tiles >= 192 || d.span / 64 < 16;
-}
-
-extern "C" int ml_conv2d_uses_pipe(const ml_conv2d_desc *d) {
-    if (!d) return 0;
-    if (d->math == ML_MATH_F16S && h256_preferred(*d) && ml_conv1x1_h256_eligible(*d)) return 2;
-    if (d->math == ML_MATH_F16S) return pipe_preferred_half(*d) && ml_conv1x1_pipe_eligible(*d);
-    if (d->tile == 4) return ml_conv1x1_pipe_eligible(*d);
-    return d->tile == 0 && pipe_preferred(*d) && ml_conv1x1_pipe_eligible(*d);
-}
-
 // The generic kernel addresses its input through 32-bit buffer offsets: a problem whose activation is >= 2 GiB (e.g. 32
 // images of 256x256x256 fp32, the largest batch the reference's MoldBatch takes, engine/layers/misc.py:273-284) is
-// cut into groups of whole images, each its own problem of the same launch.  -> number of problems written, or < 0.
-static int split_by_image_groups(const ml_conv2d_desc *descs, int n, ml_conv2d_desc *out, int cap) {
-    int m = 0;
+// cut into groups of whole images, each its own problem of the same launch.  -> p.descs / p.src / p.n.
+static int split_by_image_groups(const ml_conv2d_desc *descs, int n, ConvPlan &p) {
+    p.n = 0;
     for (int i = 0; i < n; ++i) {
         const ml_conv2d_desc &d = descs[i];
         const int es_in = d.math == ML_MATH_F16S ? 2 : 4, es_out = d.out_f16 ? 2 : 4;
         const long long img_bytes = (long long)d.H * d.W * d.in_cstride * es_in;
-        const long long limit = (1ll << 31) - 16;
-        long long per = img_bytes > 0 ? limit / img_bytes : d.B;
+        long long per = img_bytes > 0 ? ((1ll << 31) - 16) / img_bytes : d.B;
         if (per < 1) per = 1;
-        if (per >= d.B) {
-            if (m >= cap) return -1;
-            out[m++] = d;
-            continue;
+        if (per < d.B) {
+            // (image groups would renumber the images a `live` period counts)
+            ML_REQUIRE(!d.live, "conv2d: a problem with `live` images must stay below 2 GiB of activations");
+            // gn_partials is indexed by the problem's 128-row tile: a group starts at tile b0 * Ho * Wo / 128 of the whole
+            // tensor, which must be a whole number for every group
+            ML_REQUIRE(!d.gn_partials || (per * d.Ho * d.Wo) % 128 == 0,
+                       "conv2d: gn_partials on an activation >= 2 GiB needs image groups of whole 128-row tiles");
         }
-        if (d.live) return -2;          // (image groups would renumber the images a `live` period counts)
-        // gn_partials is indexed by the problem's 128-row tile: a group starts at tile b0 * Ho * Wo / 128 of the whole
-        // tensor, which must be a whole number for every group
-        if (d.gn_partials && (per * d.Ho * d.Wo) % 128) return -3;
         const long long in_img = (long long)d.H * d.W * d.in_cstride;
         const long long out_pix = d.shuffle2x2 ? 4ll * d.Ho * d.Wo : (long long)d.Ho * d.Wo;
         const long long out_img = d.out_bstride ? d.out_bstride : out_pix * d.out_cstride;
         const long long res_img = (long long)d.Ho * d.Wo * d.res_cstride;
-        for (long long b0 = 0; b0 < d.B; b0 += per) {
-            if (m >= cap) return -1;
+        long long b0 = 0;
+        do {                                         // (one group, the problem itself, when it is below 2 GiB)
+            ML_REQUIRE(p.n < MAXP, "conv2d: too many >= 2 GiB activations in one launch (more than %d image groups)", MAXP);
             ml_conv2d_desc g = d;
             g.B = (int)(d.B - b0 < per ? d.B - b0 : per);
             g.in = reinterpret_cast<const float *>(reinterpret_cast<const char *>(d.in) + b0 * in_img * es_in);
             g.out = reinterpret_cast<float *>(reinterpret_cast<char *>(d.out) + b0 * out_img * es_out);
             if (d.residual) g.residual = d.residual + b0 * res_img;
             if (d.gn_partials) g.gn_partials = d.gn_partials + (b0 * d.Ho * d.Wo / 128) * 8;   // [tile][4 waves][sum, sum of squares]
-            out[m++] = g;
-        }
+            p.src[p.n] = i;
+            p.descs[p.n++] = g;
+        } while ((b0 += per) < d.B);
     }
-    return m;
+    return ML_OK;
 }
 
 // A launch that cannot fill the chip with 128-wide tiles (small batches: one 512x512 image gives the towers 43 tiles)
@@ -1251,37 +1283,31 @@ static int split_by_image_groups(const ml_conv2d_desc *descs, int n, ml_conv2d_d
 static int narrow_tile_for_small_launch(const ml_conv2d_desc *descs, int n, int t0, bool have_ws, long long *ref_tiles) {
     *ref_tiles = -1;
     if (t0 == 3) return t0;
-    const int ref_bn = t0 == 1 ? 128 : 64;
-    long long tiles = 0;
-    int n_live = 0;
-    for (int i = 0; i < n; ++i) n_live += descs[i].live != nullptr;
-    auto tiles_of = [&](const ml_conv2d_desc &d) {          // (live problems: the estimate launch_multi uses)
-        const long long M = (long long)d.B * d.Ho * d.Wo;
-        const long long t = ((M + 127) / 128) * (d.n_pad / ref_bn);
-        return d.live ? (t + n_live - 1) / n_live : t;
-    };
+    bool any_live = false;
     for (int i = 0; i < n; ++i) {
         if (descs[i].group_cin_step) return t0;
-        tiles += tiles_of(descs[i]);
+        any_live = any_live || descs[i].live != nullptr;
     }
+    const int ref_bn = t0 == 1 ? 128 : 64;
+    long long per[MAXP];
+    const long long tiles = launch_tiles(descs, n, 128, ref_bn, per);
     long long blocks = 0;
     for (int i = 0; i < n; ++i) {
         const ml_conv2d_desc &d = descs[i];
         const int chunks = d.KH * d.KW * (d.span_pad / (d.math == ML_MATH_F16S ? 64 : 32));
-        const int splits = have_ws ? choose_splits(tiles, chunks) : 1;
-        blocks += tiles_of(d) * splits;
+        blocks += per[i] * (have_ws ? choose_splits(tiles, chunks) : 1);
     }
-    const long long resident = ml_resident_blocks(2);
+    const long long resident = ml_resident_blocks(NARROW_BLOCKS_PER_CU);
     // Fixed-capacity RoI batches (round 4): their live tiles are a third of the launch, known to the device only.  Cutting
     // K to fill the chip gave the 1-image mask head 616 blocks of 128 x 128 tiles -- one per CU, three rounds, 87 us per conv
     // and a reduce launch behind each; the same 616 blocks as 128 x 32 tiles of the WHOLE K sum sit three to a CU.  So for
-    // these launches narrow tiles come before K slices (ref_tiles = 192: choose_splits cuts nothing from there), and the
-    // narrow forms may overfill the resident slots by half (dead tiles return at once).  1 x 512^2 MobileNet graph: 1.71 ->
-    // 1.59 ms on one box.  (The same preference for ALL small launches of moderate K -- towers, FPN -- was slower: 1.59-1.61
-    // against 1.52-1.56 ms; their K slices stay.)
-    if (n_live > 0 && ref_bn == 128) {
-        if (tiles * 4 <= resident * 3 / 2) { *ref_tiles = 192; return 3; }
-        if (tiles >= 192 && tiles * 2 <= resident * 3 / 2) { *ref_tiles = tiles; return 2; }
+    // these launches narrow tiles come before K slices (ref_tiles = UNSPLIT_TILES: choose_splits cuts nothing from there),
+    // and the narrow forms may overfill the resident slots by half (dead tiles return at once).  1 x 512^2 MobileNet graph:
+    // 1.71 -> 1.59 ms on one box.  (The same preference for ALL small launches of moderate K -- towers, FPN -- was slower:
+    // 1.59-1.61 against 1.52-1.56 ms; their K slices stay.)
+    if (any_live && ref_bn == 128) {
+        if (tiles * 4 <= resident * 3 / 2) { *ref_tiles = UNSPLIT_TILES; return 3; }
+        if (tiles >= UNSPLIT_TILES && tiles * 2 <= resident * 3 / 2) { *ref_tiles = tiles; return 2; }
     }
     *ref_tiles = tiles;
     if (blocks * (ref_bn / 32) <= resident) return 3;
@@ -1317,146 +1343,118 @@ static bool x3_uses_256_row_tiles(const ml_conv2d_desc *descs, int n, int t) {
     return big >= ml_resident_blocks(1);
 }
 
-extern "C" int ml_conv2d_multi_f32(const ml_conv2d_desc *descs_in, int32_t n_in, void *workspace, int64_t workspace_bytes,
-                                   void *stream) {
+// THE decision of ml_conv2d_multi_f32 with ws_bytes of workspace (0 = none): kernel, tiles, K slices, or its refusal
+// (ML_E_BADARG, message).  The launch checks the tensor pointers; check = false: kernel and tiles only, no validate().
+static int plan_launch(const ml_conv2d_desc *descs_in, int n_in, long long ws_bytes, ConvPlan &p, bool check = true) {
     ML_REQUIRE(descs_in != nullptr && n_in >= 1 && n_in <= MAXP, "conv2d: need 1..%d problems", MAXP);
-    if (descs_in[0].tile == 6) {
-        // Winograd F(2x2,3x3) (conv_wino.hip): every problem of the launch asks for it; 64-bit addressing, no image groups
+    const ml_conv2d_desc &d0 = descs_in[0];
+    if (d0.tile == 6) {         // Winograd F(2x2,3x3) (conv_wino.hip): every problem asks for it; 64-bit addressing
         for (int i = 0; i < n_in; ++i) {
             ML_REQUIRE(descs_in[i].tile == 6, "conv2d: all problems of one launch must use the same tile shape");
-            const int rc = validate(descs_in[i]);
-            if (rc != ML_OK) return rc;
+            if (int rc = check ? validate(descs_in[i]) : ML_OK) return rc;
         }
-        return ml_conv2d_wino_launch(descs_in, n_in, reinterpret_cast<hipStream_t>(stream));
+        p.family = CONV_WINO;
+        return ML_OK;
     }
-    // the persistent 1x1 kernel has no tensor-size limit: try it before any splitting
-    if (n_in == 1 && (descs_in[0].tile == 0 || descs_in[0].tile == 4 || descs_in[0].tile == 5)) {
-        const int rc0 = validate(descs_in[0], false);
-        if (rc0 != ML_OK) return rc0;
-        ML_REQUIRE(descs_in[0].math >= ML_MATH_F32 && descs_in[0].math <= ML_MATH_F32X3, "conv2d: unknown math mode %d", descs_in[0].math);
-        int took = 0;
-        const bool half = descs_in[0].math == ML_MATH_F16S;
-        if (half && h256_preferred(descs_in[0])) {
-            const int rc = ml_conv1x1_h256_try(descs_in[0], reinterpret_cast<hipStream_t>(stream), &took);
-            if (rc != ML_OK) return rc;
-            if (took) return ML_OK;
-            ML_REQUIRE(descs_in[0].tile != 5, "conv2d: tile = 5 (256 x 256 half kernel) does not apply to this problem");
+    ML_REQUIRE(d0.math >= ML_MATH_F32 && d0.math <= ML_MATH_F32X3, "conv2d: unknown math mode %d", d0.math);
+    // the persistent 1x1 kernels have no tensor-size limit: they are considered before any splitting
+    if (n_in == 1 && (d0.tile == 0 || d0.tile == 4 || d0.tile == 5)) {
+        if (int rc = check ? validate(d0, false) : ML_OK) return rc;
+        const bool half = d0.math == ML_MATH_F16S;
+        const bool h256 = half && h256_preferred(d0) && ml_conv1x1_h256_eligible(d0);
+        ML_REQUIRE(h256 || !half || d0.tile != 5, "conv2d: tile = 5 (256 x 256 half kernel) does not apply to this problem");
+        if (h256 || (pipe_preferred(d0) && ml_conv1x1_pipe_eligible(d0))) {
+            p.family = h256 ? CONV_H256 : CONV_PIPE;
+            return ML_OK;
         }
-        if (half ? pipe_preferred_half(descs_in[0]) : (descs_in[0].tile == 4 || pipe_preferred(descs_in[0]))) {
-            const int rc = ml_conv1x1_pipe_try(descs_in[0], reinterpret_cast<hipStream_t>(stream), &took);
-            if (rc != ML_OK) return rc;
-            if (took) return ML_OK;
-        }
-        ML_REQUIRE(descs_in[0].tile != 4, "conv2d: tile = 4 (pipelined 1x1 kernel) does not apply to this problem");
+        ML_REQUIRE(d0.tile != 4, "conv2d: tile = 4 (pipelined 1x1 kernel) does not apply to this problem");
     }
-    ml_conv2d_desc split[MAXP];
-    const int n = split_by_image_groups(descs_in, n_in, split, MAXP);
-    ML_REQUIRE(n != -2, "conv2d: a problem with `live` images must stay below 2 GiB of activations");
-    ML_REQUIRE(n != -3, "conv2d: gn_partials on an activation >= 2 GiB needs image groups of whole 128-row tiles");
-    ML_REQUIRE(n >= 1, "conv2d: too many >= 2 GiB activations in one launch (more than %d image groups)", MAXP);
-    const ml_conv2d_desc *descs = split;
-    int t0 = 0;
+    p.family = CONV_GENERIC;
+    if (int rc = split_by_image_groups(descs_in, n_in, p)) return rc;
+    const ml_conv2d_desc *descs = p.descs;
+    const int n = p.n;
+    const int t0 = pick_tile(d0.cout, d0.tile);
+    bool gns = false;
     for (int i = 0; i < n; ++i) {
-        const int rc = validate(descs[i]);
-        if (rc != ML_OK) return rc;
-        const int t = pick_tile(descs[i].cout, descs[i].tile);
-        if (i == 0) t0 = t;
-        ML_REQUIRE(t == t0, "conv2d: all problems of one launch must use the same tile shape");
+        if (int rc = check ? validate(descs[i]) : ML_OK) return rc;
+        ML_REQUIRE(pick_tile(descs[i].cout, descs[i].tile) == t0, "conv2d: all problems of one launch must use the same tile shape");
         ML_REQUIRE(descs[i].math == descs[0].math, "conv2d: all problems of one launch must use the same math mode");
         ML_REQUIRE(!(descs[i].math == ML_MATH_F16S && descs[i].residual),
                    "conv2d: the fp16-storage form of the generic kernel takes no residual (only the persistent 1x1 kernel does: "
                    "stride 1, cout %% 128 == 0, span %% 64 == 0, half output)");
+        gns = gns || descs[i].gn_partials != nullptr;
     }
-    ML_REQUIRE(descs[0].math >= ML_MATH_F32 && descs[0].math <= ML_MATH_F32X3, "conv2d: unknown math mode %d", descs[0].math);
-    if (workspace) ML_REQUIRE((((uintptr_t)workspace) & 255) == 0, "conv2d: workspace must be 256-byte aligned");
+    const int math = d0.math;
+    const int t = x3_adjust_tile(descs, n, narrow_tile_for_small_launch(descs, n, t0, ws_bytes > 0, &p.ref_tiles));
+    const bool gns_kernel = gns && math != ML_MATH_F16;        // (ML_MATH_F16 has no gn_partials form: refused below)
+    ML_REQUIRE(!gns_kernel || t == 1, math == ML_MATH_F16S
+                   ? "conv2d: gn_partials needs the 128 x 128 kernel (a launch of ml_conv2d_gn_min_launch_tiles() tiles)"
+                   : "conv2d: gn_partials needs the fp32 128 x 128 kernel (a launch of >= 257 tiles)");
+    p.BM = x3_uses_256_row_tiles(descs, n, t) ? 256 : 128;
+    p.BN = t == 1 ? 128 : (t == 2 ? 64 : 32);
+    p.KC = math == ML_MATH_F16S ? 64 : 32;
+    for (p.kernel = 0; p.kernel < N_GENERIC_KERNELS; ++p.kernel) {
+        const GenericKernel &k = kGenericKernels[p.kernel];
+        if (k.math == math && k.gns == gns_kernel && k.BM == p.BM && k.BN == p.BN) break;
+    }
+    ML_REQUIRE(p.kernel < N_GENERIC_KERNELS, "conv2d: no kernel instantiation for math %d, %d x %d tiles", math, p.BM, p.BN);
+    return check ? plan_splits(p, ws_bytes) : ML_OK;
+}
+
+extern "C" int ml_conv2d_multi_f32(const ml_conv2d_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
+                                   void *stream) {
+    ML_REQUIRE(descs != nullptr && n >= 1 && n <= MAXP, "conv2d: need 1..%d problems", MAXP);
+    for (int i = 0; i < n; ++i) {          // (the plan never looks at the tensors: their pointers are checked here)
+        ML_REQUIRE(descs[i].in && descs[i].wgt && descs[i].out, "conv2d: null tensor pointer");
+        ML_REQUIRE(ml_aligned16(descs[i].in) && ml_aligned16(descs[i].wgt), "conv2d: in/wgt must be 16-byte aligned");
+    }
+    ConvPlan p;
+    if (int rc = plan_launch(descs, n, workspace ? workspace_bytes : 0, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    long long ref_tiles = -1;
-    const int t = x3_adjust_tile(descs, n, narrow_tile_for_small_launch(descs, n, t0, workspace != nullptr, &ref_tiles));
-    if (descs[0].math == ML_MATH_F16S) {
-        bool gns_h = false;
-        for (int i = 0; i < n; ++i) gns_h = gns_h || descs[i].gn_partials != nullptr;
-        ML_REQUIRE(!gns_h || t == 1, "conv2d: gn_partials needs the 128 x 128 kernel (a launch of ml_conv2d_gn_min_launch_tiles() tiles)");
-        if (gns_h) return launch_multi<2, 2, 2, 2, ML_MATH_F16S, true>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        switch (t) {
-            case 1: return launch_multi<2, 2, 2, 2, ML_MATH_F16S>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            case 2: return launch_multi<2, 2, 2, 1, ML_MATH_F16S>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            default: return launch_multi<4, 1, 1, 1, ML_MATH_F16S>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        }
+    if (p.family == CONV_WINO) return ml_conv2d_wino_launch(descs, n, s);
+    if (p.family == CONV_H256 || p.family == CONV_PIPE) {
+        int took = 0;
+        if (int rc = (p.family == CONV_H256 ? ml_conv1x1_h256_try : ml_conv1x1_pipe_try)(descs[0], s, &took)) return rc;
+        ML_REQUIRE(took, "conv2d: the persistent 1x1 kernel did not take a problem it was planned for");
+        return ML_OK;
     }
-    if (descs[0].math == ML_MATH_F16) {
-        switch (t) {
-            case 1: return launch_multi<2, 2, 2, 2, ML_MATH_F16>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            case 2: return launch_multi<2, 2, 2, 1, ML_MATH_F16>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            default: return launch_multi<4, 1, 1, 1, ML_MATH_F16>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        }
-    }
-    bool any_gns = false;
-    for (int i = 0; i < n; ++i) any_gns = any_gns || descs[i].gn_partials != nullptr;
-    ML_REQUIRE(!any_gns || t == 1, "conv2d: gn_partials needs the fp32 128 x 128 kernel (a launch of >= 257 tiles)");
-    if (descs[0].math == ML_MATH_F32X3) {
-        // Wave layout 4 x 1 (a wave = 32 rows x the whole N tile): the A fragments -- the operand that is split in
-        // registers -- are read and split by ONE wave instead of two (+3-5 % on the 3x3 convs against 2 x 2 waves).
-        if (x3_uses_256_row_tiles(descs, n, t)) {
-            if (any_gns) return launch_multi<8, 1, 1, 4, ML_MATH_F32X3, true, 3>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            return launch_multi<8, 1, 1, 4, ML_MATH_F32X3, false, 3>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        }
-        if (any_gns) return launch_multi<4, 1, 1, 4, ML_MATH_F32X3, true>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        switch (t) {
-            case 1: return launch_multi<4, 1, 1, 4, ML_MATH_F32X3>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            case 2: return launch_multi<4, 1, 1, 2, ML_MATH_F32X3>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-            default: return launch_multi<4, 1, 1, 1, ML_MATH_F32X3>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        }
-    }
-    if (any_gns) return launch_multi<2, 2, 2, 2, ML_MATH_F32, true>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-    switch (t) {
-        case 1: return launch_multi<2, 2, 2, 2, ML_MATH_F32>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        case 2: return launch_multi<2, 2, 2, 1, ML_MATH_F32>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-        default: return launch_multi<4, 1, 1, 1, ML_MATH_F32>(descs, n, workspace, workspace_bytes, s, ref_tiles);
-    }
+    if (workspace) ML_REQUIRE((((uintptr_t)workspace) & 255) == 0, "conv2d: workspace must be 256-byte aligned");
+    return kGenericKernels[p.kernel].launch(p, workspace, s);
 }
 
-// N-tile width (128 / 64 / 32) the generic kernel will use for this launch (after the small-launch narrowing); 0 on bad
-// arguments.  For reporting: which kernel instantiation a launch's time belongs to.
+// The reporting entries: one field each of the plan (kernel and tiles: unchecked; K slices: checked, refusals included).
+
+extern "C" int ml_conv2d_uses_pipe(const ml_conv2d_desc *d) {
+    ConvPlan p;
+    return plan_launch(d, 1, 0, p, false) != ML_OK ? 0 : (p.family == CONV_H256 ? 2 : p.family == CONV_PIPE);
+}
+
 extern "C" int ml_conv2d_launch_ntile(const ml_conv2d_desc *descs, int32_t n, int32_t has_workspace) {
-    if (!descs || n < 1 || n > MAXP) return 0;
-    const int t0 = pick_tile(descs[0].cout, descs[0].tile);
-    long long ref_tiles = -1;
-    const int t = x3_adjust_tile(descs, n, narrow_tile_for_small_launch(descs, n, t0, has_workspace != 0, &ref_tiles));
-    return t == 1 ? 128 : (t == 2 ? 64 : 32);
+    ConvPlan p;
+    return plan_launch(descs, n, has_workspace ? ml_conv2d_workspace_bytes() : 0, p, false) == ML_OK && p.family == CONV_GENERIC ? p.BN : 0;
 }
 
-// M-tile height (128 / 256) of the same launch; 0 on bad arguments.
 extern "C" int ml_conv2d_launch_mtile(const ml_conv2d_desc *descs, int32_t n, int32_t has_workspace) {
-    if (!descs || n < 1 || n > MAXP) return 0;
-    const int t0 = pick_tile(descs[0].cout, descs[0].tile);
-    long long ref_tiles = -1;
-    const int t = x3_adjust_tile(descs, n, narrow_tile_for_small_launch(descs, n, t0, has_workspace != 0, &ref_tiles));
-    return x3_uses_256_row_tiles(descs, n, t) ? 256 : 128;
+    ConvPlan p;
+    return plan_launch(descs, n, has_workspace ? ml_conv2d_workspace_bytes() : 0, p, false) == ML_OK && p.family == CONV_GENERIC ? p.BM : 0;
 }
 
-// K slices per problem of the launch ml_conv2d_multi_f32 would make for these problems (1 = not split; the persistent
-// 1x1 kernels never split).  splits: n ints.  For reporting / tests: which launches cut their K sum differently when
-// the batch changes.  ML_OK, or ML_E_BADARG.
 extern "C" int ml_conv2d_launch_splits(const ml_conv2d_desc *descs, int32_t n, int64_t workspace_bytes, int32_t *splits) {
     ML_REQUIRE(descs && splits && n >= 1 && n <= MAXP, "conv2d_launch_splits: need 1..%d problems", MAXP);
+    ConvPlan p;
+    if (int rc = plan_launch(descs, n, workspace_bytes, p)) return rc;
     for (int i = 0; i < n; ++i) splits[i] = 1;
-    if (descs[0].tile == 6) return ML_OK;                  // Winograd: the whole K sum in every block
-    if (n == 1 && ml_conv2d_uses_pipe(descs)) return ML_OK;
-    const int t0 = pick_tile(descs[0].cout, descs[0].tile);
-    long long ref_tiles = -1;
-    const int t = x3_adjust_tile(descs, n, narrow_tile_for_small_launch(descs, n, t0, workspace_bytes > 0, &ref_tiles));
-    const int BM = x3_uses_256_row_tiles(descs, n, t) ? 256 : 128;
-    const int BN = t == 1 ? 128 : (t == 2 ? 64 : 32);
-    const int KC = descs[0].math == ML_MATH_F16S ? 64 : 32;
-    plan_splits(descs, n, BM, BN, KC, workspace_bytes > 0, workspace_bytes, ref_tiles, splits);
+    if (p.family == CONV_GENERIC)               // (an input problem cut into image groups: the most slices of any group)
+        for (int j = 0; j < p.n; ++j)
+            if (p.splits[j] > splits[p.src[j]]) splits[p.src[j]] = p.splits[j];
     return ML_OK;
 }
 
 // Smallest launch (in 128 x 128 tiles, all problems together) that ml_conv2d_multi_f32 neither narrows to 128 x 64 / 128 x 32
 // tiles nor cuts along K on THIS device -- the size from which ml_conv2d_desc.gn_partials may be used.
 extern "C" int64_t ml_conv2d_gn_min_launch_tiles(void) {
-    const long long narrow_below = ml_resident_blocks(2) / 2 + 1;      // (blocks * 2 <= resident -> 128 x 64 tiles)
-    return narrow_below > 192 ? narrow_below : 192;                    // (choose_splits: no K slices from 192 tiles)
+    const long long narrow_below = ml_resident_blocks(NARROW_BLOCKS_PER_CU) / 2 + 1;     // (blocks * 2 <= resident -> 128 x 64 tiles)
+    return narrow_below > UNSPLIT_TILES ? narrow_below : UNSPLIT_TILES;
 }
 
 extern "C" int ml_conv2d_f32(const ml_conv2d_desc *dp, void *stream) {

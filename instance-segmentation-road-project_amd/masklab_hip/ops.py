@@ -67,7 +67,8 @@ class _Prof:
 # and what the model returns -- cls_pred, loc_pred, roi_boxes, roi_masks, seg_pred -- is fp32.  Kernels follow the
 # dtype of the tensor they are given: an fp32 tensor in this mode (MobileNet's body) runs like "f16".
 # "f32x3" = fp32 tensors and fp32-grade arithmetic on the f16 matrix pipe (ML_MATH_F32X3): every operand is split into
-# two halves (22 bits), every product is three f16 MFMAs with fp32 accumulation; 1x1 convs run on the generic kernel.
+# two halves (22 bits), every product is three f16 MFMAs with fp32 accumulation; 1x1 convs with K <= 256 (or a residual)
+# on maps of >= 4 096 pixels run on the persistent pipelined kernel, every other conv on the generic one.
 # Process-wide switch, read when a conv is launched; set it through set_conv_math().
 CONV_MATH = "f32"
 _MATH_CODE = {"f32": 0, "f16": 1, "f16s": 1, "f32x3": 3}   # per-launch code of fp32-tensor convs; half tensors select ML_MATH_F16S
@@ -273,16 +274,47 @@ def _conv_desc(x, dc, stride=1, padding="same", dilation=1, act=_lib.ACT_NONE, r
     return d, ret, (2.0 * M * p.cout * p.k_real, nbytes, shape)
 
 
-def _conv_kernel_name(p, descs=None, n=1, half=False):
-    """Name of the kernel instantiation a launch runs on (profiling hook only).  With the descriptors the library is
-    asked which N tile it will really use: small launches run on narrower tiles than the weights were packed for."""
+def _conv_kernel_name(descs, n, p, half):
+    """Name of the kernel a (non-Winograd) launch runs on (profiling hook only), as the library plans the launch: the
+    persistent 1x1 kernels, or the generic kernel's instantiation -- small launches run on narrower tiles than the weights
+    were packed for."""
     lib = _lib.load()
-    bn = lib.ml_conv2d_launch_ntile(descs, n, 1) if descs is not None and PROFILE is not None else 0
-    bm = (lib.ml_conv2d_launch_mtile(descs, n, 1) if bn else 0) or 128
-    if not bn:
-        bn = lib.ml_conv2d_ntile(p.cout, p.tile)
+    which = lib.ml_conv2d_uses_pipe(descs) if n == 1 else 0      # 1: the 128 x 128 pipelined kernel, 2: the half 256 x 256 one
+    if which:
+        return "conv1x1_h256_h" if which == 2 else (
+            "conv1x1_pipe_h" if half else ("conv1x1_pipe_x3" if CONV_MATH == "f32x3" else "conv1x1_pipe"))
+    bn = lib.ml_conv2d_launch_ntile(descs, n, 1) or lib.ml_conv2d_ntile(p.cout, p.tile)
+    bm = lib.ml_conv2d_launch_mtile(descs, n, 1) or 128
     return "conv_mfma_%dx%d%s%s" % (bm, bn, "_grouped" if p.group_cin_step else "",
                                      "_h" if half else {"f32": "", "f32x3": "_x3"}.get(CONV_MATH, "_f16"))
+
+
+def _launch_conv(descs, problems, flops, nbytes, shapes, multi):
+    """One ml_conv2d_multi_f32 launch of `descs` (problems: their (x, dc) pairs), moved onto the Winograd kernel when every
+    problem qualifies.  Its profile name (PROFILE) and K slices (LAUNCH_LOG) are the library's plan of this launch."""
+    lib = _lib.load()
+    n = len(problems)
+    x, dc = problems[0]
+    wino = _wino_select(descs, n, problems)
+    label = ("multi x%d" % n if multi else shapes[0]) + (" wino direct_flop=%.0f" % flops if wino else "")
+    if wino:
+        flops = sum(_wino_flops(descs[i]) for i in range(n))
+    ws = workspace(int(lib.ml_conv2d_workspace_bytes()), x.device, "conv")
+    if LAUNCH_LOG is not None:
+        sp = (C.c_int32 * n)()
+        _lib.check(lib.ml_conv2d_launch_splits(descs, n, ws.numel(), sp), "ml_conv2d_launch_splits")
+        LAUNCH_LOG.append((" | ".join(shapes) if multi else label, tuple(int(v) for v in sp)))
+    name = None
+    if PROFILE is not None:
+        name = "conv_wino_f32" if wino else _conv_kernel_name(descs, n, dc.p, x.dtype == torch.float16)
+    with _Prof(name, flops, nbytes, label) as prof:
+        if prof.on and name == "conv1x1_h256_h":
+            # bytes this launch stages through the CUs' L1 -> LDS path: every 256-row tile takes its 256 x K activation rows
+            # and the 256 x K weight rows of its N tile, 2 bytes each (what bounds that kernel: profiles/r04_h256_pmc.md)
+            d = descs[0]
+            M, N, K = d.B * d.Ho * d.Wo, d.cout, d.span
+            prof.rec["staged_bytes"] = float(-(-M // 256) * (N // 256) * 2 * 256 * K * 2)
+        _lib.check(lib.ml_conv2d_multi_f32(descs, n, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_multi_f32")
 
 
 def _wino_select(descs, n, problems):
@@ -350,13 +382,6 @@ def _gn_min_launch_tiles():
     return _GN_MIN_TILES
 
 
-def _log_launch(arr, n, ws, label):
-    if LAUNCH_LOG is not None:
-        sp = (C.c_int32 * n)()
-        _lib.check(_lib.load().ml_conv2d_launch_splits(arr, n, ws.numel(), sp), "ml_conv2d_launch_splits")
-        LAUNCH_LOG.append((label, tuple(int(v) for v in sp)))
-
-
 def conv2d(x, dc: DeviceConv, stride=1, padding="same", dilation=1, act=_lib.ACT_NONE,
            residual=None, out=None, out_coff=0, in_coff=0, out_view=None, out_dtype=None, gn_partials=None):
     """ml_conv2d_multi_f32 with one problem (split-K enabled through the shared workspace).
@@ -364,38 +389,18 @@ def conv2d(x, dc: DeviceConv, stride=1, padding="same", dilation=1, act=_lib.ACT
     `out[..., out_coff:out_coff+cout]` when given, else allocates.  `out_view=(tensor, elem_off,
     cstride, bstride)` writes image b's pixels at tensor.data + elem_off + b*bstride with row
     pitch cstride (used to land a level's head directly in the concatenated prediction)."""
-    lib = _lib.load()
     if x.dtype == torch.float16 and stride == 2 and dc.p.kh_real == 1 and dc.p.kw_real == 1:
         # a strided 1x1 conv on half tensors = the stride-1 kernel on the sampled pixels (ResNext.py:199-203 shortcuts)
         x, stride = subsample2_h(x), 1
     d, ret, (flops, nbytes, shape) = _conv_desc(x, dc, stride, padding, dilation, act, residual, out, out_coff,
                                                 in_coff, out_view, out_dtype, gn_partials=gn_partials)
-    ws = workspace(lib.ml_conv2d_workspace_bytes(), x.device, "conv")
-    wino = _wino_select([d], 1, [(x, dc)])
-    name = "conv_wino_f32" if wino else _conv_kernel_name(dc.p, C.byref(d), 1, half=x.dtype == torch.float16)
-    if wino:
-        shape += " wino direct_flop=%.0f" % flops
-        flops = _wino_flops(d)
-    elif PROFILE is not None:
-        which = lib.ml_conv2d_uses_pipe(C.byref(d))          # 1: the 128 x 128 pipelined kernel, 2: the half 256 x 256 one
-        if which:
-            name = "conv1x1_h256_h" if which == 2 else (
-                "conv1x1_pipe_h" if x.dtype == torch.float16 else ("conv1x1_pipe_x3" if CONV_MATH == "f32x3" else "conv1x1_pipe"))
-    _log_launch(C.byref(d), 1, ws, shape)
-    with _Prof(name, flops, nbytes, shape) as prof:
-        if prof.on and name == "conv1x1_h256_h":
-            # bytes this launch stages through the CUs' L1 -> LDS path: every 256-row tile takes its 256 x K activation rows
-            # and the 256 x K weight rows of its N tile, 2 bytes each (what bounds that kernel: profiles/r04_h256_pmc.md)
-            M, N, K = d.B * d.Ho * d.Wo, d.cout, d.span
-            prof.rec["staged_bytes"] = float(-(-M // 256) * (N // 256) * 2 * 256 * K * 2)
-        _lib.check(lib.ml_conv2d_multi_f32(C.byref(d), 1, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_multi_f32")
+    _launch_conv((_lib.ConvDesc * 1)(d), [(x, dc)], flops, nbytes, [shape], multi=False)
     return ret
 
 
 def conv2d_multi(problems):
     """One launch for several independent convs of the same tile shape.
     problems: list of dicts with keys x, dc and the keyword arguments of conv2d().  -> list of results."""
-    lib = _lib.load()
     n = len(problems)
     if n == 0:
         return []
@@ -411,16 +416,7 @@ def conv2d_multi(problems):
         flops += f
         nbytes += nb
         shapes.append(shape)
-    wino = _wino_select(arr, n, [(pr["x"], pr["dc"]) for pr in problems])
-    if wino:
-        name, label = "conv_wino_f32", "multi x%d wino direct_flop=%.0f" % (n, flops)
-        flops = sum(_wino_flops(arr[i]) for i in range(n))
-    else:
-        name, label = _conv_kernel_name(problems[0]["dc"].p, arr, n, half=problems[0]["x"].dtype == torch.float16), f"multi x{n}"
-    ws = workspace(int(lib.ml_conv2d_workspace_bytes()), problems[0]["x"].device, "conv")
-    _log_launch(arr, n, ws, " | ".join(shapes))
-    with _Prof(name, flops, nbytes, label):
-        _lib.check(lib.ml_conv2d_multi_f32(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_multi_f32")
+    _launch_conv(arr, [(pr["x"], pr["dc"]) for pr in problems], flops, nbytes, shapes, multi=True)
     return rets
 
 
