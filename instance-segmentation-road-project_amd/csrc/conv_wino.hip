@@ -7,52 +7,78 @@
 //   once to fp32 (masklab_hip/packing.py: pack_winograd).  Per position p = 4a + b the 16 products are independent
 //   GEMMs  M_p[tiles, Cout] = V_p[tiles, Cin] . U_p[Cin, Cout], accumulated over the whole K loop (no split-K).
 //
-//   Block = 256 threads = 4 waves, block tile = 64 Winograd tiles (flattened over image, tile row, tile column) x 32
-//   output channels; wave w owns tiles 16w..16w+15 x the 32 channels x all 16 positions: 2 x 16 accumulators of the
-//   16x16x4 MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of its 4
-//   tiles x 1 channel per 16-wide half).  K chunk = 8 input channels:
-//     * the raw 4x4 patches of the block's 64 tiles, [tile][16 px][8 ch] + 4 floats pad per tile (conflict-free
-//       b32 reads: lane (r, kq) hits bank 4r + kq), 33 KB; out-of-image taps are written as zeros;
-//     * the transformed weights of the chunk, [8 k][32 n][16 p] + 4 floats pad per k row, 16.5 KB (one contiguous
-//       16 KB block of the host layout, copied as is);
-//     both loaded to registers one chunk ahead (12 x 16 B per thread) and written to LDS behind a barrier.
-//   K step (4 channels): each lane reads its tile's 16 patch values of channel 4s + kq (16 ds_read_b32), applies
-//   B^T d B (32 adds) and issues 2 x 16 MFMAs whose B operands come as 8 ds_read_b128 (4 positions each).
+//   Block = 512 threads = 8 waves, one block per CU; block tile = 64 Winograd tiles (flattened over image, tile row, tile
+//   column) x 64 output channels (two 32-channel blocks of the host layout).  Wave w owns tile group tg = w & 3 (tiles
+//   16 tg .. 16 tg + 15) x channel half h = w >> 2 (32 channels) x all 16 positions: 2 x 16 accumulators of the 16x16x4
+//   MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of its 4 tiles x 1
+//   channel per 16-wide half).  The patches of a tile group are staged once and read by both channel halves.
+//   K chunk = one K step = 4 input channels, staged by LDS DMA (buffer_load_dwordx4 ... lds, 16 B per lane, 1 KB per wave
+//   instruction, 4 per wave and chunk) straight from global memory into a ring of 4 slots (32 KB each), one barrier per
+//   chunk.  Iteration c: wait until this wave's DMA of chunk c + 1 has landed (vmcnt(4): chunk c + 2 stays in flight)
+//   and its LDS reads are done (lgkmcnt(0)); barrier; DMA chunk c + 3 into the slot chunk c - 1 used; 4 MFMAs of chunk c;
+//   the LDS reads of chunk c + 1 (16 patch values + 8 B fragments, into the other of two register sets); the other 28
+//   MFMAs of chunk c.  So a step's operands are read one step ahead, across the barrier, and no MFMA waits on LDS.
+//   A slot holds
+//     * the raw 4x4 patches of the block's 64 tiles as [tg 4][px 16][r 16][4 ch] float4s: one DMA instruction = 4 px x
+//       16 tiles.  Lane (r, kq) reads channel kq of tile r at a per-lane base + px x 256 B (ds_read2st64_b32); a b32
+//       read's 32-lane group hits bank 4r + kq mod 32 (2-way: the floor for b32 reads of 16-B channel quads, as in the
+//       padded image this replaces).  Out-of-image taps and tiles past the end carry an out-of-range buffer offset and
+//       land as zeros;
+//     * the transformed weights of both channel halves as [h 2][k 4][t 2][pq 4][r 16][4 p] float4s (n = 16 t + r): one
+//       DMA instruction = one contiguous 1 KB (k, t) row of the host layout; a b128 read's 16-lane group covers r = 0..15
+//       once: conflict-free.
+//   The patch resource is rebased per block (its first tap row) and per chunk (+4 channels), so the per-lane offsets are
+//   32-bit and constant over the K loop while the tensor itself may exceed 4 GiB (the host checks that a block's rows
+//   span less than 2 GiB).  No staging registers and no exec-masked loads; the DMA of the chunks past the last one goes
+//   through empty resources, so the loop body is one basic block.
+//   K step: each lane applies B^T d B to its 16 patch values (32 adds, kept scalar: -fno-slp-vectorize in the Makefile)
+//   and issues 2 x 16 MFMAs, 4 positions per B fragment.
 //
-//   Costing (per CU, 2 blocks resident: 128 accumulators + ~100 other registers <= 256 per lane, 2 x 50 KB LDS):
-//     MFMA per chunk and wave: 2 steps x 16 positions x 2 halves = 64 x 32 cycles = 2048 cycles;
-//     VALU per chunk and wave: 2 x 32 transform adds + the 16 x 4 output-transform adds once per block: ~1 VALU per MFMA
-//       on the K loop, hidden behind the matrix pipe;
-//     staged per chunk and block: 32 KB of patches (each input pixel is read by up to 4 overlapping patches: L1 / L2
-//       hits) + 16 KB of weights = 48 KB per 2 x 2048 SIMD cycles (two resident blocks share the SIMDs) = ~12 B/clk/CU,
-//       against the ~30-39 B/clk the L1 -> LDS path moved in profiles/r04_h256_pmc.md;
-//     LDS reads per chunk and wave: 32 x b32 + 16 x b128 = 12 KB for 64 MFMAs.
+//   Costing (per CU: one block, 2 waves per SIMD; 128 accumulators + two operand sets of 48 <= 256 registers per lane,
+//   4 x 32 KB LDS):
+//     MFMA per chunk and SIMD: 2 waves x 16 positions x 2 halves = 64 x 32 cycles = 2048 cycles;
+//     VALU per chunk and wave: 32 transform adds (+ the output transform once per block): 1 VALU per MFMA, issued
+//       between MFMAs;
+//     staged per chunk and block: 16 KB of patches (each input pixel is read by up to 4 overlapping patches: L1 / L2 hits;
+//       half the patch bytes per MFMA of a 32-channel block) + 16 KB of weights = 32 KB per 2048 cycles = 16 B/clk/CU,
+//       against the ~30-39 B/clk the L1 -> LDS path moved in profiles/r04_h256_pmc.md; 4 DMA instructions per wave;
+//     LDS reads per chunk and wave: 16 x b32 + 8 x b128 = 6 KB for 32 MFMAs; the CU's LDS array: 8 waves x (8 x 8 +
+//       8 x 4) cycles + 32 KB of DMA writes = ~1000 of the chunk's 2048 cycles.
+//   Measured (profiles/r06_wino_after.md): 0.46-0.50 of the fp32 MFMA peak on the 128^2 convs, against 0.42 before; the
+//   MFMA pipe is still idle half the time with the LDS array and the texture path each under 40 % busy, so the
+//   remaining stall is not the staging bandwidth (a fifth ring slot, i.e. one more chunk in flight, changed nothing).
 //   Against the direct kernel (conv_mfma.hip, 9 x 128 / 32 = 36 chunks of 64 32x32x2 MFMAs per 128 x 128 tile): the
 //   same output takes 16 / 36 of the MFMA cycles.
 //
 //   Epilogue: Y = A^T M A per (tile, channel), bias + activation, scalar stores (16 lanes = 64 contiguous bytes) with the
 //   generic addressing: out_coff / out_cstride / out_bstride.  gn_partials: on the geometries where a block covers
-//   exactly two whole 128-pixel flattened tiles (host check wino_gn_ok), slot nt (the block's 32-channel group) of each
-//   of them gets that block's (sum, sum of squares) in fp64; the 4 groups of n_pad = 128 fill all 4 slots.
-//   All addressing is 64-bit (no buffer resources): no 2 GiB limit.  Several problems (pyramid levels) per launch; no
-//   host reads, no allocation: capturable in a hipGraph.  Fixed-capacity RoI batches (`live`): blocks that hold only
-//   non-existing images return at once, so a mask-head conv runs on the same kernel (same bits) with or without `live`.
+//   exactly two whole 128-pixel flattened tiles (host check wino_gn_ok), slots 2 nt2 + h (the block's two 32-channel
+//   groups) of each of them get that group's (sum, sum of squares) in fp64, its 4 waves added in tile-group order; the
+//   2 blocks of n_pad = 128 fill all 4 slots.  Output addressing is 64-bit.  Several problems (pyramid levels) per
+//   launch; no host reads, no allocation: capturable in a hipGraph.  Fixed-capacity RoI batches (`live`): blocks that hold
+//   only non-existing images return at once, so a mask-head conv runs on the same kernel (same bits) with or without
+//   `live`.
 #include "common.h"
 
 namespace {
 
 constexpr int WMAXP = ML_CONV_MAX_PROBLEMS;
 constexpr int WT = 64;        // Winograd tiles per block
-constexpr int WN = 32;        // output channels per block
-constexpr int WK = 8;         // input channels per chunk
-constexpr int PT_LD = 132;    // floats per tile in the patch buffer (16 px x 8 ch + 4 pad)
-constexpr int WB_LD = 516;    // floats per k row in the weight buffer (32 n x 16 p + 4 pad)
-constexpr int WCHUNK = WK * WN * 16;   // floats of transformed weights per (N block, chunk)
+constexpr int WN = 64;        // output channels per block
+constexpr int WK = 8;         // input channels per 8-channel block of the host weight layout (two K chunks)
+constexpr int WCHUNK = WK * 32 * 16;   // floats of transformed weights per (32-channel block, 8-channel block) of the host layout
+constexpr int WSTEP = 4 * 32 * 16;     // floats of transformed weights per (32-channel block, 4-channel chunk)
+constexpr int NSLOT = 4;               // LDS ring slots, one 4-channel chunk each
+constexpr int SLOT_P = WT * 16 * 4;    // floats of patches per ring slot
+constexpr int SLOT = SLOT_P + 2 * WSTEP;   // floats per ring slot (32 KB)
+constexpr int LDS_BYTES = NSLOT * SLOT * 4 + 8 * 4 * 8;   // the ring + the gn_partials exchange (8 waves x 4 doubles)
+constexpr unsigned OOB = 0x80000000u;  // buffer offset of an out-of-image tap: >= the patch resource's num_records
+constexpr long long SPAN_MAX = 0x7fffff00ll;   // bytes a block's patch offsets may reach (< OOB)
 
 struct WProblem {
     ml_conv2d_desc d;
     int TH, TW, T;            // tile rows / columns per image, tiles in all (B * TH * TW)
-    int MB, NB, nchunks;      // 64-tile blocks, 32-channel blocks, 8-channel chunks
+    int MB, NB, nchunks;      // 64-tile blocks, 64-channel blocks, 8-channel blocks (2 K chunks each)
 };
 
 struct WArgs {
@@ -60,6 +86,15 @@ struct WArgs {
     int start[WMAXP + 1];     // prefix sum of blocks per problem
     WProblem p[WMAXP];
 };
+
+// buffer_load_dwordx4 ... lds: 16 bytes per lane from (resource + voff) straight into LDS at dst + lane * 16 (dst is
+// wave-uniform and travels in M0); out-of-range lanes write zeros.  Counted in vmcnt.  (No immediate offset: the
+// instruction adds it to the LDS address as well.)
+__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, float *dst, int voff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, 0, 0, 0);
+#endif
+}
 
 __device__ __forceinline__ void bt_d_b(const float d[16], float v[16]) {
     // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]; d, v row-major 4x4
@@ -80,10 +115,8 @@ __device__ __forceinline__ void bt_d_b(const float d[16], float v[16]) {
     }
 }
 
-__global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
-    __shared__ __attribute__((aligned(16))) float lds_p[WT * PT_LD];
-    __shared__ __attribute__((aligned(16))) float lds_w[WK * WB_LD];
-    __shared__ double lds_gn[4][4];
+__global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
+    extern __shared__ __align__(16) float lds[];       // ONE LDS object: [slot 2][SLOT] ring, then the gn exchange
 
     int pi = 0;
     while (pi + 1 < args.n && (int)blockIdx.x >= args.start[pi + 1]) ++pi;
@@ -92,7 +125,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
     // blocks that share one 64-tile panel get ids congruent mod 8 (the same XCD / L2)
     const int b = (int)blockIdx.x - args.start[pi];
     const int g = b / (8 * P.NB), rr = b - g * 8 * P.NB;
-    const int nt = rr >> 3;
+    const int nt2 = rr >> 3;
     const int mt = g * 8 + (rr & 7);
     if (mt >= P.MB) return;
     if (p.live) {
@@ -105,38 +138,62 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
         if (!any) return;
     }
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tg = wave & 3, h = wave >> 2;            // compute role: tile group x channel half
     const int r = lane & 15, kq = lane >> 4;
     const int tpi = P.TH * P.TW;
 
-    // this thread's 8 staged patch slots: pixel index (b*H + y)*W + x, or -1 outside the image / past the last tile
-    int pix[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const int idx = tid + 256 * i;
-        const int tile = idx >> 5, px = (idx >> 1) & 15;
-        const int gt = mt * WT + tile;
-        pix[i] = -1;
-        if (gt < P.T) {
-            const int bi = gt / tpi, rem = gt - bi * tpi;
-            const int ty = rem / P.TW, tx = rem - ty * P.TW;
-            const int y = 2 * ty - 1 + (px >> 2), x = 2 * tx - 1 + (px & 3);
-            if (y >= 0 && y < p.H && x >= 0 && x < p.W) pix[i] = (bi * p.H + y) * p.W + x;
-        }
+    // ---- staging geometry (constant over the K loop).  Patch pieces of this wave: tile group wave >> 1, px blocks
+    // 2 (wave & 1) + i; lane (j = lane >> 4, r): tile 16 (wave >> 1) + r, px = 8 (wave & 1) + 4 i + j.
+    const int gt0 = mt * WT;
+    long long base_pix;                                // the block's first tap row, flattened (b * H + y) * W
+    {
+        const int bi = gt0 / tpi, rem = gt0 - bi * tpi, ty = rem / P.TW;
+        base_pix = ((long long)bi * p.H + max(2 * ty - 1, 0)) * p.W;
     }
     const size_t cstride = (size_t)p.in_cstride;
-    const float *in = p.in + p.in_coff + ((tid & 1) << 2);
-    const float *wsrc = p.wgt + (size_t)nt * P.nchunks * WCHUNK + tid * 4;
-
-    f32x4 rp[8], rw[4];
-    auto load_chunk = [&](int c) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            rp[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (pix[i] >= 0) rp[i] = *reinterpret_cast<const f32x4 *>(in + (size_t)pix[i] * cstride + c * WK);
+    const float *pin = p.in + p.in_coff + (size_t)base_pix * cstride;
+    int voff_p[2];
+    {
+        const int gt = gt0 + (wave >> 1) * 16 + r;
+        int bi = 0, ty = 0, tx = 0;
+        if (gt < P.T) {
+            bi = gt / tpi;
+            const int rem = gt - bi * tpi;
+            ty = rem / P.TW;
+            tx = rem - ty * P.TW;
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rw[i] = *reinterpret_cast<const f32x4 *>(wsrc + (size_t)c * WCHUNK + i * 1024);
+        for (int i = 0; i < 2; ++i) {
+            const int px = 8 * (wave & 1) + 4 * i + kq;
+            const int y = 2 * ty - 1 + (px >> 2), x = 2 * tx - 1 + (px & 3);
+            voff_p[i] = (int)OOB;
+            if (gt < P.T && y >= 0 && y < p.H && x >= 0 && x < p.W)
+                voff_p[i] = (int)((((long long)bi * p.H + y) * p.W + x - base_pix) * (long long)cstride * 4);
+        }
+    }
+    // weight pieces of this wave: channel half wave >> 2, k row wave & 3, t = i (+1024 B); lane (pq = lane >> 4, r)
+    // takes host float4 (16 t + r) * 4 + pq of that k row.  A chunk of 4 channels is half an 8-channel block of the host
+    // layout, so chunk c of a 32-channel block starts c * WSTEP floats in.
+    const int voff_w = ((wave & 3) * 512 + r * 16 + kq * 4) * 4;
+    const float *wsrc = p.wgt + (size_t)(2 * nt2 + (wave >> 2)) * P.nchunks * WCHUNK;
+    float *dst_p = lds + (wave >> 1) * 1024 + (wave & 1) * 512;
+    float *dst_w = lds + SLOT_P + (wave >> 2) * WSTEP + (wave & 3) * 512;
+    const int nsteps = 2 * P.nchunks;
+
+    // DMA of chunk c (4 channels) into ring slot c % 4; past the last chunk through empty resources (nothing is read)
+    auto stage = [&](int c) __attribute__((always_inline)) {
+        const bool real = c < nsteps;
+        const __amdgpu_buffer_rsrc_t rp =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(pin + c * 4), 0, real ? (int)OOB : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rw =
+            __builtin_amdgcn_make_buffer_rsrc((void *)(wsrc + (size_t)c * WSTEP), 0, real ? WSTEP * 4 : 0, 0x00020000);
+        const int so = (c & 3) * SLOT;
+        dma16(rp, dst_p + so, voff_p[0]);
+        dma16(rp, dst_p + so + 256, voff_p[1]);
+        dma16(rw, dst_w + so, voff_w);
+        dma16(rw, dst_w + so + 256, voff_w + 1024);
     };
 
     f32x4 acc[2][16];
@@ -145,49 +202,72 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    load_chunk(0);
-    for (int c = 0; c < P.nchunks; ++c) {
-        __syncthreads();                          // the previous chunk's LDS reads are done
+    const float *pa_lane = lds + tg * 1024 + r * 4 + kq;                    // + px * 64
+    const float *pb_lane = lds + SLOT_P + h * WSTEP + kq * 512 + r * 4;     // + t * 256 + pq * 64
+    // the LDS operands of one K step (= one chunk): the lane's 16 patch values and its 8 B fragments
+    struct Ops {
+        float d[16];
+        f32x4 b[2][4];
+    };
+    auto read_ops = [&](int c, Ops &o) __attribute__((always_inline)) {
+        const float *pb = pb_lane + (c & 3) * SLOT;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int idx = tid + 256 * i;
-            *reinterpret_cast<f32x4 *>(lds_p + (idx >> 5) * PT_LD + (idx & 31) * 4) = rp[i];
-        }
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int idx = tid + 256 * i;        // float4 index in the 16 KB chunk: k row = idx >> 7
-            *reinterpret_cast<f32x4 *>(lds_w + (idx >> 7) * WB_LD + (idx & 127) * 4) = rw[i];
-        }
-        __syncthreads();
-        if (c + 1 < P.nchunks) load_chunk(c + 1);  // in flight under this chunk's MFMAs
+            for (int pq = 0; pq < 4; ++pq) o.b[t][pq] = *reinterpret_cast<const f32x4 *>(pb + t * 256 + pq * 64);
+        const float *pa = pa_lane + (c & 3) * SLOT;
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int ch = 4 * s + kq;
-            const float *pa = lds_p + (wave * 16 + r) * PT_LD + ch;
-            float d[16], v[16];
+        for (int px = 0; px < 16; ++px) o.d[px] = pa[px * 64];
+    };
+    // chunk c's MFMAs (operands read during the previous step); the reads of chunk c + 1 go out after the first 4 of them
+    // and are pinned there.  Issued before the first MFMA they would be waited for by it: hipcc does not see the
+    // lgkmcnt(0) in front of the barrier and waits for its count of the previous step's reads, which the new ones join.
+    // Sunk to their first use (what the scheduler does by itself) they would expose their latency every step.
+    auto step = [&](int c, const Ops &cur, Ops &nxt) __attribute__((always_inline)) {
+        // chunk c + 1 has landed (this wave's DMA: vmcnt leaves chunk c + 2's 4 in flight; every wave's: the barrier), and
+        // every wave's reads of chunk c - 1 are done (lgkmcnt(0) before the barrier), so chunk c + 3 may go into its slot.
+        // A raw s_barrier: __syncthreads()'s fence would wait vmcnt(0) for the chunk still in flight.
+        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        stage(c + 3);
+        float v[16];
+        bt_d_b(cur.d, v);
 #pragma unroll
-            for (int px = 0; px < 16; ++px) d[px] = pa[px * WK];
-            bt_d_b(d, v);
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const float *pb = lds_w + ch * WB_LD + (16 * t + r) * 16;
+            for (int pq = 0; pq < 4; ++pq) {
 #pragma unroll
-                for (int pq = 0; pq < 4; ++pq) {
-                    const f32x4 bq = *reinterpret_cast<const f32x4 *>(pb + 4 * pq);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        acc[t][4 * pq + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(v[4 * pq + e], bq[e], acc[t][4 * pq + e], 0, 0, 0);
+                for (int e = 0; e < 4; ++e)
+                    acc[t][4 * pq + e] =
+                        __builtin_amdgcn_mfma_f32_16x16x4f32(v[4 * pq + e], cur.b[t][pq][e], acc[t][4 * pq + e], 0, 0, 0);
+                if (t == 0 && pq == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    read_ops(c + 1, nxt);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             }
-        }
-    }
+        __builtin_amdgcn_sched_barrier(0);
+    };
 
-    // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1]; lane holds tiles wave*16 + kq*4 + i, channel 16t + r
+    Ops oa, ob;
+    stage(0);
+    stage(1);
+    stage(2);
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    read_ops(0, oa);
+    for (int c = 0; c < nsteps; c += 2) {              // nsteps is even (span % 32 == 0): the two operand sets alternate
+        step(c, oa, ob);
+        step(c + 1, ob, oa);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the empty DMAs past the last chunk
+
+    // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1]; lane holds tiles tg*16 + kq*4 + i, channel 16t + r
+    const int nt = 2 * nt2 + h;                        // this wave's 32-channel group
     const bool gn = p.gn_partials != nullptr;      // (block-uniform; host: wino_gn_ok)
     double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
     long long f0 = 0;
     if (gn) {
-        const int gt0 = mt * WT;
         const int bi = gt0 / tpi, rem = gt0 - bi * tpi, ty = rem / P.TW, tx = rem - ty * P.TW;
         f0 = ((long long)(bi * p.Ho + 2 * ty) * p.Wo + 2 * tx) >> 7;
     }
@@ -195,7 +275,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
     const bool clampv = p.act == ML_ACT_RELU || p.act == ML_ACT_RELU6;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int gt = mt * WT + wave * 16 + kq * 4 + i;
+        const int gt = gt0 + tg * 16 + kq * 4 + i;
         if (gt >= P.T) continue;
         const int bi = gt / tpi, rem = gt - bi * tpi;
         const int ty = rem / P.TW, tx = rem - ty * P.TW;
@@ -205,7 +285,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
         const size_t pix0 = (size_t)oy * p.Wo + ox;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const int n = nt * WN + 16 * t + r;
+            const int n = nt * 32 + 16 * t + r;
             if (n >= p.cout) continue;
             float m[16];
 #pragma unroll
@@ -243,6 +323,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
         }
     }
     if (gn) {
+        double *lds_gn = reinterpret_cast<double *>(lds + NSLOT * SLOT);   // [wave 8][4]
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll
@@ -252,20 +333,23 @@ __global__ void __launch_bounds__(256, 2) conv_wino_kernel(const WArgs args) {
             }
         }
         if (lane == 0) {
-            lds_gn[wave][0] = gs[0]; lds_gn[wave][1] = gq[0];
-            lds_gn[wave][2] = gs[1]; lds_gn[wave][3] = gq[1];
+            lds_gn[wave * 4 + 0] = gs[0]; lds_gn[wave * 4 + 1] = gq[0];
+            lds_gn[wave * 4 + 2] = gs[1]; lds_gn[wave * 4 + 3] = gq[1];
         }
         __syncthreads();
-        if (tid < 2) {
-            // the block's second flattened tile: the one holding its last tile's bottom-right pixel
-            const int gt1 = mt * WT + WT - 1;
+        if (tid < 4) {
+            // thread (half hh, flattened tile ff); the block's second flattened tile: the one holding its last tile's
+            // bottom-right pixel
+            const int hh = tid >> 1, ff = tid & 1;
+            const int gt1 = gt0 + WT - 1;
             const int bi = gt1 / tpi, rem = gt1 - bi * tpi, ty = rem / P.TW, tx = rem - ty * P.TW;
             const long long f1 = ((long long)(bi * p.Ho + 2 * ty + 1) * p.Wo + 2 * tx + 1) >> 7;
-            const long long ft = tid ? f1 : f0;
+            const long long ft = ff ? f1 : f0;
+            const int slot = 2 * nt2 + hh;
             double s = 0.0, q = 0.0;
-            for (int w = 0; w < 4; ++w) { s += lds_gn[w][2 * tid]; q += lds_gn[w][2 * tid + 1]; }
-            p.gn_partials[2 * (ft * 4 + nt)] = s;
-            p.gn_partials[2 * (ft * 4 + nt) + 1] = q;
+            for (int w = 0; w < 4; ++w) { s += lds_gn[(hh * 4 + w) * 4 + 2 * ff]; q += lds_gn[(hh * 4 + w) * 4 + 2 * ff + 1]; }
+            p.gn_partials[2 * (ft * 4 + slot)] = s;
+            p.gn_partials[2 * (ft * 4 + slot) + 1] = q;
         }
     }
 }
@@ -315,6 +399,10 @@ int ml_conv2d_wino_launch(const ml_conv2d_desc *descs, int n, hipStream_t s) {
         P.MB = (int)((T + WT - 1) / WT);
         P.NB = d.n_pad / WN;
         P.nchunks = d.span_pad / WK;
+        // a block's patch offsets are 32-bit from its first tap row: its 64 tiles cover at most 64 / TW + 2 flattened tile
+        // rows, i.e. 2 (64 / TW + 2) + 2 pixel rows with the taps above and below
+        const long long span = (2ll * (WT / P.TW + 2) + 2) * d.W * d.in_cstride * 4;
+        ML_REQUIRE(span <= SPAN_MAX, "conv2d (winograd): a block's input rows exceed 2 GiB (W x in_cstride too large)");
         args.start[i] = (int)start;
         start += (long long)(P.MB + 7) / 8 * 8 * P.NB;
         ML_REQUIRE(start < (1ll << 31), "conv2d (winograd): grid too large");
@@ -330,7 +418,10 @@ int ml_conv2d_wino_launch(const ml_conv2d_desc *descs, int n, hipStream_t s) {
     }
     ML_REQUIRE(!any_gn || tiles128 >= ml_conv2d_gn_min_launch_tiles(),
                "conv2d (winograd): gn_partials needs a launch of ml_conv2d_gn_min_launch_tiles() tiles of 128 x 128");
-    hipLaunchKernelGGL(conv_wino_kernel, dim3((unsigned)start), dim3(256), 0, s, args);
+    static std::atomic<unsigned long long> lds_ok{0};
+    if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(conv_wino_kernel), LDS_BYTES, lds_ok, "conv2d (winograd)"))
+        return rc;
+    hipLaunchKernelGGL(conv_wino_kernel, dim3((unsigned)start), dim3(512), LDS_BYTES, s, args);
     ML_CHECK_LAUNCH("conv2d (winograd)");
     return ML_OK;
 }
