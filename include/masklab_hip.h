@@ -51,7 +51,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                          7: ml_stem7x7s2_pool_f16 / _f32 / _x3; ml_gconv3x3_f16 takes groups of 32 channels;
                                             ML_MATH_F32X3 on the persistent 1x1 kernel (ml_conv2d_uses_pipe);
                                             ml_mold_levels_dev_f32; (additive, same version) ml_se_desc,
-                                            ml_squeeze_excite_f32 / _f16 / _workspace_bytes, ml_add_f16                */
+                                            ml_squeeze_excite_f32 / _f16 / _workspace_bytes, ml_add_f16;
+                                            (additive, same version) ml_se_residual_desc,
+                                            ml_se_residual_f32 / _workspace_bytes                          */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -374,6 +376,39 @@ typedef struct ml_se_desc {
 int64_t ml_squeeze_excite_workspace_bytes(int32_t B, int32_t HW, int32_t C);
 int ml_squeeze_excite_f32(const ml_se_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
 int ml_squeeze_excite_f16(const ml_se_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* SE-ResNet pre-activation basic block tail (thirdparty resnet.py residual_conv_block :60-109 + ChannelSE,
+ * _common_blocks.py:88-119), fp32 NHWC [B,HW,C], one problem per call:
+ *   ML_SE_RES_GATE     g = sigmoid(W2 relu(W1 mean_hw(x) + b1) + b2)  (ChannelSE's two 1x1 convs, with bias)
+ *                      y = x * g + shortcut                          (Multiply, then Add; no ReLU after the add)
+ *                      out_act = relu(y * scale + shift)             (the next unit's bn1 + relu1, or the final bn1 + relu1)
+ *                      out_y = y                                     (optional: NULL unless the next unit takes y as
+ *                                                                     its identity shortcut)
+ *                      two launches: se_residual_pool per (sample, pool chunk) the channel sums, fp64, stored as a slab
+ *                      in the workspace (a pool chunk is a whole number of tail chunks, at most min(64, 4096 / C) of
+ *                      them per sample); se_residual_tail per (sample, tail chunk of 16384 / C pixels) the sample's
+ *                      slabs added in one fixed order, the two FC layers in fp32, then the chunk streamed once.
+ *   ML_SE_RES_BN_RELU  out_act = relu(x * scale + shift): one launch, no workspace; shortcut / w* / out_y unused
+ *                      (shortcut and out_y must be NULL).
+ * scale / shift [C] are an inference BatchNorm folded on the host (gamma / sqrt(var + eps), beta - mean * scale).
+ * w1 [C][Hd] (the 1x1 kernel [1,1,C,Hd]), b1 [Hd], w2 [Hd][C], b2 [C].  4 <= C <= 512, C % 4 == 0, 1 <= Hd <= 32.
+ * x / shortcut / out_act / out_y / scale / shift 16-byte aligned.  An output may be the very buffer of an input; no
+ * other overlap.  No atomics: the same bits run to run, under graph replay, and for image k of any batch.
+ * GATE needs workspace_bytes >= ml_se_residual_workspace_bytes(B, HW, C), 16-byte aligned; BN_RELU takes NULL.   */
+enum { ML_SE_RES_GATE = 0, ML_SE_RES_BN_RELU = 1 };
+typedef struct ml_se_residual_desc {
+    const float *x;               /* conv2 output (GATE) or the tensor to normalise (BN_RELU) */
+    const float *shortcut;        /* GATE: added after the gate; BN_RELU: NULL */
+    const float *w1, *b1;         /* [C][Hd], [Hd] */
+    const float *w2, *b2;         /* [Hd][C], [C] */
+    const float *scale, *shift;   /* [C] */
+    float *out_act;               /* relu(y * scale + shift) */
+    float *out_y;                 /* y, or NULL */
+    int32_t B, HW, C, Hd;
+    int32_t mode, reserved;
+} ml_se_residual_desc;
+int64_t ml_se_residual_workspace_bytes(int32_t B, int32_t HW, int32_t C);
+int ml_se_residual_f32(const ml_se_residual_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------- detection post-process
  * RestoreBoxes (engine/layers/detection.py:325-344): priors int32 [A,4] (cx,cy,w,h) shared by

@@ -64,6 +64,16 @@ class SeDesc(C.Structure):
                 ("live", C.c_void_p), ("live_period", C.c_int32), ("reserved", C.c_int32), ("ws_offset", C.c_int64)]
 
 
+class SeResidualDesc(C.Structure):
+    """Mirror of `ml_se_residual_desc` (include/masklab_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("shortcut", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p),
+                ("w2", C.c_void_p), ("b2", C.c_void_p), ("scale", C.c_void_p), ("shift", C.c_void_p),
+                ("out_act", C.c_void_p), ("out_y", C.c_void_p),
+                ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("Hd", C.c_int32),
+                ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
 DECONV_OUT_MAX_PROBLEMS = 4
@@ -113,6 +123,8 @@ SIGNATURES = {
     "ml_squeeze_excite_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ml_squeeze_excite_f32": (C.c_int, [C.POINTER(SeDesc), _i32, _vp, _i64, _vp]),
     "ml_squeeze_excite_f16": (C.c_int, [C.POINTER(SeDesc), _i32, _vp, _i64, _vp]),
+    "ml_se_residual_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ml_se_residual_f32": (C.c_int, [C.POINTER(SeResidualDesc), _vp, _i64, _vp]),
     "ml_restore_boxes_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "ml_detection_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ml_detection_proposal_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp]),

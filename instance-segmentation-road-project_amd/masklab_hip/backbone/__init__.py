@@ -3,3 +3,4 @@ from .base import BACKBONE_LAYERS, BackBonePreProcess, BackboneModel, load_backb
 from .mobilenet import MobileNetV1
 from .resnext import ResNeXt50
 from .resnext101 import ResNeXt101
+from .seresnet34 import SEResNet34

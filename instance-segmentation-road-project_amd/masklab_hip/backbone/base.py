@@ -1,8 +1,8 @@
 """Backbone loader + preprocess -- drop-in for reference engine/backbone/base.py
 (BackBonePreProcess :22-84, BACKBONE_LAYERS :104-182, load_backbone :185-316).
 
-Backbones on the hot path: 'resnext50' (in-tree in the reference) and 'mobilenet'
-(tf.keras.applications.MobileNet v1).  Everything else raises NotImplementedError like the
+Backbones on the hot path: 'resnext50' (in-tree in the reference), 'seresnet34' (the reference project's own model,
+vendored thirdparty/classification_models) and 'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises NotImplementedError like the
 reference does for unknown types.  BatchNormalization is folded into the conv weights at load
 time; the 3-channel stems read a channel-padded NHWC4 image written by the preprocess kernel.
 """
@@ -17,6 +17,9 @@ BACKBONE_LAYERS = {
     # build-side extension: architecture from the vendored thirdparty model zoo
     "resnext101": {"C1": "relu0", "C2": "stage1_unit3_relu", "C3": "stage2_unit4_relu",
                    "C4": "stage3_unit23_relu", "C5": "stage4_unit3_relu"},
+    # the reference project's own backbone (road_project/train.py:36-37; taps reference :126-132)
+    "seresnet34": {"C1": "relu0", "C2": "stage2_unit1_relu1", "C3": "stage3_unit1_relu1", "C4": "stage4_unit1_relu1",
+                   "C5": "relu1"},
     "mobilenet": {"C1": "conv_pw_1_relu", "C2": "conv_pw_3_relu", "C3": "conv_pw_5_relu",
                   "C4": "conv_pw_11_relu", "C5": "conv_pw_13_relu"},
 }
@@ -73,6 +76,7 @@ class BackboneModel(Layer):
         from .mobilenet import MobileNetV1
         from .resnext import ResNeXt50
         from .resnext101 import ResNeXt101
+        from .seresnet34 import SEResNet34
         bt = backbone_type.lower()
         self.backbone_type = bt
         self.backbone_outputs = tuple(backbone_outputs)
@@ -84,6 +88,10 @@ class BackboneModel(Layer):
         elif bt == 'resnext101':
             self.preprocess = BackBonePreProcess(rgb=True, mean_shift=False, normalize=0)
             self.body = ResNeXt101()
+            same = True
+        elif bt == 'seresnet34':
+            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=False, normalize=0)     # :232-234, then bn_data
+            self.body = SEResNet34()
             same = True
         elif bt == 'mobilenet':
             self.preprocess = BackBonePreProcess(rgb=False, mean_shift=False, normalize=2)    # :254-256

@@ -108,6 +108,41 @@ def _our_sublayers(specs):
     return {sc: {cls: [p for _, p in sorted(lst)] for cls, lst in d.items()} for sc, d in out.items()}
 
 
+# SE-ResNet-34's ChannelSE (thirdparty _common_blocks.py:88-119) leaves its two 1x1 convs unnamed as well: outside every
+# head scope they are `conv2d_N`, two per unit in unit order, and the backbone is built first (after K.clear_session()),
+# so they precede every head conv of the session.  This package names them `stage{s}_unit{u}_se/conv{1,2}`.
+_BACKBONE_SE_RE = re.compile(r"^stage(\d+)_unit(\d+)_se/conv([12])/")
+
+
+def _backbone_channel_se(weights, specs, table):
+    """(key, None, 'conv2d', model prefix, remainder parts) rows for the backbone's auto-named ChannelSE convs, paired
+    with the model's `stage*_unit*_se/conv*` sub-layers by creation order; [] when the model declares none."""
+    ours = sorted({(int(m.group(1)), int(m.group(2)), int(m.group(3))) for m in map(_BACKBONE_SE_RE.match, specs) if m})
+    if not ours:
+        return []
+    found = {}                                      # N -> [(key, file prefix, remainder parts)]
+    for key in weights:
+        parts = key.split("/")
+        for pos, comp in enumerate(parts[:-1]):
+            if re.sub(r"_\d+$", "", comp) in _SCOPES:
+                break
+            m = _AUTO_RE.match(comp)
+            if m and m.group(1) == "conv2d":
+                found.setdefault(int(m.group(2) or 0), []).append((key, "/".join(parts[:pos + 1]), parts[pos + 1:]))
+                break
+    if len(found) != len(ours):
+        raise ValueError(f"checkpoint has {len(found)} auto-named 'conv2d' layers outside the heads, the model's "
+                         f"backbone declares {len(ours)} ChannelSE convs: a different backbone?")
+    rows = []
+    for (s, u, i), n in zip(ours, sorted(found)):
+        target = f"stage{s}_unit{u}_se/conv{i}"
+        for key, src, rest in found[n]:
+            rows.append((key, None, "conv2d", target, rest))
+        if table is not None:
+            table.append(("backbone", "conv2d", n, found[n][0][1], target))
+    return rows
+
+
 def rename_keras_auto_names(weights, specs, table=None):
     """Rewrite the keys of a reference-named weight dict (`<...>/<scope>[_k]/<auto name>/.../<weight>`) to this
     package's names.  Keys that are not under an auto-named sub-layer are returned unchanged.  Raises ValueError
@@ -128,6 +163,7 @@ def rename_keras_auto_names(weights, specs, table=None):
                     found.setdefault((sc, m.group(1)), {})[n] = "/".join(parts[:pos + 2])
                     located.append((key, sc, m.group(1), n, parts[pos + 2:]))
                 break
+    located += _backbone_channel_se(weights, specs, table)
     rank = {}
     for (sc, cls), by_n in found.items():
         want = ours.get(sc, {}).get(cls, [])
@@ -142,7 +178,7 @@ def rename_keras_auto_names(weights, specs, table=None):
     out = dict(weights)
     dense_seen = {}
     for key, sc, cls, n, rest in located:
-        target = rank[(sc, cls, n)]
+        target = rank[(sc, cls, n)] if sc is not None else n
         if cls == "squeeze_excite":
             # .../squeeze_excite_k/dense_m/kernel: the two Dense layers are created in build() in order (misc.py:34-40)
             md = _AUTO_RE.match(rest[0])

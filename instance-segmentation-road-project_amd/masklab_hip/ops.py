@@ -806,6 +806,63 @@ def squeeze_excite_multi(problems):
     return outs
 
 
+def _se_res_check(t, name, like=None):
+    _require_dev(t, name)
+    if t.dtype != torch.float32:
+        raise ValueError(f"se_residual: `{name}` must be float32")
+    if like is not None and tuple(t.shape) != tuple(like):
+        raise ValueError(f"se_residual: `{name}` has shape {tuple(t.shape)}, expected {tuple(like)}")
+
+
+def se_residual(x, shortcut, w1, b1, w2, b2, scale, shift, want_y=False):
+    """ml_se_residual_f32 (GATE): the tail of an SE-ResNet pre-activation basic block in one launch pair --
+    g = sigmoid(w2^T relu(w1^T mean_hw(x) + b1) + b2), y = x * g + shortcut, act = relu(y * scale + shift).
+    x / shortcut: fp32 NHWC [B,H,W,C]; w1 [C, Hd], b1 [Hd], w2 [Hd, C], b2 [C], scale / shift [C] (device fp32).
+    -> (act, y if want_y else None).  Scratch from ops.workspace (graph-safe: grow-only, keyed by stream)."""
+    lib = _lib.load()
+    _se_res_check(x, "x")
+    shape = tuple(x.shape)
+    B, Cc = int(shape[0]), int(shape[-1])
+    HW = x.numel() // max(1, B * Cc)
+    _se_res_check(shortcut, "shortcut", shape)
+    if w1.dim() != 2 or w1.shape[0] != Cc:
+        raise ValueError("se_residual: w1 must be [C, Hd]")
+    Hd = int(w1.shape[1])
+    for t, name, want in ((w1, "w1", (Cc, Hd)), (b1, "b1", (Hd,)), (w2, "w2", (Hd, Cc)), (b2, "b2", (Cc,)),
+                          (scale, "scale", (Cc,)), (shift, "shift", (Cc,))):
+        _se_res_check(t, name, want)
+    act = torch.empty_like(x)
+    y = torch.empty_like(x) if want_y else None
+    d = _lib.SeResidualDesc()
+    d.x, d.shortcut, d.w1, d.b1, d.w2, d.b2 = (x.data_ptr(), shortcut.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                                               w2.data_ptr(), b2.data_ptr())
+    d.scale, d.shift, d.out_act = scale.data_ptr(), shift.data_ptr(), act.data_ptr()
+    d.out_y = y.data_ptr() if y is not None else None
+    d.B, d.HW, d.C, d.Hd, d.mode = B, HW, Cc, Hd, _lib.SE_RES_GATE
+    ws = workspace(max(16, int(lib.ml_se_residual_workspace_bytes(B, HW, Cc))), x.device, "se_residual")
+    nbytes = 4.0 * x.numel() * (4 + int(want_y))            # x read twice (pool, tail), shortcut once, act (+ y) written
+    with _Prof("se_residual", 0, nbytes, f"B={B} HW={HW} C={Cc} Hd={Hd}{' +y' if want_y else ''}"):
+        _lib.check(lib.ml_se_residual_f32(C.byref(d), _ptr(ws), ws.numel(), _stream()), "ml_se_residual_f32")
+    return act, y
+
+
+def bn_relu(x, scale, shift):
+    """ml_se_residual_f32 (BN_RELU): relu(x * scale + shift) per channel, fp32 NHWC (a folded inference BatchNorm)."""
+    lib = _lib.load()
+    _se_res_check(x, "x")
+    Cc = int(x.shape[-1])
+    B = int(x.shape[0])
+    _se_res_check(scale, "scale", (Cc,))
+    _se_res_check(shift, "shift", (Cc,))
+    out = torch.empty_like(x)
+    d = _lib.SeResidualDesc()
+    d.x, d.scale, d.shift, d.out_act = x.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.data_ptr()
+    d.B, d.HW, d.C, d.mode = B, x.numel() // max(1, B * Cc), Cc, _lib.SE_RES_BN_RELU
+    with _Prof("bn_relu", 0, 8.0 * x.numel(), f"B={B} C={Cc}"):
+        _lib.check(lib.ml_se_residual_f32(C.byref(d), None, 0, _stream()), "ml_se_residual_f32")
+    return out
+
+
 def restore_boxes(loc_pred, priors_i32):
     lib = _lib.load()
     _require_dev(loc_pred, "loc_pred")
