@@ -53,7 +53,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             ml_mold_levels_dev_f32; (additive, same version) ml_se_desc,
                                             ml_squeeze_excite_f32 / _f16 / _workspace_bytes, ml_add_f16;
                                             (additive, same version) ml_se_residual_desc,
-                                            ml_se_residual_f32 / _workspace_bytes                          */
+                                            ml_se_residual_f32 / _workspace_bytes;
+                                            (additive, same version) ml_draw_boxes_u8, ml_draw_instance_u8,
+                                            ml_draw_segmentation_u8, ml_serving_visualize_u8              */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -565,6 +567,39 @@ int ml_instance_summary_rois_f32(const int32_t *seg, int32_t seg_channels, int32
                                  const int32_t *roi_masks, float *out5, int32_t B, int32_t n, int32_t mh, int32_t mw,
                                  int32_t H, int32_t W, float default_road_size, float ioi_threshold, void *workspace,
                                  void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Serving 'visualize' output (road_project/setup/serving.py:30-40; engine/layers/misc.py:404-503).
+ * Frames are uint8 [B,H,W,3]; det int32 [B,n,6] = (cx, cy, w, h, class, conf) as UpSampleOutput writes it.
+ * blend(v, S, alpha) = uint8(trunc(clip(v + S * alpha, 0, 255))) in fp32 without fused multiply-add, S = sum over k in
+ * order of colors[k] * map_k.  Colour tables are HOST arrays [K][3] of fp32, 1 <= K <= ML_DRAW_MAX_CLASSES.
+ * `out` may be the input frame buffer itself; no other overlap is allowed.
+ * ------------------------------------------------------------------------------------------- */
+#define ML_DRAW_MAX_CLASSES 16
+
+/* DrawBoxes.call (misc.py:478-503): out = images with every row's box drawn as a white 1-pixel outline by the rule
+ * of tf.image.draw_bounding_boxes: box = max(det[:4], 0), normalised corners (c -+ size/2) / (W | H), line rows /
+ * columns trunc(corner * (H-1 | W-1)) in 64 bits; boxes that are inverted or wholly outside are skipped, lines
+ * outside the frame are not drawn.  Every row is drawn whatever its class or confidence.                   */
+int ml_draw_boxes_u8(const uint8_t *images, const int32_t *det, uint8_t *out, int32_t B, int32_t n, int32_t H, int32_t W,
+                     void *stream);
+/* DrawInstance.call (misc.py:434-475): masks = CropAndPadMask's fp32 [B,n,H,W]; per class k < K the masks of the rows
+ * with det class == k summed in row order from 0.0f, > 0.5 -> 1; then DrawSegmentation's blend.  Rows of any other
+ * class (padding: -1) are never drawn.                                                                      */
+int ml_draw_instance_u8(const uint8_t *images, const int32_t *det, const float *masks, uint8_t *out, const float *colors,
+                        int32_t K, float alpha, int32_t B, int32_t n, int32_t H, int32_t W, void *stream);
+/* DrawSegmentation.call (misc.py:404-431): maps [B,H,W,K], int32 (maps_are_f32 = 0) or fp32.                  */
+int ml_draw_segmentation_u8(const uint8_t *images, const void *maps, int32_t maps_are_f32, uint8_t *out,
+                            const float *colors, int32_t K, float alpha, int32_t B, int32_t H, int32_t W, void *stream);
+/* The whole 'visualize' output in one pass: DrawBoxes -> DrawInstance(instance colours) over CropAndPadMask of
+ * (det, ins [B,n,mh,mw] int32) -> DrawSegmentation(semantic colours) of seg [B,H,W,Ks] int32.  The pasted values are
+ * recomputed inside their boxes with CropAndPadMask's arithmetic (threshold: 50 if the batch's max conf > 50, else
+ * -100, computed on the device into threshold_ws, one int32), so the bytes equal the three layers over
+ * ml_crop_pad_mask_f32's canvases without building them.  No host synchronisation: graph-capturable.        */
+int ml_serving_visualize_u8(const uint8_t *images, const int32_t *det, const int32_t *ins, const int32_t *seg, uint8_t *out,
+                            int32_t *threshold_ws, const float *instance_colors, int32_t Ki, float instance_alpha,
+                            const float *semantic_colors, int32_t Ks, float semantic_alpha, int32_t B, int32_t n,
+                            int32_t mh, int32_t mw, int32_t H, int32_t W, void *stream);
 
 #ifdef __cplusplus
 }

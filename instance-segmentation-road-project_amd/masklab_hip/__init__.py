@@ -19,7 +19,7 @@ def get_custom_objects():
              "MaskDistribute", "PyramidRoiAlign", "ResizeLike", "AtrousSeparableConv2D", "ASPPNetwork",
              "SegmentationSubNet", "SqueezeExcite", "MobileSeparableConv2D", "DownSampleInput", "UpSampleOutput",
              "TrimInstances", "SemanticSmoothing", "CropAndPadMask", "CrackToInstance", "SummaryOutput",
-             "IncludeMyRoad", "CalculateInstanceSize"]
+             "IncludeMyRoad", "CalculateInstanceSize", "DrawSegmentation", "DrawInstance", "DrawBoxes"]
     reg = {n: getattr(L, n) for n in names}
     reg["BackBonePreProcess"] = BackBonePreProcess
     reg["GroupNormalization"] = GroupNormalization

@@ -2,7 +2,8 @@
 (Identity :206-210, ResizeLike :296-319, SqueezeExcite :24-54, MoldBatch :213-293) and of the
 deploy wrapper either side of it (DownSampleInput :143-154, UpSampleOutput :169-196) and the arithmetic
 layers of the serving graph (CropAndPadMask :358-401, CrackToInstance :524-560, SummaryOutput :563-598,
-IncludeMyRoad :601-626, CalculateInstanceSize :629-727)."""
+IncludeMyRoad :601-626, CalculateInstanceSize :629-727) and of its 'visualize' output (DrawSegmentation :404-431,
+DrawInstance :434-475, DrawBoxes :478-503)."""
 import numpy as np
 import torch
 
@@ -376,3 +377,52 @@ class SummaryOutput(Layer):
         config = super().get_config()
         config.update({'default_road_size': self.default_road_size})
         return config
+
+
+# ----------------------------------------------------------------------------- serving 'visualize' output
+class DrawSegmentation(Layer):
+    """Blend a class map into the frame (reference misc.py:404-431): inputs = [images uint8 [B,H,W,3], maps int32 /
+    float32 [B,H,W,K]] -> uint8(trunc(clip(images + (sum_k colors[k] * maps[..., k]) * alpha, 0, 255)))."""
+
+    def __init__(self, colors, alpha=.3, **kwargs):
+        self.colors = colors
+        self.alpha = alpha
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        images, maps = inputs[0], inputs[1]
+        return ops.draw_segmentation(images.contiguous(), maps.contiguous(), self.colors, self.alpha)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"colors": self.colors, "alpha": self.alpha})
+        return config
+
+
+class DrawInstance(Layer):
+    """Blend the instances into the frame by class (reference misc.py:434-475): inputs = [images uint8 [B,H,W,3],
+    det_outs int32 [B,n,6], CropAndPadMask's float32 [B,n,H,W]]; per class k the canvases of its rows summed, > 0.5,
+    then DrawSegmentation(colors, alpha).  Rows of a class without a colour (padding: -1) are never drawn."""
+
+    def __init__(self, colors, alpha=.3, **kwargs):
+        self.colors = colors
+        self.alpha = alpha
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        images, det_outs, masks = inputs[0], inputs[1], inputs[2]
+        return ops.draw_instance(images.contiguous(), det_outs.contiguous(), masks.contiguous(), self.colors, self.alpha)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"colors": self.colors, "alpha": self.alpha})
+        return config
+
+
+class DrawBoxes(Layer):
+    """White 1-pixel outlines of every detection row (reference misc.py:478-503, tf.image.draw_bounding_boxes):
+    inputs = [images uint8 [B,H,W,3], det_outs int32 [B,n,6]] -> uint8 [B,H,W,3]."""
+
+    def call(self, inputs, **kwargs):
+        images, det_outs = inputs[0], inputs[1]
+        return ops.draw_boxes(images.contiguous(), det_outs.contiguous())

@@ -1137,3 +1137,99 @@ def instance_summary(seg, masks, road_channel=1, default_road_size=3.25, ioi_thr
                                                float(default_road_size), float(ioi_threshold), _ptr(ws), _stream()),
                    "ml_instance_summary_f32")
     return out
+
+
+# ----------------------------------------------------------------------------- serving 'visualize' output
+def _palette(colors, what):
+    """[K,3] colours -> (ctypes fp32 host array, K), 1 <= K <= ML_DRAW_MAX_CLASSES."""
+    c = np.asarray(colors, dtype=np.float32)
+    if c.ndim != 2 or c.shape[1] != 3 or not 1 <= c.shape[0] <= _lib.DRAW_MAX_CLASSES:
+        raise ValueError(f"{what}: colours must be [K, 3] with 1 <= K <= {_lib.DRAW_MAX_CLASSES}, got {c.shape}")
+    return (C.c_float * c.size)(*c.ravel().tolist()), int(c.shape[0])
+
+
+def _frames(images, what):
+    _require_dev(images, "images")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        raise RuntimeError(f"{what}: uint8 [B,H,W,3] frames expected, got {images.dtype} {tuple(images.shape)}")
+    return tuple(int(v) for v in images.shape[:3])
+
+
+def _detections(det_outs, B, what):
+    _require_dev(det_outs, "det_outs")
+    if det_outs.dtype != torch.int32 or det_outs.dim() != 3 or det_outs.shape[0] != B or det_outs.shape[2] != 6:
+        raise RuntimeError(f"{what}: int32 detections [B={B},n,6] expected, got {det_outs.dtype} {tuple(det_outs.shape)}")
+    return int(det_outs.shape[1])
+
+
+def draw_boxes(images, det_outs, out=None):
+    """ml_draw_boxes_u8 (DrawBoxes): white 1-pixel outlines of every detection row.  `out` may be `images`."""
+    lib = _lib.load()
+    B, H, W = _frames(images, "draw_boxes")
+    n = _detections(det_outs, B, "draw_boxes")
+    out = torch.empty_like(images) if out is None else out
+    with _Prof("draw_boxes", 0, (images.numel() if out.data_ptr() != images.data_ptr() else 0) + out.numel() + 24 * B * n):
+        _lib.check(lib.ml_draw_boxes_u8(_ptr(images), _ptr(det_outs), _ptr(out), B, n, H, W, _stream()), "ml_draw_boxes_u8")
+    return out
+
+
+def draw_instance(images, det_outs, masks, colors, alpha, out=None):
+    """ml_draw_instance_u8 (DrawInstance) over CropAndPadMask's float32 [B,n,H,W] canvases."""
+    lib = _lib.load()
+    B, H, W = _frames(images, "draw_instance")
+    n = _detections(det_outs, B, "draw_instance")
+    _require_dev(masks, "masks")
+    if masks.dtype != torch.float32 or tuple(masks.shape) != (B, n, H, W):
+        raise RuntimeError(f"draw_instance: float32 masks [{B},{n},{H},{W}] expected, got {masks.dtype} {tuple(masks.shape)}")
+    cols, K = _palette(colors, "draw_instance")
+    out = torch.empty_like(images) if out is None else out
+    with _Prof("draw_instance", 0, 2 * images.numel() + 4 * masks.numel() + 24 * B * n):
+        _lib.check(lib.ml_draw_instance_u8(_ptr(images), _ptr(det_outs), _ptr(masks), _ptr(out), cols, K, float(alpha), B, n,
+                                           H, W, _stream()), "ml_draw_instance_u8")
+    return out
+
+
+def draw_segmentation(images, maps, colors, alpha, out=None):
+    """ml_draw_segmentation_u8 (DrawSegmentation): maps int32 or float32 [B,H,W,K]."""
+    lib = _lib.load()
+    B, H, W = _frames(images, "draw_segmentation")
+    _require_dev(maps, "maps")
+    cols, K = _palette(colors, "draw_segmentation")
+    if maps.dtype not in (torch.int32, torch.float32) or tuple(maps.shape) != (B, H, W, K):
+        raise RuntimeError(f"draw_segmentation: int32 / float32 maps [{B},{H},{W},{K}] expected, got "
+                           f"{maps.dtype} {tuple(maps.shape)}")
+    out = torch.empty_like(images) if out is None else out
+    with _Prof("draw_segmentation", 0, 2 * images.numel() + 4 * maps.numel()):
+        _lib.check(lib.ml_draw_segmentation_u8(_ptr(images), _ptr(maps), int(maps.dtype == torch.float32), _ptr(out), cols, K,
+                                               float(alpha), B, H, W, _stream()), "ml_draw_segmentation_u8")
+    return out
+
+
+def serving_visualize(images, det_outs, ins_outs, seg_outs, instance_colors, instance_alpha, semantic_colors,
+                      semantic_alpha, out=None):
+    """ml_serving_visualize_u8: DrawBoxes -> CropAndPadMask + DrawInstance -> DrawSegmentation in one pass, the same bytes
+    as the four layers without the [B,n,H,W] canvases.  images uint8 [B,H,W,3], det_outs int32 [B,n,6], ins_outs int32
+    [B,n,mh,mw], seg_outs int32 [B,H,W,Ks] -> uint8 [B,H,W,3].  No host synchronisation (graph-capturable)."""
+    lib = _lib.load()
+    B, H, W = _frames(images, "serving_visualize")
+    n = _detections(det_outs, B, "serving_visualize")
+    for t, name in ((ins_outs, "ins_outs"), (seg_outs, "seg_outs")):
+        _require_dev(t, name)
+        if t.dtype != torch.int32:
+            raise RuntimeError(f"serving_visualize: int32 `{name}` expected, got {t.dtype}")
+    ci, Ki = _palette(instance_colors, "serving_visualize")
+    cs, Ks = _palette(semantic_colors, "serving_visualize")
+    if ins_outs.dim() != 4 or tuple(ins_outs.shape[:2]) != (B, n):
+        raise RuntimeError(f"serving_visualize: instance masks [{B},{n},mh,mw] expected, got {tuple(ins_outs.shape)}")
+    if tuple(seg_outs.shape) != (B, H, W, Ks):
+        raise RuntimeError(f"serving_visualize: semantic map [{B},{H},{W},{Ks}] expected (one colour per class), got "
+                           f"{tuple(seg_outs.shape)}")
+    mh, mw = int(ins_outs.shape[2]), int(ins_outs.shape[3])
+    out = torch.empty_like(images) if out is None else out
+    thr = torch.empty((1,), dtype=torch.int32, device=images.device)
+    with _Prof("serving_visualize", 0, 2 * images.numel() + 4 * seg_outs.numel() + 4 * ins_outs.numel() + 24 * B * n,
+               f"B={B} {H}x{W} n={n}"):
+        _lib.check(lib.ml_serving_visualize_u8(_ptr(images), _ptr(det_outs), _ptr(ins_outs), _ptr(seg_outs), _ptr(out),
+                                               _ptr(thr), ci, Ki, float(instance_alpha), cs, Ks, float(semantic_alpha), B, n,
+                                               mh, mw, H, W, _stream()), "ml_serving_visualize_u8")
+    return out

@@ -13,7 +13,7 @@ from . import backbone
 from . import keras_like as K
 from .config import ModelConfiguration
 from .layers import (ASPPNetwork, BoxRegressionSubNet, ClassificationSubNet, CropAndPadMask, DetectionProposal,
-                     DownSampleInput, SummaryOutput,
+                     DownSampleInput, DrawBoxes, DrawInstance, DrawSegmentation, SummaryOutput,
                      FeaturePyramid, MaskDistribute, MaskSubNet, PriorLayer, PyramidRoiAlign, ResizeLike,
                      RestoreBoxes, SegmentationSubNet, SemanticSmoothing, TrimInstances, UpSampleOutput)
 from .prior import PriorBoxes
@@ -615,39 +615,65 @@ def construct_deploy_network(configuration: ModelConfiguration, inference_model)
 
 
 class ServingModel(K.Layer):
-    """The arithmetic half of reference road_project/setup/serving.py:16-52 (`load_serving_model_from_h5`):
-    deploy model -> CropAndPadMask -> SummaryOutput.  Returns the 'summarize' tensor float32 [B,n',11]
+    """The arithmetic of reference road_project/setup/serving.py:16-52 (`load_serving_model_from_h5`):
+    deploy model -> CropAndPadMask -> SummaryOutput, the 'summarize' tensor float32 [B,n',11]
     (class, cx, cy, w, h, conf, pixel count, instance size, horizontal size, vertical size, include_my_road).
-    The 'visualize' output (DrawBoxes / DrawInstance / DrawSegmentation / JPEG encode, :32-40) and the JPEG
-    decode in front are image I/O, not arithmetic of this path, and are not built."""
+    visualize=True adds the 'visualize' output in front, the reference's order: the frame uint8 [B,H,W,3] after
+    DrawBoxes -> DrawInstance(instance colours) -> DrawSegmentation(semantic colours) (:32-40), colours and alphas from
+    configuration.postprocess.  Only its last step, EncodeImageContent (JPEG encode), and the JPEG decode in front are
+    image I/O outside this library: the frames come in decoded and the rendered frame goes out as pixels."""
 
-    def __init__(self, configuration, deploy_model, name='serving'):
+    def __init__(self, configuration, deploy_model, name='serving', visualize=False):
         super().__init__(name=name)
+        post = configuration.postprocess
         self.deploy_model = deploy_model
         self.crop_and_pad = CropAndPadMask()
-        self.summary = SummaryOutput(default_road_size=configuration.postprocess.default_road_size)
-        self.output_names = ['summarize']
+        self.summary = SummaryOutput(default_road_size=post.default_road_size)
+        self.visualize = bool(visualize)
+        if self.visualize:
+            self.draw_boxes = DrawBoxes()
+            self.draw_instance = DrawInstance(post.instance_colors, post.instance_alpha)
+            self.draw_segmentation = DrawSegmentation(post.semantic_colors, post.semantic_alpha)
+        self.output_names = ['visualize', 'summarize'] if self.visualize else ['summarize']
         self.built = True
 
     def call(self, images, **kwargs):
         if not isinstance(images, torch.Tensor):
             images = torch.as_tensor(np.asarray(images))
         images = images.to(self.deploy_model.model.device).contiguous()
+        if self.visualize and images.dtype != torch.uint8:
+            raise ValueError(f"ServingModel(visualize=True) draws into uint8 frames, got {images.dtype}")
         det_outs, ins_outs, seg_outs = self.deploy_model(images)                            # :27-29
         if kwargs.get("materialise_masks", False):                                          # the reference's literal wiring
             crop_and_pad_masks = self.crop_and_pad([images, det_outs, ins_outs, seg_outs])  # :30
-            return self.summary([det_outs, seg_outs, crop_and_pad_masks])                   # :47-48
+            summary = self.summary([det_outs, seg_outs, crop_and_pad_masks])                # :47-48
+            if not self.visualize:
+                return summary
+            vis = self.draw_boxes([images, det_outs])                                       # :34
+            vis = self.draw_instance([vis, det_outs, crop_and_pad_masks])                   # :35-37
+            vis = self.draw_segmentation([vis, seg_outs])                                   # :38-40
+            return [vis, summary]
         # CropAndPadMask folded into SummaryOutput: same numbers bit for bit, no [B,n,H,W] tensor
-        return self.summary([det_outs, seg_outs, ins_outs], from_rois=True)
+        summary = self.summary([det_outs, seg_outs, ins_outs], from_rois=True)
+        if not self.visualize:
+            return summary
+        # the three Draw* layers over CropAndPadMask in one kernel: same bytes, no [B,n,H,W] tensor
+        from . import ops
+        di, ds = self.draw_instance, self.draw_segmentation
+        vis = ops.serving_visualize(images, det_outs.contiguous(), ins_outs.contiguous(), seg_outs.contiguous(), di.colors,
+                                    di.alpha, ds.colors, ds.alpha)
+        return [vis, summary]
 
     def predict(self, images, **kwargs):
         out = self.call(images, **kwargs)
         torch.cuda.synchronize(self.deploy_model.model.device)
+        if self.visualize:
+            return [o.cpu().numpy() for o in out]
         return out.cpu().numpy()
 
 
-def construct_serving_network(configuration: ModelConfiguration, deploy_model):
-    return ServingModel(configuration, deploy_model)
+def construct_serving_network(configuration: ModelConfiguration, deploy_model, visualize=False):
+    return ServingModel(configuration, deploy_model, visualize=visualize)
 
 
 def load_masklab_inference_model_from_weights(weights, config: ModelConfiguration, device="cuda"):
