@@ -1,7 +1,7 @@
 // HBM-bound NHWC kernels: preprocess, depthwise 3x3, max-pool, bilinear (align_corners),
-// global mean, channel scale, fill.  All are float4-vectorised over channels so a wave reads
-// 1 KiB contiguous per instruction; none has inter-block reuse, so no LDS staging is used
-// (re-reads of the 3x3 halo are served by L1/L2).
+// global mean, channel scale, fill.  All are vectorised over channels, 16 bytes per lane (float4, or 8 halves for the
+// fp16-storage instantiations of depthwise 3x3, max-pool, bilinear and global mean), so a wave reads 1 KiB contiguous
+// per instruction; none has inter-block reuse, so no LDS staging is used (re-reads of the 3x3 halo are served by L1/L2).
 #include "common.h"
 
 namespace {
@@ -38,22 +38,75 @@ __global__ void preprocess_kernel(const void *in, int is_u8, float *out, long lo
     }
 }
 
-// ------------------------------------------------------------------ depthwise 3x3
-__global__ void dwconv3x3_kernel(const float *__restrict__ in, const float *__restrict__ wgt,
-                                 const float *__restrict__ bias, float *__restrict__ out,
-                                 int H, int W, int C4, int in_cs, int in_co, int out_cs, int out_co,
+// ---- the NHWC kernels below are written once over the storage type T (float or _Float16) and run the same arithmetic in
+// fp32 on the converted values, ONE rounding at the store: a lane moves V = 16 / sizeof(T) channels (4 floats or 8 halves)
+template <class T> constexpr int VEC = 16 / (int)sizeof(T);
+
+// V channels at p <-> floats, as 16-byte accesses (N = a multiple of V: the fp32 weights of a half lane are two float4)
+template <class T, int N>
+__device__ __forceinline__ void load_f(const T *p, float (&v)[N]) {
+    typedef T Tv __attribute__((ext_vector_type(VEC<T>)));
+#pragma unroll
+    for (int k = 0; k < N / VEC<T>; ++k) {
+        const Tv x = *reinterpret_cast<const Tv *>(p + k * VEC<T>);
+#pragma unroll
+        for (int e = 0; e < VEC<T>; ++e) v[k * VEC<T> + e] = (float)x[e];
+    }
+}
+template <class T>
+__device__ __forceinline__ void store_f(T *p, const float (&v)[VEC<T>]) {
+    typedef T Tv __attribute__((ext_vector_type(VEC<T>)));
+    Tv x;
+#pragma unroll
+    for (int e = 0; e < VEC<T>; ++e) x[e] = (T)v[e];
+    *reinterpret_cast<Tv *>(p) = x;
+}
+
+// what the two storage types do differently: the max-pool's start value and max (fp32: fmaxf; fp16: a compare-select on
+// the halves themselves); the bilinear weight of a sample position o s (fp32: o s - floor(o s) rounded once, an fma; fp16:
+// o s rounded first); global_mean's block shape (channel lanes x row groups, 256 threads)
+template <class T> struct Elt;
+template <> struct Elt<float> {
+    static constexpr float LOWEST = -3.4e38f;
+    static __device__ __forceinline__ float max(float m, float x) { return fmaxf(m, x); }
+    static __device__ __forceinline__ float frac(float o, float s, float fl) { return fmaf(o, s, -fl); }
+    static constexpr int MEAN_Q = 16;                   // 16 float4 lanes x 16 row groups: 256 contiguous bytes per row group
+};
+template <> struct Elt<_Float16> {
+    static constexpr float LOWEST = -65504.f;
+    static __device__ __forceinline__ _Float16 max(_Float16 m, _Float16 x) { return x > m ? x : m; }
+    static __device__ __forceinline__ float frac(float o, float s, float fl) {
+#pragma clang fp contract(off)
+        return o * s - fl;
+    }
+    static constexpr int MEAN_Q = 8;                    // 8 lanes of 8 halves x 32 row groups: 128 contiguous bytes per row group
+};
+
+// ------------------------------------------------------------------ depthwise 3x3 (dilated): engine/layers/semantic.py:63-64;
+// weights / bias fp32
+template <class T>
+__global__ void dwconv3x3_kernel(const T *__restrict__ in, const float *__restrict__ wgt,
+                                 const float *__restrict__ bias, T *__restrict__ out,
+                                 int H, int W, int CV, int in_cs, int in_co, int out_cs, int out_co,
                                  int Ho, int Wo, int stride, int dil, int pad_t, int pad_l, int act,
                                  long long total) {
+    constexpr int V = VEC<T>;
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
     if (idx >= total) return;
-    const int c4 = (int)(idx % C4);
-    long long pix = idx / C4;
+    const int cv = (int)(idx % CV);
+    long long pix = idx / CV;
     const int ox = (int)(pix % Wo); pix /= Wo;
     const int oy = (int)(pix % Ho);
     const int b = (int)(pix / Ho);
-    const int c = c4 * 4;
-    const int C = C4 * 4;
-    f32x4 acc = bias ? *reinterpret_cast<const f32x4 *>(bias + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+    const int c = cv * V;
+    const int C = CV * V;
+    float acc[V];
+    if (bias) {
+        load_f(bias + c, acc);
+    } else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = 0.f;
+    }
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
         const int iy = oy * stride - pad_t + kh * dil;
@@ -62,32 +115,38 @@ __global__ void dwconv3x3_kernel(const float *__restrict__ in, const float *__re
         for (int kw = 0; kw < 3; ++kw) {
             const int ix = ox * stride - pad_l + kw * dil;
             if ((unsigned)ix >= (unsigned)W) continue;
-            const f32x4 x = *reinterpret_cast<const f32x4 *>(
-                in + ((long long)(b * H + iy) * W + ix) * in_cs + in_co + c);
-            const f32x4 w = *reinterpret_cast<const f32x4 *>(wgt + (kh * 3 + kw) * C + c);
-            acc += x * w;
+            float x[V], w[V];
+            load_f(in + ((long long)(b * H + iy) * W + ix) * in_cs + in_co + c, x);
+            load_f(wgt + (kh * 3 + kw) * C + c, w);
+#pragma unroll
+            for (int e = 0; e < V; ++e) acc[e] += x[e] * w[e];
         }
     }
-    f32x4 o;
-    o[0] = ml_apply_act(acc[0], act); o[1] = ml_apply_act(acc[1], act);
-    o[2] = ml_apply_act(acc[2], act); o[3] = ml_apply_act(acc[3], act);
-    *reinterpret_cast<f32x4 *>(out + ((long long)(b * Ho + oy) * Wo + ox) * out_cs + out_co + c) = o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) acc[e] = ml_apply_act(acc[e], act);
+    store_f(out + ((long long)(b * Ho + oy) * Wo + ox) * out_cs + out_co + c, acc);
 }
 
-// ------------------------------------------------------------------ max pool 3x3 s2 (zero pad, input >= 0)
-__global__ void maxpool3x3s2_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                    int H, int W, int C4, int Ho, int Wo, int pad_t, int pad_l,
+// ------------------------------------------------------------------ max pool 3x3 s2 (zero pad, input >= 0): ZeroPadding2D(1) +
+// MaxPooling2D(3, 2), engine/backbone/ResNext.py:351-352; on the stored values themselves
+template <class T>
+__global__ void maxpool3x3s2_kernel(const T *__restrict__ in, T *__restrict__ out,
+                                    int H, int W, int CV, int Ho, int Wo, int pad_t, int pad_l,
                                     long long total) {
+    constexpr int V = VEC<T>;
+    typedef T Tv __attribute__((ext_vector_type(V)));
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
     if (idx >= total) return;
-    const int c4 = (int)(idx % C4);
-    long long pix = idx / C4;
+    const int cv = (int)(idx % CV);
+    long long pix = idx / CV;
     const int ox = (int)(pix % Wo); pix /= Wo;
     const int oy = (int)(pix % Ho);
     const int b = (int)(pix / Ho);
-    const int C = C4 * 4;
+    const int C = CV * V;
     bool any_pad = false;
-    f32x4 m = {-3.4e38f, -3.4e38f, -3.4e38f, -3.4e38f};
+    Tv m;
+#pragma unroll
+    for (int e = 0; e < V; ++e) m[e] = (T)Elt<T>::LOWEST;
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
         const int iy = oy * 2 - pad_t + kh;
@@ -95,26 +154,30 @@ __global__ void maxpool3x3s2_kernel(const float *__restrict__ in, float *__restr
         for (int kw = 0; kw < 3; ++kw) {
             const int ix = ox * 2 - pad_l + kw;
             if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) { any_pad = true; continue; }
-            const f32x4 x = *reinterpret_cast<const f32x4 *>(in + ((long long)(b * H + iy) * W + ix) * C + c4 * 4);
-            m[0] = fmaxf(m[0], x[0]); m[1] = fmaxf(m[1], x[1]);
-            m[2] = fmaxf(m[2], x[2]); m[3] = fmaxf(m[3], x[3]);
+            const Tv x = *reinterpret_cast<const Tv *>(in + ((long long)(b * H + iy) * W + ix) * C + cv * V);
+#pragma unroll
+            for (int e = 0; e < V; ++e) m[e] = Elt<T>::max(m[e], x[e]);
         }
     }
     if (any_pad) {  // the explicit ZeroPadding2D contributes zeros to the window
-        m[0] = fmaxf(m[0], 0.f); m[1] = fmaxf(m[1], 0.f); m[2] = fmaxf(m[2], 0.f); m[3] = fmaxf(m[3], 0.f);
+#pragma unroll
+        for (int e = 0; e < V; ++e) m[e] = Elt<T>::max((T)0.f, m[e]);
     }
-    *reinterpret_cast<f32x4 *>(out + ((long long)(b * Ho + oy) * Wo + ox) * C + c4 * 4) = m;
+    *reinterpret_cast<Tv *>(out + ((long long)(b * Ho + oy) * Wo + ox) * C + cv * V) = m;
 }
 
-// ------------------------------------------------------------------ bilinear, align_corners=True
-__global__ void bilinear_ac_kernel(const float *__restrict__ in, const float *__restrict__ add,
-                                   float *__restrict__ out, int H, int W, int C4, int in_cs, int in_co,
+// ------------------------------------------------------------------ bilinear, align_corners=True (+ FPN Add / concat-slice
+// store): tf.compat.v1.image.resize_bilinear(align_corners=True), engine/layers/misc.py:306
+template <class T>
+__global__ void bilinear_ac_kernel(const T *__restrict__ in, const T *__restrict__ add,
+                                   T *__restrict__ out, int H, int W, int CV, int in_cs, int in_co,
                                    int Ho, int Wo, float sy, float sx, int add_cs, int add_co,
                                    int out_cs, int out_co, long long total) {
+    constexpr int V = VEC<T>;
     const long long idx = (long long)blockIdx.x * TPB + threadIdx.x;
     if (idx >= total) return;
-    const int c = (int)(idx % C4) * 4;
-    long long pix = idx / C4;
+    const int c = (int)(idx % CV) * V;
+    long long pix = idx / CV;
     const int ox = (int)(pix % Wo); pix /= Wo;
     const int oy = (int)(pix % Ho);
     const int b = (int)(pix / Ho);
@@ -123,50 +186,66 @@ __global__ void bilinear_ac_kernel(const float *__restrict__ in, const float *__
     const float fly = floorf(fy), flx = floorf(fx);
     const int y0 = max((int)fly, 0), x0 = max((int)flx, 0);
     const int y1 = min((int)ceilf(fy), H - 1), x1 = min((int)ceilf(fx), W - 1);
-    const float ty = fy - fly, tx = fx - flx;
-    const float *base = in + (long long)b * H * W * in_cs + in_co + c;
-    const f32x4 tl = *reinterpret_cast<const f32x4 *>(base + ((long long)y0 * W + x0) * in_cs);
-    const f32x4 tr = *reinterpret_cast<const f32x4 *>(base + ((long long)y0 * W + x1) * in_cs);
-    const f32x4 bl = *reinterpret_cast<const f32x4 *>(base + ((long long)y1 * W + x0) * in_cs);
-    const f32x4 br = *reinterpret_cast<const f32x4 *>(base + ((long long)y1 * W + x1) * in_cs);
-    const f32x4 top = tl + (tr - tl) * tx;
-    const f32x4 bot = bl + (br - bl) * tx;
-    f32x4 v = top + (bot - top) * ty;
+    const float ty = Elt<T>::frac((float)oy, sy, fly), tx = Elt<T>::frac((float)ox, sx, flx);
+    const T *base = in + (long long)b * H * W * in_cs + in_co + c;
+    float tl[V], tr[V], bl[V], br[V], v[V];
+    load_f(base + ((long long)y0 * W + x0) * in_cs, tl);
+    load_f(base + ((long long)y0 * W + x1) * in_cs, tr);
+    load_f(base + ((long long)y1 * W + x0) * in_cs, bl);
+    load_f(base + ((long long)y1 * W + x1) * in_cs, br);
     const long long opix = (long long)(b * Ho + oy) * Wo + ox;
-    if (add) v += *reinterpret_cast<const f32x4 *>(add + opix * add_cs + add_co + c);
-    *reinterpret_cast<f32x4 *>(out + opix * out_cs + out_co + c) = v;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        const float top = tl[e] + (tr[e] - tl[e]) * tx;
+        const float bot = bl[e] + (br[e] - bl[e]) * tx;
+        v[e] = top + (bot - top) * ty;
+    }
+    if (add) {
+        float a[V];
+        load_f(add + opix * add_cs + add_co + c, a);
+#pragma unroll
+        for (int e = 0; e < V; ++e) v[e] += a[e];
+    }
+    store_f(out + opix * out_cs + out_co + c, v);
 }
 
-// ------------------------------------------------------------------ global mean over HW
-// grid (ceil(C4 / 16), B), block 256 = 16 row-groups x 16 channel-quads (256 contiguous bytes per row group); fp64
-// accumulation, the 16 partial sums of a channel added in a fixed order.  (The first layout -- 64 quads x 4 row groups
-// -- gave ASPP's pooling branch 64 blocks for 67 MB: 79 us.)
-__global__ void global_mean_kernel(const float *__restrict__ in, float *__restrict__ out, int HW, int C4) {
-    __shared__ double red[16][16][4];
-    const int q = threadIdx.x & 15;
-    const int g = threadIdx.x >> 4;
-    const int c4 = blockIdx.x * 16 + q;
+// ------------------------------------------------------------------ global mean over HW (tf.reduce_mean, semantic.py:149)
+// grid (ceil(CV / Q), B), block 256 = Q channel lanes x 256 / Q row groups (Elt<T>::MEAN_Q); fp64 accumulation, the partial
+// sums of a channel added in a fixed order.  (The first fp32 layout -- 64 lanes x 4 row groups -- gave ASPP's pooling branch
+// 64 blocks for 67 MB: 79 us.)
+template <class T>
+__global__ void global_mean_kernel(const T *__restrict__ in, T *__restrict__ out, int HW, int CV) {
+    constexpr int V = VEC<T>, Q = Elt<T>::MEAN_Q, G = 256 / Q;
+    __shared__ double red[G][Q][V];
+    const int q = threadIdx.x & (Q - 1);
+    const int g = threadIdx.x / Q;
+    const int cv = blockIdx.x * Q + q;
     const int b = blockIdx.y;
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-    if (c4 < C4) {
-        const float *p = in + (long long)b * HW * C4 * 4 + c4 * 4;
-        for (int i = g; i < HW; i += 16) {
-            const f32x4 x = *reinterpret_cast<const f32x4 *>(p + (long long)i * C4 * 4);
-            s0 += x[0]; s1 += x[1]; s2 += x[2]; s3 += x[3];
+    double s[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) s[e] = 0;
+    if (cv < CV) {
+        const T *p = in + (long long)b * HW * CV * V + cv * V;
+        for (int i = g; i < HW; i += G) {
+            float x[V];
+            load_f(p + (long long)i * CV * V, x);
+#pragma unroll
+            for (int e = 0; e < V; ++e) s[e] += (double)x[e];
         }
     }
-    red[g][q][0] = s0; red[g][q][1] = s1; red[g][q][2] = s2; red[g][q][3] = s3;
-    __syncthreads();
-    if (g == 0 && c4 < C4) {
-        f32x4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < V; ++e) red[g][q][e] = s[e];
+    __syncthreads();
+    if (g == 0 && cv < CV) {
+        float o[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
             double t = 0;
 #pragma unroll
-            for (int k = 0; k < 16; ++k) t += red[k][q][e];
+            for (int k = 0; k < G; ++k) t += red[k][q][e];
             o[e] = (float)(t / (double)HW);
         }
-        *reinterpret_cast<f32x4 *>(out + (long long)b * C4 * 4 + c4 * 4) = o;
+        store_f(out + (long long)b * CV * V + cv * V, o);
     }
 }
 
@@ -194,6 +273,81 @@ __global__ void fill_kernel(float *x, float v, long long n) {
     if (i < n) x[i] = v;
 }
 
+// ---- launchers shared by the fp32 and fp16 entry points: `name` leads every message; channel counts, strides and offsets
+// are multiples of V = VEC<T>
+template <class T> constexpr const char *C_NOTE = sizeof(T) == 2 ? " (C % 8)" : "";
+
+template <class T>
+int dwconv3x3_launch(const char *name, const void *in, const float *wgt, const float *bias, void *out, int B, int H, int W,
+                     int C, int in_cstride, int in_coff, int out_cstride, int out_coff, int Ho, int Wo, int stride, int dil,
+                     int pad_t, int pad_l, int act, void *stream) {
+    constexpr int V = VEC<T>;
+    ML_REQUIRE(in && wgt && out, "%s: null pointer", name);
+    ML_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % V == 0, "%s: bad dims (C %% %d)", name, V);
+    ML_REQUIRE(in_cstride % V == 0 && in_coff % V == 0 && out_cstride % V == 0 && out_coff % V == 0,
+               "%s: channel strides/offsets must be multiples of %d", name, V);
+    ML_REQUIRE(in_coff + C <= in_cstride && out_coff + C <= out_cstride, "%s: slice exceeds buffer", name);
+    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(wgt) && ml_aligned16(out) && (!bias || ml_aligned16(bias)),
+               "%s: pointers must be 16-byte aligned", name);
+    ML_REQUIRE((long long)B * H * W < (1ll << 31) && stride > 0 && dil > 0, "%s: geometry out of range", name);
+    const long long total = (long long)B * Ho * Wo * (C / V);
+    hipLaunchKernelGGL(dwconv3x3_kernel<T>, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream,
+                       reinterpret_cast<const T *>(in), wgt, bias, reinterpret_cast<T *>(out), H, W, C / V, in_cstride, in_coff,
+                       out_cstride, out_coff, Ho, Wo, stride, dil, pad_t, pad_l, act, total);
+    ML_CHECK_LAUNCH(name);
+    return ML_OK;
+}
+
+template <class T>
+int maxpool3x3s2_launch(const char *name, const void *in, void *out, int B, int H, int W, int C, int Ho, int Wo, int pad_t,
+                        int pad_l, void *stream) {
+    constexpr int V = VEC<T>;
+    ML_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && C > 0 && C % V == 0, "%s: bad arguments%s", name, C_NOTE<T>);
+    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "%s: pointers must be 16-byte aligned", name);
+    ML_REQUIRE((long long)B * H * W < (1ll << 31), "%s: too many pixels", name);
+    const long long total = (long long)B * Ho * Wo * (C / V);
+    ML_REQUIRE(total < (1ll << 31) * TPB, "%s: grid too large", name);
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<T>, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream,
+                       reinterpret_cast<const T *>(in), reinterpret_cast<T *>(out), H, W, C / V, Ho, Wo, pad_t, pad_l, total);
+    ML_CHECK_LAUNCH(name);
+    return ML_OK;
+}
+
+template <class T>
+int resize_bilinear_ac_launch(const char *name, const void *in, const void *add, void *out, int B, int H, int W, int C,
+                              int in_cstride, int in_coff, int Ho, int Wo, int add_cstride, int add_coff, int out_cstride,
+                              int out_coff, void *stream) {
+    constexpr int V = VEC<T>;
+    ML_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % V == 0, "%s: bad arguments%s", name,
+               C_NOTE<T>);
+    ML_REQUIRE(in_cstride % V == 0 && in_coff % V == 0 && out_cstride % V == 0 && out_coff % V == 0,
+               "%s: channel strides/offsets must be multiples of %d", name, V);
+    ML_REQUIRE(in_coff + C <= in_cstride && out_coff + C <= out_cstride, "%s: slice exceeds buffer", name);
+    if (add) ML_REQUIRE(add_cstride % V == 0 && add_coff % V == 0 && add_coff + C <= add_cstride && ml_aligned16(add),
+                        "%s: bad add view", name);
+    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "%s: pointers must be 16-byte aligned", name);
+    const float sy = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
+    const float sx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
+    const long long total = (long long)B * Ho * Wo * (C / V);
+    hipLaunchKernelGGL(bilinear_ac_kernel<T>, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream,
+                       reinterpret_cast<const T *>(in), reinterpret_cast<const T *>(add), reinterpret_cast<T *>(out), H, W, C / V,
+                       in_cstride, in_coff, Ho, Wo, sy, sx, add_cstride, add_coff, out_cstride, out_coff, total);
+    ML_CHECK_LAUNCH(name);
+    return ML_OK;
+}
+
+template <class T>
+int global_mean_launch(const char *name, const void *in, void *out, int B, int HW, int C, void *stream) {
+    constexpr int V = VEC<T>, Q = Elt<T>::MEAN_Q;
+    ML_REQUIRE(in && out && B > 0 && HW > 0 && C > 0 && C % V == 0, "%s: bad arguments%s", name, C_NOTE<T>);
+    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "%s: pointers must be 16-byte aligned", name);
+    const int CV = C / V;
+    hipLaunchKernelGGL(global_mean_kernel<T>, dim3((CV + Q - 1) / Q, B), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const T *>(in), reinterpret_cast<T *>(out), HW, CV);
+    ML_CHECK_LAUNCH(name);
+    return ML_OK;
+}
+
 }  // namespace
 
 extern "C" int ml_preprocess_f32(const void *in, int32_t is_u8, float *out, int64_t npix, int32_t out_c,
@@ -215,62 +369,50 @@ extern "C" int ml_dwconv3x3_f32(const float *in, const float *wgt, const float *
                                 int32_t H, int32_t W, int32_t C, int32_t in_cstride, int32_t in_coff,
                                 int32_t out_cstride, int32_t out_coff, int32_t Ho, int32_t Wo, int32_t stride,
                                 int32_t dil, int32_t pad_t, int32_t pad_l, int32_t act, void *stream) {
-    ML_REQUIRE(in && wgt && out, "dwconv3x3: null pointer");
-    ML_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0, "dwconv3x3: bad dims (C %% 4)");
-    ML_REQUIRE(in_cstride % 4 == 0 && in_coff % 4 == 0 && out_cstride % 4 == 0 && out_coff % 4 == 0,
-               "dwconv3x3: channel strides/offsets must be multiples of 4");
-    ML_REQUIRE(in_coff + C <= in_cstride && out_coff + C <= out_cstride, "dwconv3x3: slice exceeds buffer");
-    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(wgt) && ml_aligned16(out) && (!bias || ml_aligned16(bias)),
-               "dwconv3x3: pointers must be 16-byte aligned");
-    ML_REQUIRE((long long)B * H * W < (1ll << 31) && stride > 0 && dil > 0, "dwconv3x3: geometry out of range");
-    const long long total = (long long)B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(dwconv3x3_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, in, wgt, bias, out,
-                       H, W, C / 4, in_cstride, in_coff, out_cstride, out_coff, Ho, Wo, stride, dil, pad_t, pad_l,
-                       act, total);
-    ML_CHECK_LAUNCH("dwconv3x3");
-    return ML_OK;
+    return dwconv3x3_launch<float>("dwconv3x3", in, wgt, bias, out, B, H, W, C, in_cstride, in_coff, out_cstride, out_coff, Ho,
+                                   Wo, stride, dil, pad_t, pad_l, act, stream);
+}
+
+extern "C" int ml_dwconv3x3_f16(const void *in, const float *wgt, const float *bias, void *out, int32_t B, int32_t H,
+                                int32_t W, int32_t C, int32_t in_cstride, int32_t in_coff, int32_t out_cstride,
+                                int32_t out_coff, int32_t Ho, int32_t Wo, int32_t stride, int32_t dil, int32_t pad_t,
+                                int32_t pad_l, int32_t act, void *stream) {
+    return dwconv3x3_launch<_Float16>("dwconv3x3_f16", in, wgt, bias, out, B, H, W, C, in_cstride, in_coff, out_cstride,
+                                      out_coff, Ho, Wo, stride, dil, pad_t, pad_l, act, stream);
 }
 
 extern "C" int ml_maxpool3x3s2_f32(const float *in, float *out, int32_t B, int32_t H, int32_t W, int32_t C,
                                    int32_t Ho, int32_t Wo, int32_t pad_t, int32_t pad_l, void *stream) {
-    ML_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool: bad arguments");
-    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "maxpool: pointers must be 16-byte aligned");
-    ML_REQUIRE((long long)B * H * W < (1ll << 31), "maxpool: too many pixels");
-    const long long total = (long long)B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(maxpool3x3s2_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, in, out, H, W,
-                       C / 4, Ho, Wo, pad_t, pad_l, total);
-    ML_CHECK_LAUNCH("maxpool");
-    return ML_OK;
+    return maxpool3x3s2_launch<float>("maxpool", in, out, B, H, W, C, Ho, Wo, pad_t, pad_l, stream);
+}
+
+extern "C" int ml_maxpool3x3s2_f16(const void *in, void *out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho,
+                                   int32_t Wo, int32_t pad_t, int32_t pad_l, void *stream) {
+    return maxpool3x3s2_launch<_Float16>("maxpool_f16", in, out, B, H, W, C, Ho, Wo, pad_t, pad_l, stream);
 }
 
 extern "C" int ml_resize_bilinear_ac_f32(const float *in, const float *add, float *out, int32_t B, int32_t H,
                                          int32_t W, int32_t C, int32_t in_cstride, int32_t in_coff, int32_t Ho,
                                          int32_t Wo, int32_t add_cstride, int32_t add_coff, int32_t out_cstride,
                                          int32_t out_coff, void *stream) {
-    ML_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 4 == 0,
-               "resize_bilinear: bad arguments");
-    ML_REQUIRE(in_cstride % 4 == 0 && in_coff % 4 == 0 && out_cstride % 4 == 0 && out_coff % 4 == 0,
-               "resize_bilinear: channel strides/offsets must be multiples of 4");
-    ML_REQUIRE(in_coff + C <= in_cstride && out_coff + C <= out_cstride, "resize_bilinear: slice exceeds buffer");
-    if (add) ML_REQUIRE(add_cstride % 4 == 0 && add_coff % 4 == 0 && add_coff + C <= add_cstride && ml_aligned16(add),
-                        "resize_bilinear: bad add view");
-    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "resize_bilinear: pointers must be 16-byte aligned");
-    const float sy = Ho > 1 ? (float)(H - 1) / (float)(Ho - 1) : 0.f;
-    const float sx = Wo > 1 ? (float)(W - 1) / (float)(Wo - 1) : 0.f;
-    const long long total = (long long)B * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(bilinear_ac_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, in, add, out, H, W,
-                       C / 4, in_cstride, in_coff, Ho, Wo, sy, sx, add_cstride, add_coff, out_cstride, out_coff, total);
-    ML_CHECK_LAUNCH("resize_bilinear");
-    return ML_OK;
+    return resize_bilinear_ac_launch<float>("resize_bilinear", in, add, out, B, H, W, C, in_cstride, in_coff, Ho, Wo, add_cstride,
+                                            add_coff, out_cstride, out_coff, stream);
+}
+
+extern "C" int ml_resize_bilinear_ac_f16(const void *in, const void *add, void *out, int32_t B, int32_t H, int32_t W,
+                                         int32_t C, int32_t in_cstride, int32_t in_coff, int32_t Ho, int32_t Wo,
+                                         int32_t add_cstride, int32_t add_coff, int32_t out_cstride, int32_t out_coff,
+                                         void *stream) {
+    return resize_bilinear_ac_launch<_Float16>("resize_bilinear_f16", in, add, out, B, H, W, C, in_cstride, in_coff, Ho, Wo,
+                                               add_cstride, add_coff, out_cstride, out_coff, stream);
 }
 
 extern "C" int ml_global_mean_f32(const float *in, float *out, int32_t B, int32_t HW, int32_t C, void *stream) {
-    ML_REQUIRE(in && out && B > 0 && HW > 0 && C > 0 && C % 4 == 0, "global_mean: bad arguments");
-    ML_REQUIRE(ml_aligned16(in) && ml_aligned16(out), "global_mean: pointers must be 16-byte aligned");
-    const int C4 = C / 4;
-    hipLaunchKernelGGL(global_mean_kernel, dim3((C4 + 15) / 16, B), dim3(256), 0, (hipStream_t)stream, in, out, HW, C4);
-    ML_CHECK_LAUNCH("global_mean");
-    return ML_OK;
+    return global_mean_launch<float>("global_mean", in, out, B, HW, C, stream);
+}
+
+extern "C" int ml_global_mean_f16(const void *in, void *out, int32_t B, int32_t HW, int32_t C, void *stream) {
+    return global_mean_launch<_Float16>("global_mean_f16", in, out, B, HW, C, stream);
 }
 
 extern "C" int ml_scale_channels_f32(float *x, const float *s, int32_t B, int32_t HW, int32_t C, void *stream) {

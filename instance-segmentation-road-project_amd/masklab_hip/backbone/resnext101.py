@@ -158,10 +158,8 @@ class ResNeXt101(Layer):
         import torch
         half = ops.half_storage()            # fp16-storage mode: the body's tensors AND its taps are IEEE half
         taps = {}
-        if half and "C1" not in wanted and self.conv0.dev is not None:
-            x = ops.stem_pool_h(x, self.conv0.dev)        # stem + pool in one pass (csrc/stem_h.hip)
-        elif ops.CONV_MATH in ("f32", "f32x3") and "C1" not in wanted and self.conv0.dev is not None:
-            x = ops.stem_pool(x, self.conv0.dev)          # fp32-tensor twins (csrc/stem_f32.hip, stem_x3.hip): same bits as the pair below
+        if "C1" not in wanted and self.conv0.dev is not None and ops.has_fused_stem():
+            x = ops.stem_pool(x, self.conv0.dev)     # stem + pool in one pass (csrc/stem.hip): same bits as the pair below
         else:
             x = self.conv0(x, out_dtype=torch.float16 if half else None)
             taps["C1"] = x

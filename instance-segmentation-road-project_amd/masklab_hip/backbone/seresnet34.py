@@ -163,7 +163,7 @@ class SEResNet34(Layer):
             raise NotImplementedError("the 'f16s' conv math (fp16 storage) is not built for the seresnet34 backbone: its "
                                       "SE block tail is fp32-only -- use 'f32', 'f32x3' or 'f16'")
         taps = {}
-        if ops.CONV_MATH in ("f32", "f32x3") and "C1" not in wanted and self.conv0.dev is not None:
+        if "C1" not in wanted and self.conv0.dev is not None and ops.has_fused_stem():
             x = ops.stem_pool(x, self.conv0.dev)            # stem + bn0 + relu0 + pooling0 in one pass
         else:
             x = self.conv0(x)

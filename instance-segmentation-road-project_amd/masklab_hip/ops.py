@@ -133,6 +133,7 @@ class DeviceConv:
         self._wgt_h = None
         self._wgt_x3 = None
         self._wgt_wino = None
+        self._wgt_stem_h = None
 
     @property
     def wgt_wino(self):
@@ -157,6 +158,14 @@ class DeviceConv:
             both = np.ascontiguousarray(np.concatenate([hi, lo], axis=2))            # [rows, chunks, 64] halves
             self._wgt_x3 = torch.from_numpy(both.view(np.float32).reshape(rows, ktot)).to(self.wgt.device)
         return self._wgt_x3
+
+    @property
+    def wgt_stem_h(self):
+        """The row-span stem packing rounded to IEEE half, same layout ([64][7 x 32]) -- what the fused fp16-storage stem
+        (stem_pool in "f16s") reads; made on first use."""
+        if self._wgt_stem_h is None:
+            self._wgt_stem_h = torch.from_numpy(np.ascontiguousarray(self.p.wgt, np.float32).astype(np.float16)).to(self.wgt.device)
+        return self._wgt_stem_h
 
     @property
     def span_pad_h(self):
@@ -511,48 +520,38 @@ def dwconv3x3(x, wgt, bias, stride=1, padding="same", dilation=1, act=_lib.ACT_N
     return out
 
 
-def stem_pool_h(x4, dc: "DeviceConv"):
-    """ml_stem7x7s2_pool_f16: the ResNeXt stem (7x7 stride-2 conv + folded BN + ReLU) and the 3x3 stride-2 max-pool behind
-    it in ONE kernel, fp32 NHWC4 image in, half pooled map out -- the fp16-storage mode only (the un-pooled stem output is
-    never written).  `dc` = the stem's row-span DeviceConv; its weights rounded to half are made on first use."""
-    lib = _lib.load()
-    _require_dev(x4, "x4")
-    p = dc.p
-    B, H, W, c4 = x4.shape
-    if x4.dtype != torch.float32 or c4 != 4 or p.cpp_shift == 30 or p.KH != 7 or p.span_pad != 32 or p.cout != 64 or p.n_pad != 64:
-        raise ValueError("stem_pool_h: needs the fp32 NHWC4 image and the 7x7 / 64-filter row-span stem packing")
-    wh = getattr(dc, "_stem_wgt_h", None)
-    if wh is None:
-        wh = dc._stem_wgt_h = torch.from_numpy(np.ascontiguousarray(p.wgt, np.float32).astype(np.float16)).to(x4.device)
-    Hc, Wc = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    Hp, Wp = (Hc + 2 - 3) // 2 + 1, (Wc + 2 - 3) // 2 + 1
-    out = torch.empty((B, Hp, Wp, 64), dtype=torch.float16, device=x4.device)
-    with _Prof("stem7x7s2_pool_h", 2.0 * B * Hc * Wc * 64 * 147, 16 * B * H * W + 2 * out.numel() + 2 * 64 * 224,
-               f"B={B} HxW={H}x{W} -> {Hp}x{Wp}x64"):
-        _lib.check(lib.ml_stem7x7s2_pool_f16(_ptr(x4), _ptr(wh), _ptr(dc.bias), _ptr(out), B, H, W, Hp, Wp, _stream()),
-                   "ml_stem7x7s2_pool_f16")
-    return out
+def has_fused_stem():
+    """True when the current conv math has the fused stem + max-pool kernel (stem_pool): "f32", "f32x3" and "f16s".
+    "f16" (fp32 tensors, f16 operands) has none: its stem runs as conv2d + maxpool3x3s2."""
+    return CONV_MATH in ("f32", "f32x3", "f16s")
 
 
 def stem_pool(x4, dc: "DeviceConv"):
-    """ml_stem7x7s2_pool_f32 / _x3: the fp32-tensor twins of stem_pool_h, in the current conv math ("f32": exact fp32
-    products, only those with a non-zero weight; "f32x3": the split-operand products) -- the same bits as
-    conv2d(stem, relu) + maxpool3x3s2 in that math, without the un-pooled map in memory."""
+    """ml_stem7x7s2_pool_f32 / _x3 / _f16: the ResNeXt stem (7x7 stride-2 conv + folded BN + ReLU) and the 3x3 stride-2
+    max-pool behind it in ONE kernel, fp32 NHWC4 image in, the un-pooled stem output never written -- in the current conv
+    math: "f32" exact fp32 products (only those with a non-zero weight), "f32x3" the split-operand products, "f16s" operands
+    rounded to half and a half pooled map.  The same bits as conv2d(stem, relu) + maxpool3x3s2 in that math.
+    `dc` = the stem's row-span DeviceConv."""
     lib = _lib.load()
     _require_dev(x4, "x4")
     p = dc.p
     B, H, W, c4 = x4.shape
     if x4.dtype != torch.float32 or c4 != 4 or p.cpp_shift == 30 or p.KH != 7 or p.span_pad != 32 or p.cout != 64 or p.n_pad != 64:
         raise ValueError("stem_pool: needs the fp32 NHWC4 image and the 7x7 / 64-filter row-span stem packing")
-    if CONV_MATH not in ("f32", "f32x3"):
+    if not has_fused_stem():
         raise ValueError(f"stem_pool: no fused stem in conv math {CONV_MATH!r}")
-    x3 = CONV_MATH == "f32x3"
+    if CONV_MATH == "f16s":
+        label, fn, w, dtype = "stem7x7s2_pool_h", lib.ml_stem7x7s2_pool_f16, dc.wgt_stem_h, torch.float16
+    elif CONV_MATH == "f32x3":
+        label, fn, w, dtype = "stem7x7s2_pool_x3", lib.ml_stem7x7s2_pool_x3, dc.wgt_x3, torch.float32
+    else:
+        label, fn, w, dtype = "stem7x7s2_pool", lib.ml_stem7x7s2_pool_f32, dc.wgt, torch.float32
     Hc, Wc = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     Hp, Wp = (Hc + 2 - 3) // 2 + 1, (Wc + 2 - 3) // 2 + 1
-    out = torch.empty((B, Hp, Wp, 64), dtype=torch.float32, device=x4.device)
-    with _Prof("stem7x7s2_pool_x3" if x3 else "stem7x7s2_pool", 2.0 * B * Hc * Wc * 64 * 147,
-               16 * B * H * W + 4 * out.numel() + 4 * 64 * 224, f"B={B} HxW={H}x{W} -> {Hp}x{Wp}x64"):
-        fn, w = (lib.ml_stem7x7s2_pool_x3, dc.wgt_x3) if x3 else (lib.ml_stem7x7s2_pool_f32, dc.wgt)
+    out = torch.empty((B, Hp, Wp, 64), dtype=dtype, device=x4.device)
+    es = out.element_size()
+    with _Prof(label, 2.0 * B * Hc * Wc * 64 * 147, 16 * B * H * W + es * out.numel() + es * 64 * 224,
+               f"B={B} HxW={H}x{W} -> {Hp}x{Wp}x64"):
         _lib.check(fn(_ptr(x4), _ptr(w), _ptr(dc.bias), _ptr(out), B, H, W, Hp, Wp, _stream()), "ml_stem7x7s2_pool")
     return out
 

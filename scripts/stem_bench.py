@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The fp32-tensor ResNeXt stem: fused conv 7x7 s2 + ReLU + max-pool (csrc/stem_f32.hip; --math f32x3: stem_x3.hip) against the
-two launches it replaces.
+"""The ResNeXt stem: fused conv 7x7 s2 + ReLU + max-pool (csrc/stem.hip, in the conv math --math: f32, f32x3 or f16s) against
+the two launches it replaces.
 Usage (GPU box): python scripts/stem_bench.py [--lib experiment.so] [--reps 20]"""
 import argparse
 import os
@@ -16,7 +16,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None, help="an experiment build of the library (the product path has no override)")
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--math", default="f32", choices=("f32", "f32x3"))
+    ap.add_argument("--math", default="f32", choices=("f32", "f32x3", "f16s"))
     args = ap.parse_args()
     from masklab_hip import _lib, ops, packing
     if args.lib:
@@ -26,12 +26,13 @@ def main():
     w = (rng.normal(size=(7, 7, 3, 64)) * 0.08).astype(np.float32)
     b = rng.normal(size=(64,)).astype(np.float32)
     dc = ops.DeviceConv(packing.pack_rowspan(w, b), "cuda")
+    dtype = torch.float16 if args.math == "f16s" else None          # the fp16-storage stem stores half
     for B, H, W in [(8, 1024, 1024), (16, 1280, 1280), (1, 1024, 1024), (1, 512, 512)]:
         x4 = torch.zeros((B, H, W, 4), device="cuda")
         x4[..., :3] = torch.from_numpy(rng.normal(size=(B, H, W, 3)).astype(np.float32)).cuda()
 
         def two():
-            return ops.maxpool3x3s2(ops.conv2d(x4, dc, stride=2, padding=((3, 3), (3, 3)), act=_lib.ACT_RELU), pad=1)
+            return ops.maxpool3x3s2(ops.conv2d(x4, dc, stride=2, padding=((3, 3), (3, 3)), act=_lib.ACT_RELU, out_dtype=dtype), pad=1)
 
         def one():
             return ops.stem_pool(x4, dc)
