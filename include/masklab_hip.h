@@ -55,7 +55,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_se_residual_desc,
                                             ml_se_residual_f32 / _workspace_bytes;
                                             (additive, same version) ml_draw_boxes_u8, ml_draw_instance_u8,
-                                            ml_draw_segmentation_u8, ml_serving_visualize_u8              */
+                                            ml_draw_segmentation_u8, ml_serving_visualize_u8;
+                                            (additive, same version) ml_se_bottleneck_desc,
+                                            ml_se_bottleneck_f32 / _f16 / _workspace_bytes                 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -411,6 +413,31 @@ typedef struct ml_se_residual_desc {
 } ml_se_residual_desc;
 int64_t ml_se_residual_workspace_bytes(int32_t B, int32_t HW, int32_t C);
 int ml_se_residual_f32(const ml_se_residual_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* SE-ResNet-50 / SE-ResNeXt-50 post-activation bottleneck tail (thirdparty senet.py SEResNetBottleneck :46-88,
+ * SEResNeXtBottleneck :91-134, ChannelSE _common_blocks.py:88-119), NHWC [B,HW,C], one problem per call:
+ *   g   = sigmoid(W2 relu(W1 mean_hw(c3) + b1) + b2)   (ChannelSE's two 1x1 convs with bias; fp64, once per sample,
+ *                                                        kept as g_hi = fp32(g) and g_lo = fp32(g - g_hi))
+ *   out = relu(c3 * g + residual)                      fp32: the reference's two fp32 ops, Multiply (c3 * g_hi), then
+ *                                                      Add; half: fma(c3, g_lo, fma(c3, g_hi, residual)) in fp32; ReLU,
+ *                                                      one rounding at the store
+ * three launches: per (sample, pool chunk) fp64 channel sums into workspace slabs; per sample the gate into the
+ * workspace; per (sample, chunk) the stream.  _f32: float tensors; _f16: IEEE-half c3 / residual / out.
+ * w1 [C][Hd] (the 1x1 kernel [1,1,C,Hd]), b1 [Hd], w2 [Hd][C], b2 [C], fp32 in both.  4 <= C <= 2048, C % 4 == 0
+ * (C % 8 == 0 for _f16), 1 <= Hd <= 128.  c3 / residual / out 16-byte aligned.  out may be the very buffer of c3 or of
+ * residual; no other overlap.  No atomics: the same bits run to run, under graph replay, and for image k of any batch.
+ * workspace_bytes >= ml_se_bottleneck_workspace_bytes(B, HW, C), 16-byte aligned.                                  */
+typedef struct ml_se_bottleneck_desc {
+    const void *c3;               /* bn3(conv3(.)): float or half */
+    const void *residual;         /* the unit's shortcut, same type */
+    const float *w1, *b1;         /* [C][Hd], [Hd] */
+    const float *w2, *b2;         /* [Hd][C], [C] */
+    void *out;                    /* relu(c3 * g + residual), same type */
+    int32_t B, HW, C, Hd;
+} ml_se_bottleneck_desc;
+int64_t ml_se_bottleneck_workspace_bytes(int32_t B, int32_t HW, int32_t C);
+int ml_se_bottleneck_f32(const ml_se_bottleneck_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
+int ml_se_bottleneck_f16(const ml_se_bottleneck_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------- detection post-process
  * RestoreBoxes (engine/layers/detection.py:325-344): priors int32 [A,4] (cx,cy,w,h) shared by

@@ -73,6 +73,13 @@ class SeResidualDesc(C.Structure):
                 ("mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SeBottleneckDesc(C.Structure):
+    """Mirror of `ml_se_bottleneck_desc` (include/masklab_hip.h)."""
+    _fields_ = [("c3", C.c_void_p), ("residual", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p),
+                ("w2", C.c_void_p), ("b2", C.c_void_p), ("out", C.c_void_p),
+                ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("Hd", C.c_int32)]
+
+
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
@@ -125,6 +132,9 @@ SIGNATURES = {
     "ml_squeeze_excite_f16": (C.c_int, [C.POINTER(SeDesc), _i32, _vp, _i64, _vp]),
     "ml_se_residual_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ml_se_residual_f32": (C.c_int, [C.POINTER(SeResidualDesc), _vp, _i64, _vp]),
+    "ml_se_bottleneck_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ml_se_bottleneck_f32": (C.c_int, [C.POINTER(SeBottleneckDesc), _vp, _i64, _vp]),
+    "ml_se_bottleneck_f16": (C.c_int, [C.POINTER(SeBottleneckDesc), _vp, _i64, _vp]),
     "ml_restore_boxes_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "ml_detection_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ml_detection_proposal_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp]),

@@ -3,4 +3,5 @@ from .base import BACKBONE_LAYERS, BackBonePreProcess, BackboneModel, load_backb
 from .mobilenet import MobileNetV1
 from .resnext import ResNeXt50
 from .resnext101 import ResNeXt101
+from .senet import SEResNet50, SEResNeXt50
 from .seresnet34 import SEResNet34

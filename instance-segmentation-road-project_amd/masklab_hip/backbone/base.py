@@ -2,7 +2,8 @@
 (BackBonePreProcess :22-84, BACKBONE_LAYERS :104-182, load_backbone :185-316).
 
 Backbones on the hot path: 'resnext50' (in-tree in the reference), 'seresnet34' (the reference project's own model,
-vendored thirdparty/classification_models) and 'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises NotImplementedError like the
+vendored thirdparty/classification_models), 'seresnet50' and 'seresnext50' (the same vendored model zoo, senet.py) and
+'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises NotImplementedError like the
 reference does for unknown types.  BatchNormalization is folded into the conv weights at load
 time; the 3-channel stems read a channel-padded NHWC4 image written by the preprocess kernel.
 """
@@ -20,6 +21,11 @@ BACKBONE_LAYERS = {
     # the reference project's own backbone (road_project/train.py:36-37; taps reference :126-132)
     "seresnet34": {"C1": "relu0", "C2": "stage2_unit1_relu1", "C3": "stage3_unit1_relu1", "C4": "stage4_unit1_relu1",
                    "C5": "relu1"},
+    # vendored thirdparty senet.py (reference :133-146): Keras auto-named Activations, see backbone/senet.py
+    "seresnet50": {"C1": "activation", "C2": "activation_15", "C3": "activation_35", "C4": "activation_65",
+                   "C5": "activation_80"},
+    "seresnext50": {"C1": "activation", "C2": "activation_16", "C3": "activation_36", "C4": "activation_66",
+                    "C5": "activation_80"},
     "mobilenet": {"C1": "conv_pw_1_relu", "C2": "conv_pw_3_relu", "C3": "conv_pw_5_relu",
                   "C4": "conv_pw_11_relu", "C5": "conv_pw_13_relu"},
 }
@@ -76,6 +82,7 @@ class BackboneModel(Layer):
         from .mobilenet import MobileNetV1
         from .resnext import ResNeXt50
         from .resnext101 import ResNeXt101
+        from .senet import SEResNet50, SEResNeXt50
         from .seresnet34 import SEResNet34
         bt = backbone_type.lower()
         self.backbone_type = bt
@@ -92,6 +99,10 @@ class BackboneModel(Layer):
         elif bt == 'seresnet34':
             self.preprocess = BackBonePreProcess(rgb=True, mean_shift=False, normalize=0)     # :232-234, then bn_data
             self.body = SEResNet34()
+            same = True
+        elif bt in ('seresnet50', 'seresnext50'):
+            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=True, normalize=3)      # :220-223 / :238-241
+            self.body = SEResNet50() if bt == 'seresnet50' else SEResNeXt50()
             same = True
         elif bt == 'mobilenet':
             self.preprocess = BackBonePreProcess(rgb=False, mean_shift=False, normalize=2)    # :254-256
@@ -187,8 +198,8 @@ def load_backbone(backbone_type="resnet50", backbone_outputs=('C3', 'C4', 'C5', 
     if backbone_type.lower() not in BACKBONE_LAYERS:
         raise NotImplementedError(
             f"backbone_type must be one of {list(BACKBONE_LAYERS.keys())} (got '{backbone_type}'); the other "
-            f"reference backbones need un-vendored keras_applications / efficientnet weights and are outside "
-            f"the accelerated hot path")
+            f"reference backbones build on code the reference does not vendor (keras_applications, "
+            f"tf.keras.applications, efficientnet) and are outside the accelerated hot path")
     model = BackboneModel(backbone_type, backbone_outputs, num_features)
     model.build((None, None, None, 3))
     return model

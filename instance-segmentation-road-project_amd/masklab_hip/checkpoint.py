@@ -114,33 +114,71 @@ def _our_sublayers(specs):
 _BACKBONE_SE_RE = re.compile(r"^stage(\d+)_unit(\d+)_se/conv([12])/")
 
 
-def _backbone_channel_se(weights, specs, table):
-    """(key, None, 'conv2d', model prefix, remainder parts) rows for the backbone's auto-named ChannelSE convs, paired
-    with the model's `stage*_unit*_se/conv*` sub-layers by creation order; [] when the model declares none."""
-    ours = sorted({(int(m.group(1)), int(m.group(2)), int(m.group(3))) for m in map(_BACKBONE_SE_RE.match, specs) if m})
-    if not ours:
-        return []
-    found = {}                                      # N -> [(key, file prefix, remainder parts)]
+def _backbone_auto(weights, cls):
+    """{N: [(key, file prefix, remainder parts)]} of the checkpoint's auto-named `cls` layers outside every head scope."""
+    found = {}
     for key in weights:
         parts = key.split("/")
         for pos, comp in enumerate(parts[:-1]):
             if re.sub(r"_\d+$", "", comp) in _SCOPES:
                 break
-            m = _AUTO_RE.match(comp)
-            if m and m.group(1) == "conv2d":
+            m = _BACKBONE_AUTO_RE.match(comp)
+            if m and m.group(1) == cls:
                 found.setdefault(int(m.group(2) or 0), []).append((key, "/".join(parts[:pos + 1]), parts[pos + 1:]))
                 break
-    if len(found) != len(ours):
-        raise ValueError(f"checkpoint has {len(found)} auto-named 'conv2d' layers outside the heads, the model's "
-                         f"backbone declares {len(ours)} ChannelSE convs: a different backbone?")
+    return found
+
+
+def _pair_by_order(weights, cls, targets, what, table):
+    found = _backbone_auto(weights, cls)
+    if len(found) != len(targets):
+        raise ValueError(f"checkpoint has {len(found)} auto-named '{cls}' layers outside the heads, the model's "
+                         f"backbone declares {len(targets)} {what}: a different backbone?")
     rows = []
-    for (s, u, i), n in zip(ours, sorted(found)):
-        target = f"stage{s}_unit{u}_se/conv{i}"
+    for target, n in zip(targets, sorted(found)):
         for key, src, rest in found[n]:
-            rows.append((key, None, "conv2d", target, rest))
+            rows.append((key, None, cls, target, rest))
         if table is not None:
-            table.append(("backbone", "conv2d", n, found[n][0][1], target))
+            table.append(("backbone", cls, n, found[n][0][1], target))
     return rows
+
+
+# SE-ResNet-50 / SE-ResNeXt-50 (thirdparty senet.py) name none of their layers: every Conv2D and BatchNormalization of the
+# backbone is `conv2d_N` / `batch_normalization_N`, created in this order -- the stem's conv and BN, then per unit conv1,
+# bn1, the 32 group convs (or the one dense 3x3), bn2, conv3, bn3, [shortcut conv, shortcut BN], the two ChannelSE convs.
+_BACKBONE_AUTO_RE = re.compile(r"^(conv2d|batch_normalization)(?:_(\d+))?$")
+_SENET50_UNIT_RE = re.compile(r"^stage(\d+)_unit(\d+)_conv3/kernel$")
+
+
+def _senet50_order(specs):
+    """(conv prefixes, BN prefixes) of an SE-ResNet-50 / SE-ResNeXt-50 model in the reference's creation order."""
+    units = sorted((int(m.group(1)), int(m.group(2))) for m in map(_SENET50_UNIT_RE.match, specs) if m)
+    convs, bns = ["conv0"], ["bn0"]
+    for s, u in units:
+        b = f"stage{s}_unit{u}_"
+        groups = sorted(int(m.group(1)) for m in (re.match(r"^%sconv2/group(\d+)/kernel$" % b, k) for k in specs) if m)
+        convs += [b + "conv1"] + ([f"{b}conv2/group{g}" for g in groups] or [b + "conv2"]) + [b + "conv3"]
+        bns += [b + "bn1", b + "bn2", b + "bn3"]
+        if f"{b}sc/kernel" in specs:
+            convs.append(b + "sc")
+            bns.append(b + "sc_bn")
+        convs += [b + "se/conv1", b + "se/conv2"]
+    return convs, bns
+
+
+def _backbone_channel_se(weights, specs, table):
+    """(key, None, class, model prefix, remainder parts) rows for the backbone's auto-named layers, paired with the
+    model's sub-layers by creation order: every conv and BN of an SE-ResNet-50 / SE-ResNeXt-50 backbone, SE-ResNet-34's
+    `stage*_unit*_se/conv*` ChannelSE convs; [] when the model declares none."""
+    if any(map(_SENET50_UNIT_RE.match, specs)) and any(map(_BACKBONE_SE_RE.match, specs)):
+        convs, bns = _senet50_order(specs)
+        return (_pair_by_order(weights, "conv2d", convs, "convs", table) +
+                _pair_by_order(weights, "batch_normalization", bns, "BatchNormalizations", table))
+    ours = sorted({(int(m.group(1)), int(m.group(2)), int(m.group(3))) for m in map(_BACKBONE_SE_RE.match, specs) if m})
+    if not ours:
+        return []
+    return _pair_by_order(weights, "conv2d", [f"stage{s}_unit{u}_se/conv{i}" for s, u, i in ours], "ChannelSE convs",
+                          table)
 
 
 def rename_keras_auto_names(weights, specs, table=None):

@@ -277,8 +277,12 @@ class GroupedConv2D(Conv2D):
         Ho, Wo, _, _ = packing.resolve_padding(H, W, 3, 3, self.strides[0], 1, self.padding)
         return (input_shape[0], Ho, Wo, self.filters)
 
+    def kernel(self, weights):
+        """The [3,3,filters(in), c(m)] kernel: out[g*c+m] = sum_i conv(x[g*c+i], kernel[.., g*c+i, m])."""
+        return self._get(weights, "depthwise_kernel")
+
     def folded(self, weights):
-        k = self._get(weights, "depthwise_kernel")          # [3,3,filters(in), c(m)]
+        k = self.kernel(weights)                            # [3,3,filters(in), c(m)]
         b = None
         if self.fold_bn:
             name, eps, scale = self.fold_bn[:3]

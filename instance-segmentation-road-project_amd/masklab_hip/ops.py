@@ -805,12 +805,12 @@ def squeeze_excite_multi(problems):
     return outs
 
 
-def _se_res_check(t, name, like=None):
+def _se_res_check(t, name, like=None, op="se_residual"):
     _require_dev(t, name)
     if t.dtype != torch.float32:
-        raise ValueError(f"se_residual: `{name}` must be float32")
+        raise ValueError(f"{op}: `{name}` must be float32")
     if like is not None and tuple(t.shape) != tuple(like):
-        raise ValueError(f"se_residual: `{name}` has shape {tuple(t.shape)}, expected {tuple(like)}")
+        raise ValueError(f"{op}: `{name}` has shape {tuple(t.shape)}, expected {tuple(like)}")
 
 
 def se_residual(x, shortcut, w1, b1, w2, b2, scale, shift, want_y=False):
@@ -843,6 +843,47 @@ def se_residual(x, shortcut, w1, b1, w2, b2, scale, shift, want_y=False):
     with _Prof("se_residual", 0, nbytes, f"B={B} HW={HW} C={Cc} Hd={Hd}{' +y' if want_y else ''}"):
         _lib.check(lib.ml_se_residual_f32(C.byref(d), _ptr(ws), ws.numel(), _stream()), "ml_se_residual_f32")
     return act, y
+
+
+def se_bottleneck(c3, residual, w1, b1, w2, b2, out=None):
+    """ml_se_bottleneck_f32 / _f16: the tail of an SE-ResNet-50 / SE-ResNeXt-50 bottleneck unit in three launches --
+    g = sigmoid(w2^T relu(w1^T mean_hw(c3) + b1) + b2) once per sample, out = relu(c3 * g + residual).
+    c3 / residual: contiguous NHWC [B,H,W,C], both float32 or both float16 (fp32 arithmetic, one rounding at the store);
+    w1 [C, Hd], b1 [Hd], w2 [Hd, C], b2 [C] device fp32.  `out` (same shape and dtype) may be c3 itself; else allocated.
+    Scratch from ops.workspace (graph-safe: grow-only, keyed by stream)."""
+    lib = _lib.load()
+    _require_dev(c3, "c3")
+    _require_dev(residual, "residual")
+    if c3.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"se_bottleneck: c3 must be float32 or float16, got {c3.dtype}")
+    shape = tuple(c3.shape)
+    if residual.dtype != c3.dtype or tuple(residual.shape) != shape:
+        raise ValueError(f"se_bottleneck: residual {tuple(residual.shape)} / {residual.dtype} does not match c3 "
+                         f"{shape} / {c3.dtype}")
+    B, Cc = int(shape[0]), int(shape[-1])
+    HW = c3.numel() // max(1, B * Cc)
+    if w1.dim() != 2 or w1.shape[0] != Cc:
+        raise ValueError("se_bottleneck: w1 must be [C, Hd]")
+    Hd = int(w1.shape[1])
+    for t, name, want in ((w1, "w1", (Cc, Hd)), (b1, "b1", (Hd,)), (w2, "w2", (Hd, Cc)), (b2, "b2", (Cc,))):
+        _se_res_check(t, name, want, "se_bottleneck")
+    if out is None:
+        out = torch.empty_like(c3)
+    else:
+        _require_dev(out, "out")
+        if out.dtype != c3.dtype or tuple(out.shape) != shape:
+            raise ValueError("se_bottleneck: out must have c3's shape and dtype")
+    d = _lib.SeBottleneckDesc()
+    d.c3, d.residual, d.out = c3.data_ptr(), residual.data_ptr(), out.data_ptr()
+    d.w1, d.b1, d.w2, d.b2 = w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr()
+    d.B, d.HW, d.C, d.Hd = B, HW, Cc, Hd
+    half = c3.dtype == torch.float16
+    ws = workspace(max(16, int(lib.ml_se_bottleneck_workspace_bytes(B, HW, Cc))), c3.device, "se_bottleneck")
+    nbytes = c3.element_size() * 4.0 * c3.numel()           # c3 read twice (pool, tail), residual once, out written once
+    with _Prof("se_bottleneck_h" if half else "se_bottleneck", 0, nbytes, f"B={B} HW={HW} C={Cc} Hd={Hd}"):
+        fn = lib.ml_se_bottleneck_f16 if half else lib.ml_se_bottleneck_f32
+        _lib.check(fn(C.byref(d), _ptr(ws), ws.numel(), _stream()), "ml_se_bottleneck")
+    return out
 
 
 def bn_relu(x, scale, shift):
