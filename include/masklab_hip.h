@@ -57,7 +57,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_draw_boxes_u8, ml_draw_instance_u8,
                                             ml_draw_segmentation_u8, ml_serving_visualize_u8;
                                             (additive, same version) ml_se_bottleneck_desc,
-                                            ml_se_bottleneck_f32 / _f16 / _workspace_bytes                 */
+                                            ml_se_bottleneck_f32 / _f16 / _workspace_bytes;
+                                            (additive, same version) ml_jpeg_encode_u8 / _capacity /
+                                            _workspace_bytes                                               */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -627,6 +629,30 @@ int ml_serving_visualize_u8(const uint8_t *images, const int32_t *det, const int
                             int32_t *threshold_ws, const float *instance_colors, int32_t Ki, float instance_alpha,
                             const float *semantic_colors, int32_t Ks, float semantic_alpha, int32_t B, int32_t n,
                             int32_t mh, int32_t mw, int32_t H, int32_t W, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Serving 'visualize' content: EncodeImageContent (engine/layers/misc.py:343-351, tf.io.encode_jpeg with its
+ * defaults).  Baseline sequential DCT, 8 bit, Y Cb Cr sampled 2x2 / 1x1 / 1x1 in one interleaved scan, no restart
+ * markers, the Annex K quantisation tables scaled by the libjpeg quality rule (s = 5000 / q below 50, else 200 - 2 q;
+ * Q = clamp((base * s + 50) / 100, 1, 255)), the four Annex K Huffman tables, a JFIF APP0 header (300 x 300 dpi).
+ * Samples: Y = (FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16, Cb = (-FIX(.16874) R - FIX(.33126) G +
+ * FIX(.5) B + (128 << 16) + 32767) >> 16, Cr = (FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ * with FIX(x) = int(x * 65536 + 0.5); planes padded to a multiple of 16 by replicating the last column and row (those
+ * samples are encoded: no "dummy" blocks); chroma the 2x2 box (a + b + c + d + bias) >> 2, bias 1 / 2 in even / odd
+ * output columns; level shift -128; the orthonormal 8x8 DCT of T.81 A.3.3 in fp32; coefficient = trunc(|v| / Q + 0.5)
+ * with the sign of v.
+ * ------------------------------------------------------------------------------------------- */
+/* Bytes per image that no H x W frame can exceed at any quality: the header, twice (byte stuffing) the scan at the
+ * longest code plus magnitude bits for every coefficient (DC 11 + 11, AC 16 + 10 bits), EOI; a multiple of 16.
+ * ML_E_BADARG for a non-positive dimension, one above 65535 or a frame whose bit offsets pass 32 bits.       */
+int64_t ml_jpeg_encode_capacity(int32_t H, int32_t W);
+int64_t ml_jpeg_encode_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* images uint8 [B,H,W,3] -> out uint8 [B,capacity]: image b's file is out[b][0 .. lengths[b]), lengths int32 [B].
+ * 1 <= quality <= 100 (the reference uses 95), capacity >= ml_jpeg_encode_capacity(H, W), workspace 16-byte
+ * aligned and of ml_jpeg_encode_workspace_bytes(B, H, W); no buffer may overlap another.  The bytes depend only on
+ * (frame, quality).  No host synchronisation: graph-capturable.                                              */
+int ml_jpeg_encode_u8(const uint8_t *images, int32_t B, int32_t H, int32_t W, int32_t quality, uint8_t *out,
+                      int64_t capacity, int32_t *lengths, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,8 @@ def get_custom_objects():
              "MaskDistribute", "PyramidRoiAlign", "ResizeLike", "AtrousSeparableConv2D", "ASPPNetwork",
              "SegmentationSubNet", "SqueezeExcite", "MobileSeparableConv2D", "DownSampleInput", "UpSampleOutput",
              "TrimInstances", "SemanticSmoothing", "CropAndPadMask", "CrackToInstance", "SummaryOutput",
-             "IncludeMyRoad", "CalculateInstanceSize", "DrawSegmentation", "DrawInstance", "DrawBoxes"]
+             "IncludeMyRoad", "CalculateInstanceSize", "DrawSegmentation", "DrawInstance", "DrawBoxes", "EncodeImageContent",
+             "DecodeImageContent"]
     reg = {n: getattr(L, n) for n in names}
     reg["BackBonePreProcess"] = BackBonePreProcess
     reg["GroupNormalization"] = GroupNormalization

@@ -159,6 +159,9 @@ SIGNATURES = {
     "ml_draw_instance_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _f32] + [_i32] * 4 + [_vp]),
     "ml_draw_segmentation_u8": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i32, _f32] + [_i32] * 3 + [_vp]),
     "ml_serving_visualize_u8": (C.c_int, [_vp] * 7 + [_i32, _f32, _vp, _i32, _f32] + [_i32] * 6 + [_vp]),
+    "ml_jpeg_encode_capacity": (_i64, [_i32, _i32]),
+    "ml_jpeg_encode_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ml_jpeg_encode_u8": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _i64, _vp, _vp, _vp]),
 }
 DRAW_MAX_CLASSES = 16    # ML_DRAW_MAX_CLASSES
 

@@ -3,7 +3,7 @@ from .detection import *  # noqa: F401,F403
 from .detection import (BoxRegressionSubNet, ClassificationSubNet, DetectionProposal, FeaturePyramid,
                         NormalizeBoxes, PriorLayer, RestoreBoxes)
 from .instance import MaskDistribute, MaskSubNet, PyramidRoiAlign, TrimInstances
-from .misc import (CalculateInstanceSize, CrackToInstance, CropAndPadMask, DownSampleInput, DrawBoxes, DrawInstance,
-                   DrawSegmentation, Identity, IncludeMyRoad, MobileSeparableConv2D, MoldBatch, ReLU, ResizeLike,
-                   SqueezeExcite, SummaryOutput, UpSampleOutput)
+from .misc import (CalculateInstanceSize, CrackToInstance, CropAndPadMask, DecodeImageContent, DownSampleInput, DrawBoxes,
+                   DrawInstance, DrawSegmentation, EncodeImageContent, Identity, IncludeMyRoad, MobileSeparableConv2D,
+                   MoldBatch, ReLU, ResizeLike, SqueezeExcite, SummaryOutput, UpSampleOutput)
 from .semantic import ASPPNetwork, AtrousSeparableConv2D, SegmentationSubNet, SemanticSmoothing

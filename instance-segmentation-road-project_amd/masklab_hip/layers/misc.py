@@ -3,7 +3,8 @@
 deploy wrapper either side of it (DownSampleInput :143-154, UpSampleOutput :169-196) and the arithmetic
 layers of the serving graph (CropAndPadMask :358-401, CrackToInstance :524-560, SummaryOutput :563-598,
 IncludeMyRoad :601-626, CalculateInstanceSize :629-727) and of its 'visualize' output (DrawSegmentation :404-431,
-DrawInstance :434-475, DrawBoxes :478-503)."""
+DrawInstance :434-475, DrawBoxes :478-503) and the two codec layers at its ends (DecodeImageContent :328-340 on the
+host, EncodeImageContent :343-351 on the device)."""
 import numpy as np
 import torch
 
@@ -426,3 +427,55 @@ class DrawBoxes(Layer):
     def call(self, inputs, **kwargs):
         images, det_outs = inputs[0], inputs[1]
         return ops.draw_boxes(images.contiguous(), det_outs.contiguous())
+
+
+# ----------------------------------------------------------------------------- serving: image content in and out
+class EncodeImageContent(Layer):
+    """JPEG-encode the first frame of the batch (reference misc.py:343-351, tf.io.encode_jpeg with its defaults):
+    inputs uint8 [B,H,W,3] on the device -> NumPy object array [1] holding the file as `bytes`.  The encoder runs on the
+    device (ops.encode_jpeg); the length is read first, then exactly that many bytes are copied."""
+
+    def __init__(self, quality=95, **kwargs):
+        self.quality = quality
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        buffer, lengths = ops.encode_jpeg(inputs[0:1].contiguous(), self.quality)
+        contents = np.empty((1,), dtype=object)
+        contents[0] = ops.jpeg_contents(buffer, lengths)[0]
+        return contents
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"quality": self.quality})
+        return config
+
+
+class DecodeImageContent(Layer):
+    """Decode an image file (jpg, png ...) into a frame (reference misc.py:328-340, tf.io.decode_image(channels=3)):
+    `bytes`, or a length-1 sequence / array of them -> uint8 [1,H,W,3] tensor (on `device` if given).  Decoding runs on
+    the host through Pillow, imported lazily."""
+
+    def __init__(self, device=None, **kwargs):
+        self.device = device
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        if not isinstance(inputs, (bytes, bytearray, memoryview)):
+            items = list(np.asarray(inputs, dtype=object).reshape(-1))
+            if len(items) != 1:                                                          # tf.reshape(inputs, shape=())
+                raise ValueError(f"DecodeImageContent takes one image content, got {len(items)}")
+            inputs = items[0]
+            if not isinstance(inputs, (bytes, bytearray, memoryview)):
+                raise ValueError(f"DecodeImageContent takes the bytes of an image file, got {type(inputs).__name__}")
+        try:
+            from PIL import Image
+        except ImportError as e:
+            raise ImportError("DecodeImageContent decodes on the host with Pillow (PIL), which is not installed: install "
+                              "Pillow, or decode the request yourself and give the uint8 [1,H,W,3] frame to the "
+                              "deploy / serving model") from e
+        import io
+        with Image.open(io.BytesIO(bytes(inputs))) as im:
+            frame = np.array(im.convert("RGB"), dtype=np.uint8)
+        image = torch.from_numpy(frame)[None]
+        return image.to(self.device) if self.device is not None else image

@@ -1273,3 +1273,46 @@ def serving_visualize(images, det_outs, ins_outs, seg_outs, instance_colors, ins
                                                _ptr(thr), ci, Ki, float(instance_alpha), cs, Ks, float(semantic_alpha), B, n,
                                                mh, mw, H, W, _stream()), "ml_serving_visualize_u8")
     return out
+
+
+# ----------------------------------------------------------------------------- serving 'visualize' content (JPEG)
+_jpeg_capacity = {}
+
+
+def jpeg_capacity(H, W):
+    """ml_jpeg_encode_capacity: bytes no H x W frame's file can exceed at any quality."""
+    cap = _jpeg_capacity.get((H, W))
+    if cap is None:
+        cap = int(_lib.load().ml_jpeg_encode_capacity(H, W))
+        if cap < 0:
+            _lib.check(cap, "ml_jpeg_encode_capacity")
+        _jpeg_capacity[(H, W)] = cap
+    return cap
+
+
+def encode_jpeg(images, quality=95):
+    """ml_jpeg_encode_u8 (EncodeImageContent, tf.io.encode_jpeg's defaults): uint8 [B,H,W,3] -> (buffer uint8
+    [B,capacity], lengths int32 [B]); image b's file is buffer[b, :lengths[b]].  Both stay on the device and nothing is
+    read back (graph-capturable); the bytes past a length are unspecified."""
+    lib = _lib.load()
+    B, H, W = _frames(images, "encode_jpeg")
+    if not isinstance(quality, (int, np.integer)) or isinstance(quality, bool) or not 1 <= quality <= 100:
+        raise ValueError(f"encode_jpeg: quality must be an integer in 1..100, got {quality!r}")
+    cap = jpeg_capacity(H, W)
+    nbytes = int(lib.ml_jpeg_encode_workspace_bytes(B, H, W))
+    if nbytes < 0:
+        _lib.check(nbytes, "ml_jpeg_encode_workspace_bytes")
+    ws = workspace(nbytes, images.device, "jpeg")
+    out = torch.empty((B, cap), dtype=torch.uint8, device=images.device)
+    lengths = torch.empty((B,), dtype=torch.int32, device=images.device)
+    with _Prof("jpeg_encode", 0, images.numel(), f"B={B} {H}x{W} q={quality}"):
+        _lib.check(lib.ml_jpeg_encode_u8(_ptr(images), B, H, W, int(quality), _ptr(out), cap, _ptr(lengths), _ptr(ws),
+                                         _stream()), "ml_jpeg_encode_u8")
+    return out, lengths
+
+
+def jpeg_contents(buffer, lengths):
+    """The files of encode_jpeg as host `bytes`, one per image: the lengths are read first, then exactly that many
+    bytes of each row are copied."""
+    n = lengths.cpu().tolist()                                    # synchronises with the encoder's stream
+    return [bytes(buffer[b, :k].cpu().numpy()) for b, k in enumerate(n)]

@@ -13,7 +13,7 @@ from . import backbone
 from . import keras_like as K
 from .config import ModelConfiguration
 from .layers import (ASPPNetwork, BoxRegressionSubNet, ClassificationSubNet, CropAndPadMask, DetectionProposal,
-                     DownSampleInput, DrawBoxes, DrawInstance, DrawSegmentation, SummaryOutput,
+                     DownSampleInput, DrawBoxes, DrawInstance, DrawSegmentation, EncodeImageContent, SummaryOutput,
                      FeaturePyramid, MaskDistribute, MaskSubNet, PriorLayer, PyramidRoiAlign, ResizeLike,
                      RestoreBoxes, SegmentationSubNet, SemanticSmoothing, TrimInstances, UpSampleOutput)
 from .prior import PriorBoxes
@@ -620,11 +620,15 @@ class ServingModel(K.Layer):
     (class, cx, cy, w, h, conf, pixel count, instance size, horizontal size, vertical size, include_my_road).
     visualize=True adds the 'visualize' output in front, the reference's order: the frame uint8 [B,H,W,3] after
     DrawBoxes -> DrawInstance(instance colours) -> DrawSegmentation(semantic colours) (:32-40), colours and alphas from
-    configuration.postprocess.  Only its last step, EncodeImageContent (JPEG encode), and the JPEG decode in front are
-    image I/O outside this library: the frames come in decoded and the rendered frame goes out as pixels."""
+    configuration.postprocess.  encode=True (with visualize=True) finishes it like the reference (:41): the first output
+    is EncodeImageContent's JPEG content, encoded on the device (ops.encode_jpeg) -- `call` returns (buffer uint8
+    [B,capacity], lengths int32 [B]) in its place, both on the device, and `predict` one `bytes` per image.  The frames
+    come in decoded; masklab_hip.serving puts DecodeImageContent in front."""
 
-    def __init__(self, configuration, deploy_model, name='serving', visualize=False):
+    def __init__(self, configuration, deploy_model, name='serving', visualize=False, encode=False):
         super().__init__(name=name)
+        if encode and not visualize:
+            raise ValueError("ServingModel(encode=True) encodes the 'visualize' output: it needs visualize=True")
         post = configuration.postprocess
         self.deploy_model = deploy_model
         self.crop_and_pad = CropAndPadMask()
@@ -634,8 +638,15 @@ class ServingModel(K.Layer):
             self.draw_boxes = DrawBoxes()
             self.draw_instance = DrawInstance(post.instance_colors, post.instance_alpha)
             self.draw_segmentation = DrawSegmentation(post.semantic_colors, post.semantic_alpha)
+        self.encode = bool(encode)
+        if self.encode:
+            self.encode_content = EncodeImageContent()
         self.output_names = ['visualize', 'summarize'] if self.visualize else ['summarize']
         self.built = True
+
+    def _content(self, vis):
+        from . import ops
+        return ops.encode_jpeg(vis, self.encode_content.quality) if self.encode else vis
 
     def call(self, images, **kwargs):
         if not isinstance(images, torch.Tensor):
@@ -652,7 +663,7 @@ class ServingModel(K.Layer):
             vis = self.draw_boxes([images, det_outs])                                       # :34
             vis = self.draw_instance([vis, det_outs, crop_and_pad_masks])                   # :35-37
             vis = self.draw_segmentation([vis, seg_outs])                                   # :38-40
-            return [vis, summary]
+            return [self._content(vis), summary]                                            # :41
         # CropAndPadMask folded into SummaryOutput: same numbers bit for bit, no [B,n,H,W] tensor
         summary = self.summary([det_outs, seg_outs, ins_outs], from_rois=True)
         if not self.visualize:
@@ -662,18 +673,21 @@ class ServingModel(K.Layer):
         di, ds = self.draw_instance, self.draw_segmentation
         vis = ops.serving_visualize(images, det_outs.contiguous(), ins_outs.contiguous(), seg_outs.contiguous(), di.colors,
                                     di.alpha, ds.colors, ds.alpha)
-        return [vis, summary]
+        return [self._content(vis), summary]
 
     def predict(self, images, **kwargs):
         out = self.call(images, **kwargs)
         torch.cuda.synchronize(self.deploy_model.model.device)
+        if self.encode:
+            from . import ops
+            return [ops.jpeg_contents(*out[0]), out[1].cpu().numpy()]
         if self.visualize:
             return [o.cpu().numpy() for o in out]
         return out.cpu().numpy()
 
 
-def construct_serving_network(configuration: ModelConfiguration, deploy_model, visualize=False):
-    return ServingModel(configuration, deploy_model, visualize=visualize)
+def construct_serving_network(configuration: ModelConfiguration, deploy_model, visualize=False, encode=False):
+    return ServingModel(configuration, deploy_model, visualize=visualize, encode=encode)
 
 
 def load_masklab_inference_model_from_weights(weights, config: ModelConfiguration, device="cuda"):
@@ -695,8 +709,9 @@ def load_masklab_inference_model_from_h5(save_path, config: ModelConfiguration, 
     writes it (needs `h5py`, imported lazily; the layer-name re-wiring of :515-586 becomes masklab_hip/checkpoint.py's
     name mapping) or the .npz tools/convert_keras_h5.py makes of it.  The networks are built from `config` (the
     reference rebuilds them from the loaded Keras model; `config.json` saved beside the weights, engine/train.py:31-32,
-    is that configuration).  serving=True puts DecodeImageContent (JPEG bytes in, misc.py:328-337) in front -- image I/O,
-    outside this library: decode on the host and call the serving=False model."""
+    is that configuration).  serving=True puts DecodeImageContent (JPEG bytes in, misc.py:328-337) in front: here that
+    wiring lives in masklab_hip.serving.load_serving_model_from_h5 (content bytes in, [JPEG content, summary] out),
+    built on the serving=False model; this function keeps refusing it."""
     if serving:
         raise NotImplementedError("load_masklab_inference_model_from_h5(serving=True) wraps the model in "
                                   "DecodeImageContent (JPEG byte strings in): image decoding is outside the accelerated "
