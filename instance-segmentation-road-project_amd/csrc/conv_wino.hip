@@ -12,41 +12,54 @@
 //   16 tg .. 16 tg + 15) x channel half h = w >> 2 (32 channels) x all 16 positions: 2 x 16 accumulators of the 16x16x4
 //   MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of its 4 tiles x 1
 //   channel per 16-wide half).  The patches of a tile group are staged once and read by both channel halves.
-//   K chunk = one K step = 4 input channels, staged by LDS DMA (buffer_load_dwordx4 ... lds, 16 B per lane, 1 KB per wave
-//   instruction, 4 per wave and chunk) straight from global memory into a ring of 4 slots (32 KB each), one barrier per
-//   chunk.  Iteration c: wait until this wave's DMA of chunk c + 1 has landed (vmcnt(4): chunk c + 2 stays in flight)
-//   and its LDS reads are done (lgkmcnt(0)); barrier; DMA chunk c + 3 into the slot chunk c - 1 used; 4 MFMAs of chunk c;
-//   the LDS reads of chunk c + 1 (16 patch values + 8 B fragments, into the other of two register sets); the other 28
-//   MFMAs of chunk c.  So a step's operands are read one step ahead, across the barrier, and no MFMA waits on LDS.
-//   A slot holds
-//     * the raw 4x4 patches of the block's 64 tiles as [tg 4][px 16][r 16][4 ch] float4s: one DMA instruction = 4 px x
-//       16 tiles.  Lane (r, kq) reads channel kq of tile r at a per-lane base + px x 256 B (ds_read2st64_b32); a b32
-//       read's 32-lane group hits bank 4r + kq mod 32 (2-way: the floor for b32 reads of 16-B channel quads, as in the
-//       padded image this replaces).  Out-of-image taps and tiles past the end carry an out-of-range buffer offset and
-//       land as zeros;
-//     * the transformed weights of both channel halves as [h 2][k 4][t 2][pq 4][r 16][4 p] float4s (n = 16 t + r): one
-//       DMA instruction = one contiguous 1 KB (k, t) row of the host layout; a b128 read's 16-lane group covers r = 0..15
-//       once: conflict-free.
-//   The patch resource is rebased per block (its first tap row) and per chunk (+4 channels), so the per-lane offsets are
+//   K step = 4 input channels = 32 MFMAs per wave.  Staging is by LDS DMA (buffer_load_dwordx4 ... lds, 16 B per lane, 1 KB
+//   per wave instruction) straight from global memory into two rings, with ONE barrier per two K steps:
+//     * patches in chunks of 8 channels (two K steps), 3 slots of 32 KB, 4 DMA instructions per wave and chunk.  A slot holds
+//       the raw 4x4 patches of the block's 64 tiles as [tg 4][px 16][tile 16][8 ch]; one DMA instruction = 2 px x 16 tiles x
+//       8 channels, a pixel's 32 contiguous bytes fetched by two ADJACENT lanes, so the instruction touches 32 lines of 128 B
+//       where a 4-channel chunk (one pixel per lane) touched 64: half the texture-path work per staged byte.  The two 16-byte
+//       channel quads of tile r sit in the order (q ^ (r >> 2 & 1)): lane (r, kq) reads channel kq of its K step's quad at a
+//       per-lane base + px x 512 B (ds_read2st64_b32), and a b32 read's 32-lane group hits 16 banks (2-way, as with the
+//       4-channel slots; unswizzled 8-channel tiles would be 4-way).  Out-of-image taps and tiles past the end carry an
+//       out-of-range buffer offset and land as zeros;
+//     * transformed weights per K step, 4 slots of 16 KB, 2 DMA instructions per wave and step: both channel halves as
+//       [h 2][k 4][t 2][pq 4][r 16][4 p] float4s (n = 16 t + r), one DMA instruction = one contiguous 1 KB (k, t) row of the
+//       host layout; a b128 read's 16-lane group covers r = 0..15 once: conflict-free.
+//   3 x 32 KB + 4 x 16 KB = 160 KB, all of the CU's LDS; the gn_partials exchange (256 B) reuses the ring's head after the
+//   loop.  Why these counts: operands are read into registers one K step ahead, so during iteration j (steps 2j, 2j + 1)
+//   the waves read patch chunks j and j + 1 and the weights of steps 2j + 1 and 2j + 2 while chunk j + 2 and the weights of
+//   steps 2j + 3 and 2j + 4 are written: 3 patch slots and 4 weight slots are the fewest that need no second barrier.  (Two
+//   64 KB slots of 8 channels each would have to be written while still being read.)  A DMA has one whole iteration, two K
+//   steps, to land: the distance the 4-slot ring of 4-channel chunks gave, now at a shorter step.
+//   Iteration j: s_waitcnt vmcnt(0) lgkmcnt(0) (this wave's DMAs of iteration j - 1 have landed, its LDS reads are done);
+//   s_barrier (every wave's); then two K steps.  A step is 32 MFMAs on operands that are already in registers AND already
+//   transformed, so it opens on the matrix pipe; placed among them and pinned there by sched_barriers:
+//     after the 4th MFMA    the LDS reads of the next step (16 patch values + 8 B fragments, into the other register set);
+//     after the 6th, 12th.. one DMA instruction each, 6 MFMAs apart: 5 in the iteration's first step (the 4 patch pieces,
+//                           which may miss L2, then weights), 3 in its second, the last one 14 MFMAs before the barrier;
+//     after the 17th..32nd  two adds each of the next step's input transform B^T d B (32 adds, kept scalar:
+//                           -fno-slp-vectorize in the Makefile), in the shadow of this step's MFMAs.
+//   The patch resource is rebased per block (its first tap row) and per chunk (+8 channels), so the per-lane offsets are
 //   32-bit and constant over the K loop while the tensor itself may exceed 4 GiB (the host checks that a block's rows
 //   span less than 2 GiB).  No staging registers and no exec-masked loads; the DMA of the chunks past the last one goes
 //   through empty resources, so the loop body is one basic block.
-//   K step: each lane applies B^T d B to its 16 patch values (32 adds, kept scalar: -fno-slp-vectorize in the Makefile)
-//   and issues 2 x 16 MFMAs, 4 positions per B fragment.
 //
-//   Costing (per CU: one block, 2 waves per SIMD; 128 accumulators + two operand sets of 48 <= 256 registers per lane,
-//   4 x 32 KB LDS):
-//     MFMA per chunk and SIMD: 2 waves x 16 positions x 2 halves = 64 x 32 cycles = 2048 cycles;
-//     VALU per chunk and wave: 32 transform adds (+ the output transform once per block): 1 VALU per MFMA, issued
-//       between MFMAs;
-//     staged per chunk and block: 16 KB of patches (each input pixel is read by up to 4 overlapping patches: L1 / L2 hits;
-//       half the patch bytes per MFMA of a 32-channel block) + 16 KB of weights = 32 KB per 2048 cycles = 16 B/clk/CU,
-//       against the ~30-39 B/clk the L1 -> LDS path moved in profiles/r04_h256_pmc.md; 4 DMA instructions per wave;
-//     LDS reads per chunk and wave: 16 x b32 + 8 x b128 = 6 KB for 32 MFMAs; the CU's LDS array: 8 waves x (8 x 8 +
-//       8 x 4) cycles + 32 KB of DMA writes = ~1000 of the chunk's 2048 cycles.
-//   Measured (profiles/r06_wino_after.md): 0.46-0.50 of the fp32 MFMA peak on the 128^2 convs, against 0.42 before; the
-//   MFMA pipe is still idle half the time with the LDS array and the texture path each under 40 % busy, so the
-//   remaining stall is not the staging bandwidth (a fifth ring slot, i.e. one more chunk in flight, changed nothing).
+//   Costing (per CU: one block, 2 waves per SIMD; 234 VGPRs, no scratch, no spills; 163840 B of LDS):
+//     MFMA per K step and SIMD: 2 waves x 16 positions x 2 halves = 64 x 32 cycles = 2048 cycles;
+//     VALU per step and wave: 32 transform adds (+ the output transform once per block), 2 per MFMA gap;
+//     staged per step and block: 16 KB of patches + 16 KB of weights; per two steps 32 patch DMA instructions of 32 lines
+//       and 32 weight DMA instructions of 8 lines;
+//     LDS reads per step and wave: 16 x b32 + 8 x b128 = 6 KB for 32 MFMAs.
+//   Where a step's time went before this layout (profiles/r09_wino_staging.md; one K step measured as the difference of the
+//   160- and 128-channel launches of the same 1024-block grid, / 8 steps / 4 rounds): 1.54 us = ~3700 cycles at 2.4 GHz
+//   for 2048 cycles of MFMA.  With the patch DMAs sent through empty resources (same instructions, no line fetched) the
+//   old kernel took 1.20 us per step, with the weight DMAs 1.60 (no change), with its 4 DMAs moved from the step's head to
+//   after the 16th MFMA 1.23: the loss was the patch DMAs' texture-path work, queued by all 8 waves at the head of every
+//   step in front of their MFMAs.  This kernel: 1.21 us per step (~2900 cycles); with empty patch resources 1.10, with
+//   every DMA empty 1.05; with a step's DMAs in one burst at its head instead of spread 1.31.  So halving the lines per
+//   patch instruction and spreading the issue each pay, ~0.1 us of texture-path queueing is left, and ~480 cycles per step
+//   beyond the MFMAs remain with no memory traffic at all (barrier, LDS reads, transform).  s_setprio 1 for waves 4-7
+//   measured as no gain and is left out; a second copy of the loop with another DMA phase for waves 4-7 spills.
 //   Against the direct kernel (conv_mfma.hip, 9 x 128 / 32 = 36 chunks of 64 32x32x2 MFMAs per 128 x 128 tile): the
 //   same output takes 16 / 36 of the MFMA cycles.
 //
@@ -65,20 +78,29 @@ namespace {
 constexpr int WMAXP = ML_CONV_MAX_PROBLEMS;
 constexpr int WT = 64;        // Winograd tiles per block
 constexpr int WN = 64;        // output channels per block
-constexpr int WK = 8;         // input channels per 8-channel block of the host weight layout (two K chunks)
+constexpr int WK = 8;         // input channels per 8-channel block of the host weight layout = one patch chunk (two K steps)
 constexpr int WCHUNK = WK * 32 * 16;   // floats of transformed weights per (32-channel block, 8-channel block) of the host layout
-constexpr int WSTEP = 4 * 32 * 16;     // floats of transformed weights per (32-channel block, 4-channel chunk)
-constexpr int NSLOT = 4;               // LDS ring slots, one 4-channel chunk each
-constexpr int SLOT_P = WT * 16 * 4;    // floats of patches per ring slot
-constexpr int SLOT = SLOT_P + 2 * WSTEP;   // floats per ring slot (32 KB)
-constexpr int LDS_BYTES = NSLOT * SLOT * 4 + 8 * 4 * 8;   // the ring + the gn_partials exchange (8 waves x 4 doubles)
+constexpr int WSTEP = 4 * 32 * 16;     // floats of transformed weights per (32-channel block, 4-channel K step)
+constexpr int NSLOT_P = 3;             // patch ring: slots of one 8-channel chunk (two K steps) each
+constexpr int SLOT_P = WT * 16 * 8;    // floats of patches per patch slot (32 KB)
+constexpr int NSLOT_W = 4;             // weight ring: slots of one 4-channel K step each
+constexpr int SLOT_W = 2 * WSTEP;      // floats of weights per weight slot (both channel halves, 16 KB)
+constexpr int RING_W = NSLOT_P * SLOT_P;   // the weight ring follows the patch ring
+constexpr int LDS_BYTES = (RING_W + NSLOT_W * SLOT_W) * 4;   // 160 KB: all of a CU's LDS; the gn exchange reuses its head
+static_assert(LDS_BYTES == 160 * 1024, "the two rings fill the CU's LDS");
+// Experiment builds (make wino-exp; never the default library): WINO_EXP bit 0 sends the patch DMAs, bit 1 the weight
+// DMAs through empty resources (same instructions, no line fetched, WRONG outputs: for timing only); WINO_EXP = 4 issues
+// a step's DMAs in one burst at the step's head instead of spread through its MFMAs.
+#ifndef WINO_EXP
+#define WINO_EXP 0
+#endif
 constexpr unsigned OOB = 0x80000000u;  // buffer offset of an out-of-image tap: >= the patch resource's num_records
 constexpr long long SPAN_MAX = 0x7fffff00ll;   // bytes a block's patch offsets may reach (< OOB)
 
 struct WProblem {
     ml_conv2d_desc d;
     int TH, TW, T;            // tile rows / columns per image, tiles in all (B * TH * TW)
-    int MB, NB, nchunks;      // 64-tile blocks, 64-channel blocks, 8-channel blocks (2 K chunks each)
+    int MB, NB, nchunks;      // 64-tile blocks, 64-channel blocks, 8-channel chunks (2 K steps each)
 };
 
 struct WArgs {
@@ -96,27 +118,31 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, float *dst, i
 #endif
 }
 
-__device__ __forceinline__ void bt_d_b(const float d[16], float v[16]) {
-    // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]; d, v row-major 4x4
-    float t[16];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j];
-        t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j];
-        t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j];
-        t[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2];
-        v[i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2];
-        v[i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1];
-        v[i * 4 + 3] = t[i * 4 + 1] - t[i * 4 + 3];
+// Operation k of 32 of V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1] (d, t, v row-major 4x4): 0..15 the column
+// pass t = B^T d (column k >> 2), 16..31 the row pass v = t B (row (k - 16) >> 2).  One add each, so the K loop can place
+// them singly among its MFMAs; k is a constant after unrolling.
+__device__ __forceinline__ void bt_d_b_op(int k, const float d[16], float t[16], float v[16]) {
+    if (k < 16) {
+        const int j = k >> 2;
+        switch (k & 3) {
+            case 0: t[0 * 4 + j] = d[0 * 4 + j] - d[2 * 4 + j]; break;
+            case 1: t[1 * 4 + j] = d[1 * 4 + j] + d[2 * 4 + j]; break;
+            case 2: t[2 * 4 + j] = d[2 * 4 + j] - d[1 * 4 + j]; break;
+            default: t[3 * 4 + j] = d[1 * 4 + j] - d[3 * 4 + j]; break;
+        }
+    } else {
+        const int i = (k - 16) >> 2;
+        switch (k & 3) {
+            case 0: v[i * 4 + 0] = t[i * 4 + 0] - t[i * 4 + 2]; break;
+            case 1: v[i * 4 + 1] = t[i * 4 + 1] + t[i * 4 + 2]; break;
+            case 2: v[i * 4 + 2] = t[i * 4 + 2] - t[i * 4 + 1]; break;
+            default: v[i * 4 + 3] = t[i * 4 + 1] - t[i * 4 + 3]; break;
+        }
     }
 }
 
 __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
-    extern __shared__ __align__(16) float lds[];       // ONE LDS object: [slot 2][SLOT] ring, then the gn exchange
+    extern __shared__ __align__(16) float lds[];       // ONE LDS object: the patch ring, then the weight ring
 
     int pi = 0;
     while (pi + 1 < args.n && (int)blockIdx.x >= args.start[pi + 1]) ++pi;
@@ -144,8 +170,9 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     const int r = lane & 15, kq = lane >> 4;
     const int tpi = P.TH * P.TW;
 
-    // ---- staging geometry (constant over the K loop).  Patch pieces of this wave: tile group wave >> 1, px blocks
-    // 2 (wave & 1) + i; lane (j = lane >> 4, r): tile 16 (wave >> 1) + r, px = 8 (wave & 1) + 4 i + j.
+    // ---- staging geometry (constant over the K loop).  Patch pieces of this wave: tile group wave >> 1, px pairs
+    // 4 (wave & 1) + i; lane l: px = 8 (wave & 1) + 2 i + (l >> 5), tile 16 (wave >> 1) + rt with rt = (l >> 1) & 15, channel
+    // quad (l & 1) ^ (rt >> 2 & 1) of the chunk's 8 channels: a lane pair fetches one pixel's 32 contiguous bytes.
     const int gt0 = mt * WT;
     long long base_pix;                                // the block's first tap row, flattened (b * H + y) * W
     {
@@ -154,9 +181,11 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     }
     const size_t cstride = (size_t)p.in_cstride;
     const float *pin = p.in + p.in_coff + (size_t)base_pix * cstride;
-    int voff_p[2];
+    int voff_p[4];
     {
-        const int gt = gt0 + (wave >> 1) * 16 + r;
+        const int rt = (lane >> 1) & 15;
+        const int quad = (lane & 1) ^ ((rt >> 2) & 1);
+        const int gt = gt0 + (wave >> 1) * 16 + rt;
         int bi = 0, ty = 0, tx = 0;
         if (gt < P.T) {
             bi = gt / tpi;
@@ -165,35 +194,32 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
             tx = rem - ty * P.TW;
         }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int px = 8 * (wave & 1) + 4 * i + kq;
+        for (int i = 0; i < 4; ++i) {
+            const int px = 8 * (wave & 1) + 2 * i + (lane >> 5);
             const int y = 2 * ty - 1 + (px >> 2), x = 2 * tx - 1 + (px & 3);
             voff_p[i] = (int)OOB;
             if (gt < P.T && y >= 0 && y < p.H && x >= 0 && x < p.W)
-                voff_p[i] = (int)((((long long)bi * p.H + y) * p.W + x - base_pix) * (long long)cstride * 4);
+                voff_p[i] = (int)((((long long)bi * p.H + y) * p.W + x - base_pix) * (long long)cstride * 4) + quad * 16;
         }
     }
     // weight pieces of this wave: channel half wave >> 2, k row wave & 3, t = i (+1024 B); lane (pq = lane >> 4, r)
-    // takes host float4 (16 t + r) * 4 + pq of that k row.  A chunk of 4 channels is half an 8-channel block of the host
-    // layout, so chunk c of a 32-channel block starts c * WSTEP floats in.
+    // takes host float4 (16 t + r) * 4 + pq of that k row.  A K step of 4 channels is half an 8-channel block of the host
+    // layout, so step s of a 32-channel block starts s * WSTEP floats in.
     const int voff_w = ((wave & 3) * 512 + r * 16 + kq * 4) * 4;
     const float *wsrc = p.wgt + (size_t)(2 * nt2 + (wave >> 2)) * P.nchunks * WCHUNK;
-    float *dst_p = lds + (wave >> 1) * 1024 + (wave & 1) * 512;
-    float *dst_w = lds + SLOT_P + (wave >> 2) * WSTEP + (wave & 3) * 512;
-    const int nsteps = 2 * P.nchunks;
+    float *dst_p = lds + (wave >> 1) * 2048 + (wave & 1) * 1024;
+    float *dst_w = lds + RING_W + (wave >> 2) * WSTEP + (wave & 3) * 512;
+    const int nch = P.nchunks, nsteps = 2 * P.nchunks;
 
-    // DMA of chunk c (4 channels) into ring slot c % 4; past the last chunk through empty resources (nothing is read)
-    auto stage = [&](int c) __attribute__((always_inline)) {
-        const bool real = c < nsteps;
-        const __amdgpu_buffer_rsrc_t rp =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(pin + c * 4), 0, real ? (int)OOB : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rw =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(wsrc + (size_t)c * WSTEP), 0, real ? WSTEP * 4 : 0, 0x00020000);
-        const int so = (c & 3) * SLOT;
-        dma16(rp, dst_p + so, voff_p[0]);
-        dma16(rp, dst_p + so + 256, voff_p[1]);
-        dma16(rw, dst_w + so, voff_w);
-        dma16(rw, dst_w + so + 256, voff_w + 1024);
+    // resources of patch chunk j (8 channels) and of the weights of K step s; past the end empty (nothing lands, nothing
+    // of it is used), so the loop body is one basic block
+    auto rsrc_p = [&](int j) __attribute__((always_inline)) {
+        const bool real = j < nch && !(WINO_EXP & 1);
+        return __builtin_amdgcn_make_buffer_rsrc((void *)(pin + j * 8), 0, real ? (int)OOB : 0, 0x00020000);
+    };
+    auto rsrc_w = [&](int s) __attribute__((always_inline)) {
+        const bool real = s < nsteps && !(WINO_EXP & 2);
+        return __builtin_amdgcn_make_buffer_rsrc((void *)(wsrc + (size_t)s * WSTEP), 0, real ? WSTEP * 4 : 0, 0x00020000);
     };
 
     f32x4 acc[2][16];
@@ -202,63 +228,107 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const float *pa_lane = lds + tg * 1024 + r * 4 + kq;                    // + px * 64
-    const float *pb_lane = lds + SLOT_P + h * WSTEP + kq * 512 + r * 4;     // + t * 256 + pq * 64
-    // the LDS operands of one K step (= one chunk): the lane's 16 patch values and its 8 B fragments
+    // lane (r, kq) reads channel kq of K step `half` of tile r: its quad sits at 4 (half ^ (r >> 2 & 1)) of the tile's 8
+    const float *pa_lane0 = lds + tg * 2048 + r * 8 + 4 * ((r >> 2) & 1) + kq;          // + px * 128
+    const float *pa_lane1 = lds + tg * 2048 + r * 8 + 4 * (((r >> 2) & 1) ^ 1) + kq;
+    const float *pb_lane = lds + RING_W + h * WSTEP + kq * 512 + r * 4;                 // + t * 256 + pq * 64
+    // the LDS operands of one K step: the lane's 16 patch values (d, transformed to v during the step before their use)
+    // and its 8 B fragments
     struct Ops {
-        float d[16];
+        float d[16], t[16], v[16];
         f32x4 b[2][4];
     };
-    auto read_ops = [&](int c, Ops &o) __attribute__((always_inline)) {
-        const float *pb = pb_lane + (c & 3) * SLOT;
+    auto read_ops = [&](const float *pa, const float *pb, Ops &o) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int pq = 0; pq < 4; ++pq) o.b[t][pq] = *reinterpret_cast<const f32x4 *>(pb + t * 256 + pq * 64);
-        const float *pa = pa_lane + (c & 3) * SLOT;
 #pragma unroll
-        for (int px = 0; px < 16; ++px) o.d[px] = pa[px * 64];
-    };
-    // chunk c's MFMAs (operands read during the previous step); the reads of chunk c + 1 go out after the first 4 of them
-    // and are pinned there.  Issued before the first MFMA they would be waited for by it: hipcc does not see the
-    // lgkmcnt(0) in front of the barrier and waits for its count of the previous step's reads, which the new ones join.
-    // Sunk to their first use (what the scheduler does by itself) they would expose their latency every step.
-    auto step = [&](int c, const Ops &cur, Ops &nxt) __attribute__((always_inline)) {
-        // chunk c + 1 has landed (this wave's DMA: vmcnt leaves chunk c + 2's 4 in flight; every wave's: the barrier), and
-        // every wave's reads of chunk c - 1 are done (lgkmcnt(0) before the barrier), so chunk c + 3 may go into its slot.
-        // A raw s_barrier: __syncthreads()'s fence would wait vmcnt(0) for the chunk still in flight.
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        stage(c + 3);
-        float v[16];
-        bt_d_b(cur.d, v);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int pq = 0; pq < 4; ++pq) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    acc[t][4 * pq + e] =
-                        __builtin_amdgcn_mfma_f32_16x16x4f32(v[4 * pq + e], cur.b[t][pq][e], acc[t][4 * pq + e], 0, 0, 0);
-                if (t == 0 && pq == 0) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    read_ops(c + 1, nxt);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        __builtin_amdgcn_sched_barrier(0);
+        for (int px = 0; px < 16; ++px) o.d[px] = pa[px * 128];
     };
 
+    // One K step: 32 MFMAs on operands whose patch values were transformed during the previous step, so the step opens on
+    // the matrix pipe.  Among them, pinned by sched_barriers: after the 4th the LDS reads of the next step (issued before
+    // the first MFMA they would be waited for by it: hipcc waits for its own count of outstanding reads); after the 6th,
+    // 12th, ... one DMA instruction each (NDMA of them, 6 MFMAs apart: the texture path takes one at a time and a burst of
+    // them queues the waves in front of their MFMAs); after the 17th .. 32nd two adds each of the next step's input
+    // transform, in the shadow of this step's MFMAs.
+    auto step = [&](const Ops &cur, Ops &nxt, const float *pa, const float *pb, const int ndma, auto dma) __attribute__((always_inline)) {
+#if WINO_EXP == 4
+#pragma unroll
+        for (int q = 0; q < ndma; ++q) dma(q);
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+        for (int m = 0; m < 32; ++m) {
+            const int t = m >> 4, pq = (m >> 2) & 3, e = m & 3;
+            acc[t][4 * pq + e] =
+                __builtin_amdgcn_mfma_f32_16x16x4f32(cur.v[4 * pq + e], cur.b[t][pq][e], acc[t][4 * pq + e], 0, 0, 0);
+            if (m == 3) {
+                __builtin_amdgcn_sched_barrier(0);
+                read_ops(pa, pb, nxt);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#if WINO_EXP != 4
+            if (m % 6 == 5 && m / 6 < ndma) {
+                __builtin_amdgcn_sched_barrier(0);
+                dma(m / 6);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#endif
+            if (m >= 16) {
+                bt_d_b_op(2 * (m - 16), nxt.d, nxt.t, nxt.v);
+                bt_d_b_op(2 * (m - 16) + 1, nxt.d, nxt.t, nxt.v);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+
+    // prologue: chunk 0 and K step 0 first, then what iteration 0's barrier needs
+    {
+        const __amdgpu_buffer_rsrc_t rp0 = rsrc_p(0), rp1 = rsrc_p(1), rw0 = rsrc_w(0), rw1 = rsrc_w(1), rw2 = rsrc_w(2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dma16(rp0, dst_p + i * 256, voff_p[i]);
+        dma16(rw0, dst_w, voff_w);
+        dma16(rw0, dst_w + 256, voff_w + 1024);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dma16(rp1, dst_p + SLOT_P + i * 256, voff_p[i]);
+        dma16(rw1, dst_w + SLOT_W, voff_w);
+        dma16(rw1, dst_w + SLOT_W + 256, voff_w + 1024);
+        dma16(rw2, dst_w + 2 * SLOT_W, voff_w);
+        dma16(rw2, dst_w + 2 * SLOT_W + 256, voff_w + 1024);
+    }
     Ops oa, ob;
-    stage(0);
-    stage(1);
-    stage(2);
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    read_ops(0, oa);
-    for (int c = 0; c < nsteps; c += 2) {              // nsteps is even (span % 32 == 0): the two operand sets alternate
-        step(c, oa, ob);
-        step(c + 1, ob, oa);
+    read_ops(pa_lane0, pb_lane, oa);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) bt_d_b_op(k, oa.d, oa.t, oa.v);
+
+    // Iteration j = K steps 2 j and 2 j + 1 = patch chunk j.  At its barrier every wave's DMA of patch chunk j + 1 and of
+    // the weights of steps 2 j + 1 and 2 j + 2 has landed (vmcnt(0): all were issued during iteration j - 1, the last of
+    // them 14 MFMAs before its end), and every wave has read chunk j - 1 and the weights up to step 2 j (lgkmcnt(0)), so
+    // chunk j + 2 and the weights of steps 2 j + 3 and 2 j + 4 may go into their slots.  A raw s_barrier: __syncthreads()'s
+    // fence is not needed, the waits are explicit.
+    int ps0 = 0, ps1 = SLOT_P, ps2 = 2 * SLOT_P;       // patch slots of chunks j, j + 1, j + 2
+    for (int j = 0; j < nch; ++j) {
+        const int w0 = (2 * j) & 3;                    // weight slot of step 2 j (0 or 2) and of step 2 j + 4
+        const int wa = ((w0 ^ 2) + 1) * SLOT_W, wb = w0 * SLOT_W;   // weight slots of steps 2 j + 3 and 2 j + 4
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const __amdgpu_buffer_rsrc_t rp = rsrc_p(j + 2), rwa = rsrc_w(2 * j + 3), rwb = rsrc_w(2 * j + 4);
+        // the 8 DMA instructions of the iteration: 5 in its first step (the patches first: they may miss L2), 3 in its second
+        auto dma = [&](int q) __attribute__((always_inline)) {
+            if (q < 4) dma16(rp, dst_p + ps2 + q * 256, voff_p[q]);
+            else if (q < 6) dma16(rwa, dst_w + wa + (q - 4) * 256, voff_w + (q - 4) * 1024);
+            else dma16(rwb, dst_w + wb + (q - 6) * 256, voff_w + (q - 6) * 1024);
+        };
+        step(oa, ob, pa_lane1 + ps0, pb_lane + (w0 + 1) * SLOT_W, 5, dma);
+        step(ob, oa, pa_lane0 + ps1, pb_lane + (w0 ^ 2) * SLOT_W, 3, [&](int q) __attribute__((always_inline)) { dma(q + 5); });
+        const int ps = ps0;
+        ps0 = ps1;
+        ps1 = ps2;
+        ps2 = ps;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the empty DMAs past the last chunk
 
@@ -323,7 +393,8 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         }
     }
     if (gn) {
-        double *lds_gn = reinterpret_cast<double *>(lds + NSLOT * SLOT);   // [wave 8][4]
+        double *lds_gn = reinterpret_cast<double *>(lds);   // [wave 8][4], over the ring's head: every wave is past its
+        __syncthreads();                                    // last LDS read and its last DMA has landed (vmcnt(0) above)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
 #pragma unroll

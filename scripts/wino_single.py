@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """One Winograd launch (conv_wino_f32) of a chosen head shape, N times -- the program scripts/kernel_pmc.sh runs under
 rocprofv3 --pmc, and the A/B timer of two library builds.  GPU box:
-    python3 scripts/wino_single.py [--shape tower|decoder|mask|all] [--reps N] [--lib PATH] [--save DIR] [--time]
+    python3 scripts/wino_single.py [--shape all|NAME[,NAME...]] [--reps N] [--lib PATH] [--save DIR] [--time]
 Shapes (8 x 1024^2 ResNeXt-50 bench step):
   tower   : the P3-P7 tower launch, `multi x5`: 8 images at 128^2, 64^2, 32^2, 16^2, 8^2, 128 -> 128, relu
   decoder : the 128^2 semantic / decoder conv, 8 images, 160 -> 128, relu
   mask    : the 14 x 14 mask-head launch, `multi x3`: 800 RoIs (100 per image) over three levels (400 / 250 / 150), 128 -> 128
+  level128: the decoder's grid at 128 -> 128: with `decoder` (the same 1024 blocks, 8 K steps more) the time per K step
 --lib loads another build of the library (the product path has no override), so the parent's build and this one can be
 timed in alternating processes; --save writes the sha256 of each output tensor's bytes to DIR/<shape>.sha256 (compare two builds
 bit for bit); --time prints
@@ -26,6 +27,7 @@ SHAPES = {
     "tower": (128, 128, [(8, 128), (8, 64), (8, 32), (8, 16), (8, 8)]),
     "decoder": (160, 128, [(8, 128)]),
     "mask": (128, 128, [(400, 14), (250, 14), (150, 14)]),
+    "level128": (128, 128, [(8, 128)]),
 }
 
 
@@ -46,7 +48,7 @@ def setup(name, seed=0):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shape", default="all", choices=("all",) + tuple(SHAPES))
+    ap.add_argument("--shape", default="all", help="all (the three shipped shapes) or a comma-separated list of " + ", ".join(SHAPES))
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--lib", default=None, help="an experiment build of the library")
     ap.add_argument("--save", default=None, metavar="DIR", help="write the sha256 of each output to DIR/<shape>.sha256")
@@ -55,7 +57,10 @@ def main():
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
     ops.set_conv_math("f32")
-    for name in (SHAPES if args.shape == "all" else (args.shape,)):
+    names = ("tower", "decoder", "mask") if args.shape == "all" else tuple(args.shape.split(","))
+    if any(n not in SHAPES for n in names):
+        ap.error("--shape: all or names out of " + ", ".join(SHAPES))
+    for name in names:
         probs, flops = setup(name)
         ops.PROFILE = []
         ops.conv2d_multi(probs)
