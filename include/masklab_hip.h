@@ -59,7 +59,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_se_bottleneck_desc,
                                             ml_se_bottleneck_f32 / _f16 / _workspace_bytes;
                                             (additive, same version) ml_jpeg_encode_u8 / _capacity /
-                                            _workspace_bytes                                               */
+                                            _workspace_bytes;
+                                            (additive, same version) ml_jpeg_decode_info / _packed_bytes /
+                                            _entropy / _workspace_bytes / _u8 / _reference_host           */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -653,6 +655,64 @@ int64_t ml_jpeg_encode_workspace_bytes(int32_t B, int32_t H, int32_t W);
  * (frame, quality).  No host synchronisation: graph-capturable.                                              */
 int ml_jpeg_encode_u8(const uint8_t *images, int32_t B, int32_t H, int32_t W, int32_t quality, uint8_t *out,
                       int64_t capacity, int32_t *lengths, void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Serving request: DecodeImageContent for baseline JPEG, the bytes libjpeg-turbo's default decode gives (JDCT_ISLOW,
+ * fancy upsampling: what Pillow and tf.io.decode_jpeg use).  The host parses and Huffman-decodes the stream into a
+ * packed sparse form (no device needed); the device does the per-pixel work.  All of it is integer arithmetic, >> is
+ * arithmetic, DESCALE(x, n) = (x + (1 << (n - 1))) >> n:
+ *   dequantise c[i] = coef[i] * Q[i] (natural order);
+ *   the 8x8 IDCT of Loeffler, Ligtenberg and Moschytz with CONST_BITS 13, PASS1_BITS 2 (constants round(x * 8192):
+ *   2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172), down the columns with DESCALE 11, then along
+ *   the rows with DESCALE 18; sample = clamp(v + 128, 0, 255).  A block with only a DC term is the constant
+ *   clamp(((dc * Q0 + 4) >> 3) + 128);
+ *   of a component's padded plane only the first ceil(H v / vmax) rows and ceil(W h / hmax) columns are read;
+ *   2x2 chroma ("h2v2 fancy"): the real plane replicated by one sample on every side, colsum = 3 c[r][x] + c[r - 1][x]
+ *   for output row 2r and 3 c[r][x] + c[r + 1][x] for row 2r + 1, out[2x] = (3 colsum[x] + colsum[x - 1] + 8) >> 4,
+ *   out[2x + 1] = (3 colsum[x] + colsum[x + 1] + 7) >> 4;
+ *   with FIX(a) = int(a * 65536 + 0.5), cb = Cb - 128, cr = Cr - 128: R = clamp(Y + ((FIX(1.402) cr + 32768) >> 16)),
+ *   G = clamp(Y + ((-FIX(.34414) cb + 32768 - FIX(.71414) cr) >> 16)), B = clamp(Y + ((FIX(1.772) cb + 32768) >> 16));
+ *   4:4:4 has no upsampling step, grayscale writes Y to the three channels.
+ * The IDCT runs in 64-bit integers: the formulas hold as written for every int16 coefficient (libjpeg itself wraps
+ * once dequantised or pass-1 values leave 16 bits, which no stream encoded from pixels does).
+ *
+ * Taken: SOF0, 8 bit, Huffman, one interleaved scan of three components sampled 2x2/1x1/1x1 (ML_JPEG_420) or all 1x1
+ * (ML_JPEG_444), or one 1x1 component (ML_JPEG_GRAY); any table ids and contents (8-bit DQT); DRI restart intervals;
+ * APPn / COM are skipped; a side of at most 16384.  Not taken ("unsupported", a normal answer): progressive, extended,
+ * lossless and arithmetic frames, other sampling, 4 components, an Adobe APP14 transform other than YCbCr, components
+ * 'R' 'G' 'B' without a JFIF marker, scans of fewer components than the frame, 16-bit DQT, anything that is not a JPEG.
+ *
+ * Packed form of one image (16-byte aligned, a multiple of 16 bytes): 224-byte header { u32 magic, i32 H, W, mode,
+ * u32 blocks, entries, bytes, reserved, u8 Q[3][64] per component in natural order }, u32 block_start[blocks + 1],
+ * u32 word[entries]: natural-order index << 16 | the int16 value's 16 bits.  Blocks in scan order; a block's first
+ * word is its un-predicted DC term (always present); indices < 64, distinct within a block; offsets monotone.
+ * ------------------------------------------------------------------------------------------- */
+enum { ML_JPEG_GRAY = 0, ML_JPEG_444 = 1, ML_JPEG_420 = 2 };
+#define ML_JPEG_UNSUPPORTED 1
+/* Host.  info int32[4] = { H, W, mode, blocks }.  ML_OK: the device path takes the stream; ML_JPEG_UNSUPPORTED: it does
+ * not (ml_last_error says why; also for a header that cannot be read) -- decode it elsewhere.                */
+int ml_jpeg_decode_info(const uint8_t *data, int64_t n, int32_t *info);
+/* Host.  Bytes no packed form of this stream exceeds (the header, the offsets, and per block the smaller of 64 words
+ * and what n bytes of scan can hold at two bits a word); ML_E_BADARG if the stream is not taken.              */
+int64_t ml_jpeg_decode_packed_bytes(const uint8_t *data, int64_t n);
+/* Host.  Huffman-decodes the whole scan into `packed` (4-byte aligned, `capacity` bytes) and returns the bytes
+ * written, or ML_E_BADARG with the reason: a truncated segment or scan, an undefined table, a code that is not in
+ * its table, a run past coefficient 63, a DC category above 11 or an AC size above 10, a wrong or missing RSTn, a
+ * missing EOI, a full buffer.  Never reads beyond data[n) or writes beyond packed[capacity).                 */
+int64_t ml_jpeg_decode_entropy(const uint8_t *data, int64_t n, void *packed, int64_t capacity);
+/* Device.  Planar uint8 Y, Cb, Cr of B images (1 <= B <= 32) between the two launches.                       */
+int64_t ml_jpeg_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t mode);
+/* Device.  `packed`: B packed images of the same H, W and mode in one device buffer, image b at byte offsets[b]
+ * (host array of B + 1, offsets[B] = the end; 16-byte aligned) -> out uint8 [B,H,W,3] (4-byte aligned, below 2^31
+ * bytes).  Two
+ * launches on `stream`, no host read, no atomics: one writer per byte.  H, W, mode must be those of the packed images
+ * (the kernels trust the packed form as ml_jpeg_decode_entropy writes it).                                    */
+int ml_jpeg_decode_u8(const void *packed, const int64_t *offsets, int32_t B, int32_t H, int32_t W, int32_t mode,
+                      uint8_t *out, void *workspace, void *stream);
+/* Host.  The same per-thread code in CPU loops, every pointer in host memory; it also verifies the packed form's
+ * invariants.  For checking the arithmetic without a device -- not a product path.                            */
+int ml_jpeg_decode_reference_host(const void *packed, const int64_t *offsets, int32_t B, int32_t H, int32_t W,
+                                  int32_t mode, uint8_t *out, void *workspace);
 
 #ifdef __cplusplus
 }

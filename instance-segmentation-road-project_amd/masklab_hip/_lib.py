@@ -162,7 +162,16 @@ SIGNATURES = {
     "ml_jpeg_encode_capacity": (_i64, [_i32, _i32]),
     "ml_jpeg_encode_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ml_jpeg_encode_u8": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _i64, _vp, _vp, _vp]),
+    "ml_jpeg_decode_info": (C.c_int, [_vp, _i64, _vp]),
+    "ml_jpeg_decode_packed_bytes": (_i64, [_vp, _i64]),
+    "ml_jpeg_decode_entropy": (_i64, [_vp, _i64, _vp, _i64]),
+    "ml_jpeg_decode_workspace_bytes": (_i64, [_i32] * 4),
+    "ml_jpeg_decode_u8": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp, _vp, _vp]),
+    "ml_jpeg_decode_reference_host": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp, _vp]),
 }
+JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*
+JPEG_UNSUPPORTED = 1                        # ML_JPEG_UNSUPPORTED
+JPEG_DECODE_MAX_BATCH = 32
 DRAW_MAX_CLASSES = 16    # ML_DRAW_MAX_CLASSES
 
 _lib = None

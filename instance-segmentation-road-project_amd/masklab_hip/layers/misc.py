@@ -453,12 +453,24 @@ class EncodeImageContent(Layer):
 
 class DecodeImageContent(Layer):
     """Decode an image file (jpg, png ...) into a frame (reference misc.py:328-340, tf.io.decode_image(channels=3)):
-    `bytes`, or a length-1 sequence / array of them -> uint8 [1,H,W,3] tensor (on `device` if given).  Decoding runs on
-    the host through Pillow, imported lazily."""
+    `bytes`, or a length-1 sequence / array of them -> uint8 [1,H,W,3] tensor (on `device` if given).
 
-    def __init__(self, device=None, **kwargs):
+    With a GPU `device` (and `on_device` not False) a baseline JPEG -- 8 bit, Huffman, 4:2:0, 4:4:4 or grayscale in one
+    scan -- is decoded on the device (ops.decode_jpeg: the bytes libjpeg-turbo's default decode gives) and Pillow is
+    not imported.  Every other content (progressive or 4:2:2 JPEG, png ...), and every content when `device` is None
+    or `on_device` is False, is decoded on the host through Pillow, imported lazily.  So is a baseline stream the strict
+    device-path parser finds malformed (libjpeg tolerates some of those with a warning); without Pillow that stream
+    raises ops.JpegDecodeError with the parser's reason."""
+
+    def __init__(self, device=None, on_device=None, **kwargs):
         self.device = device
+        self.on_device = on_device
         super().__init__(**kwargs)
+
+    def _decodes_on_device(self):
+        if self.device is None or self.on_device is False:
+            return False
+        return torch.device(self.device).type == "cuda"
 
     def call(self, inputs, **kwargs):
         if not isinstance(inputs, (bytes, bytearray, memoryview)):
@@ -468,9 +480,19 @@ class DecodeImageContent(Layer):
             inputs = items[0]
             if not isinstance(inputs, (bytes, bytearray, memoryview)):
                 raise ValueError(f"DecodeImageContent takes the bytes of an image file, got {type(inputs).__name__}")
+        malformed = None
+        if self._decodes_on_device():
+            try:
+                return ops.decode_jpeg(bytes(inputs), self.device)
+            except ops.UnsupportedJpeg:
+                pass                                                                     # the host path below takes it
+            except ops.JpegDecodeError as e:
+                malformed = e                                                            # libjpeg may tolerate it: ask Pillow
         try:
             from PIL import Image
         except ImportError as e:
+            if malformed is not None:
+                raise malformed
             raise ImportError("DecodeImageContent decodes on the host with Pillow (PIL), which is not installed: install "
                               "Pillow, or decode the request yourself and give the uint8 [1,H,W,3] frame to the "
                               "deploy / serving model") from e
@@ -479,3 +501,8 @@ class DecodeImageContent(Layer):
             frame = np.array(im.convert("RGB"), dtype=np.uint8)
         image = torch.from_numpy(frame)[None]
         return image.to(self.device) if self.device is not None else image
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"device": None if self.device is None else str(self.device), "on_device": self.on_device})
+        return config

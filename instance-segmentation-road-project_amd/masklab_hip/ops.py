@@ -6,6 +6,7 @@ slice of a wider buffer so concat / add are fused into the producing kernel.
 There is no torch compute and no CPU fallback here.
 """
 import ctypes as C
+import threading
 
 import numpy as np
 import torch
@@ -1316,3 +1317,110 @@ def jpeg_contents(buffer, lengths):
     bytes of each row are copied."""
     n = lengths.cpu().tolist()                                    # synchronises with the encoder's stream
     return [bytes(buffer[b, :k].cpu().numpy()) for b, k in enumerate(n)]
+
+
+# ----------------------------------------------------------------------------- serving request content (JPEG)
+class UnsupportedJpeg(Exception):
+    """The stream is not one the device decoder takes (progressive, 4:2:2, not a JPEG ...): decode it elsewhere."""
+
+
+class JpegDecodeError(ValueError):
+    """A baseline stream the device decoder takes, but malformed (truncated, a code that is not in its table ...)."""
+
+
+def _last_error():
+    msg = _lib.load().ml_last_error()
+    return msg.decode() if msg else "?"
+
+
+def jpeg_info(content):
+    """ml_jpeg_decode_info: (H, W, mode, blocks) of a stream the device path takes, else UnsupportedJpeg.  Host only."""
+    info = (C.c_int32 * 4)()
+    status = _lib.load().ml_jpeg_decode_info(content, len(content), info)
+    if status == _lib.JPEG_UNSUPPORTED:
+        raise UnsupportedJpeg(_last_error())
+    _lib.check(status, "ml_jpeg_decode_info")
+    return tuple(info)
+
+
+class _Staging:
+    """Two pinned host buffers used in turn; each remembers the event that closes its last upload, so the copy of call n
+    is never overwritten by call n + 1 (call n + 2 waits for it).  One per device and host thread."""
+
+    def __init__(self):
+        self.slots = [[None, None], [None, None]]
+        self.turn = 0
+
+    def take(self, nbytes):
+        slot = self.slots[self.turn]
+        self.turn ^= 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        if slot[0] is None or slot[0].numel() < nbytes:
+            slot[0] = torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True)
+        return slot
+
+
+_jpeg_staging = threading.local()                                 # .by_device: {device: _Staging}, dies with its thread
+
+
+def decode_jpeg(contents, device):
+    """Baseline JPEG `bytes` (or a list of at most 32 of them, all of one H x W and sampling mode) -> uint8 [B,H,W,3] on `device`, the
+    bytes libjpeg-turbo's default decode gives.  The host Huffman-decodes into pinned staging memory
+    (ml_jpeg_decode_entropy), one asynchronous copy uploads the packed coefficients, two launches reconstruct
+    (ml_jpeg_decode_u8); nothing is read back.  UnsupportedJpeg: a stream the device path does not take;
+    JpegDecodeError: a malformed one; ValueError: mixed sizes or modes."""
+    lib = _lib.load()
+    single = isinstance(contents, (bytes, bytearray, memoryview))
+    items = [bytes(c) for c in ([contents] if single else contents)]
+    if not 1 <= len(items) <= _lib.JPEG_DECODE_MAX_BATCH:
+        raise ValueError(f"decode_jpeg: 1 .. {_lib.JPEG_DECODE_MAX_BATCH} streams a call, got {len(items)}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"decode_jpeg: a CUDA/HIP device expected, got {device} (no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    infos = [jpeg_info(c) for c in items]
+    H, W = infos[0][:2]
+    if any(i[:2] != (H, W) for i in infos):
+        raise ValueError(f"decode_jpeg: the streams of a call must have one size, got {[i[:2] for i in infos]}")
+    mode = infos[0][2]
+    if any(i[2] != mode for i in infos):
+        raise ValueError(f"decode_jpeg: the streams of a call must have one sampling mode, got {[i[2] for i in infos]}")
+    out = torch.empty((len(items), H, W, 3), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _decode_jpeg_group(lib, items, H, W, mode, device, out)
+    return out
+
+
+def _decode_jpeg_group(lib, items, H, W, mode, device, out):
+    B = len(items)
+    bounds = []
+    for c in items:
+        n = int(lib.ml_jpeg_decode_packed_bytes(c, len(c)))
+        if n < 0:
+            _lib.check(n, "ml_jpeg_decode_packed_bytes")
+        bounds.append(n)
+    by_device = _jpeg_staging.__dict__.setdefault("by_device", {})
+    slot = by_device.setdefault(str(device), _Staging()).take(sum(bounds))
+    host = slot[0]
+    offsets = (C.c_int64 * (B + 1))()
+    at = 0
+    for b, c in enumerate(items):
+        offsets[b] = at
+        n = int(lib.ml_jpeg_decode_entropy(c, len(c), C.c_void_p(host.data_ptr() + at), bounds[b]))
+        if n < 0:
+            raise JpegDecodeError(f"decode_jpeg: stream {b}: {_last_error()}")
+        at += (n + 15) // 16 * 16
+    offsets[B] = at
+    nbytes = int(lib.ml_jpeg_decode_workspace_bytes(B, H, W, mode))
+    if nbytes < 0:
+        _lib.check(nbytes, "ml_jpeg_decode_workspace_bytes")
+    packed = torch.empty(at, dtype=torch.uint8, device=device)
+    packed.copy_(host[:at], non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    ws = workspace(nbytes, device, "jpeg_decode")
+    with _Prof("jpeg_decode", 0, at + 2 * nbytes + out.numel(), f"B={B} {H}x{W} mode={mode}"):
+        _lib.check(lib.ml_jpeg_decode_u8(_ptr(packed), offsets, B, H, W, mode, _ptr(out), _ptr(ws), _stream()),
+                   "ml_jpeg_decode_u8")

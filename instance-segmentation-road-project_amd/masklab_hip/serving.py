@@ -1,11 +1,13 @@
 """The serving model of reference road_project/setup/serving.py:17-53: the bytes of an image file in,
 [JPEG content of the rendered frame, summary] out.
 
-    DecodeImageContent (host, Pillow) -> deploy model -> DrawBoxes / DrawInstance / DrawSegmentation (one kernel)
+    DecodeImageContent (baseline JPEG: Huffman decoding on the host, everything per pixel on the device; any other
+    content: host, Pillow) -> deploy model -> DrawBoxes / DrawInstance / DrawSegmentation (one kernel)
     -> EncodeImageContent (baseline JPEG, encoded on the device) and SummaryOutput
 
 The reference saves this graph as a TensorFlow SavedModel for its gRPC front end (save_serving_model, :56-72); here it
-is a callable.  Decoding on the device is open."""
+is a callable.  A baseline JPEG request needs no Pillow; entropy decoding on the device, 4:2:2 and progressive streams
+are open."""
 import numpy as np
 
 from . import retinamasklab as R
