@@ -61,7 +61,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_jpeg_encode_u8 / _capacity /
                                             _workspace_bytes;
                                             (additive, same version) ml_jpeg_decode_info / _packed_bytes /
-                                            _entropy / _workspace_bytes / _u8 / _reference_host           */
+                                            _entropy / _workspace_bytes / _u8 / _reference_host;
+                                            (additive, same version) ml_jpeg_entropy_geometry / _plan_bytes /
+                                            _plan / _workspace_bytes / _device / _reference_host          */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -713,6 +715,64 @@ int ml_jpeg_decode_u8(const void *packed, const int64_t *offsets, int32_t B, int
  * invariants.  For checking the arithmetic without a device -- not a product path.                            */
 int ml_jpeg_decode_reference_host(const void *packed, const int64_t *offsets, int32_t B, int32_t H, int32_t W,
                                   int32_t mode, uint8_t *out, void *workspace);
+
+/* ---------------------------------------------------------------------------------------------
+ * The entropy half of the request decoder on the device.  Contract: for every stream ml_jpeg_decode_info answers
+ * ML_OK for, status 0 means that `packed` holds the packed form ml_jpeg_decode_entropy writes, byte for byte over the
+ * `bytes` of its header (the 224-byte header, block_start[blocks + 1], one word per non-zero coefficient with the DC
+ * term un-predicted and first, the zero padding to 16 bytes): ml_jpeg_decode_u8 then runs on it unchanged.  A non-zero
+ * status means: run the host decoder, which stays the oracle and says what is wrong, if anything is.
+ *
+ * Self-synchronising parallel Huffman decoding.  The raw scan is cut into subsequences of geometry[0] bits, one
+ * thread each, geometry[1] subsequences a workgroup.  Every thread decodes from a guessed state, takes over its
+ * predecessor's exit state until the two agree (inside a workgroup in rounds, across workgroups in a fixed number of
+ * launches: no workgroup waits on another), a prefix sum gives each subsequence its word and block positions and DC
+ * predictors, and a last pass decodes from the settled states, stores, checks every condition the host decoder
+ * checks and that each thread ends in the state its successor began in.  FF 00 stuffing is undone in place; an RSTn
+ * marker resets a thread to block 0 of an MCU.  Every read is bounded by the file's length, every store by the
+ * capacity.  Launches on `stream`, no host read; the statuses are in device memory.  Where the status is not 0 the
+ * words behind the header are cleared (every block reads as empty: ml_jpeg_decode_u8 may safely follow in the stream).
+ *
+ * Outcome, int32 status[4 b ..]: the status below; the block index it refers to, or -1; the most rounds a
+ * workgroup needed to settle; the last launch (0 ..) in which a state crossed a workgroup boundary.           */
+enum {
+    ML_JPEG_ENTROPY_OK = 0,
+    ML_JPEG_ENTROPY_BAD_CODE = 1,    /* a code that is not in its table                                        */
+    ML_JPEG_ENTROPY_BAD_DC = 2,      /* DC category above 11                                                   */
+    ML_JPEG_ENTROPY_BAD_AC = 3,      /* AC size above 10, or a run/size symbol n0 other than EOB and ZRL       */
+    ML_JPEG_ENTROPY_RUN = 4,         /* a run past coefficient 63                                              */
+    ML_JPEG_ENTROPY_TRUNCATED = 5,   /* the scan ends inside a block                                           */
+    ML_JPEG_ENTROPY_BLOCKS = 6,      /* the scan does not hold `blocks` blocks                                 */
+    ML_JPEG_ENTROPY_RESTART = 7,     /* an RSTn that is not due, out of sequence or repeated                   */
+    ML_JPEG_ENTROPY_NO_EOI = 8,      /* no EOI after the last MCU                                              */
+    ML_JPEG_ENTROPY_CAPACITY = 9,    /* a store beyond `capacity` was withheld                                 */
+    ML_JPEG_ENTROPY_ASK_HOST = 10,   /* whole bytes between an MCU's last bit and a due RSTn: whether the host decoder
+                                        takes the marker depends on how far its reader had read ahead          */
+    ML_JPEG_ENTROPY_NOT_SYNCED = 11, /* the states had not settled within the fixed rounds: a well-formed stream
+                                        may end so; it takes precedence over the codes above, which may follow from it */
+    ML_JPEG_ENTROPY_BAD_PLAN = 12    /* the plan is not this file's, or the capacity is below the fixed part   */
+};
+/* Host.  geometry int32[2] = { bits per subsequence, subsequences per workgroup }.                            */
+int ml_jpeg_entropy_geometry(int32_t *geometry);
+/* Host.  The plan of one stream (ml_jpeg_entropy_plan_bytes() bytes, 8-byte aligned; 16-byte aligned slots in a batch):
+ * geometry, the scan's offset, its first marker that is no RSTn, the restart interval, the dequantisation tables, and per component the DC and AC
+ * Huffman tables in lookup form (9-bit `fast` table, maxcode / valoff / vals for longer codes).  ML_E_BADARG with the
+ * host decoder's reason for a stream that is not taken, truncated before SOS or without one of its tables.    */
+int64_t ml_jpeg_entropy_plan_bytes(void);
+int ml_jpeg_entropy_plan(const uint8_t *data, int64_t n, void *plan);
+/* Host.  Workspace of a call over B streams (1 <= B <= 32), stream b being file_offsets[b + 1] - file_offsets[b] bytes. */
+int64_t ml_jpeg_entropy_workspace_bytes(const int64_t *file_offsets, int32_t B);
+/* Device.  files: the raw files in one device buffer, stream b at byte file_offsets[b] (host array of B + 1);
+ * plans: B plans, ml_jpeg_entropy_plan_bytes() apart; packed: stream b's packed form goes to byte packed_offsets[b]
+ * (host array of B + 1, multiples of 16; the room up to packed_offsets[b + 1] is its capacity, at least
+ * ml_jpeg_decode_packed_bytes); status int32 [4 B] and workspace in device memory, plans / packed / status / workspace 16-byte
+ * aligned.  Six launches, graph-capturable.                                                                    */
+int ml_jpeg_entropy_device(const uint8_t *files, const int64_t *file_offsets, const void *plans, int32_t B, void *packed,
+                           const int64_t *packed_offsets, int32_t *status, void *workspace, void *stream);
+/* Host.  The same stages in CPU loops over one stream, every pointer in host memory (workspace:
+ * ml_jpeg_entropy_workspace_bytes of {0, n}, 8-byte aligned; status int32[4]).  Not a product path.            */
+int ml_jpeg_entropy_reference_host(const uint8_t *file, int64_t n, const void *plan, void *packed, int64_t capacity,
+                                   int32_t *status, void *workspace);
 
 #ifdef __cplusplus
 }

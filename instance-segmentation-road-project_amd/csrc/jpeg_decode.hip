@@ -782,3 +782,849 @@ extern "C" int ml_jpeg_decode_reference_host(const void *packed, const int64_t *
     for (long long t = 0; t < (total + 3) / 4; ++t) pixels_body((Index)t, (const uint8_t *)workspace, g, H, W, (Index)total, out);
     return ML_OK;
 }
+
+// ============================================================================= entropy decoding on the device
+// The Huffman half of the decoder as kernels: the raw file and a small plan go up, the packed form above comes out, byte
+// for byte what ml_jpeg_decode_entropy writes.  Self-synchronising parallel decoding: the scan is cut into subsequences of
+// SUB_BYTES raw bytes, one thread each.
+//   1 sync    (SYNC_LAUNCHES launches of one kernel) every thread decodes its subsequence from a guessed state (bit 0 of
+//             its first byte, block 0 of an MCU, k = 0; thread 0 of a stream holds the true state) and keeps its exit
+//             state and counts: words, blocks, the DC differences summed per component since the last restart marker.
+//             Then, at most SYNC_ROUNDS times, every thread takes its predecessor's exit state as its entry state and,
+//             if that changed it, decodes again; a workgroup whose states all agree stops.  The first thread of a
+//             workgroup takes the exit state the previous workgroup's last thread left in the launch before (two
+//             buffers, one per launch parity: no workgroup waits on or races with another).
+//   2 scan    one workgroup per stream: exclusive prefix of (words, blocks, DC predictors) over the subsequences, the
+//             predictors restarting where a subsequence saw a restart marker.
+//   3 write   decode once more from the settled entry states, storing block_start and the words (the DC word already
+//             un-predicted: the predictor at entry comes from the scan).  Every malformed-stream condition of the host
+//             decoder counts here, every store is bounded, and each thread compares its exit state with its successor's
+//             entry state: a stream whose states had not settled ends ML_JPEG_ENTROPY_NOT_SYNCED, never with wrong words
+//             under status 0.  The thread that completes the last block looks for EOI and writes the header.
+//   4 finish  folds the error word and the done flag into the stream's four status words, and clears the packed words of
+//             a stream that failed: the block and pixel kernels may follow in the stream before anybody reads a status.
+// A state is (raw bit position, k, block in MCU, fresh: nothing decoded since a restart marker, end: the supply ended).
+// In a guessed state nothing is an error: a code that is not in the table consumes 16 bits as symbol 0, a bad category
+// or run ends the block, a symbol the supply cannot finish jumps over an RSTn marker (block 0, k = 0) or ends the thread.
+// The write pass applies the same rules, so its counts are those of the sync pass, and records the error.
+// One answer of the host decoder depends on how far its 64-bit reader has read ahead, which no thread can know: whether
+// it takes a due restart marker that whole bytes separate from the MCU's last bit.  That ends ML_JPEG_ENTROPY_ASK_HOST:
+// the caller runs the host decoder, as for every non-zero status.  (The EOI rule needs no search: the plan names the
+// scan's first marker that is no RSTn, and the last RSTn before it.)
+namespace {
+
+constexpr int SUB_BYTES = 128, SUB_BITS = 8 * SUB_BYTES;           // one thread's share of the raw scan
+constexpr int SYNC_TPB = 256;                                      // subsequences per workgroup
+constexpr int SYNC_ROUNDS = SYNC_TPB, SYNC_LAUNCHES = 3;           // a state can cross a whole workgroup in one launch
+constexpr int FILL_SKIP = 16;                                      // fill bytes passed over before a marker
+constexpr uint32_t PLAN_MAGIC = 0x4E4C504Au;                       // "JPLN"
+constexpr int64_t MAX_FILE = 1ll << 28;                            // bit positions stay below 2^31
+
+struct DevTable {
+    uint16_t fast[512];
+    int32_t maxcode[17], valoff[17], nvals;
+    uint8_t vals[256];
+};
+
+struct Plan {
+    uint32_t magic;
+    int32_t height, width, mode;
+    uint32_t nblk, per_mcu, restart, scan, n, nsub;
+    uint32_t end_marker, last_rst;                                 // first marker of the scan that is no RSTn (n: none); last RSTn before it + 1 (0: none)
+    uint8_t q[MAX_COMPONENTS][64];
+    uint8_t zigzag[64];
+    DevTable dc[MAX_COMPONENTS], ac[MAX_COMPONENTS];               // by component
+};
+static_assert(sizeof(Plan) % 8 == 0, "plans are copied as words");
+constexpr int PLAN_BYTES = (int)((sizeof(Plan) + 15) / 16 * 16);
+
+struct State {
+    uint32_t pos, kb;                                              // kb: k | block in MCU << 8 | fresh << 16 | end << 17
+};
+constexpr uint32_t FRESH = 1u << 16, END = 1u << 17;
+__host__ __device__ inline bool same(const State &a, const State &b) { return a.pos == b.pos && a.kb == b.kb; }
+
+struct Count {
+    uint32_t words, blocks;
+    int32_t dc0, dc1, dc2;
+    uint32_t reset;
+};
+
+// a then b
+__host__ __device__ inline Count combine(const Count &a, const Count &b) {
+    Count c;
+    c.words = a.words + b.words;
+    c.blocks = a.blocks + b.blocks;
+    c.dc0 = b.reset ? b.dc0 : a.dc0 + b.dc0;
+    c.dc1 = b.reset ? b.dc1 : a.dc1 + b.dc1;
+    c.dc2 = b.reset ? b.dc2 : a.dc2 + b.dc2;
+    c.reset = a.reset | b.reset;
+    return c;
+}
+
+// one stream's share of the workspace
+struct Region {
+    State *entry, *exit, *wg_exit;                                 // [nsub], [nsub], [2][nwg]
+    Count *count, *prefix;                                         // [nsub]
+    uint32_t *ctl;                                                 // error word (code << 24 | block), done, most rounds, last launch that changed a state
+};
+
+__host__ __device__ inline uint32_t sub_cap_of(uint32_t n) { return (n + SUB_BYTES - 1) / SUB_BYTES; }   // whatever the scan's offset
+inline uint32_t sub_bound(int64_t n) { return sub_cap_of((uint32_t)n); }
+inline uint32_t wg_bound(int64_t n) { return (sub_bound(n) + SYNC_TPB - 1) / SYNC_TPB; }
+inline long long region_bytes(int64_t n) {
+    return round16((long long)sub_bound(n) * (2 * sizeof(State) + 2 * sizeof(Count)) + 2ll * wg_bound(n) * sizeof(State) + 16);
+}
+__host__ __device__ inline Region region_of(uint8_t *ws, uint32_t sub_cap, uint32_t wg_cap) {
+    Region r;
+    r.entry = reinterpret_cast<State *>(ws);
+    r.exit = r.entry + sub_cap;
+    r.wg_exit = r.exit + sub_cap;
+    r.count = reinterpret_cast<Count *>(r.wg_exit + 2 * wg_cap);
+    r.prefix = r.count + sub_cap;
+    r.ctl = reinterpret_cast<uint32_t *>(r.prefix + sub_cap);
+    return r;
+}
+
+struct Streams {                                                   // kernel argument: where stream b's buffers are
+    long long file_at[MAX_BATCH], packed_at[MAX_BATCH], ws_at[MAX_BATCH];
+    uint32_t file_n[MAX_BATCH], capacity[MAX_BATCH];
+};
+
+// The host decoder's BitReader over the raw file, every read below n.  ff: bit j set if the j-th last byte taken was an
+// FF (it stands for two raw bytes), which gives the raw position of the next bit.
+#ifdef __HIP_DEVICE_COMPILE__
+typedef const __attribute__((address_space(3))) uint8_t *LdsBytes;   // keeps the window's loads LDS loads, not flat ones
+#else
+typedef const uint8_t *LdsBytes;
+#endif
+
+struct DevReader {
+    const uint8_t *f;
+    LdsBytes win;                                            // bytes [lo, lo + len) of the file, staged in LDS (len 0: none)
+    uint32_t lo, len;
+    uint32_t n, p;
+    uint64_t acc;
+    int avail;
+    uint32_t ff;
+    bool stopped;
+};
+
+__host__ __device__ inline void reader_at(DevReader &r, uint32_t byte) {
+    r.p = byte;
+    r.acc = 0;
+    r.avail = 0;
+    r.ff = 0;
+    r.stopped = false;
+}
+
+__host__ __device__ inline uint32_t byte_at(const DevReader &r, uint32_t p) {   // p < n
+    const uint32_t x = p - r.lo;
+    return x < r.len ? r.win[x] : r.f[p];
+}
+
+__host__ __device__ inline void refill(DevReader &r) {
+    while (r.avail <= 56 && !r.stopped) {
+        if (r.p >= r.n) {
+            r.stopped = true;
+            break;
+        }
+        const uint32_t b = byte_at(r, r.p);
+        if (b == 0xFFu) {
+            if (r.p + 1 >= r.n || byte_at(r, r.p + 1) != 0) {
+                r.stopped = true;
+                break;
+            }
+            r.p += 2;
+            r.ff = r.ff << 1 | 1u;
+        } else {
+            ++r.p;
+            r.ff <<= 1;
+        }
+        r.acc = (r.acc << 8) | b;
+        r.avail += 8;
+    }
+}
+
+__host__ __device__ inline uint32_t peek(const DevReader &r, int nbits) {   // nbits 1 .. 16, zeros past the supply
+    const uint64_t v = r.avail >= nbits ? r.acc >> (r.avail - nbits) : r.acc << (nbits - r.avail);
+    return (uint32_t)(v & ((1u << nbits) - 1u));
+}
+
+__host__ __device__ inline int popcount8(uint32_t v) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return __popc(v);
+#else
+    return __builtin_popcount(v);
+#endif
+}
+
+// raw bit position of the next bit
+__host__ __device__ inline uint32_t cursor(const DevReader &r) {
+    const int nb = (r.avail + 7) >> 3;                             // bytes taken that still hold unread bits, <= 8
+    const uint32_t byte = r.p - (uint32_t)nb - (uint32_t)popcount8(r.ff & ((1u << nb) - 1u));
+    return byte * 8u + (uint32_t)((8 - (r.avail & 7)) & 7);
+}
+
+__host__ __device__ inline void reader_from(DevReader &r, uint32_t pos) {
+    reader_at(r, pos >> 3);
+    const int skip = (int)(pos & 7u);
+    if (skip) {
+        refill(r);
+        r.avail = r.avail >= 8 ? r.avail - skip : 0;
+    }
+}
+
+enum { SYM_NO_CODE = -2, SYM_TRUNCATED = -1 };
+
+__host__ __device__ inline int dev_symbol(DevReader &r, const DevTable &t) {
+    if (r.avail < 16) refill(r);
+    const uint32_t e = t.fast[peek(r, 9)];
+    if (e) {
+        const int len = (int)(e >> 8);
+        if (len > r.avail) return SYM_TRUNCATED;
+        r.avail -= len;
+        return (int)(e & 255u);
+    }
+    for (int len = 10; len <= 16; ++len) {
+        const int32_t code = (int32_t)peek(r, len), top = t.maxcode[len];
+        if (top >= 0 && code <= top) {
+            if (len > r.avail) return SYM_TRUNCATED;
+            const int32_t at = t.valoff[len] + code;
+            if (at < 0 || at >= t.nvals || at >= 256) return SYM_NO_CODE;
+            r.avail -= len;
+            return t.vals[at];
+        }
+    }
+    return r.avail < 16 ? SYM_TRUNCATED : SYM_NO_CODE;
+}
+
+// `size` <= 15 more bits as a signed value; false if the supply ends first
+__host__ __device__ inline bool dev_extend(DevReader &r, int size, int &v) {
+    v = 0;
+    if (size == 0) return true;
+    if (r.avail < size) refill(r);
+    if (r.avail < size) return false;
+    const int u = (int)peek(r, size);
+    r.avail -= size;
+    v = u >> (size - 1) ? u : u - (1 << size) + 1;
+    return true;
+}
+
+// The reader has stopped: the RSTn number if that is what stopped it (after at most FILL_SKIP fill bytes), else -1.
+__host__ __device__ inline int restart_marker(const DevReader &r, uint32_t &after) {
+    uint32_t q = r.p;
+    for (int i = 0; i < FILL_SKIP && q + 2 < r.n && byte_at(r, q) == 0xFF && byte_at(r, q + 1) == 0xFF; ++i) ++q;
+    if (q + 2 > r.n || byte_at(r, q) != 0xFF) return -1;
+    const int m = (int)byte_at(r, q + 1);
+    after = q + 2;
+    return m >= 0xD0 && m <= 0xD7 ? m - 0xD0 : -1;
+}
+
+__host__ __device__ inline State guess_state(const Plan &pl, const uint8_t *f, uint32_t i) {
+    State s;
+    uint32_t byte = pl.scan + i * SUB_BYTES;
+    s.kb = 0;
+    if (i > 0 && byte < pl.n && f[byte - 1] == 0xFF) {             // begins inside a pair: on a stuffed 00, or on RSTn's number
+        const uint32_t b = f[byte];
+        if (b == 0) ++byte;
+        else if (b >= 0xD0 && b <= 0xD7) ++byte, s.kb = FRESH;
+    }
+    s.pos = byte * 8u;
+    return s;
+}
+
+__host__ __device__ inline void raise_to(uint32_t *at, uint32_t word) {
+#ifdef __HIP_DEVICE_COMPILE__
+    atomicMax(at, word);
+#else
+    if (word > *at) *at = word;
+#endif
+}
+__host__ __device__ inline void flag(uint32_t *ctl, int code, uint32_t blk) {
+    raise_to(ctl, (uint32_t)code << 24 | (blk < 0xFFFFFFu ? blk : 0xFFFFFFu));
+}
+
+struct Window {                                                    // a workgroup's part of the file in LDS
+    LdsBytes bytes;
+    uint32_t lo, len;
+};
+
+struct WriteTo {                                                   // the write pass only
+    uint8_t *packed;
+    uint32_t capacity;
+    Count base;                                                    // words, blocks and DC predictors at entry
+    uint32_t *ctl;
+    State next;                                                    // the successor's entry state
+    bool has_next;
+};
+
+// Thread i of a stream: its subsequence from `entry`.  Decodes every symbol that starts below its last bit.
+template <bool WRITE>
+__host__ __device__ inline void decode_subsequence(const Plan &pl, const uint8_t *f, const Window &win, uint32_t i, State entry, State &exit,
+                                                   Count &count, const WriteTo &w) {
+    count.words = count.blocks = count.reset = 0;
+    count.dc0 = count.dc1 = count.dc2 = 0;
+    exit = entry;
+    if (entry.kb & END) return;
+    const uint32_t last = pl.scan + (i + 1) * SUB_BYTES;
+    const uint32_t end_bits = (last < pl.n ? last : pl.n) * 8u;
+    const uint32_t fixed = (uint32_t)sizeof(PackedHeader) + 4u * (pl.nblk + 1u);
+    const uint32_t room = WRITE ? (w.capacity - fixed) / 4u : 0u;  // capacity >= fixed + 4 nblk: checked by the entry point
+    uint32_t *block_start = WRITE ? reinterpret_cast<uint32_t *>(w.packed + sizeof(PackedHeader)) : nullptr;
+    uint32_t *entries = WRITE ? block_start + pl.nblk + 1 : nullptr;
+    uint32_t blk = WRITE ? w.base.blocks : 0u, widx = WRITE ? w.base.words : 0u;
+    int pred0 = WRITE ? w.base.dc0 : 0, pred1 = WRITE ? w.base.dc1 : 0, pred2 = WRITE ? w.base.dc2 : 0;
+    if (WRITE && blk > pl.nblk) return;                            // past the last block: whoever got there has spoken
+    DevReader r;
+    r.f = f;
+    r.win = win.bytes;
+    r.lo = win.lo;
+    r.len = win.len;
+    r.n = pl.n;
+    reader_from(r, entry.pos);
+    uint32_t k = entry.kb & 255u, b = (entry.kb >> 8) & 255u;
+    bool fresh = (entry.kb & FRESH) != 0, ended = false, done = false;
+    for (int step = 0; step < SUB_BITS + 64; ++step) {             // every step consumes a bit, passes a marker or ends
+        if (r.avail < 16) refill(r);
+        if (cursor(r) >= end_bits) break;
+        bool stop = false;                                         // the supply cannot finish the symbol
+        if (k == 0 && b == 0) {                                    // between MCUs
+            if (WRITE && blk >= pl.nblk) {
+                done = true;
+                break;
+            }
+            const uint32_t mcu = WRITE ? blk / pl.per_mcu : 0u;
+            const bool due = WRITE && pl.restart && mcu && mcu % pl.restart == 0 && !fresh;
+            if (r.stopped && r.avail < 8) {
+                uint32_t after = 0;
+                const int m = restart_marker(r, after);
+                if (m >= 0) {
+                    if (WRITE && (fresh || !due || (uint32_t)m != ((mcu / pl.restart - 1u) & 7u))) flag(w.ctl, ML_JPEG_ENTROPY_RESTART, blk);
+                    reader_at(r, after);
+                    fresh = true;
+                    count.reset = 1;
+                    count.dc0 = count.dc1 = count.dc2 = 0;
+                    pred0 = pred1 = pred2 = 0;
+                    continue;
+                }
+            }
+            if (due) flag(w.ctl, ML_JPEG_ENTROPY_ASK_HOST, blk);   // the host takes the marker if its reader has reached it
+        }
+        const uint32_t comp = pl.mode == ML_JPEG_420 ? (b < 4u ? 0u : b - 3u) : pl.mode == ML_JPEG_444 ? b : 0u;
+        const uint32_t c = comp < (uint32_t)MAX_COMPONENTS ? comp : 0u;
+        bool block_ends = false;
+        if (k == 0) {
+            int sym = dev_symbol(r, pl.dc[c]);
+            if (sym == SYM_TRUNCATED) {
+                stop = true;
+            } else {
+                if (sym == SYM_NO_CODE) {
+                    if (WRITE) flag(w.ctl, ML_JPEG_ENTROPY_BAD_CODE, blk);
+                    r.avail -= r.avail < 16 ? r.avail : 16;
+                    sym = 0;
+                }
+                if (sym > 11) {
+                    if (WRITE) flag(w.ctl, ML_JPEG_ENTROPY_BAD_DC, blk);
+                    sym = 0;
+                }
+                int diff;
+                if (!dev_extend(r, sym, diff)) {
+                    stop = true;
+                } else {
+                    if (c == 0) count.dc0 += diff, pred0 += diff;
+                    else if (c == 1) count.dc1 += diff, pred1 += diff;
+                    else count.dc2 += diff, pred2 += diff;
+                    if (WRITE) {
+                        if (blk < pl.nblk) block_start[blk] = widx;
+                        const int pred = c == 0 ? pred0 : c == 1 ? pred1 : pred2;
+                        if (widx < room) entries[widx] = (uint32_t)(uint16_t)(int16_t)pred;
+                        else flag(w.ctl, ML_JPEG_ENTROPY_CAPACITY, blk);
+                        ++widx;
+                        ++blk;                                     // blk: the block after the one being decoded
+                    }
+                    ++count.words;
+                    ++count.blocks;
+                    fresh = false;
+                    k = 1;
+                }
+            }
+        } else {
+            const uint32_t at = WRITE ? blk - 1u : 0u;             // the block these coefficients belong to
+            int sym = dev_symbol(r, pl.ac[c]);
+            if (sym == SYM_TRUNCATED) {
+                stop = true;
+            } else {
+                if (sym == SYM_NO_CODE) {
+                    if (WRITE) flag(w.ctl, ML_JPEG_ENTROPY_BAD_CODE, at);
+                    r.avail -= r.avail < 16 ? r.avail : 16;
+                    sym = 0;
+                }
+                const uint32_t run = (uint32_t)sym >> 4, size = (uint32_t)sym & 15u;
+                if (size == 0) {
+                    if (run == 15u) {
+                        k += 16;
+                        if (k > 64u && WRITE) flag(w.ctl, ML_JPEG_ENTROPY_RUN, at);
+                        block_ends = k >= 64u;
+                    } else {
+                        if (run != 0u && WRITE) flag(w.ctl, ML_JPEG_ENTROPY_BAD_AC, at);
+                        block_ends = true;
+                    }
+                } else {
+                    if (size > 10u && WRITE) flag(w.ctl, ML_JPEG_ENTROPY_BAD_AC, at);
+                    k += run;
+                    int v;
+                    if (!dev_extend(r, (int)size, v)) {
+                        stop = true;
+                    } else if (k > 63u) {
+                        if (WRITE) flag(w.ctl, ML_JPEG_ENTROPY_RUN, at);
+                        block_ends = true;
+                    } else {
+                        if (WRITE) {
+                            if (widx < room) entries[widx] = (uint32_t)pl.zigzag[k] << 16 | (uint32_t)(uint16_t)(int16_t)v;
+                            else flag(w.ctl, ML_JPEG_ENTROPY_CAPACITY, at);
+                            ++widx;
+                        }
+                        ++count.words;
+                        ++k;
+                        block_ends = k >= 64u;
+                    }
+                }
+            }
+        }
+        if (stop) {                                                // the reader has stopped short of the symbol
+            if (WRITE) flag(w.ctl, ML_JPEG_ENTROPY_TRUNCATED, k ? blk - 1u : blk);
+            uint32_t after = 0;
+            if (restart_marker(r, after) >= 0) {
+                reader_at(r, after);
+                fresh = true;
+                count.reset = 1;
+                count.dc0 = count.dc1 = count.dc2 = 0;
+                pred0 = pred1 = pred2 = 0;
+                k = b = 0;
+                continue;
+            }
+            ended = true;
+            break;
+        }
+        if (block_ends) {
+            k = 0;
+            b = b + 1u >= pl.per_mcu ? 0u : b + 1u;
+        }
+    }
+    exit.pos = ended ? r.p * 8u : cursor(r);                       // (the bits left before a stop are never read again)
+    exit.kb = (k & 255u) | b << 8 | (fresh ? FRESH : 0u) | (ended ? END : 0u);
+    if (!WRITE) return;
+    if (!done) {
+        if (ended) return;                                         // flagged where it ended
+        if (!w.has_next) flag(w.ctl, blk >= pl.nblk && k == 0 && b == 0 ? ML_JPEG_ENTROPY_NO_EOI : ML_JPEG_ENTROPY_TRUNCATED, blk);
+        else if (!same(exit, w.next)) flag(w.ctl, ML_JPEG_ENTROPY_NOT_SYNCED, blk);
+        return;
+    }
+    // The last block is complete.  The host passes over bytes that are no marker: EOI must be the first marker from
+    // here on, which is the scan's first marker that is no RSTn (no decoder gets past that one) unless an RSTn lies between.
+    const uint32_t here = cursor(r) >> 3;
+    if (pl.end_marker + 2u > pl.n || f[pl.end_marker + 1u] != 0xD9 || pl.last_rst > here) flag(w.ctl, ML_JPEG_ENTROPY_NO_EOI, blk);
+    block_start[pl.nblk] = widx;
+    const uint32_t used = fixed + 4u * widx, bytes = (used + 15u) / 16u * 16u;
+    PackedHeader *h = reinterpret_cast<PackedHeader *>(w.packed);
+    h->magic = MAGIC;
+    h->height = pl.height;
+    h->width = pl.width;
+    h->mode = pl.mode;
+    h->blocks = pl.nblk;
+    h->entries = widx;
+    h->bytes = bytes <= w.capacity ? bytes : used;
+    h->reserved = 0;
+    for (int c = 0; c < MAX_COMPONENTS; ++c)
+        for (int x = 0; x < 64; ++x) h->q[c][x] = pl.q[c][x];
+    if (bytes <= w.capacity)
+        for (uint32_t x = widx; fixed + 4u * x < bytes; ++x) entries[x] = 0u;
+    w.ctl[1] = 1u;
+}
+
+// what the kernels rely on in a plan that came from device memory: the file's length, the subsequence count the
+// workspace was sized for, a capacity that holds the fixed part and one word a block
+__host__ __device__ inline bool plan_fits(const Plan &pl, uint32_t file_n, uint32_t capacity) {
+    if (pl.magic != PLAN_MAGIC || pl.n != file_n || pl.scan > pl.n || pl.nsub != sub_cap_of(pl.n - pl.scan)) return false;
+    if (pl.end_marker > pl.n || pl.last_rst > pl.n) return false;
+    if (pl.per_mcu != 1u && pl.per_mcu != 3u && pl.per_mcu != 6u) return false;
+    if (pl.nblk == 0u || pl.nblk > (1u << 24)) return false;
+    return (unsigned long long)capacity >= sizeof(PackedHeader) + 4ull * (pl.nblk + 1u) + 4ull * pl.nblk;
+}
+
+// one stream's exclusive prefix, chunk by chunk: thread t of nt takes subsequences [t per, (t + 1) per)
+__host__ __device__ inline Count chunk_sum(const Count *count, uint32_t lo, uint32_t hi) {
+    Count s = {0u, 0u, 0, 0, 0, 0u};
+    for (uint32_t i = lo; i < hi; ++i) s = combine(s, count[i]);
+    return s;
+}
+__host__ __device__ inline void chunk_prefix(const Count *count, Count *prefix, uint32_t lo, uint32_t hi, Count run) {
+    for (uint32_t i = lo; i < hi; ++i) {
+        prefix[i] = run;
+        run = combine(run, count[i]);
+    }
+}
+
+// A stream that did not end with status 0: thread g clears its share of everything behind the header, so that the
+// block and pixel kernels, which may run before anybody reads the status, find every block empty.
+constexpr uint32_t CLEAR_BYTES = 16;
+__host__ __device__ inline void clear_packed(uint8_t *packed, uint32_t capacity, uint32_t g) {
+    const uint32_t words = (capacity - (uint32_t)sizeof(PackedHeader)) / 4u;
+    uint32_t *w = reinterpret_cast<uint32_t *>(packed + sizeof(PackedHeader));
+    for (uint32_t x = g * (CLEAR_BYTES / 4u); x < (g + 1u) * (CLEAR_BYTES / 4u) && x < words; ++x) w[x] = 0u;
+}
+
+__host__ __device__ inline void finish_stream(const uint32_t *ctl, int32_t *status) {
+    const uint32_t err = ctl[0];
+    status[0] = err ? (int32_t)(err >> 24) : ctl[1] ? ML_JPEG_ENTROPY_OK : ML_JPEG_ENTROPY_BLOCKS;
+    status[1] = err ? (int32_t)(err & 0xFFFFFFu) : -1;
+    status[2] = (int32_t)ctl[2];
+    status[3] = (int32_t)ctl[3];
+}
+
+__device__ inline void load_plan(Plan &lds, const uint8_t *plans, int b) {
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(plans + (size_t)b * PLAN_BYTES);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(&lds);
+    for (uint32_t x = threadIdx.x; x < sizeof(Plan) / 4; x += blockDim.x) dst[x] = src[x];
+    __syncthreads();
+}
+
+// The workgroup's subsequences and WINDOW_TAIL bytes beyond them (a thread's last symbol, a marker and its fill bytes)
+// go to LDS in aligned 32-bit loads; what a thread reads outside the window it reads from memory.
+constexpr uint32_t WINDOW_TAIL = 256, WINDOW_WORDS = (SYNC_TPB * SUB_BYTES + WINDOW_TAIL + 4) / 4;
+__device__ inline Window stage_window(uint32_t *lds, const uint8_t *f, uint32_t first, uint32_t n) {
+    const uint32_t lo = first - (uint32_t)((uintptr_t)(f + first) & 3u);   // first >= scan > 3: the headers precede it
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(f + lo);
+    uint32_t words = 0;
+    if (lo <= first && lo < n) words = min((n - lo) / 4u, WINDOW_WORDS);   // whole words inside the file only
+    for (uint32_t x = threadIdx.x; x < words; x += blockDim.x) lds[x] = src[x];
+    __syncthreads();
+    Window w;
+    w.bytes = (LdsBytes)lds;
+    w.lo = lo;
+    w.len = 4u * words;
+    return w;
+}
+
+__global__ __launch_bounds__(SYNC_TPB) void jpeg_entropy_sync_kernel(const uint8_t *files, const uint8_t *plans, uint8_t *workspace,
+                                                                     Streams st, int launch) {
+    __shared__ Plan pl;
+    __shared__ State handed[SYNC_TPB];
+    __shared__ uint32_t staged[WINDOW_WORDS];
+    const int b = blockIdx.y, t = threadIdx.x;
+    load_plan(pl, plans, b);
+    const uint32_t nsub = pl.nsub, wg = blockIdx.x, i = wg * SYNC_TPB + t;
+    if (!plan_fits(pl, st.file_n[b], st.capacity[b]) || wg * SYNC_TPB >= nsub) return;   // uniform over the workgroup
+    const uint32_t sub_cap = sub_cap_of(st.file_n[b]), wg_cap = (sub_cap + SYNC_TPB - 1) / SYNC_TPB;
+    const Region rg = region_of(workspace + st.ws_at[b], sub_cap, wg_cap);
+    const uint8_t *f = files + st.file_at[b];
+    const bool live = i < nsub;
+    const WriteTo none = {};
+    const Window win = stage_window(staged, f, pl.scan + wg * SYNC_TPB * SUB_BYTES, pl.n);
+    State entry = {0u, END}, exit = entry;
+    Count count = {0u, 0u, 0, 0, 0, 0u};
+    bool decode = false;                                           // one call site: the decoder is inlined once
+    if (launch == 0) {
+        if (i == 0) rg.ctl[0] = rg.ctl[1] = rg.ctl[2] = rg.ctl[3] = 0u;
+        if (live) entry = guess_state(pl, f, i);
+        decode = live;
+    } else if (live) {
+        entry = rg.entry[i];
+        exit = rg.exit[i];
+        count = rg.count[i];
+        if (t == 0 && wg > 0) {
+            const State got = rg.wg_exit[((launch - 1) & 1) * wg_cap + wg - 1];
+            decode = !same(got, entry);
+            if (decode) {
+                entry = got;
+                raise_to(rg.ctl + 3, (uint32_t)launch);
+            }
+        }
+    }
+    int round = 0;
+    for (;; ++round) {
+        if (decode) decode_subsequence<false>(pl, f, win, i, entry, exit, count, none);
+        if (round == SYNC_ROUNDS) break;
+        handed[t] = exit;
+        __syncthreads();
+        decode = live && t > 0 && !same(handed[t - 1], entry);
+        if (decode) entry = handed[t - 1];
+        if (!__syncthreads_or(decode)) break;
+    }
+    if (t == 0 && round) raise_to(rg.ctl + 2, (uint32_t)round);
+    if (live) {
+        rg.entry[i] = entry;
+        rg.exit[i] = exit;
+        rg.count[i] = count;
+        if (t == SYNC_TPB - 1 || i == nsub - 1) rg.wg_exit[(launch & 1) * wg_cap + wg] = exit;
+    }
+}
+
+constexpr int SCAN_TPB = 256;
+__global__ __launch_bounds__(SCAN_TPB) void jpeg_entropy_scan_kernel(const uint8_t *plans, uint8_t *workspace, Streams st) {
+    __shared__ Count part[SCAN_TPB];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const Plan *pl = reinterpret_cast<const Plan *>(plans + (size_t)b * PLAN_BYTES);
+    const uint32_t sub_cap = sub_cap_of(st.file_n[b]), wg_cap = (sub_cap + SYNC_TPB - 1) / SYNC_TPB;
+    const uint32_t nsub = plan_fits(*pl, st.file_n[b], st.capacity[b]) ? pl->nsub : 0u;
+    const Region rg = region_of(workspace + st.ws_at[b], sub_cap, wg_cap);
+    const uint32_t per = (nsub + SCAN_TPB - 1) / SCAN_TPB;
+    const uint32_t lo = min(nsub, (uint32_t)t * per), hi = min(nsub, lo + per);
+    part[t] = chunk_sum(rg.count, lo, hi);
+    __syncthreads();
+    for (int d = 1; d < SCAN_TPB; d <<= 1) {                       // inclusive scan of the chunk sums, in order
+        Count v = part[t];
+        if (t >= d) v = combine(part[t - d], v);
+        __syncthreads();
+        part[t] = v;
+        __syncthreads();
+    }
+    const Count zero = {0u, 0u, 0, 0, 0, 0u};
+    chunk_prefix(rg.count, rg.prefix, lo, hi, t ? part[t - 1] : zero);
+}
+
+__global__ __launch_bounds__(SYNC_TPB) void jpeg_entropy_write_kernel(const uint8_t *files, const uint8_t *plans, uint8_t *workspace,
+                                                                      uint8_t *packed, Streams st) {
+    __shared__ Plan pl;
+    __shared__ uint32_t staged[WINDOW_WORDS];
+    const int b = blockIdx.y;
+    load_plan(pl, plans, b);
+    const uint32_t nsub = pl.nsub, i = blockIdx.x * SYNC_TPB + threadIdx.x;
+    const uint32_t sub_cap = sub_cap_of(st.file_n[b]), wg_cap = (sub_cap + SYNC_TPB - 1) / SYNC_TPB;
+    if (!plan_fits(pl, st.file_n[b], st.capacity[b]) || blockIdx.x * SYNC_TPB >= nsub) return;   // uniform over the workgroup
+    const Window win = stage_window(staged, files + st.file_at[b], pl.scan + blockIdx.x * SYNC_TPB * SUB_BYTES, pl.n);
+    if (i >= nsub) return;
+    const Region rg = region_of(workspace + st.ws_at[b], sub_cap, wg_cap);
+    WriteTo w;
+    w.packed = packed + st.packed_at[b];
+    w.capacity = st.capacity[b];
+    w.base = rg.prefix[i];
+    w.ctl = rg.ctl;
+    w.has_next = i + 1 < nsub;
+    w.next = w.has_next ? rg.entry[i + 1] : rg.entry[i];
+    State exit;
+    Count count;
+    decode_subsequence<true>(pl, files + st.file_at[b], win, i, rg.entry[i], exit, count, w);
+}
+
+__global__ __launch_bounds__(SYNC_TPB) void jpeg_entropy_finish_kernel(const uint8_t *plans, uint8_t *workspace, uint8_t *packed, Streams st,
+                                                                       int32_t *status) {
+    const int b = blockIdx.y;
+    const uint32_t g = blockIdx.x * SYNC_TPB + threadIdx.x;
+    const uint32_t sub_cap = sub_cap_of(st.file_n[b]), wg_cap = (sub_cap + SYNC_TPB - 1) / SYNC_TPB;
+    int32_t out[4] = {ML_JPEG_ENTROPY_BAD_PLAN, -1, 0, 0};
+    if (plan_fits(*reinterpret_cast<const Plan *>(plans + (size_t)b * PLAN_BYTES), st.file_n[b], st.capacity[b]))
+        finish_stream(region_of(workspace + st.ws_at[b], sub_cap, wg_cap).ctl, out);
+    if (g == 0) *reinterpret_cast<int4 *>(status + 4 * b) = make_int4(out[0], out[1], out[2], out[3]);
+    if (out[0] != ML_JPEG_ENTROPY_OK) clear_packed(packed + st.packed_at[b], st.capacity[b], g);
+}
+
+void device_table(const HuffTable &t, DevTable &d) {
+    memcpy(d.fast, t.fast, sizeof(d.fast));
+    memcpy(d.maxcode, t.maxcode, sizeof(d.maxcode));
+    memcpy(d.valoff, t.valoff, sizeof(d.valoff));
+    d.maxcode[0] = -1;
+    d.valoff[0] = 0;
+    d.nvals = t.nvals;
+    memset(d.vals, 0, sizeof(d.vals));
+    memcpy(d.vals, t.vals, (size_t)t.nvals);
+}
+
+int check_plan(const char *what, const void *plan, const Plan *&pl, int64_t n, int64_t capacity) {
+    pl = (const Plan *)plan;
+    ML_REQUIRE(capacity > 0 && capacity < (1ll << 32) && plan_fits(*pl, (uint32_t)n, (uint32_t)capacity),
+               "%s: not the plan of this %lld-byte stream, or a capacity (%lld) below the header, the offsets and one word a block", what,
+               (long long)n, (long long)capacity);
+    return ML_OK;
+}
+
+}  // namespace
+
+extern "C" int ml_jpeg_entropy_geometry(int32_t *geometry) {
+    ML_REQUIRE(geometry, "jpeg_entropy_geometry: null pointer");
+    geometry[0] = SUB_BITS;
+    geometry[1] = SYNC_TPB;
+    return ML_OK;
+}
+
+extern "C" int64_t ml_jpeg_entropy_plan_bytes(void) { return PLAN_BYTES; }
+
+extern "C" int ml_jpeg_entropy_plan(const uint8_t *data, int64_t n, void *plan) {
+    const char *what = "jpeg_entropy_plan";
+    ML_REQUIRE(data && n > 0 && plan, "%s: null pointer or empty stream", what);
+    ML_REQUIRE((((uintptr_t)plan) & 7u) == 0, "%s: plan must be 8-byte aligned", what);
+    ML_REQUIRE(n < MAX_FILE, "%s: a stream of %lld bytes (below %lld)", what, (long long)n, (long long)MAX_FILE);
+    Stream s;
+    if (parse_stream(data, n, s, what) != PARSE_OK) return ML_E_BADARG;
+    Geometry g;
+    const int e = geometry(s.H, s.W, s.mode, g, what);
+    if (e != ML_OK) return e;
+    for (int c = 0; c < s.ncomp; ++c) {
+        ML_REQUIRE(s.q_defined[s.comp[c].tq], "%s: quantisation table %d is not defined", what, s.comp[c].tq);
+        ML_REQUIRE(s.dc[s.comp[c].td].defined, "%s: DC Huffman table %d is not defined", what, s.comp[c].td);
+        ML_REQUIRE(s.ac[s.comp[c].ta].defined, "%s: AC Huffman table %d is not defined", what, s.comp[c].ta);
+    }
+    memset(plan, 0, PLAN_BYTES);
+    Plan *pl = (Plan *)plan;
+    pl->magic = PLAN_MAGIC;
+    pl->height = s.H;
+    pl->width = s.W;
+    pl->mode = s.mode;
+    pl->nblk = g.nblk;
+    pl->per_mcu = g.per_mcu;
+    pl->restart = (uint32_t)s.restart;
+    pl->scan = (uint32_t)s.scan;
+    pl->n = (uint32_t)n;
+    pl->nsub = sub_bound(n - s.scan);
+    pl->end_marker = (uint32_t)n;
+    for (const uint8_t *p = data + s.scan, *end = data + n; (p = (const uint8_t *)memchr(p, 0xFF, (size_t)(end - p))) != nullptr; ++p) {
+        if (p + 2 > end) break;
+        if (p[1] == 0x00 || p[1] == 0xFF) continue;               // a stuffed FF, a fill byte
+        if (p[1] < 0xD0 || p[1] > 0xD7) {
+            pl->end_marker = (uint32_t)(p - data);
+            break;
+        }
+        pl->last_rst = (uint32_t)(p - data) + 1u;
+    }
+    memcpy(pl->zigzag, ZIGZAG, 64);
+    for (int c = 0; c < MAX_COMPONENTS; ++c) {
+        const Component &k = s.comp[c < s.ncomp ? c : 0];
+        memcpy(pl->q[c], c < s.ncomp ? s.q[k.tq] : pl->q[c], 64);
+        device_table(s.dc[k.td], pl->dc[c]);
+        device_table(s.ac[k.ta], pl->ac[c]);
+    }
+    return ML_OK;
+}
+
+namespace {
+int entropy_streams(const char *what, const int64_t *file_offsets, int32_t B, Streams &st, long long &ws_total, uint32_t &max_wg) {
+    ML_REQUIRE(file_offsets, "%s: null pointer", what);
+    ML_REQUIRE(B > 0 && B <= MAX_BATCH, "%s: bad dims (B %d; 1 .. %d)", what, B, MAX_BATCH);
+    memset(&st, 0, sizeof(st));
+    ws_total = 0;
+    max_wg = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = file_offsets[b + 1] - file_offsets[b];
+        ML_REQUIRE(file_offsets[b] >= 0 && n > 0 && n < MAX_FILE, "%s: file_offsets[%d] = %lld, file_offsets[%d] = %lld", what, b,
+                   (long long)file_offsets[b], b + 1, (long long)file_offsets[b + 1]);
+        st.file_at[b] = file_offsets[b];
+        st.file_n[b] = (uint32_t)n;
+        st.ws_at[b] = ws_total;
+        ws_total += region_bytes(n);
+        if (wg_bound(n) > max_wg) max_wg = wg_bound(n);
+    }
+    return ML_OK;
+}
+}  // namespace
+
+extern "C" int64_t ml_jpeg_entropy_workspace_bytes(const int64_t *file_offsets, int32_t B) {
+    Streams st;
+    long long total;
+    uint32_t max_wg;
+    const int e = entropy_streams("jpeg_entropy_workspace_bytes", file_offsets, B, st, total, max_wg);
+    return e != ML_OK ? e : total;
+}
+
+extern "C" int ml_jpeg_entropy_device(const uint8_t *files, const int64_t *file_offsets, const void *plans, int32_t B, void *packed,
+                                      const int64_t *packed_offsets, int32_t *status, void *workspace, void *stream) {
+    const char *what = "jpeg_entropy_device";
+    ML_REQUIRE(files && plans && packed && packed_offsets && status && workspace, "%s: null pointer", what);
+    Streams st;
+    long long total;
+    uint32_t max_wg;
+    const int e = entropy_streams(what, file_offsets, B, st, total, max_wg);
+    if (e != ML_OK) return e;
+    ML_REQUIRE(ml_aligned16(packed) && ml_aligned16(workspace) && ml_aligned16(plans) && ml_aligned16(status),
+               "%s: plans, packed, status and workspace must be 16-byte aligned", what);
+    for (int b = 0; b < B; ++b) {
+        const int64_t cap = packed_offsets[b + 1] - packed_offsets[b];
+        ML_REQUIRE(packed_offsets[b] >= 0 && packed_offsets[b] % 16 == 0 && cap >= (long long)sizeof(PackedHeader) + 8 && cap < (1ll << 32),
+                   "%s: packed_offsets[%d] = %lld, packed_offsets[%d] = %lld", what, b, (long long)packed_offsets[b], b + 1,
+                   (long long)packed_offsets[b + 1]);
+        st.packed_at[b] = packed_offsets[b];
+        st.capacity[b] = (uint32_t)cap;
+    }
+    uint32_t max_cap = 0;
+    for (int b = 0; b < B; ++b) max_cap = st.capacity[b] > max_cap ? st.capacity[b] : max_cap;
+    hipStream_t s = (hipStream_t)stream;
+    for (int launch = 0; launch < SYNC_LAUNCHES; ++launch)
+        hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3(max_wg, B), dim3(SYNC_TPB), 0, s, files, (const uint8_t *)plans,
+                           (uint8_t *)workspace, st, launch);
+    hipLaunchKernelGGL(jpeg_entropy_scan_kernel, dim3(B), dim3(SCAN_TPB), 0, s, (const uint8_t *)plans, (uint8_t *)workspace, st);
+    hipLaunchKernelGGL(jpeg_entropy_write_kernel, dim3(max_wg, B), dim3(SYNC_TPB), 0, s, files, (const uint8_t *)plans,
+                       (uint8_t *)workspace, (uint8_t *)packed, st);
+    hipLaunchKernelGGL(jpeg_entropy_finish_kernel, dim3((max_cap / CLEAR_BYTES + SYNC_TPB) / SYNC_TPB, B), dim3(SYNC_TPB), 0, s,
+                       (const uint8_t *)plans, (uint8_t *)workspace, (uint8_t *)packed, st, status);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+// The same stages in CPU loops over one stream, every pointer in host memory.
+extern "C" int ml_jpeg_entropy_reference_host(const uint8_t *file, int64_t n, const void *plan, void *packed, int64_t capacity,
+                                              int32_t *status, void *workspace) {
+    const char *what = "jpeg_entropy_reference_host";
+    ML_REQUIRE(file && n > 0 && n < MAX_FILE && plan && packed && status && workspace, "%s: null pointer or bad length", what);
+    ML_REQUIRE((((uintptr_t)status) & 3u) == 0 && (((uintptr_t)packed) & 3u) == 0 && (((uintptr_t)workspace) & 7u) == 0 && (((uintptr_t)plan) & 7u) == 0,
+               "%s: plan and workspace must be 8-byte, packed 4-byte aligned", what);
+    const Plan *plp;
+    const int e = check_plan(what, plan, plp, n, capacity);
+    if (e != ML_OK) return e;
+    const Plan &pl = *plp;
+    const uint32_t sub_cap = sub_bound(n), wg_cap = wg_bound(n), nsub = pl.nsub;
+    const Region rg = region_of((uint8_t *)workspace, sub_cap, wg_cap);
+    const WriteTo none = {};
+    const Window win = {nullptr, 0u, 0u};
+    rg.ctl[0] = rg.ctl[1] = rg.ctl[2] = rg.ctl[3] = 0u;
+    for (int launch = 0; launch < SYNC_LAUNCHES; ++launch) {
+        for (uint32_t wg = 0; wg * SYNC_TPB < nsub; ++wg) {
+            const uint32_t first = wg * SYNC_TPB, live = nsub - first < (uint32_t)SYNC_TPB ? nsub - first : (uint32_t)SYNC_TPB;
+            State handed[SYNC_TPB];
+            if (launch == 0) {
+                for (uint32_t t = 0; t < live; ++t) {
+                    rg.entry[first + t] = guess_state(pl, file, first + t);
+                    decode_subsequence<false>(pl, file, win, first + t, rg.entry[first + t], rg.exit[first + t], rg.count[first + t], none);
+                }
+            } else if (wg > 0) {
+                const State got = rg.wg_exit[((launch - 1) & 1) * wg_cap + wg - 1];
+                if (!same(got, rg.entry[first])) {
+                    raise_to(rg.ctl + 3, (uint32_t)launch);
+                    rg.entry[first] = got;
+                    decode_subsequence<false>(pl, file, win, first, got, rg.exit[first], rg.count[first], none);
+                }
+            }
+            int round = 0;
+            for (; round < SYNC_ROUNDS; ++round) {
+                bool any = false;
+                for (uint32_t t = 0; t < live; ++t) handed[t] = rg.exit[first + t];
+                for (uint32_t t = 1; t < live; ++t) {
+                    if (same(handed[t - 1], rg.entry[first + t])) continue;
+                    any = true;
+                    rg.entry[first + t] = handed[t - 1];
+                    decode_subsequence<false>(pl, file, win, first + t, handed[t - 1], rg.exit[first + t], rg.count[first + t], none);
+                }
+                if (!any) break;
+            }
+            if (round) raise_to(rg.ctl + 2, (uint32_t)round);
+            rg.wg_exit[(launch & 1) * wg_cap + wg] = rg.exit[first + live - 1];
+        }
+    }
+    const Count zero = {0u, 0u, 0, 0, 0, 0u};
+    chunk_prefix(rg.count, rg.prefix, 0, nsub, zero);
+    for (uint32_t i = 0; i < nsub; ++i) {
+        WriteTo w;
+        w.packed = (uint8_t *)packed;
+        w.capacity = (uint32_t)capacity;
+        w.base = rg.prefix[i];
+        w.ctl = rg.ctl;
+        w.has_next = i + 1 < nsub;
+        w.next = w.has_next ? rg.entry[i + 1] : rg.entry[i];
+        State exit;
+        Count count;
+        decode_subsequence<true>(pl, file, win, i, rg.entry[i], exit, count, w);
+    }
+    finish_stream(rg.ctl, status);
+    if (status[0] != ML_JPEG_ENTROPY_OK)
+        for (uint32_t g = 0; g * CLEAR_BYTES < (uint32_t)capacity; ++g) clear_packed((uint8_t *)packed, (uint32_t)capacity, g);
+    return ML_OK;
+}

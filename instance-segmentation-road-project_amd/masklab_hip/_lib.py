@@ -168,6 +168,12 @@ SIGNATURES = {
     "ml_jpeg_decode_workspace_bytes": (_i64, [_i32] * 4),
     "ml_jpeg_decode_u8": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp, _vp, _vp]),
     "ml_jpeg_decode_reference_host": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "ml_jpeg_entropy_geometry": (C.c_int, [_vp]),
+    "ml_jpeg_entropy_plan_bytes": (_i64, []),
+    "ml_jpeg_entropy_plan": (C.c_int, [_vp, _i64, _vp]),
+    "ml_jpeg_entropy_workspace_bytes": (_i64, [_vp, _i32]),
+    "ml_jpeg_entropy_device": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "ml_jpeg_entropy_reference_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
 }
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*
 JPEG_UNSUPPORTED = 1                        # ML_JPEG_UNSUPPORTED

@@ -460,11 +460,15 @@ class DecodeImageContent(Layer):
     not imported.  Every other content (progressive or 4:2:2 JPEG, png ...), and every content when `device` is None
     or `on_device` is False, is decoded on the host through Pillow, imported lazily.  So is a baseline stream the strict
     device-path parser finds malformed (libjpeg tolerates some of those with a warning); without Pillow that stream
-    raises ops.JpegDecodeError with the parser's reason."""
+    raises ops.JpegDecodeError with the parser's reason.  `entropy` ("host", "device" or None for
+    ops.JPEG_ENTROPY_DEFAULT) says where the Huffman decoding of such a stream runs; the pixels are the same."""
 
-    def __init__(self, device=None, on_device=None, **kwargs):
+    def __init__(self, device=None, on_device=None, entropy=None, **kwargs):
+        if entropy is not None and entropy not in ops.JPEG_ENTROPY:
+            raise ValueError(f"DecodeImageContent: entropy must be one of {ops.JPEG_ENTROPY} or None, got {entropy!r}")
         self.device = device
         self.on_device = on_device
+        self.entropy = entropy
         super().__init__(**kwargs)
 
     def _decodes_on_device(self):
@@ -483,7 +487,7 @@ class DecodeImageContent(Layer):
         malformed = None
         if self._decodes_on_device():
             try:
-                return ops.decode_jpeg(bytes(inputs), self.device)
+                return ops.decode_jpeg(bytes(inputs), self.device, entropy=self.entropy)
             except ops.UnsupportedJpeg:
                 pass                                                                     # the host path below takes it
             except ops.JpegDecodeError as e:
@@ -504,5 +508,6 @@ class DecodeImageContent(Layer):
 
     def get_config(self):
         config = super().get_config()
-        config.update({"device": None if self.device is None else str(self.device), "on_device": self.on_device})
+        config.update({"device": None if self.device is None else str(self.device), "on_device": self.on_device,
+                       "entropy": self.entropy})
         return config

@@ -1364,13 +1364,28 @@ class _Staging:
 _jpeg_staging = threading.local()                                 # .by_device: {device: _Staging}, dies with its thread
 
 
-def decode_jpeg(contents, device):
+JPEG_ENTROPY = ("host", "device")
+JPEG_ENTROPY_DEFAULT = "host"                                     # what entropy=None means
+
+
+def _jpeg_entropy(entropy, what):
+    entropy = JPEG_ENTROPY_DEFAULT if entropy is None else entropy
+    if entropy not in JPEG_ENTROPY:
+        raise ValueError(f"{what}: entropy must be one of {JPEG_ENTROPY}, got {entropy!r}")
+    return entropy
+
+
+def decode_jpeg(contents, device, entropy=None):
     """Baseline JPEG `bytes` (or a list of at most 32 of them, all of one H x W and sampling mode) -> uint8 [B,H,W,3] on `device`, the
-    bytes libjpeg-turbo's default decode gives.  The host Huffman-decodes into pinned staging memory
+    bytes libjpeg-turbo's default decode gives.  entropy="host": the host Huffman-decodes into pinned staging memory
     (ml_jpeg_decode_entropy), one asynchronous copy uploads the packed coefficients, two launches reconstruct
-    (ml_jpeg_decode_u8); nothing is read back.  UnsupportedJpeg: a stream the device path does not take;
-    JpegDecodeError: a malformed one; ValueError: mixed sizes or modes."""
+    (ml_jpeg_decode_u8); nothing is read back.  entropy="device": the raw files and their plans go up, the Huffman
+    decoding runs in kernels (ml_jpeg_entropy_device) in front of the same two launches, and the B status words are
+    read back; if one of them is not 0 the call is decoded again by the host path, which also words every error.
+    UnsupportedJpeg: a stream the device path does not take; JpegDecodeError: a malformed one; ValueError: mixed
+    sizes or modes."""
     lib = _lib.load()
+    entropy = _jpeg_entropy(entropy, "decode_jpeg")
     single = isinstance(contents, (bytes, bytearray, memoryview))
     items = [bytes(c) for c in ([contents] if single else contents)]
     if not 1 <= len(items) <= _lib.JPEG_DECODE_MAX_BATCH:
@@ -1389,7 +1404,8 @@ def decode_jpeg(contents, device):
         raise ValueError(f"decode_jpeg: the streams of a call must have one sampling mode, got {[i[2] for i in infos]}")
     out = torch.empty((len(items), H, W, 3), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _decode_jpeg_group(lib, items, H, W, mode, device, out)
+        if entropy != "device" or not _decode_jpeg_group_device(lib, items, H, W, mode, device, out):
+            _decode_jpeg_group(lib, items, H, W, mode, device, out)
     return out
 
 
@@ -1424,3 +1440,95 @@ def _decode_jpeg_group(lib, items, H, W, mode, device, out):
     with _Prof("jpeg_decode", 0, at + 2 * nbytes + out.numel(), f"B={B} {H}x{W} mode={mode}"):
         _lib.check(lib.ml_jpeg_decode_u8(_ptr(packed), offsets, B, H, W, mode, _ptr(out), _ptr(ws), _stream()),
                    "ml_jpeg_decode_u8")
+
+
+def jpeg_entropy_geometry():
+    """ml_jpeg_entropy_geometry: (bits per subsequence, subsequences per workgroup) of the device entropy decoder."""
+    g = (C.c_int32 * 2)()
+    _lib.check(_lib.load().ml_jpeg_entropy_geometry(g), "ml_jpeg_entropy_geometry")
+    return tuple(g)
+
+
+def _jpeg_entropy_launch(lib, items, device):
+    """Upload the files and their plans and enqueue ml_jpeg_entropy_device -> (packed uint8 tensor, packed offsets
+    c_int64 [B + 1], status int32 [B,4] tensor), all on the device and nothing read; None if a stream has no plan (the
+    host decoder then says why)."""
+    B = len(items)
+    plan_bytes = int(lib.ml_jpeg_entropy_plan_bytes())
+    file_offsets = (C.c_int64 * (B + 1))()
+    packed_offsets = (C.c_int64 * (B + 1))()
+    at, room = B * plan_bytes, 0
+    for b, c in enumerate(items):
+        n = int(lib.ml_jpeg_decode_packed_bytes(c, len(c)))
+        if n < 0:
+            _lib.check(n, "ml_jpeg_decode_packed_bytes")
+        packed_offsets[b] = room
+        room += (n + 15) // 16 * 16
+        file_offsets[b] = at
+        at += len(c)
+    file_offsets[B], packed_offsets[B] = at, room
+    by_device = _jpeg_staging.__dict__.setdefault("by_device", {})
+    slot = by_device.setdefault(str(device), _Staging()).take(at)
+    host = slot[0]
+    for b, c in enumerate(items):
+        if lib.ml_jpeg_entropy_plan(c, len(c), C.c_void_p(host.data_ptr() + b * plan_bytes)) != 0:
+            return None
+        C.memmove(host.data_ptr() + file_offsets[b], c, len(c))
+    for b in range(B + 1):
+        file_offsets[b] -= B * plan_bytes                         # relative to the first file
+    nbytes = int(lib.ml_jpeg_entropy_workspace_bytes(file_offsets, B))
+    if nbytes < 0:
+        _lib.check(nbytes, "ml_jpeg_entropy_workspace_bytes")
+    up = torch.empty(at, dtype=torch.uint8, device=device)
+    up.copy_(host[:at], non_blocking=True)
+    slot[1] = torch.cuda.Event()
+    slot[1].record()
+    packed = torch.empty(room, dtype=torch.uint8, device=device)
+    status = torch.empty((B, 4), dtype=torch.int32, device=device)
+    ws = workspace(nbytes, device, "jpeg_entropy")
+    with _Prof("jpeg_entropy", 0, at + room, f"B={B}"):
+        _lib.check(lib.ml_jpeg_entropy_device(C.c_void_p(up.data_ptr() + B * plan_bytes), file_offsets, _ptr(up), B,
+                                              _ptr(packed), packed_offsets, _ptr(status), _ptr(ws), _stream()),
+                   "ml_jpeg_entropy_device")
+    return packed, packed_offsets, status
+
+
+def _decode_jpeg_group_device(lib, items, H, W, mode, device, out):
+    """The device entropy decoder in front of the two launches of ml_jpeg_decode_u8, on one stream; the statuses are the
+    one host read.  False: a stream did not end with status 0 and `out` is to be decoded by the host path."""
+    launched = _jpeg_entropy_launch(lib, items, device)
+    if launched is None:
+        return False
+    packed, packed_offsets, status = launched
+    B = len(items)
+    nbytes = int(lib.ml_jpeg_decode_workspace_bytes(B, H, W, mode))
+    if nbytes < 0:
+        _lib.check(nbytes, "ml_jpeg_decode_workspace_bytes")
+    ws = workspace(nbytes, device, "jpeg_decode")
+    # (a stream that failed has had its words cleared by the entropy decoder's last launch: every block reads as empty)
+    with _Prof("jpeg_decode", 0, packed.numel() + 2 * nbytes + out.numel(), f"B={B} {H}x{W} mode={mode}"):
+        _lib.check(lib.ml_jpeg_decode_u8(_ptr(packed), packed_offsets, B, H, W, mode, _ptr(out), _ptr(ws), _stream()),
+                   "ml_jpeg_decode_u8")
+    return not bool(status[:, 0].any().item())
+
+
+def jpeg_entropy_device(contents, device):
+    """ml_jpeg_entropy_device alone, for tests: `bytes` or a list of them -> (packed uint8 tensor on `device`, offsets
+    list [B + 1] -- stream b's packed form starts at offsets[b] --, status int32 [B,4] NumPy array: status, block,
+    most rounds, last launch that moved a state across workgroups)."""
+    lib = _lib.load()
+    single = isinstance(contents, (bytes, bytearray, memoryview))
+    items = [bytes(c) for c in ([contents] if single else contents)]
+    if not 1 <= len(items) <= _lib.JPEG_DECODE_MAX_BATCH:
+        raise ValueError(f"jpeg_entropy_device: 1 .. {_lib.JPEG_DECODE_MAX_BATCH} streams a call, got {len(items)}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"jpeg_entropy_device: a CUDA/HIP device expected, got {device} (no CPU fallback)")
+    for c in items:
+        jpeg_info(c)
+    with torch.cuda.device(device):
+        launched = _jpeg_entropy_launch(lib, items, device)
+        if launched is None:
+            raise JpegDecodeError(f"jpeg_entropy_device: {_last_error()}")
+        packed, offsets, status = launched
+        return packed, list(offsets), status.cpu().numpy()
