@@ -135,8 +135,14 @@ typedef struct ml_conv2d_desc {
     const int32_t *live;    /* NULL, or a DEVICE int: the batch is a fixed-capacity RoI batch (the mask head run
                                without a host read of the RoI counts, instance.py:121-134 + MoldBatch misc.py:231-286)
                                in which image i exists iff i % live_period < max(1, *live); tiles that hold only
-                               non-existing images compute and store nothing.  Generic and Winograd kernels. */
-    int32_t live_period;    /* RoI slots per image (B % live_period == 0); ignored when live == NULL      */
+                               non-existing images compute and store nothing (a tile = the 128 consecutive output rows
+                               of a block, 256 on the 256-row ML_MATH_F32X3 form, the 64 tiles of a Winograd block).
+                               Rows of non-existing images inside a tile that runs are computed from whatever their
+                               input holds and may be stored (NaN from NaN): nobody may read them; a launch cut along
+                               K leaves them unwritten.  No row of an existing image depends on a non-existing one.
+                               Generic and Winograd kernels. */
+    int32_t live_period;    /* RoI slots per image (B % live_period == 0, Ho * Wo * live_period >= 128: an image's
+                               slots fill at least one 128-row tile); ignored when live == NULL          */
     int32_t reserved1;
     double *gn_partials;    /* NULL, or [ceil(M/128)][4][2] DEVICE doubles: the epilogue also writes (sum, sum of squares)
                                of the values each 128-row tile stores, one pair per wave of the block (4 per tile) --
@@ -272,7 +278,9 @@ typedef struct ml_deconv_out_problem {
     int32_t hw, w, rois_per_image, reserved0;
     int64_t out_image_stride, out_base;
     const int32_t *live;   /* NULL, or a device int: RoI slot j of an image exists iff j < max(1, *live) (fixed-capacity
-                              batch with rois_per_image = the capacity); tiles of non-existing slots are skipped */
+                              batch with rois_per_image = the capacity, hw * rois_per_image >= 128); 128-pixel tiles
+                              that hold only non-existing slots are skipped: nothing of them is read or written.
+                              Non-existing slots inside a tile that runs are computed from whatever x holds there */
 } ml_deconv_out_problem;
 int ml_deconv2x2_out1x1_f32(const ml_deconv_out_problem *probs, int32_t nprob, int32_t K, int32_t c_mid, int32_t ncls,
                             int32_t cp, int32_t act_mid, int32_t act_out, void *stream);
@@ -336,8 +344,9 @@ typedef struct ml_gn_desc {
     int32_t dtype;                 /* 0: x / y are float; 1: x / y point to IEEE half (fp16-storage heads;
                                       HWC/G and C multiples of 8); gamma / beta are float either way */
     const int32_t *live;           /* NULL, or a device int: sample n exists iff n % live_period < max(1, *live)
-                                      (fixed-capacity RoI batches, as ml_conv2d_desc.live); others are skipped   */
-    int32_t live_period, reserved;
+                                      (fixed-capacity RoI batches, as ml_conv2d_desc.live); nothing of the others
+                                      is read or written, in place or not                                        */
+    int32_t live_period, reserved; /* N % live_period == 0                                                       */
     const double *partials;        /* NULL, or per chunk (n * G + g) `n_partials` consecutive (sum, sum of squares) pairs
                                       written by the producing conv (ml_conv2d_desc.gn_partials: the chunk's 128-row
                                       tiles, HWC/G a multiple of 128 * C): added in that order, no statistics pass    */
@@ -491,7 +500,8 @@ int ml_roi_crop_resize_f32(const float *fmap, const float *rows, int32_t row_str
                            int32_t level, int32_t n_l, int32_t ch, int32_t cw,
                            float img_h, float img_w, int32_t box_off, int32_t box_rows,
                            const int32_t *live /* NULL, or a device int: with n_l = cap (no host read of the counts) only
-                                                  slots j < max(1, *live) are written (crop or -1 fill) */,
+                                                  slots j < max(1, *live) are written (crop or -1 fill), in roi_fmaps
+                                                  and in roi_boxes; the others keep what they held */,
                            void *stream);
 /* The same with fmap / roi_fmaps in IEEE half (C % 8 == 0): the mask head of the fp16 path; boxes and rows stay fp32. */
 int ml_roi_crop_resize_f16(const void *fmap, const float *rows, int32_t row_stride, int32_t row_off,

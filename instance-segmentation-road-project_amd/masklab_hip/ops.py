@@ -956,9 +956,10 @@ def mask_distribute(rows, max_k, base_size, has_k=False, want_k=False):
     return slots, lcounts, lmax, kvals
 
 
-def roi_crop_resize(fmap, rows, slots, lcounts, level, n_l, crop_size, img_hw, roi_boxes, box_off, live=None):
+def roi_crop_resize(fmap, rows, slots, lcounts, level, n_l, crop_size, img_hw, roi_boxes, box_off, live=None, out=None):
     """rows [B,cap,6] (cx,cy,w,h,cls,conf) or [B,cap,7] dist_boxes (k first).  live: device int32 [1] = the level's
-    RoI maximum when the launch runs at capacity (n_l = cap): slots past max(1, live) are not written."""
+    RoI maximum when the launch runs at capacity (n_l = cap): slots past max(1, live) are not written.  out: the
+    [B,n_l,ch,cw,C] tensor of fmap's dtype to write the crops into (None: allocated here)."""
     lib = _lib.load()
     _require_dev(fmap, "fmap")
     B, Hf, Wf, Cc = fmap.shape
@@ -966,7 +967,13 @@ def roi_crop_resize(fmap, rows, slots, lcounts, level, n_l, crop_size, img_hw, r
     roff = rs - 6
     L = slots.shape[1]
     ch, cw = crop_size
-    out = torch.empty((B, n_l, ch, cw, Cc), dtype=fmap.dtype, device=fmap.device)
+    if out is None:
+        out = torch.empty((B, n_l, ch, cw, Cc), dtype=fmap.dtype, device=fmap.device)
+    else:
+        _require_dev(out, "out")
+        if tuple(out.shape) != (B, n_l, ch, cw, Cc) or out.dtype != fmap.dtype:
+            raise ValueError(f"roi_crop_resize: out {tuple(out.shape)} / {out.dtype} does not match "
+                             f"{(B, n_l, ch, cw, Cc)} / {fmap.dtype}")
     fn = lib.ml_roi_crop_resize_f16 if fmap.dtype == torch.float16 else lib.ml_roi_crop_resize_f32
     _lib.check(fn(_ptr(fmap), _ptr(rows), rs, roff, _ptr(slots), _ptr(lcounts), _ptr(out),
                   _ptr(roi_boxes), B, Hf, Wf, Cc, cap, L, level, n_l, ch, cw,
