@@ -63,7 +63,8 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_jpeg_decode_info / _packed_bytes /
                                             _entropy / _workspace_bytes / _u8 / _reference_host;
                                             (additive, same version) ml_jpeg_entropy_geometry / _plan_bytes /
-                                            _plan / _workspace_bytes / _device / _reference_host          */
+                                            _plan / _workspace_bytes / _device / _reference_host;
+                                            (additive, same version) ml_conv1x1_dual_f32 / _f16             */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -453,6 +454,22 @@ typedef struct ml_se_bottleneck_desc {
 int64_t ml_se_bottleneck_workspace_bytes(int32_t B, int32_t HW, int32_t C);
 int ml_se_bottleneck_f32(const ml_se_bottleneck_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
 int ml_se_bottleneck_f16(const ml_se_bottleneck_desc *desc, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* The projection unit of a ResNet-50 stage (Keras-Applications resnet50.py conv_block: Add(bn(res*_branch2c(a)),
+ * bn(res*_branch1(x))) + ReLU) as ONE GEMM over the concatenated K of two source tensors, NHWC:
+ *   out[b, i, j, n] = relu( sum_k a[b, i, j, k] Wa[k, n] + sum_l x[b, s i, s j, l] Wx[l, n] + bias[n] )
+ * a [B, Ho, Wo, Ka], x [B, H, W, Kx] read in place at stride s in {1, 2} (Ho = (H - 1) / s + 1, Wo likewise; no subsample
+ * copy, no concatenation buffer, no shortcut tensor), out [B, Ho, Wo, N].  wgt [N][Ka + Kx]: row n holds Wa[:, n] then
+ * Wx[:, n], both BatchNorms folded; bias [N] fp32 = the sum of the two folded biases.
+ * _f32: float tensors and weights, exact fp32 products (v_mfma_f32_32x32x2_f32), each output one fp32 fma chain in k order.
+ * _f16: IEEE-half a / x / wgt / out, fp16 MFMA with fp32 accumulation, bias and ReLU in fp32, one rounding at the store.
+ * Ka and Kx positive multiples of the K chunk (32 floats / 64 halves), N a multiple of 128, every pointer 16-byte aligned,
+ * every tensor below 2 GiB; anything else is ML_E_BADARG (nothing is launched), and the caller runs the unit as two convs.
+ * No atomics, no split K: the same bits run to run, under graph replay, and for image k of any batch.             */
+int ml_conv1x1_dual_f32(const float *a, const float *x, const float *wgt, const float *bias, float *out,
+                        int32_t B, int32_t H, int32_t W, int32_t Ka, int32_t Kx, int32_t N, int32_t stride, void *stream);
+int ml_conv1x1_dual_f16(const void *a, const void *x, const void *wgt, const float *bias, void *out,
+                        int32_t B, int32_t H, int32_t W, int32_t Ka, int32_t Kx, int32_t N, int32_t stride, void *stream);
 
 /* ---------------------------------------------------------------- detection post-process
  * RestoreBoxes (engine/layers/detection.py:325-344): priors int32 [A,4] (cx,cy,w,h) shared by

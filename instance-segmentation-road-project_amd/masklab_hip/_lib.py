@@ -135,6 +135,8 @@ SIGNATURES = {
     "ml_se_bottleneck_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "ml_se_bottleneck_f32": (C.c_int, [C.POINTER(SeBottleneckDesc), _vp, _i64, _vp]),
     "ml_se_bottleneck_f16": (C.c_int, [C.POINTER(SeBottleneckDesc), _vp, _i64, _vp]),
+    "ml_conv1x1_dual_f32": (C.c_int, [_vp] * 5 + [_i32] * 7 + [_vp]),
+    "ml_conv1x1_dual_f16": (C.c_int, [_vp] * 5 + [_i32] * 7 + [_vp]),
     "ml_restore_boxes_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "ml_detection_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "ml_detection_proposal_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp]),

@@ -1,10 +1,11 @@
 """Backbone loader + preprocess -- drop-in for reference engine/backbone/base.py
 (BackBonePreProcess :22-84, BACKBONE_LAYERS :104-182, load_backbone :185-316).
 
-Backbones on the hot path: 'resnext50' (in-tree in the reference), 'seresnet34' (the reference project's own model,
-vendored thirdparty/classification_models), 'seresnet50' and 'seresnext50' (the same vendored model zoo, senet.py) and
-'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises NotImplementedError like the
-reference does for unknown types.  BatchNormalization is folded into the conv weights at load
+Backbones on the hot path: 'resnet50' (the reference's default: tf.keras.applications.ResNet50, the legacy
+Keras-Applications model, restated in backbone/resnet50.py), 'resnext50' (in-tree in the reference), 'seresnet34' (the
+reference project's own model, vendored thirdparty/classification_models), 'seresnet50' and 'seresnext50' (the same
+vendored model zoo, senet.py) and 'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises
+NotImplementedError like the reference does for unknown types.  BatchNormalization is folded into the conv weights at load
 time; the 3-channel stems read a channel-padded NHWC4 image written by the preprocess kernel.
 """
 from .. import ops
@@ -13,6 +14,9 @@ from ..layers.misc import Identity
 from ..normalization import GroupNormalization
 
 BACKBONE_LAYERS = {
+    # the reference's default (reference :105-111): Keras auto-named Activations of the legacy Keras-Applications ResNet50
+    "resnet50": {"C1": 'activation', "C2": 'activation_9', "C3": "activation_21", "C4": "activation_39",
+                 "C5": "activation_48"},
     "resnext50": {"C1": 'conv1_relu', "C2": 'conv2_block3_out', "C3": "conv3_block4_out",
                   "C4": "conv4_block6_out", "C5": "conv5_block3_out"},
     # build-side extension: architecture from the vendored thirdparty model zoo
@@ -80,6 +84,7 @@ class BackboneModel(Layer):
     def __init__(self, backbone_type, backbone_outputs, num_features, **kwargs):
         super().__init__(name=backbone_type, **kwargs)
         from .mobilenet import MobileNetV1
+        from .resnet50 import ResNet50
         from .resnext import ResNeXt50
         from .resnext101 import ResNeXt101
         from .senet import SEResNet50, SEResNeXt50
@@ -88,7 +93,11 @@ class BackboneModel(Layer):
         self.backbone_type = bt
         self.backbone_outputs = tuple(backbone_outputs)
         self.num_features = num_features
-        if bt == 'resnext50':
+        if bt == 'resnet50':
+            self.preprocess = BackBonePreProcess(rgb=False, mean_shift=True, normalize=0)     # :190-193
+            self.body = ResNet50()
+            same = True
+        elif bt == 'resnext50':
             self.preprocess = BackBonePreProcess(rgb=True, mean_shift=True, normalize=2)      # :215-217
             self.body = ResNeXt50()
             same = True

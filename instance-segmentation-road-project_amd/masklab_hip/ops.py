@@ -904,6 +904,92 @@ def bn_relu(x, scale, shift):
     return out
 
 
+# How ResNet-50's four projection units (the first block of each stage) run: "on" = one GEMM over the concatenated K of the
+# block's 3x3 output and its input (conv1x1_dual; conv maths "f32" and "f16s" only), "off" = the shortcut conv, then the
+# 2c conv with the shortcut as its residual.  No other backbone reads it.  "on" is the default because the whole forward at
+# 8 x 1024^2 measured faster with it by more than the spread in both maths (scripts/resnet50_timing.py).
+PROJECTION_FUSION = "on"
+
+
+def set_projection_fusion(mode):
+    global PROJECTION_FUSION
+    if mode not in ("on", "off"):
+        raise ValueError(f"projection fusion must be 'on' or 'off', got {mode!r}")
+    PROJECTION_FUSION = mode
+
+
+def projection_fused():
+    """True when a ResNet-50 projection unit launched now takes the one-GEMM kernel."""
+    return PROJECTION_FUSION == "on" and CONV_MATH in ("f32", "f16s")
+
+
+class DeviceDualConv:
+    """The two 1x1 convs of a projection unit -- `dc_a` on the 3x3 output (its BN folded, no activation), `dc_x` the
+    shortcut on the block input at `stride` -- and their one-GEMM operand: wgt [N][Ka + Kx] (row n = Wa[:, n] then
+    Wx[:, n]) with bias = the sum of the two folded biases, made here once from the folded Keras kernels [1,1,K,N].
+    `dc_a` / `dc_x`: the two convs' packings where the caller already holds them (a layer pair), else made here."""
+
+    def __init__(self, ka, ba, kx, bx, device, dc_a=None, dc_x=None):
+        from .packing import pack_dense
+        ka, kx = np.asarray(ka, np.float32), np.asarray(kx, np.float32)
+        if ka.shape[:2] != (1, 1) or kx.shape[:2] != (1, 1) or ka.shape[3] != kx.shape[3]:
+            raise ValueError(f"DeviceDualConv: two 1x1 kernels of one output width expected, got {ka.shape} and {kx.shape}")
+        self.Ka, self.Kx, self.N = int(ka.shape[2]), int(kx.shape[2]), int(ka.shape[3])
+        zero = np.zeros(self.N, np.float64)
+        ba = zero if ba is None else np.asarray(ba, np.float64)
+        bx = zero if bx is None else np.asarray(bx, np.float64)
+        self.dc_a = dc_a if dc_a is not None else DeviceConv(pack_dense(ka, ba.astype(np.float32)), device)
+        self.dc_x = dc_x if dc_x is not None else DeviceConv(pack_dense(kx, bx.astype(np.float32)), device)
+        w = np.ascontiguousarray(np.concatenate([ka[0, 0].T, kx[0, 0].T], axis=1))              # [N][Ka + Kx]
+        self.wgt = torch.from_numpy(w).to(device)
+        self.bias = torch.from_numpy((ba + bx).astype(np.float32)).to(device)
+        self._wgt_h = None
+
+    @property
+    def wgt_h(self):
+        """The operand rounded to IEEE half (what the two convs' own half packings hold); made on first use."""
+        if self._wgt_h is None:
+            self._wgt_h = self.wgt.cpu().to(torch.float16).to(self.wgt.device)
+        return self._wgt_h
+
+
+def conv1x1_dual(a, x, packed: DeviceDualConv, stride_b=1):
+    """ml_conv1x1_dual_f32 / _f16: relu(a @ Wa + x[:, ::s, ::s] @ Wx + bias) in ONE launch -- a [B,Ho,Wo,Ka] and
+    x [B,H,W,Kx] contiguous NHWC, both float32 (exact fp32 products) or both float16 (fp16 MFMA, fp32 accumulate, one
+    rounding at the store); s = stride_b in {1, 2}, Ho = (H - 1) // s + 1.  x is read in place at its stride.  Shapes the
+    kernel does not take (ML_E_BADARG: a K that is no multiple of its chunk, N % 128, a tensor of 2 GiB) run as the two
+    launches the unit is made of: the shortcut conv, then the conv on `a` with the shortcut as residual and ReLU."""
+    lib = _lib.load()
+    _require_dev(a, "a")
+    _require_dev(x, "x")
+    if a.dtype not in (torch.float32, torch.float16) or x.dtype != a.dtype:
+        raise ValueError(f"conv1x1_dual: a and x must both be float32 or both float16, got {a.dtype} and {x.dtype}")
+    if stride_b not in (1, 2):
+        raise ValueError(f"conv1x1_dual: stride_b must be 1 or 2, got {stride_b}")
+    B, H, W, Kx = x.shape
+    Ho, Wo = (H - 1) // stride_b + 1, (W - 1) // stride_b + 1
+    if tuple(a.shape) != (B, Ho, Wo, packed.Ka) or Kx != packed.Kx:
+        raise ValueError(f"conv1x1_dual: a {tuple(a.shape)} / x {tuple(x.shape)} do not match the packed unit "
+                         f"(Ka={packed.Ka}, Kx={packed.Kx}, stride {stride_b})")
+    half = a.dtype == torch.float16
+    out = torch.empty((B, Ho, Wo, packed.N), dtype=a.dtype, device=a.device)
+    M, es = B * Ho * Wo, a.element_size()
+    fn, w = (lib.ml_conv1x1_dual_f16, packed.wgt_h) if half else (lib.ml_conv1x1_dual_f32, packed.wgt)
+    with _Prof("conv1x1_dual_h" if half else "conv1x1_dual", 2.0 * M * packed.N * (packed.Ka + Kx),
+               es * (M * (packed.Ka + Kx) + M * packed.N + w.numel()),
+               f"M={M} N={packed.N} Ka={packed.Ka} Kx={Kx} s{stride_b} HxW={H}x{W}") as prof:
+        status = fn(_ptr(a), _ptr(x), _ptr(w), _ptr(packed.bias), _ptr(out), B, H, W, packed.Ka, Kx, packed.N, stride_b,
+                    _stream())
+        if status == -1:                     # ML_E_BADARG: not a shape of this kernel, nothing was launched
+            prof.on = False
+        else:
+            _lib.check(status, "ml_conv1x1_dual")
+    if status == -1:
+        sc = conv2d(x, packed.dc_x, stride=stride_b, padding="valid")
+        return conv2d(a, packed.dc_a, padding="valid", act=_lib.ACT_RELU, residual=sc)
+    return out
+
+
 def restore_boxes(loc_pred, priors_i32):
     lib = _lib.load()
     _require_dev(loc_pred, "loc_pred")
