@@ -4,14 +4,23 @@
 Backbones on the hot path: 'resnet50' (the reference's default: tf.keras.applications.ResNet50, the legacy
 Keras-Applications model, restated in backbone/resnet50.py), 'resnext50' (in-tree in the reference), 'seresnet34' (the
 reference project's own model, vendored thirdparty/classification_models), 'seresnet50' and 'seresnext50' (the same
-vendored model zoo, senet.py) and 'mobilenet' (tf.keras.applications.MobileNet v1).  Everything else raises
-NotImplementedError like the reference does for unknown types.  BatchNormalization is folded into the conv weights at load
-time; the 3-channel stems read a channel-padded NHWC4 image written by the preprocess kernel.
+vendored model zoo, senet.py), 'resnext101' (a build-side extension: the model zoo's resnext.py, which the reference
+never wires in) and 'mobilenet' (tf.keras.applications.MobileNet v1); BACKBONES pairs each with its body class, preprocess
+and extra-level padding, and the six residual bodies share backbone/body.py.  Everything else raises NotImplementedError
+like the reference does for unknown types.  BatchNormalization is folded into the conv weights at load time; the
+3-channel stems read a channel-padded NHWC4 image written by the preprocess kernel.
 """
 from .. import ops
 from ..keras_like import Conv2D, DepthwiseConv2D, GroupedConv2D, Layer
 from ..layers.misc import Identity
 from ..normalization import GroupNormalization
+from .body import input_affine
+from .mobilenet import MobileNetV1
+from .resnet50 import ResNet50
+from .resnext import ResNeXt50
+from .resnext101 import ResNeXt101
+from .senet import SEResNet50, SEResNeXt50
+from .seresnet34 import SEResNet34
 
 BACKBONE_LAYERS = {
     # the reference's default (reference :105-111): Keras auto-named Activations of the legacy Keras-Applications ResNet50
@@ -32,6 +41,18 @@ BACKBONE_LAYERS = {
                     "C5": "activation_80"},
     "mobilenet": {"C1": "conv_pw_1_relu", "C2": "conv_pw_3_relu", "C3": "conv_pw_5_relu",
                   "C4": "conv_pw_11_relu", "C5": "conv_pw_13_relu"},
+}
+
+# backbone_type -> (body class, BackBonePreProcess arguments, padding of the extra-level convs); reference :190-279, and
+# :292-314 for the padding: mobilenet pads ((0, 1), (0, 1)) + valid, the others 'same'
+BACKBONES = {
+    "resnet50": (ResNet50, dict(rgb=False, mean_shift=True, normalize=0), 'same'),                    # :190-193
+    "resnext50": (ResNeXt50, dict(rgb=True, mean_shift=True, normalize=2), 'same'),                   # :215-217
+    "resnext101": (ResNeXt101, dict(rgb=True, mean_shift=False, normalize=0), 'same'),                # then bn_data
+    "seresnet34": (SEResNet34, dict(rgb=True, mean_shift=False, normalize=0), 'same'),                # :232-234, then bn_data
+    "seresnet50": (SEResNet50, dict(rgb=True, mean_shift=True, normalize=3), 'same'),                 # :220-223
+    "seresnext50": (SEResNeXt50, dict(rgb=True, mean_shift=True, normalize=3), 'same'),               # :238-241
+    "mobilenet": (MobileNetV1, dict(rgb=False, mean_shift=False, normalize=2), ((0, 1), (0, 1))),     # :254-256
 }
 
 
@@ -83,50 +104,20 @@ class BackboneModel(Layer):
 
     def __init__(self, backbone_type, backbone_outputs, num_features, **kwargs):
         super().__init__(name=backbone_type, **kwargs)
-        from .mobilenet import MobileNetV1
-        from .resnet50 import ResNet50
-        from .resnext import ResNeXt50
-        from .resnext101 import ResNeXt101
-        from .senet import SEResNet50, SEResNeXt50
-        from .seresnet34 import SEResNet34
         bt = backbone_type.lower()
+        if bt not in BACKBONES:
+            raise NotImplementedError(
+                f"backbone_type must be one of {list(BACKBONES)} on the MI355X path (got '{backbone_type}')")
+        body, preprocess, pad = BACKBONES[bt]
         self.backbone_type = bt
         self.backbone_outputs = tuple(backbone_outputs)
         self.num_features = num_features
-        if bt == 'resnet50':
-            self.preprocess = BackBonePreProcess(rgb=False, mean_shift=True, normalize=0)     # :190-193
-            self.body = ResNet50()
-            same = True
-        elif bt == 'resnext50':
-            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=True, normalize=2)      # :215-217
-            self.body = ResNeXt50()
-            same = True
-        elif bt == 'resnext101':
-            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=False, normalize=0)
-            self.body = ResNeXt101()
-            same = True
-        elif bt == 'seresnet34':
-            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=False, normalize=0)     # :232-234, then bn_data
-            self.body = SEResNet34()
-            same = True
-        elif bt in ('seresnet50', 'seresnext50'):
-            self.preprocess = BackBonePreProcess(rgb=True, mean_shift=True, normalize=3)      # :220-223 / :238-241
-            self.body = SEResNet50() if bt == 'seresnet50' else SEResNeXt50()
-            same = True
-        elif bt == 'mobilenet':
-            self.preprocess = BackBonePreProcess(rgb=False, mean_shift=False, normalize=2)    # :254-256
-            self.body = MobileNetV1()
-            same = False
-        else:
-            raise NotImplementedError(
-                f"backbone_type must be one of {list(BACKBONE_LAYERS.keys())} on the MI355X path "
-                f"(got '{backbone_type}')")
+        self.preprocess = BackBonePreProcess(**preprocess)
+        self.body = body()
         self.taps = [k for k in ("C1", "C2", "C3", "C4", "C5") if k in self.backbone_outputs]
         if not self.taps:
             raise ValueError("backbone_outputs must name at least one C-level")
         self.identities = {k: Identity(name=k) for k in self.taps}
-        # extra levels (reference :292-314): mobilenet pads ((0,1),(0,1)) + valid, others 'same'
-        pad = 'same' if same else ((0, 1), (0, 1))
         self.p6_conv = Conv2D(num_features, (3, 3), strides=(2, 2), padding=pad, activation='relu', name='P6_conv')
         self.p6_norm = GroupNormalization(name='P6_norm')          # default groups=32 (Appendix B.2)
         self.p7_conv = Conv2D(num_features, (3, 3), strides=(2, 2), padding=pad, activation='relu', name='P7_conv')
@@ -163,8 +154,9 @@ class BackboneModel(Layer):
 
     def load_weights(self, weights, device):
         super().load_weights(weights, device)
-        if hasattr(self.body, "input_affine"):
-            self.preprocess.extra_affine = self.body.input_affine(weights)
+        eps = getattr(self.body, "INPUT_BN_EPS", None)
+        if eps is not None:
+            self.preprocess.extra_affine = input_affine(weights, eps)
 
     def call(self, images, **kwargs):
         x = self.preprocess(images)

@@ -21,7 +21,8 @@ ops.set_projection_fusion("on") it runs as ONE GEMM over the concatenated K of y
 "f32" and "f16s"), x read in place at the block's stride and the shortcut tensor never written; "off", and in "f32x3" /
 "f16", it is the shortcut conv followed by the 2c conv with the shortcut as residual."""
 from .. import ops
-from ..keras_like import Conv2D, Layer
+from ..keras_like import Conv2D
+from .body import ResidualBody
 
 BN_EPS = 1e-3
 STAGES = ((2, "abc", (64, 64, 256), 1), (3, "abcd", (128, 128, 512), 2), (4, "abcdef", (256, 256, 1024), 2),
@@ -82,52 +83,12 @@ class _Block:
         return self.conv2c(y, residual=self.shortcut(x))
 
 
-class ResNet50(Layer):
+class ResNet50(ResidualBody):
     def __init__(self, **kwargs):
         super().__init__(name=kwargs.pop("name", "resnet50_body"), **kwargs)
         # synthetic init: the stem reads raw mean-shifted pixels (rms ~ 74), so bn_conv1's gamma starts at ~ 1 / 100
-        self.conv1 = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)),
-                            fold_bn=("bn_conv1", BN_EPS, True, (0.005, 0.015)), activation='relu', image_input=True,
-                            kernel_initializer="he_normal", bias_initializer="normal", name="conv1")
+        self.stem = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)),
+                           fold_bn=("bn_conv1", BN_EPS, True, (0.005, 0.015)), activation='relu', image_input=True,
+                           kernel_initializer="he_normal", bias_initializer="normal", name="conv1")
         self.stages = [[_Block(filters, stage, b, stride if b == "a" else 1, b == "a") for b in blocks]
                        for stage, blocks, filters, stride in STAGES]
-
-    def build(self, input_shape):
-        s = self.conv1.build(input_shape)
-        taps = {"C1": s}
-        H, W = s[1], s[2]
-        s = (s[0], None if H is None else (H + 2 - 3) // 2 + 1, None if W is None else (W + 2 - 3) // 2 + 1, s[3])
-        for tap, stage in zip(("C2", "C3", "C4", "C5"), self.stages):
-            for blk in stage:
-                s = blk.build(s)
-            taps[tap] = s
-        self.built = True
-        return taps
-
-    def children(self):
-        return [self.conv1] + [l for st in self.stages for blk in st for l in blk.layers()]
-
-    def weight_specs(self):
-        out = {}
-        for ch in self.children():
-            out.update(ch.weight_specs())
-        return out
-
-    def call(self, x, wanted=("C3", "C4", "C5"), **kwargs):
-        import torch
-        half = ops.half_storage()            # fp16-storage mode: the body's tensors AND its taps are IEEE half
-        taps = {}
-        if "C1" not in wanted and self.conv1.dev is not None and ops.has_fused_stem():
-            x = ops.stem_pool(x, self.conv1.dev)     # stem + pool in one pass (csrc/stem.hip): same bits as the pair below
-        else:
-            x = self.conv1(x, out_dtype=torch.float16 if half else None)
-            taps["C1"] = x
-            x = ops.maxpool3x3s2(x, pad=1)                     # pool1_pad + max_pooling2d
-        last = max(int(t[1]) for t in wanted)
-        for tap, stage in zip(("C2", "C3", "C4", "C5"), self.stages):
-            if int(tap[1]) > last:
-                break
-            for blk in stage:
-                x = blk(x)
-            taps[tap] = x
-        return taps

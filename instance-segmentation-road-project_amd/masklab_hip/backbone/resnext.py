@@ -4,8 +4,8 @@ converted checkpoint loads by name.  Every BatchNormalization (eps 1.001e-5) is 
 preceding conv; ReLU / residual Add are conv-epilogue fusions; the grouped 3x3
 (DepthwiseConv2D(depth_multiplier=c) + Split/Reduce/MergeGroups, :212-219) is one MFMA conv over
 block-diagonal packed weights."""
-from .. import ops
-from ..keras_like import Conv2D, GroupedConv2D, Layer
+from ..keras_like import Conv2D, GroupedConv2D
+from .body import ResidualBody
 
 BN_EPS = 1.001e-5
 
@@ -46,58 +46,19 @@ class _Block:
         return self.conv3(y, residual=sc)          # relu(shortcut + bn(conv)) fused in the epilogue
 
 
-class ResNeXt50(Layer):
+class ResNeXt50(ResidualBody):
     STAGES = (("conv2", 128, 3, 1), ("conv3", 256, 4, 2), ("conv4", 512, 6, 2), ("conv5", 1024, 3, 2))  # :407-410
 
     def __init__(self, **kwargs):
         super().__init__(name=kwargs.pop("name", "resnext50_body"), **kwargs)
-        # stem (:343-349): ZeroPadding2D(3) + Conv 7x7 s2 (no bias) + BN + ReLU on the NHWC4 image
-        self.conv1 = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False,
-                            fold_bn=("conv1_bn", BN_EPS, True), activation='relu', image_input=True,
-                            kernel_initializer="he_normal", name="conv1_conv")
+        # stem (:343-349): ZeroPadding2D(3) + Conv 7x7 s2 (no bias) + BN + ReLU on the NHWC4 image; the pool is
+        # pool1_pad + pool1_pool (:351-352)
+        self.stem = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False,
+                           fold_bn=("conv1_bn", BN_EPS, True), activation='relu', image_input=True,
+                           kernel_initializer="he_normal", name="conv1_conv")
         self.stages = []
         for name, filters, blocks, stride1 in self.STAGES:                                     # :235-253
             stage = [_Block(filters, stride1, True, f"{name}_block1")]
             for i in range(2, blocks + 1):
                 stage.append(_Block(filters, 1, False, f"{name}_block{i}"))
             self.stages.append(stage)
-
-    def build(self, input_shape):
-        s = self.conv1.build(input_shape)
-        taps = {"C1": s}
-        H, W = s[1], s[2]
-        s = (s[0], None if H is None else (H + 2 - 3) // 2 + 1, None if W is None else (W + 2 - 3) // 2 + 1, s[3])
-        for tap, stage in zip(("C2", "C3", "C4", "C5"), self.stages):
-            for blk in stage:
-                s = blk.build(s)
-            taps[tap] = s
-        self.built = True
-        return taps
-
-    def children(self):
-        return [self.conv1] + [l for st in self.stages for blk in st for l in blk.layers()]
-
-    def weight_specs(self):
-        out = {}
-        for ch in self.children():
-            out.update(ch.weight_specs())
-        return out
-
-    def call(self, x, wanted=("C3", "C4", "C5"), **kwargs):
-        import torch
-        half = ops.half_storage()            # fp16-storage mode: the body's tensors AND its taps are IEEE half
-        taps = {}
-        if "C1" not in wanted and self.conv1.dev is not None and ops.has_fused_stem():
-            x = ops.stem_pool(x, self.conv1.dev)     # stem + pool in one pass (csrc/stem.hip): same bits as the pair below
-        else:
-            x = self.conv1(x, out_dtype=torch.float16 if half else None)
-            taps["C1"] = x
-            x = ops.maxpool3x3s2(x, pad=1)                     # pool1_pad + pool1_pool (:351-352)
-        last = max(int(t[1]) for t in wanted)
-        for tap, stage in zip(("C2", "C3", "C4", "C5"), self.stages):
-            for blk in stage:
-                x = blk(x)
-            taps[tap] = x
-            if int(tap[1]) >= last:
-                break
-        return taps

@@ -9,7 +9,8 @@ Layer names follow the vendored file; BatchNorm eps = 2e-5 (:44-54).  GroupConv2
 import numpy as np
 
 from .. import _lib, ops, packing
-from ..keras_like import Conv2D, Layer, WeightSpec
+from ..keras_like import Conv2D
+from .body import ResidualBody
 
 BN_EPS = 2e-5
 REPETITIONS = (3, 4, 23, 3)
@@ -103,12 +104,14 @@ class _Unit:
         return self.conv3(self.conv2(self.conv1(x)), residual=sc)
 
 
-class ResNeXt101(Layer):
+class ResNeXt101(ResidualBody):
+    INPUT_BN_EPS = BN_EPS
+
     def __init__(self, repetitions=REPETITIONS, **kwargs):
         super().__init__(name=kwargs.pop("name", "resnext101_body"), **kwargs)
-        self.conv0 = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False,
-                            fold_bn=("bn0", BN_EPS, True), activation='relu', image_input=True,
-                            kernel_initializer="he_normal", name="conv0")
+        self.stem = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False,
+                           fold_bn=("bn0", BN_EPS, True), activation='relu', image_input=True,
+                           kernel_initializer="he_normal", name="conv0")
         self.stages = []
         for stage, rep in enumerate(repetitions):
             filters = 128 * 2 ** stage
@@ -117,58 +120,3 @@ class ResNeXt101(Layer):
                 stride = 1 if (stage == 0 or block > 0) else 2
                 units.append(_Unit(filters, stage, block, stride, conv_shortcut=(block == 0)))
             self.stages.append(units)
-
-    def build(self, input_shape):
-        self.add_weight_bn_data()
-        s = self.conv0.build(input_shape)
-        taps = {"C1": s}
-        H, W = s[1], s[2]
-        s = (s[0], None if H is None else (H + 2 - 3) // 2 + 1, None if W is None else (W + 2 - 3) // 2 + 1, s[3])
-        for tap, units in zip(("C2", "C3", "C4", "C5"), self.stages):
-            for u in units:
-                s = u.build(s)
-            taps[tap] = s
-        self.built = True
-        return taps
-
-    def add_weight_bn_data(self):
-        # input BatchNorm, scale=False: beta / moving stats over raw 0..255 RGB
-        self._bn_data = {
-            "bn_data/beta": WeightSpec((3,), "normal", stddev=0.1),
-            "bn_data/moving_mean": WeightSpec((3,), "uniform", low=100.0, high=130.0),
-            "bn_data/moving_variance": WeightSpec((3,), "uniform", low=3000.0, high=5000.0),
-        }
-
-    def children(self):
-        return [self.conv0] + [l for st in self.stages for u in st for l in u.layers()]
-
-    def weight_specs(self):
-        out = dict(self._bn_data)
-        for ch in self.children():
-            out.update(ch.weight_specs())
-        return out
-
-    def input_affine(self, weights):
-        """(mean, divisor, shift) realising bn_data inside the preprocess kernel."""
-        mean = np.asarray(weights["bn_data/moving_mean"], np.float64)
-        div = np.sqrt(np.asarray(weights["bn_data/moving_variance"], np.float64) + BN_EPS)
-        return mean.astype(np.float32), div.astype(np.float32), np.asarray(weights["bn_data/beta"], np.float32)
-
-    def call(self, x, wanted=("C3", "C4", "C5"), **kwargs):
-        import torch
-        half = ops.half_storage()            # fp16-storage mode: the body's tensors AND its taps are IEEE half
-        taps = {}
-        if "C1" not in wanted and self.conv0.dev is not None and ops.has_fused_stem():
-            x = ops.stem_pool(x, self.conv0.dev)     # stem + pool in one pass (csrc/stem.hip): same bits as the pair below
-        else:
-            x = self.conv0(x, out_dtype=torch.float16 if half else None)
-            taps["C1"] = x
-            x = ops.maxpool3x3s2(x, pad=1)
-        last = max(int(t[1]) for t in wanted)
-        for tap, units in zip(("C2", "C3", "C4", "C5"), self.stages):
-            for u in units:
-                x = u(x)
-            taps[tap] = x
-            if int(tap[1]) >= last:
-                break
-        return taps

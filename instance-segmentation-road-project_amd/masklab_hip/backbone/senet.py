@@ -20,8 +20,8 @@ order): conv0 / bn0, stage{s}_unit{u}_{conv1, bn1, conv2, bn2, conv3, bn3, sc, s
 import numpy as np
 
 from .. import ops
-from ..keras_like import Conv2D, GroupedConv2D, Layer
-from .seresnet34 import ChannelSE
+from ..keras_like import Conv2D, GroupedConv2D
+from .body import ChannelSE, ResidualBody
 
 BN_EPS = 9.999999747378752e-06
 REPETITIONS = (3, 4, 6, 3)
@@ -83,6 +83,9 @@ class _Unit:
             assert tuple(self.sc.build(shape)[1:]) == tuple(s[1:]) or None in s, (shape, s)
         return s
 
+    def __call__(self, x):
+        return self.tail(x, self.conv1(x))
+
     def tail(self, x, y1):
         """y1 = conv1(x) -> the unit's output; c3 is overwritten by it."""
         residual = self.sc(x) if self.sc is not None else x
@@ -91,79 +94,18 @@ class _Unit:
         return ops.se_bottleneck(c3, residual, se.w1, se.b1, se.w2, se.b2, out=c3)
 
 
-class _SENet50(Layer):
+class _SENet50(ResidualBody):
     GROUPED = None
 
     def __init__(self, repetitions=REPETITIONS, **kwargs):
         super().__init__(**kwargs)
-        self.conv0 = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False, fold_bn=("bn0", BN_EPS, True),
-                            activation='relu', image_input=True, kernel_initializer="he_normal", name="conv0")
+        self.stem = Conv2D(64, 7, strides=2, padding=((3, 3), (3, 3)), use_bias=False, fold_bn=("bn0", BN_EPS, True),
+                           activation='relu', image_input=True, kernel_initializer="he_normal", name="conv0")
         self.stages = []
         for stage, rep in enumerate(repetitions):
             filters = 256 * 2 ** stage
             self.stages.append([_Unit(filters, stage, block, 2 if (block == 0 and stage > 0) else 1, self.GROUPED)
                                 for block in range(rep)])
-
-    def units(self):
-        return [u for st in self.stages for u in st]
-
-    def build(self, input_shape):
-        s = self.conv0.build(input_shape)
-        taps = {"C1": s}
-        H, W = s[1], s[2]
-        s = (s[0], None if H is None else (H + 2 - 3) // 2 + 1, None if W is None else (W + 2 - 3) // 2 + 1, s[3])
-        for si, units in enumerate(self.stages):
-            for bi, u in enumerate(units):
-                if self.GROUPED and bi == 0 and si > 0:
-                    taps[f"C{si + 1}"] = u.conv1.build(s)
-                s = u.build(s)
-            if not self.GROUPED or si == len(self.stages) - 1:
-                taps[f"C{si + 2}"] = s
-        self.built = True
-        return taps
-
-    def children(self):
-        return [self.conv0] + [l for u in self.units() for l in u.layers()]
-
-    def weight_specs(self):
-        out = {}
-        for ch in self.children():
-            out.update(ch.weight_specs())
-        return out
-
-    def call(self, x, wanted=("C3", "C4", "C5"), **kwargs):
-        import torch
-        half = ops.half_storage()            # fp16-storage mode: the body's tensors AND its taps are IEEE half
-        taps = {}
-        if "C1" not in wanted and self.conv0.dev is not None and ops.has_fused_stem():
-            x = ops.stem_pool(x, self.conv0.dev)     # stem + pool in one pass (csrc/stem.hip): same bits as the pair below
-        else:
-            x = self.conv0(x, out_dtype=torch.float16 if half else None)
-            taps["C1"] = x
-            x = ops.maxpool3x3s2(x, pad=1)
-        last = max(int(t[1]) for t in wanted)
-        if last < 2:
-            return taps
-        for si, units in enumerate(self.stages):
-            for bi, u in enumerate(units):
-                y1 = u.conv1(x)
-                if self.GROUPED and bi == 0 and si > 0:
-                    taps[f"C{si + 1}"] = y1              # the next stage's conv1 ReLU is the previous stage's tap
-                    if si + 1 >= last:
-                        return taps
-                x = u.tail(x, y1)
-            if not self.GROUPED or si == len(self.stages) - 1:
-                taps[f"C{si + 2}"] = x
-                if si + 2 >= last:
-                    return taps
-        return taps
-
-
-class SEResNeXt50(_SENet50):
-    GROUPED = True
-
-    def __init__(self, **kwargs):
-        super().__init__(name=kwargs.pop("name", "seresnext50_body"), **kwargs)
 
 
 class SEResNet50(_SENet50):
@@ -171,3 +113,32 @@ class SEResNet50(_SENet50):
 
     def __init__(self, **kwargs):
         super().__init__(name=kwargs.pop("name", "seresnet50_body"), **kwargs)
+
+
+class SEResNeXt50(_SENet50):
+    """Its C2..C4 are the conv1 ReLU of the NEXT stage's first unit, not the stage outputs."""
+    GROUPED = True
+
+    def __init__(self, **kwargs):
+        super().__init__(name=kwargs.pop("name", "seresnext50_body"), **kwargs)
+
+    def stage_shapes(self, s):
+        taps = {}
+        for si, units in enumerate(self.stages):
+            for bi, u in enumerate(units):
+                if bi == 0 and si > 0:
+                    taps[f"C{si + 1}"] = u.conv1.build(s)
+                s = u.build(s)
+        taps["C5"] = s
+        return taps
+
+    def run_stages(self, x, taps, last):
+        for si, units in enumerate(self.stages):
+            for bi, u in enumerate(units):
+                y1 = u.conv1(x)
+                if bi == 0 and si > 0:
+                    taps[f"C{si + 1}"] = y1              # the next stage's conv1 ReLU is the previous stage's tap
+                    if si + 1 >= last:
+                        return
+                x = u.tail(x, y1)
+        taps["C5"] = x

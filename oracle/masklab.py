@@ -221,33 +221,31 @@ def mobilenet_v1(x, w):
     return taps
 
 
-PREPROCESS = {  # base.py:190-279
-    "resnext50": dict(rgb=True, mean_shift=True, normalize=2),
-    "mobilenet": dict(rgb=False, mean_shift=False, normalize=2),
-    "resnext101": dict(rgb=True, mean_shift=False, normalize=0),     # extension: raw RGB into bn_data
+# backbone type -> (body function (x, w) -> taps C1..C5, backbone_preprocess arguments, padding of the extra-level convs);
+# base.py:190-279, :292-314
+BACKBONES = {
+    "resnext50": (resnext50, dict(rgb=True, mean_shift=True, normalize=2), "same"),
+    "mobilenet": (mobilenet_v1, dict(rgb=False, mean_shift=False, normalize=2), ((0, 1), (0, 1))),
+    "resnext101": (resnext101, dict(rgb=True, mean_shift=False, normalize=0), "same"),    # extension: raw RGB into bn_data
 }
 
 
-def backbone_forward(images, w, backbone_type, backbone_outputs, literal_groups=True):
+def backbone_forward(images, w, backbone_type, backbone_outputs, literal_groups=True, bodies=None):
     """load_backbone graph, engine/backbone/base.py:185-316.  Returns (names, tensors)
-    in the model's output order: C-taps ascending, then P6, P7."""
+    in the model's output order: C-taps ascending, then P6, P7.  `bodies`: a table like BACKBONES to look the type up in."""
+    bodies = BACKBONES if bodies is None else bodies
     bt = backbone_type.lower()
-    if bt not in PREPROCESS:
+    if bt not in bodies:
         raise NotImplementedError(bt)
-    x = backbone_preprocess(images, **PREPROCESS[bt])
-    if bt == "resnext50":
-        taps = resnext50(x, w, literal_groups)
-    elif bt == "resnext101":
-        taps = resnext101(x, w)
-    else:
-        taps = mobilenet_v1(x, w)
+    body, preprocess, pad = bodies[bt]
+    x = backbone_preprocess(images, **preprocess)
+    taps = body(x, w, literal_groups) if body is resnext50 else body(x, w)
     names, feats = [], []
     for key in ("C1", "C2", "C3", "C4", "C5"):                                        # :287-290
         if key in backbone_outputs:
             names.append(key); feats.append(taps[key])
     last = feats[-1]
-    pad = ((0, 1), (0, 1)) if bt == "mobilenet" else "same"                           # :292-314
-    p6 = T.relu(T.conv2d(last, w["P6_conv/kernel"], w["P6_conv/bias"], stride=2, padding=pad))
+    p6 = T.relu(T.conv2d(last, w["P6_conv/kernel"], w["P6_conv/bias"], stride=2, padding=pad))   # :292-314
     if "P6" in backbone_outputs:
         names.append("P6"); feats.append(p6)                                          # pre-norm
     g6 = T.group_norm(p6, w["P6_norm/gamma"], w["P6_norm/beta"], 32)                  # default groups

@@ -9,7 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import masklab as O
 
-TOL = 1e-3
+from backbone_cases import TOL, check_model as _check
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -32,20 +32,6 @@ def _build(bt, seed=3, hot_cls=False):
                 w[k] = (w[k] * 8.0).astype(np.float32)
     model.load_weights(w, "cuda:0")
     return cfg, model, w
-
-
-def _check(model, got, want):
-    for name, g, r in zip(model.output_names, got, want):
-        assert g.shape == r.shape, (name, g.shape, r.shape)
-        if name == "roi_boxes":
-            np.testing.assert_array_equal(g[..., 4], r[..., 4], err_msg="class ids")
-            np.testing.assert_array_equal(g == -1, r == -1, err_msg="padding pattern")
-            # pixel coordinates are O(100): fp32 relative tolerance; confidences absolute
-            np.testing.assert_allclose(g[..., :4], r[..., :4], rtol=1e-5, atol=TOL)
-            np.testing.assert_allclose(g[..., 5], r[..., 5], rtol=0, atol=TOL)
-            continue
-        err = float(np.max(np.abs(g.astype(np.float64) - r))) if g.size else 0.0
-        assert err <= TOL, (name, err)
 
 
 @pytest.mark.parametrize("bt", ["mobilenet", "resnext50", "resnext101"])

@@ -448,7 +448,7 @@ def test_maxpool3x3s2():
 def test_preprocess(bt, dtype):
     from masklab_hip.backbone import BackBonePreProcess
     img = RNG.integers(0, 256, (2, 9, 7, 3)).astype(dtype)
-    kw = O.PREPROCESS[bt]
+    kw = O.BACKBONES[bt][1]
     ref = O.backbone_preprocess(img.astype(np.float32), **kw)
     got = host(BackBonePreProcess(**kw)(dev(img)))
     assert got.shape == (2, 9, 7, 4) and np.all(got[..., 3] == 0)

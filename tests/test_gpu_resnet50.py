@@ -4,7 +4,7 @@ bars tests/test_gpu_ops.py (fp32 1x1 conv with residual: atol 3e-5) and tests/te
 with residual: rtol 2^-10, atol 1e-4 against the half-rounded fp64 value) already apply, bit-stable run to run and per
 image, with the pixels of `x` a strided unit must NOT read filled with 1e3; a K that is no multiple of the chunk is
 refused by the library and run by `ops` as the two launches; the backbone taps against the test-side restatement
-(tests/resnet50_ref.py) in every conv math with the fusion on and off (the bars of tests/test_gpu_senet.py; f16s is
+(tests/backbone_refs.py) in every conv math with the fusion on and off (the bars of tests/test_gpu_senet.py; f16s is
 reported, not gated, as there); the default ModelConfiguration() end to end against the oracle with detections, their
 order, device counts and one hipGraph; an .npz checkpoint through load_masklab_inference_model_from_h5 to the deploy
 model.  -m gpu."""
@@ -18,17 +18,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import masklab as O
 
-import resnet50_ref as REF
+from backbone_cases import _need_gpu, dev, host    # noqa: F401  (_need_gpu: autouse)
+import backbone_cases as CASES
+from backbone_refs import RESNET50 as REF
 
-TOL = 1e-3
 F32_ATOL = 3e-5                              # tests/test_gpu_ops.py test_conv1x1_pipelined_kernel
 HALF_RTOL, HALF_ATOL = 2.0 ** -10, 1e-4      # tests/test_gpu_f16_storage.py
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 @pytest.fixture(params=["on", "off"])
@@ -38,15 +33,6 @@ def fusion(request):
     ops.set_projection_fusion(request.param)
     yield request.param
     ops.set_projection_fusion(before)
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
 
 
 # ------------------------------------------------------------------ the dual kernel
@@ -168,12 +154,7 @@ _TAPS = {}
 def _taps_fixture(shape, outputs):
     """(backbone with weights loaded, images, restated taps) -- made once per shape and shared, unchanged."""
     if shape not in _TAPS:
-        from masklab_hip import backbone as BB
-        from masklab_hip import keras_like as K
-        K.clear_session()
-        bb = BB.load_backbone("resnet50", backbone_outputs=outputs, num_features=128)
-        w = K.init_weights(bb.weight_specs(), shape[1])
-        bb.load_weights(w, torch.device("cuda:0"))
+        bb, w = CASES.load_backbone("resnet50", outputs, seed=shape[1])
         images = np.random.default_rng(shape[2]).integers(0, 256, shape, dtype=np.uint8)
         names, want = REF.backbone_forward(images.astype(np.float32), w, "resnet50", outputs)
         assert names == bb.output_names
@@ -189,29 +170,13 @@ def test_backbone_taps_match_the_restatement(shape, outputs, fusion):
     """f32 / f32x3 within the BASELINE tolerance, f16 (fp16 operands, fp32 tensors) within the SE-ResNet f16 bar; f16s
     (half tensors from the stem on, half taps) is reported, not gated.  With the fusion on, the four projection units of
     "f32" and "f16s" run on the one-GEMM kernel; "f32x3" and "f16" keep the two launches either way."""
-    from masklab_hip import ops
     bb, images, names, want = _taps_fixture(shape, outputs)
     for math in ("f32", "f32x3", "f16", "f16s"):
-        ops.set_conv_math(math)
-        ops.PROFILE = []
-        try:
-            got = [host(t) for t in bb(dev(images))]
-            recs = ops.PROFILE
-        finally:
-            ops.PROFILE = None
-            ops.set_conv_math("f32")
-        dual = [r["kernel"] for r in recs if "dual" in r["kernel"]]
+        got, kernels = CASES.run_backbone(bb, images, math)
+        dual = [k for k in kernels if "dual" in k]
         fused = fusion == "on" and math in ("f32", "f16s")
         assert dual == ([{"f32": "conv1x1_dual", "f16s": "conv1x1_dual_h"}[math]] * 4 if fused else []), (math, dual)
-        errs = {}
-        for n, g, r in zip(names, got, want):
-            assert g.shape == r.shape, (n, g.shape, r.shape)
-            assert g.dtype == (np.float16 if math == "f16s" else np.float32), (math, n, g.dtype)
-            errs[n] = float(np.max(np.abs(g.astype(np.float64) - r)))
-            bar = TOL if math in ("f32", "f32x3") else 3e-2 * max(1.0, float(np.abs(r).max()) / 4)
-            if math != "f16s":
-                assert errs[n] <= bar, (math, fusion, n, errs[n], bar)
-        print(f"\n[resnet50 taps] fusion {fusion} {shape} {math}: " + " ".join(f"{n}={e:.3g}" for n, e in errs.items()))
+        CASES.check_taps(names, got, want, math, f"resnet50 taps fusion {fusion} {shape}")
 
 
 # ------------------------------------------------------------------ end to end
@@ -223,35 +188,14 @@ def _fixture():
     """(cfg, weights, images, oracle outputs, kept rows) of the DEFAULT ModelConfiguration() with an order-stable logit
     scale from the restated forward -- made once and shared, unchanged."""
     if not _E2E:
-        from masklab_hip import ModelConfiguration, retinamasklab as R
-        from oracle import fixtures as FX
+        from masklab_hip import ModelConfiguration
         cfg = ModelConfiguration()
         assert cfg.backbone.backbone_type == "resnet50"
-        _, model = R.construct_masklab_networks(cfg)
-        w = model.init_weights(E2E_SEED)
-        images = np.random.default_rng(E2E_SHAPE[1] + E2E_SHAPE[2]).integers(0, 256, E2E_SHAPE, dtype=np.uint8)
-        c1, l1 = O.inference_forward(cfg, w, images, literal_groups=False, with_instance=False, with_semantic=False)
-        scale, thr = FX.choose_logit_scale(cfg, c1, l1, E2E_SHAPE[1], E2E_SHAPE[2])
-        assert scale is not None, "no order-stable logit scale on the grid"
-        w = FX.scale_cls_logits(w, scale)
-        cfg.detection.min_confidence = thr
+        _, w, images = CASES.order_stable_fixture(cfg, E2E_SHAPE, E2E_SEED)
         want, internals = O.inference_forward(cfg, w, images, literal_groups=False, return_internals=True)
         assert len(internals["kept"]) > 0, "fixture produced no detections"
         _E2E.update(cfg=cfg, w=w, images=images, want=want, kept=internals["kept"])
     return _E2E
-
-
-def _check_model(model, got, want):
-    for name, g, r in zip(model.output_names, got, want):
-        assert g.shape == r.shape, (name, g.shape, r.shape)
-        if name == "roi_boxes":
-            np.testing.assert_array_equal(g[..., 4], r[..., 4], err_msg="class ids")
-            np.testing.assert_array_equal(g == -1, r == -1, err_msg="padding pattern")
-            np.testing.assert_allclose(g[..., :4], r[..., :4], rtol=1e-5, atol=TOL)
-            np.testing.assert_allclose(g[..., 5], r[..., 5], rtol=0, atol=TOL)
-            continue
-        err = float(np.max(np.abs(g.astype(np.float64) - r))) if g.size else 0.0
-        assert err <= TOL, (name, err)
 
 
 def test_end_to_end_on_the_default_configuration(monkeypatch, fusion):
@@ -263,48 +207,15 @@ def test_end_to_end_on_the_default_configuration(monkeypatch, fusion):
     assert model.backbone_network.backbone_type == "resnet50"
     assert model.backbone_network.output_names == ['C3', 'C4', 'C5', 'P6', 'P7']
     model.load_weights(fx["w"], "cuda:0")
-    got = model.predict(images, want_kept=True)
-    det = model.last_detections
-    counts, kept = det["counts"].cpu().numpy(), det["kept"].cpu().numpy()
-    for b in range(E2E_SHAPE[0]):
-        np.testing.assert_array_equal(kept[b, :counts[b]], kept_ref[kept_ref[:, 0] == b][:, 1:])
-    _check_model(model, got, want)
-    model.device_counts = True                       # stage 2 at capacity, no host read inside the forward
-    eager = model.predict(images)
-    _check_model(model, eager, want)
-    model.enable_graphs(True)                        # the whole forward as ONE hipGraph: first pass captures, then replays
-    for _ in range(2):
-        replay = model.predict(images)
-        for name, g, r in zip(model.output_names, replay, eager):
-            np.testing.assert_array_equal(g, r, err_msg=name)
-    model.enable_graphs(False)
-    model.device_counts = "auto"
+    CASES.check_kept_rows_device_counts_and_graph(model, images, want, kept_ref)
 
 
 def test_checkpoint_to_deploy_model(tmp_path, monkeypatch):
     """An .npz keyed by the Keras names through load_masklab_inference_model_from_h5 -> DeployModel on a 272x480 frame
     (down-sampled to a 136x240 working size) against oracle.deploy_forward with the restated backbone."""
-    from masklab_hip import ModelConfiguration, retinamasklab as R
+    from masklab_hip import ModelConfiguration
     REF.patch(monkeypatch)
     cfg = ModelConfiguration()
     cfg.postprocess.resolution = (136, 240)
-    _, model = R.construct_masklab_networks(cfg)
-    w = model.init_weights(3)
-    for k in w:
-        if k.startswith("classification_sub_net/") and k.endswith("/output/kernel"):
-            w[k] = (w[k] * 8.0).astype(np.float32)          # some anchors pass min_confidence
-    assert "res5a_branch1/kernel" in w and "bn_conv1/moving_mean" in w
-    path = tmp_path / "resnet50.npz"
-    np.savez(path, **w)
-    deploy = R.load_masklab_inference_model_from_h5(str(path), cfg, device="cuda:0")
-    images = np.random.default_rng(272).integers(0, 256, (1, 272, 480, 3), dtype=np.uint8)
-    det, inst, sem = deploy.predict(images)
-    wdet, winst, wsem = O.deploy_forward(cfg, w, images, literal_groups=False)
-    assert det.dtype == inst.dtype == sem.dtype == np.int32
-    assert det.shape == wdet.shape and inst.shape == winst.shape and sem.shape == wsem.shape == images.shape
-    assert (wdet[..., 4] >= 0).sum() > 0, "fixture produced no detections"
-    assert 0 < wsem.mean() < 1 and 0 < winst.mean() < 1, "fixture thresholds are degenerate"
-    np.testing.assert_array_equal(det[..., 4], wdet[..., 4])                   # labels and padding pattern
-    assert np.abs(det - wdet).max() <= 1                                       # truncation of x*ratio at an integer
-    assert (det != wdet).mean() < 0.02
-    assert (inst != winst).mean() < 1e-3 and (sem != wsem).mean() < 1e-3      # flips only at |v - 0.5| < 1e-3
+    w = CASES.check_checkpoint_to_deploy(cfg, tmp_path / "resnet50.npz", (1, 272, 480, 3), seed=272)
+    assert "res5a_branch1/kernel" in w and "bn_conv1/moving_mean" in w      # keyed by the Keras names

@@ -2,7 +2,7 @@
 builds it with no arguments, with the reference's taps and sizes; weight names, shapes, creation order and the parameter
 total equal the fixture (tests/golden/resnet50_layers.json: taps read from the reference, the inventory of the published
 legacy Keras-Applications model); the BatchNorm + bias fold and the one-GEMM packing of a projection unit agree with the
-unfolded fp64 formulation; the test-side restatement (tests/resnet50_ref.py) agrees with an independent
+unfolded fp64 formulation; the test-side restatement (tests/backbone_refs.py) agrees with an independent
 torch.nn.functional formulation and keeps random-init taps O(1); a Keras-named checkpoint converts (.npz and an h5-shaped
 file); the new C entry points validate their arguments; unknown backbones still raise."""
 import importlib.util
@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-import resnet50_ref as REF
+from backbone_refs import RESNET50 as REF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "resnet50_layers.json")))
@@ -193,11 +193,7 @@ def test_bn_and_bias_fold_of_a_projection_unit_against_fp64():
 
 
 def test_restatement_delegates_every_other_backbone(monkeypatch):
-    from oracle import masklab as O
-    REF.patch(monkeypatch)
-    assert O.backbone_forward is REF.backbone_forward
-    with pytest.raises(NotImplementedError):
-        O.backbone_forward(np.zeros((1, 32, 32, 3), np.float32), {}, "no_such_backbone", ("C5",))
+    REF.check_patch_keeps_the_oracle_backbones(monkeypatch)
 
 
 def test_unknown_backbones_still_raise():

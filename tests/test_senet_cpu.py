@@ -2,8 +2,8 @@
 the reference's load_backbone offers): the loader builds both with the reference's taps and sizes, BACKBONE_LAYERS equals
 the reference's entries, weight names and shapes are the expected Keras-shaped ones and their creation order is the
 reference's (tests/golden/senet_layers.json, recorded from the reference's own builder), the test-side restatement
-(tests/senet_ref.py) agrees with an independent torch.nn.functional formulation and keeps random-init taps O(1), a Keras
-checkpoint with auto-named layers converts, and the new C entry points validate their arguments."""
+(tests/backbone_refs.py) agrees with an independent torch.nn.functional formulation and keeps random-init taps O(1), a
+Keras checkpoint with auto-named layers converts, and the new C entry points validate their arguments."""
 import ctypes
 import importlib.util
 import json
@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-import senet_ref as REF
+from backbone_refs import SENET as REF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "senet_layers.json")))
@@ -208,11 +208,7 @@ def test_random_init_keeps_every_tap_order_one(bt):
 
 
 def test_restatement_delegates_every_other_backbone(monkeypatch):
-    from oracle import masklab as O
-    REF.patch(monkeypatch)
-    assert O.backbone_forward is REF.backbone_forward
-    with pytest.raises(NotImplementedError):
-        O.backbone_forward(np.zeros((1, 32, 32, 3), np.float32), {}, "no_such_backbone", ("C5",))
+    REF.check_patch_keeps_the_oracle_backbones(monkeypatch)
 
 
 def _fake_keras_file(weights):

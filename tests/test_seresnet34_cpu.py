@@ -1,6 +1,6 @@
 """CPU tests of the SE-ResNet-34 backbone (the reference project's own model, road_project/train.py:36-37): the loader
 builds it with the reference's taps and sizes, its weight names and shapes are the Keras ones of the vendored
-thirdparty/classification_models source, the test-side restatement (tests/seresnet34_ref.py) agrees with an independent
+thirdparty/classification_models source, the test-side restatement (tests/backbone_refs.py) agrees with an independent
 torch.nn.functional formulation and keeps random-init taps O(1), a Keras checkpoint with auto-numbered ChannelSE convs
 converts, and the new C entry points validate their arguments."""
 import ctypes
@@ -11,7 +11,7 @@ import re
 import numpy as np
 import pytest
 
-import seresnet34_ref as REF
+from backbone_refs import SERESNET34 as REF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -142,11 +142,7 @@ def test_random_init_keeps_every_tap_order_one():
 
 
 def test_restatement_delegates_every_other_backbone(monkeypatch):
-    from oracle import masklab as O
-    REF.patch(monkeypatch)
-    assert O.backbone_forward is REF.backbone_forward
-    with pytest.raises(NotImplementedError):
-        O.backbone_forward(np.zeros((1, 32, 32, 3), np.float32), {}, "no_such_backbone", ("C5",))
+    REF.check_patch_keeps_the_oracle_backbones(monkeypatch)
 
 
 def _fake_keras_file(weights):
