@@ -801,6 +801,70 @@ int ml_jpeg_entropy_device(const uint8_t *files, const int64_t *file_offsets, co
 int ml_jpeg_entropy_reference_host(const uint8_t *file, int64_t n, const void *plan, void *packed, int64_t capacity,
                                    int32_t *status, void *workspace);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation: the reference's evaluation loop (road_project/train.py:101-209) and its metric layers
+ * (engine/metrics.py) as integer counting kernels (csrc/evaluate.hip).  Every kernel counts into zeroed int64
+ * outputs with integer atomics: the same bits run to run; no float atomics.  All on `stream`, no host read.
+ *
+ * The loop's contract per image (what masklab_hip/evaluate.py and tests/evaluate_ref.py both follow):
+ *   boxes     matched on the HOST in float64 (train.py:144-182): iou = intersection / union of the (cx, cy, w, h) boxes,
+ *             times label equality, pairs = np.where(iou > 0.5) in row-major order; NaN compares false; a predicted
+ *             row with conf < 0 and a ground-truth row with label < 0 never pair.
+ *   pred mask of detection row j (train.py:125-141): in float64 xmin = clip(cx - w/2, 0, W), xmax, ymin, ymax likewise;
+ *             start / end = those truncated to int32; bw = end.x - start.x, bh = end.y - start.y.  Canvas pixel (y, x) is
+ *             set iff it lies in [start.y, end.y) x [start.x, end.x) and the bilinear sample of max(mask_j, 0) at
+ *             (y - start.y, x - start.x) of a bh x bw resize is > 0.5.  The resize is OpenCV's INTER_LINEAR for a float64
+ *             image, restated per axis: scale = 1 / (dst / src) in float64; f = float32((d + 0.5) * scale - 0.5);
+ *             s = floor(f); f -= s in float32; s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0; weights
+ *             1.f - f and f (float32); the two taps of a source row are combined first, then the two rows, in float64.
+ *             bw <= 0 or bh <= 0 is an EMPTY mask (the reference raises inside cv2.resize).  This restatement, not a run
+ *             of OpenCV, is what the kernels are held to.
+ *   gt mask   pixel set iff its byte is non-zero (int8 -1 from a 0 / 255 mask counts).
+ *   pair      intersection and union = pred area + gt area - intersection as integers; the host divides in float64
+ *             (0 for an empty union, where the reference adds NaN).
+ *   semantic  per class, #(gt > 0.5 and pr > 0.5) and #(gt > 0.5 or pr > 0.5).
+ * ------------------------------------------------------------------------------------------- */
+#define ML_EVAL_MAX_CLASSES 16
+#define ML_EVAL_MAX_MASK 16368      /* mh * mw of ml_eval_mask_pairs: 64 KiB of LDS less the reduction's own words */
+enum { ML_EVAL_F32 = 0, ML_EVAL_F16 = 1, ML_EVAL_I32 = 2, ML_EVAL_U8 = 3 };
+/* gt [B,G,H,W] int8 or uint8 (H*W < 2^31) -> out int64 [B,G]: non-zero bytes per mask.  HBM-bound: 16-byte loads,
+ * scalar bytes in front of the first 16-byte boundary and for the last (H*W - head) mod 16.                      */
+int ml_eval_mask_area(const void *gt, int32_t B, int32_t G, int32_t H, int32_t W, int64_t *out, void *stream);
+/* det [B,n,6] int32, ins [B,n,mh,mw] int32 (mh*mw <= ML_EVAL_MAX_MASK: the mask is held in LDS), gt as above, gt_area from
+ * ml_eval_mask_area, pairs int32 [P,3] = (b, pr_i, gt_i) on the device -> out int64 [P,2] = (intersection, union).
+ * The blocks of a pair walk only its box.  A pair with an index out of range gets (-1, -1) and reads nothing.     */
+int ml_eval_mask_pairs(const int32_t *det, const int32_t *ins, const void *gt, const int64_t *gt_area, const int32_t *pairs,
+                       int32_t P, int32_t B, int32_t n, int32_t mh, int32_t mw, int32_t G, int32_t H, int32_t W, int64_t *out,
+                       void *stream);
+/* pr int32 [B,H,W,C], gt uint8 [B,H,W,C] (16-byte aligned, C <= ML_EVAL_MAX_CLASSES, H*W*C < 2^31, B <= 65535)
+ * -> out int64 [B,C,2] = (intersection, union) of gt > 0.5 and pr > 0.5.                                           */
+int ml_eval_semantic_counts(const int32_t *pr, const uint8_t *gt, int32_t B, int32_t H, int32_t W, int32_t C, int64_t *out,
+                            void *stream);
+/* ClassBinaryIOU.call (engine/metrics.py:83-99): seg_true, seg_pred [B,HW,C] of dtype ML_EVAL_* (both the same, or u8
+ * truth with i32 predictions; limits as above) -> counts int64 [B,C,3] = #(true > thr), #(pred > thr), #(both), and
+ * iou float32 [C,B] = intersection / (area_true + area_pred - intersection) in float32, 1 where the union is 0.  Values are
+ * compared with the float32 threshold as they are (f16 widened exactly); TensorFlow would round the threshold to the
+ * map's type first, the same thing at 0.5.                                                                          */
+int ml_eval_class_binary_iou(const void *seg_true, int32_t true_dtype, const void *seg_pred, int32_t pred_dtype, int32_t B,
+                             int64_t HW, int32_t C, float threshold, int64_t *counts, float *iou, void *stream);
+/* DetectionIOUMetric.call (engine/metrics.py:118-165): proposed [B,n_proposed,6], gt [B,n_gt,6] float32, rows padded
+ * with -1 -> out float32 [3,B] = precision, recall, fmeasure.  Float32 with FP contraction off: CalculateIOU with its
+ * + 1e-5, the logical_or ignore mask as written, K.epsilon() = 1e-7 -- the bits of oracle/metrics.py.             */
+int ml_eval_detection_metric_f32(const float *proposed, const float *gt, int32_t B, int32_t n_proposed, int32_t n_gt, float *out,
+                                 void *stream);
+/* ConfusionMatrixMetric.call (engine/metrics.py:16-60): cls_true, cls_pred float32 [N,C], mask float32 [N] -> counts
+ * int64 [4] = tp, fp, fn, tn (argmax per anchor, the first maximum wins; the prediction counts as background unless its
+ * row maximum > threshold, the truth unless mask == 0; anchors with mask == -1 are dropped) and metrics float32 [4] =
+ * precision, recall, accuracy, fmeasure from them in float32.                                                      */
+int ml_eval_confusion_f32(const float *cls_true, const float *cls_pred, const float *mask, int64_t N, int32_t C, float threshold,
+                          int64_t *counts, float *metrics, void *stream);
+/* Host.  The per-thread code of the mask-area, mask-pair and semantic kernels in CPU loops, every pointer in host
+ * memory; a section whose inputs are null is skipped (gt -> out_area; pairs -> out_pairs, which needs det, ins, gt;
+ * pr_sem, gt_sem -> out_sem).  For checking the arithmetic without a device -- not a product path.                 */
+int ml_eval_reference_host(const int32_t *det, const int32_t *ins, const void *gt, const int32_t *pairs, int32_t P,
+                           const int32_t *pr_sem, const uint8_t *gt_sem, int32_t B, int32_t n, int32_t mh, int32_t mw, int32_t G,
+                           int32_t H, int32_t W, int32_t C, int64_t *out_area, int64_t *out_pairs, int64_t *out_sem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,4 +24,6 @@ def get_custom_objects():
     reg = {n: getattr(L, n) for n in names}
     reg["BackBonePreProcess"] = BackBonePreProcess
     reg["GroupNormalization"] = GroupNormalization
+    from . import metrics
+    reg.update({n: getattr(metrics, n) for n in metrics.__all__})
     return reg

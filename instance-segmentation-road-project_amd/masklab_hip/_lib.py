@@ -176,7 +176,16 @@ SIGNATURES = {
     "ml_jpeg_entropy_workspace_bytes": (_i64, [_vp, _i32]),
     "ml_jpeg_entropy_device": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "ml_jpeg_entropy_reference_host": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "ml_eval_mask_area": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _vp]),
+    "ml_eval_mask_pairs": (C.c_int, [_vp] * 5 + [_i32] * 8 + [_vp, _vp]),
+    "ml_eval_semantic_counts": (C.c_int, [_vp, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "ml_eval_class_binary_iou": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "ml_eval_detection_metric_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
+    "ml_eval_confusion_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "ml_eval_reference_host": (C.c_int, [_vp] * 4 + [_i32, _vp, _vp] + [_i32] * 8 + [_vp] * 3),
 }
+EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3     # ML_EVAL_*
+EVAL_MAX_CLASSES = 16                                  # ML_EVAL_MAX_CLASSES
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*
 JPEG_UNSUPPORTED = 1                        # ML_JPEG_UNSUPPORTED
 JPEG_DECODE_MAX_BATCH = 32

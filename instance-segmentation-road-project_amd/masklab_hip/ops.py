@@ -1625,3 +1625,154 @@ def jpeg_entropy_device(contents, device):
             raise JpegDecodeError(f"jpeg_entropy_device: {_last_error()}")
         packed, offsets, status = launched
         return packed, list(offsets), status.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- evaluation (csrc/evaluate.hip)
+_EVAL_DTYPE = {torch.float32: _lib.EVAL_F32, torch.float16: _lib.EVAL_F16, torch.int32: _lib.EVAL_I32,
+               torch.uint8: _lib.EVAL_U8}
+
+
+def _require_bytes(gt, name):
+    _require_dev(gt, name)
+    if gt.dtype not in (torch.int8, torch.uint8) or gt.dim() != 4:
+        raise RuntimeError(f"masklab_hip: `{name}` must be an int8 or uint8 [B,G,H,W] tensor, got {gt.dtype} {tuple(gt.shape)}")
+
+
+def eval_mask_area(gt):
+    """ml_eval_mask_area: gt [B,G,H,W] int8 / uint8 -> int64 [B,G], the non-zero pixels of every ground-truth mask."""
+    _require_bytes(gt, "gt")
+    B, G, H, W = gt.shape
+    out = torch.empty((B, G), dtype=torch.int64, device=gt.device)
+    with _Prof("eval_mask_area", 0, gt.numel()):
+        _lib.check(_lib.load().ml_eval_mask_area(_ptr(gt), B, G, H, W, _ptr(out), _stream()), "ml_eval_mask_area")
+    return out
+
+
+def eval_mask_pairs(det, ins, gt, gt_area, pairs):
+    """ml_eval_mask_pairs: det [B,n,6] int32, ins [B,n,h,w] int32, gt [B,G,H,W] int8 / uint8, gt_area int64 [B,G],
+    pairs int32 [P,3] = (b, pr_i, gt_i) -> int64 [P,2] = (intersection, union); (-1, -1) for an index out of range."""
+    _require_bytes(gt, "gt")
+    for t, name, dt in ((det, "det", torch.int32), (ins, "ins", torch.int32), (gt_area, "gt_area", torch.int64),
+                        (pairs, "pairs", torch.int32)):
+        _require_dev(t, name)
+        if t.dtype != dt:
+            raise RuntimeError(f"eval_mask_pairs: `{name}` must be {dt}, got {t.dtype}")
+    B, G, H, W = gt.shape
+    if det.dim() != 3 or det.shape[0] != B or det.shape[2] != 6 or ins.dim() != 4 or tuple(ins.shape[:2]) != tuple(det.shape[:2]) \
+            or tuple(gt_area.shape) != (B, G) or pairs.dim() != 2 or pairs.shape[1] != 3:
+        raise ValueError(f"eval_mask_pairs: shapes det {tuple(det.shape)} ins {tuple(ins.shape)} gt {tuple(gt.shape)} "
+                         f"gt_area {tuple(gt_area.shape)} pairs {tuple(pairs.shape)} do not fit")
+    n, mh, mw = ins.shape[1:]
+    P = int(pairs.shape[0])
+    out = torch.empty((P, 2), dtype=torch.int64, device=gt.device)
+    with _Prof("eval_mask_pairs", 0, 0):
+        _lib.check(_lib.load().ml_eval_mask_pairs(_ptr(det), _ptr(ins), _ptr(gt), _ptr(gt_area), _ptr(pairs), P, B, n, mh, mw,
+                                                  G, H, W, _ptr(out), _stream()), "ml_eval_mask_pairs")
+    return out
+
+
+def eval_semantic_counts(pr, gt):
+    """ml_eval_semantic_counts: pr int32 [B,H,W,C], gt uint8 [B,H,W,C] -> int64 [B,C,2] = (intersection, union) of the
+    pixels > 0.5."""
+    _require_dev(pr, "pr")
+    _require_dev(gt, "gt")
+    if pr.dtype != torch.int32 or gt.dtype != torch.uint8 or pr.dim() != 4 or pr.shape != gt.shape:
+        raise RuntimeError(f"eval_semantic_counts: int32 predictions and uint8 ground truth of one [B,H,W,C] shape expected, "
+                           f"got {pr.dtype} {tuple(pr.shape)} and {gt.dtype} {tuple(gt.shape)}")
+    B, H, W, Cc = pr.shape
+    out = torch.empty((B, Cc, 2), dtype=torch.int64, device=pr.device)
+    with _Prof("eval_semantic_counts", 0, 5 * pr.numel()):
+        _lib.check(_lib.load().ml_eval_semantic_counts(_ptr(pr), _ptr(gt), B, H, W, Cc, _ptr(out), _stream()),
+                   "ml_eval_semantic_counts")
+    return out
+
+
+def class_binary_iou(seg_true, seg_pred, threshold):
+    """ml_eval_class_binary_iou: [B,H,W,C] maps -> (counts int64 [B,C,3] = true, pred, both; iou float32 [C,B])."""
+    _require_dev(seg_true, "seg_true")
+    _require_dev(seg_pred, "seg_pred")
+    if seg_true.dtype not in _EVAL_DTYPE or seg_pred.dtype not in _EVAL_DTYPE:
+        raise RuntimeError(f"class_binary_iou: float32, float16, int32 or uint8 maps expected, got {seg_true.dtype}, {seg_pred.dtype}")
+    if seg_true.dim() != 4 or seg_true.shape != seg_pred.shape:
+        raise ValueError(f"class_binary_iou: two [B,H,W,C] maps of one shape expected, got {tuple(seg_true.shape)}, {tuple(seg_pred.shape)}")
+    B, H, W, Cc = seg_true.shape
+    counts = torch.empty((B, Cc, 3), dtype=torch.int64, device=seg_true.device)
+    iou = torch.empty((Cc, B), dtype=torch.float32, device=seg_true.device)
+    with _Prof("class_binary_iou", 0, seg_true.numel() * (seg_true.element_size() + seg_pred.element_size())):
+        _lib.check(_lib.load().ml_eval_class_binary_iou(_ptr(seg_true), _EVAL_DTYPE[seg_true.dtype], _ptr(seg_pred),
+                                                        _EVAL_DTYPE[seg_pred.dtype], B, H * W, Cc, float(threshold), _ptr(counts),
+                                                        _ptr(iou), _stream()), "ml_eval_class_binary_iou")
+    return counts, iou
+
+
+def detection_iou_metric(proposed, gt):
+    """ml_eval_detection_metric_f32: proposed [B,n,6], gt [B,m,6] float32 -> float32 [3,B] = precision, recall, fmeasure."""
+    for t, name in ((proposed, "proposed_boxes"), (gt, "gt_boxes")):
+        _require_dev(t, name)
+        if t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != 6:
+            raise RuntimeError(f"detection_iou_metric: `{name}` must be float32 [B,n,6], got {t.dtype} {tuple(t.shape)}")
+    if proposed.shape[0] != gt.shape[0]:
+        raise ValueError("detection_iou_metric: the batch sizes differ")
+    B = proposed.shape[0]
+    out = torch.empty((3, B), dtype=torch.float32, device=proposed.device)
+    with _Prof("detection_iou_metric", 0, 4 * (proposed.numel() + gt.numel())):
+        _lib.check(_lib.load().ml_eval_detection_metric_f32(_ptr(proposed), _ptr(gt), B, proposed.shape[1], gt.shape[1], _ptr(out),
+                                                            _stream()), "ml_eval_detection_metric_f32")
+    return out
+
+
+def confusion_matrix_metric(cls_true, cls_pred, mask, threshold):
+    """ml_eval_confusion_f32: cls_true, cls_pred float32 [B,A,C], mask float32 [B,A] -> (counts int64 [4] = tp, fp, fn, tn;
+    metrics float32 [4] = precision, recall, accuracy, fmeasure)."""
+    for t, name in ((cls_true, "cls_true"), (cls_pred, "cls_pred"), (mask, "mask")):
+        _require_dev(t, name)
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"confusion_matrix_metric: `{name}` must be float32, got {t.dtype}")
+    if cls_true.shape != cls_pred.shape or cls_true.dim() < 2 or mask.numel() * cls_true.shape[-1] != cls_true.numel():
+        raise ValueError(f"confusion_matrix_metric: shapes {tuple(cls_true.shape)}, {tuple(cls_pred.shape)}, {tuple(mask.shape)} do not fit")
+    counts = torch.empty((4,), dtype=torch.int64, device=cls_true.device)
+    metrics = torch.empty((4,), dtype=torch.float32, device=cls_true.device)
+    with _Prof("confusion_matrix_metric", 0, 4 * (2 * cls_true.numel() + mask.numel())):
+        _lib.check(_lib.load().ml_eval_confusion_f32(_ptr(cls_true), _ptr(cls_pred), _ptr(mask), mask.numel(), cls_true.shape[-1],
+                                                     float(threshold), _ptr(counts), _ptr(metrics), _stream()),
+                   "ml_eval_confusion_f32")
+    return counts, metrics
+
+
+def eval_reference_host(det=None, ins=None, gt=None, pairs=None, pr_sem=None, gt_sem=None):
+    """ml_eval_reference_host: the per-thread code of the three evaluation kernels in CPU loops over NumPy arrays (for
+    tests without a device; not a product path).  -> (area int64 [B,G] | None, pairs int64 [P,2] | None, semantic int64
+    [B,C,2] | None) for the sections whose inputs are given."""
+    def arr(a, dtypes):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        if a.dtype not in dtypes:
+            raise TypeError(f"eval_reference_host: {a.dtype} where one of {dtypes} is expected")
+        return a if a.ctypes.data % 16 == 0 else a.copy()          # a slice of a batch: a fresh buffer is aligned
+
+    det, ins, pairs, pr_sem = (arr(a, (np.int32,)) for a in (det, ins, pairs, pr_sem))
+    gt, gt_sem = arr(gt, (np.int8, np.uint8)), arr(gt_sem, (np.uint8,))
+    B = n = mh = mw = G = H = W = Cc = 1
+    area = out_pairs = out_sem = None
+    if gt is not None:
+        B, G, H, W = gt.shape
+        area = np.zeros((B, G), np.int64)
+    if pairs is not None:
+        if gt is None or det is None or ins is None or det.shape[:2] != ins.shape[:2] or det.shape[0] != B or det.shape[2] != 6:
+            raise ValueError("eval_reference_host: the pair section needs det [B,n,6], ins [B,n,h,w] and gt [B,G,H,W]")
+        n, mh, mw = ins.shape[1:]
+        pairs = pairs.reshape(-1, 3)
+        out_pairs = np.zeros((pairs.shape[0], 2), np.int64)
+    if pr_sem is not None or gt_sem is not None:
+        if pr_sem is None or gt_sem is None or pr_sem.shape != gt_sem.shape or pr_sem.ndim != 4:
+            raise ValueError("eval_reference_host: the semantic section needs pr_sem and gt_sem of one [B,H,W,C] shape")
+        if gt is not None and pr_sem.shape[:3] != (B, H, W):
+            raise ValueError("eval_reference_host: the masks and the semantic maps differ in B, H or W")
+        B, H, W, Cc = pr_sem.shape
+        out_sem = np.zeros((B, Cc, 2), np.int64)
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(0)
+    _lib.check(_lib.load().ml_eval_reference_host(p(det), p(ins), p(gt), p(pairs), 0 if pairs is None else pairs.shape[0],
+                                                  p(pr_sem), p(gt_sem), B, n, mh, mw, G, H, W, Cc, p(area), p(out_pairs),
+                                                  p(out_sem)), "ml_eval_reference_host")
+    return area, out_pairs, out_sem
