@@ -1307,6 +1307,17 @@ __device__ inline Window stage_window(uint32_t *lds, const uint8_t *f, uint32_t 
     return w;
 }
 
+// Every stream's four control words, cleared in a launch of their own in front of the first sync launch: the workgroups of
+// one launch run in no order, so a workgroup that clears them itself can wipe the rounds another one has already raised
+// into ctl[2] (and the workspace holds whatever the call before left there).  One thread per stream.
+__global__ void jpeg_entropy_clear_kernel(uint8_t *workspace, Streams st, int B) {
+    const int b = (int)threadIdx.x;
+    if (b >= B) return;
+    const uint32_t sub_cap = sub_cap_of(st.file_n[b]), wg_cap = (sub_cap + SYNC_TPB - 1) / SYNC_TPB;
+    uint32_t *ctl = region_of(workspace + st.ws_at[b], sub_cap, wg_cap).ctl;
+    ctl[0] = ctl[1] = ctl[2] = ctl[3] = 0u;
+}
+
 __global__ __launch_bounds__(SYNC_TPB) void jpeg_entropy_sync_kernel(const uint8_t *files, const uint8_t *plans, uint8_t *workspace,
                                                                      Streams st, int launch) {
     __shared__ Plan pl;
@@ -1326,8 +1337,7 @@ __global__ __launch_bounds__(SYNC_TPB) void jpeg_entropy_sync_kernel(const uint8
     Count count = {0u, 0u, 0, 0, 0, 0u};
     bool decode = false;                                           // one call site: the decoder is inlined once
     if (launch == 0) {
-        if (i == 0) rg.ctl[0] = rg.ctl[1] = rg.ctl[2] = rg.ctl[3] = 0u;
-        if (live) entry = guess_state(pl, f, i);
+        if (live) entry = guess_state(pl, f, i);                   // (ctl: cleared by jpeg_entropy_clear_kernel)
         decode = live;
     } else if (live) {
         entry = rg.entry[i];
@@ -1548,6 +1558,7 @@ extern "C" int ml_jpeg_entropy_device(const uint8_t *files, const int64_t *file_
     uint32_t max_cap = 0;
     for (int b = 0; b < B; ++b) max_cap = st.capacity[b] > max_cap ? st.capacity[b] : max_cap;
     hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(jpeg_entropy_clear_kernel, dim3(1), dim3(MAX_BATCH), 0, s, (uint8_t *)workspace, st, B);
     for (int launch = 0; launch < SYNC_LAUNCHES; ++launch)
         hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3(max_wg, B), dim3(SYNC_TPB), 0, s, files, (const uint8_t *)plans,
                            (uint8_t *)workspace, st, launch);

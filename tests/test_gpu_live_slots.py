@@ -619,10 +619,11 @@ def test_refusals(conv_math):
 
 
 # ------------------------------------------------------------------ the whole forward on poisoned allocations
-def test_forward_does_not_depend_on_what_empty_memory_holds(monkeypatch):
-    """Fixed-capacity stage 2, eager: the forward again with every float32 / float16 torch.empty / empty_like result filled
-    with NaN (integer tensors left alone: no index is ever made from poison) returns the same bits -- no output depends on
-    a slot nobody wrote, which is what the caching allocator hands out in service."""
+def test_forward_does_not_depend_on_what_empty_memory_holds():
+    """Fixed-capacity stage 2, eager: the forward again on stale memory (tests/dirty_memory.py: every workspace and every
+    torch.empty / empty_like result of any dtype filled with 0xFF bytes -- NaN as a float, -1 as an integer) returns the same
+    bits -- no output depends on a slot nobody wrote, which is what the caching allocator hands out in service."""
+    import dirty_memory as DM
     from masklab_hip import ModelConfiguration, retinamasklab as R
     cfg = ModelConfiguration()
     cfg.backbone.backbone_type = "mobilenet"
@@ -641,15 +642,8 @@ def test_forward_does_not_depend_on_what_empty_memory_holds(monkeypatch):
     slots = (cfg.instance.max_k + 1) * cfg.detection.nms_max_output_size
     assert n_det > 0 and boxes.shape[1] < slots, "the fixture needs detections and dead slots"
 
-    real_empty, real_empty_like = torch.empty, torch.empty_like
-
-    def poison(t):
-        return t.fill_(NAN) if t.dtype in (torch.float32, torch.float16) else t
-
-    monkeypatch.setattr(torch, "empty", lambda *a, **k: poison(real_empty(*a, **k)))
-    monkeypatch.setattr(torch, "empty_like", lambda *a, **k: poison(real_empty_like(*a, **k)))
-    second = model.predict(images)
-    monkeypatch.undo()
+    with DM.poisoned():
+        second = model.predict(images)
     for name, a, b in zip(model.output_names, first, second):
         assert a.shape == b.shape and a.dtype == b.dtype, name
         assert not np.isnan(b).any(), name
