@@ -865,6 +865,63 @@ int ml_eval_reference_host(const int32_t *det, const int32_t *ins, const void *g
                            const int32_t *pr_sem, const uint8_t *gt_sem, int32_t B, int32_t n, int32_t mh, int32_t mw, int32_t G,
                            int32_t H, int32_t W, int32_t C, int64_t *out_area, int64_t *out_pairs, int64_t *out_sem);
 
+/* ---------------------------------------------------------------------------------------------
+ * Trainer forward: the reference's target assignment (AssignBoxes engine/layers/detection.py:589-697, AssignMasks
+ * instance.py:296-386, AssignSeg semantic.py:304-311) and its four loss layers (engine/losses.py), forward only
+ * (csrc/train_targets.hip).  All on `stream`, no host read.  No float atomics: a sum is float64 partials per block in
+ * `workspace` (ml_train_workspace_bytes) added in block order by a finishing kernel -- the same bits run to run.  Per-element
+ * terms are float32 with FP contraction off, as tests/trainer_ref.py evaluates them; sums are float64.
+ * NOT supported: gradients; predictions or truths in float16 (cast first); more than ML_EVAL_MAX_CLASSES semantic classes;
+ * more than 32 images in ml_train_mask_loss_f32 (MoldBatch); gt_masks other than int8 / uint8; NaN boxes (a NaN IoU orders
+ * above every number in the packed maximum, where tf.argmax leaves it unspecified).
+ * The reference's quirks are kept: a ground truth whose best prior also has IoU >= 0.5 enters that prior twice (loc_true
+ * is a SUM over match entries, the label is the LAST entry's); an IoU in [0.4, 0.5) to ANY ground truth makes the anchor
+ * ignored even if it is positive for another; a valid ground truth with IoU 0 everywhere is assigned to prior 0; BoxLoss
+ * updates its moving statistics on every call and picks the quadratic branch where |d| - beta/2 < beta.
+ * ------------------------------------------------------------------------------------------- */
+#define ML_TRAIN_MAX_BLOCKS 512     /* partial sums per image */
+enum { ML_TRAIN_MASK_I8 = 0, ML_TRAIN_MASK_U8 = 1 };
+/* bytes of `workspace` for the loss kernels below on B images and C classes (C = 1 serves ml_train_box_loss_f32)     */
+int64_t ml_train_workspace_bytes(int32_t B, int32_t C);
+/* CalculateIOU.call (detection.py:391-422): aa [n, aa_stride], bb [m, bb_stride] float32 rows of (cx, cy, w, h, ...)
+ * -> out float32 [n,m], the bits of oracle/metrics.py::calculate_iou.                                                 */
+int ml_train_calculate_iou_f32(const float *aa, int32_t aa_stride, int32_t n, const float *bb, int32_t bb_stride, int32_t m, float *out,
+                               void *stream);
+/* gt_boxes [B,G,6] float32 (cx, cy, w, h, class, conf; rows padded with -1), pr_boxes [A,4] int32 (one table for the batch)
+ * -> best int32 [B,G]: the FIRST index of the row maximum of iou[b,g,:] = CalculateIOU * (gt cx != -1); a row of zeros
+ * gives 0.  keys: uint64 [B,G] scratch (packed (IoU bits, ~index) under an integer atomic maximum).                   */
+int ml_train_best_prior_f32(const float *gt_boxes, const int32_t *pr_boxes, int32_t B, int32_t G, int32_t A, void *keys, int32_t *best,
+                            void *stream);
+/* AssignBoxes.call: -> cls_true [B,A,C] (one-hot without the background column), loc_true [B,A,4], assign_mask [B,A]
+ * (-1 ignored, 0 positive, 1 negative), all float32.  One thread per anchor, the ground truths tiled through LDS.    */
+int ml_train_assign_boxes_f32(const float *gt_boxes, const int32_t *pr_boxes, const int32_t *best, int32_t B, int32_t G, int32_t A,
+                              int32_t C, float *cls_true, float *loc_true, float *assign_mask, void *stream);
+/* ClassLoss.call (losses.py:21-41): cls_true, cls_pred [B,A,C], assign_mask [B,A], cls_exists [B,C] float32 -> out [B].  */
+int ml_train_class_loss_f32(const float *cls_true, const float *cls_pred, const float *assign_mask, const float *cls_exists, int32_t B,
+                            int32_t A, int32_t C, float weight, float alpha, float gamma, void *workspace, float *out, void *stream);
+/* BoxLoss.call (losses.py:76-104): loc_true, loc_pred [B,A,4] (16-byte aligned), assign_mask [B,A] -> out [B].  With
+ * use_adjust, `state` float32 [8] = moving_mean[4], moving_var[4] in device memory is read AND updated (three passes:
+ * mean, variance, loss); without, beta is the constant and `state` may be null (one pass).                           */
+int ml_train_box_loss_f32(const float *loc_true, const float *loc_pred, const float *assign_mask, int32_t B, int32_t A, float weight,
+                          float momentum, float one_minus_momentum, float beta, int32_t use_adjust, float *state, void *workspace,
+                          float *out, void *stream);
+/* AssignMasks.call: roi_boxes [B,R,6], gt_boxes [B,G,6] float32, gt_masks [B,G,H,W] int8 / uint8 (ML_TRAIN_MASK_*)
+ * -> out int32 [B,R,mh,mw]: the matched class where the crop sample is > 0.5, otherwise C; an unmatched RoI is C.      */
+int ml_train_assign_masks(const float *roi_boxes, const float *gt_boxes, const void *gt_masks, int32_t mask_dtype, int32_t B, int32_t R,
+                          int32_t G, int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t C, float threshold, int32_t *out,
+                          void *stream);
+/* MaskLoss.call (losses.py:126-159): mask_true int32 [B,R,mh,mw], mask_pred float32 [B,R,mh,mw,C] -> out [B];
+ * keep = 1 - label_smoothing, half_smooth = label_smoothing / 2; roi_loss: float32 [B,R] scratch (the per-RoI means).  */
+int ml_train_mask_loss_f32(const int32_t *mask_true, const float *mask_pred, int32_t B, int32_t R, int32_t mh, int32_t mw, int32_t C,
+                           float weight, float keep, float half_smooth, float *roi_loss, float *out, void *stream);
+/* AssignSeg.call: gt_seg [B,H,W,C] float32 or uint8 (ML_EVAL_F32 / ML_EVAL_U8) -> out float32 [B,oh,ow,C] =
+ * round-half-to-even of resize_bilinear(align_corners=True).                                                          */
+int ml_train_assign_seg(const void *gt_seg, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C, int32_t oh, int32_t ow, float *out,
+                        void *stream);
+/* SegLoss.call (losses.py:179-193): seg_true, seg_pred [B,HW,C], seg_exist [B,C] float32 (C <= ML_EVAL_MAX_CLASSES) -> out [B]. */
+int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
+                          float weight, float keep, float half_smooth, void *workspace, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 //   * the per-thread bodies are __host__ __device__ functions of a thread index t out of T: ml_eval_reference_host runs
 //     the mask-area, mask-pair and semantic bodies in CPU loops, so the CPU tests hold this very code to NumPy.
 #include "common.h"
+#include "box_iou.h"
 
 #pragma clang fp contract(off)
 
@@ -286,21 +287,7 @@ __global__ void pairs_finish_kernel(const int32_t *pairs, const long long *gt_ar
 }
 
 // ----------------------------------------------------------------------------- DetectionIOUMetric
-// NumPy's minimum / maximum hand a NaN on; fminf / fmaxf would drop it.
-__host__ __device__ inline float np_min(float a, float b) { return (a != a || a < b) ? a : b; }
-__host__ __device__ inline float np_max(float a, float b) { return (a != a || a > b) ? a : b; }
-
-// CalculateIOU.call (engine/layers/detection.py:391-422) for one (proposal, ground truth) pair, float32
-__host__ __device__ inline float box_iou(const float *a, const float *g) {
-    const float areas = g[2] * g[3] + a[2] * a[3];
-    const float ay1 = a[1] - a[3] / 2.f, ax1 = a[0] - a[2] / 2.f, ay2 = a[1] + a[3] / 2.f, ax2 = a[0] + a[2] / 2.f;
-    const float gy1 = g[1] - g[3] / 2.f, gx1 = g[0] - g[2] / 2.f, gy2 = g[1] + g[3] / 2.f, gx2 = g[0] + g[2] / 2.f;
-    const float in_w = np_max(0.f, np_min(gx2, ax2) - np_max(gx1, ax1));
-    const float in_h = np_max(0.f, np_min(gy2, ay2) - np_max(gy1, ay1));
-    const float inter = in_w * in_h;
-    return inter / ((areas - inter) + 1e-5f);
-}
-
+// box_iou (CalculateIOU.call for one pair) and NumPy's minimum / maximum: box_iou.h, shared with train_targets.hip
 __host__ __device__ inline float masked_iou(const float *a, const float *g) {     // metrics.py:136-147, logical_or as written
     return box_iou(a, g) * ((a[0] != -1.f || g[0] != -1.f) ? 1.f : 0.f);
 }

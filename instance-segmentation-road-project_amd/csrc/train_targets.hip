@@ -1,0 +1,634 @@
+// The trainer network's forward tail: the reference's target assignment (AssignBoxes detection.py:589-697, AssignMasks
+// instance.py:296-386, AssignSeg semantic.py:304-311) and its four loss layers (engine/losses.py).  The contract is in
+// include/masklab_hip.h ("Trainer forward"); what matters here:
+//
+//   * no float atomics.  A sum is per-thread float64 -> wave shuffle tree -> one LDS word per wave -> one float64 partial
+//     per block in the workspace, and a finishing kernel adds the partials of an image in block order: the same bits run
+//     to run.  Integer atomics appear only where the order cannot matter (the packed (IoU, index) maximum).
+//   * per-element terms are float32 with FP contraction OFF, operation by operation as NumPy evaluates
+//     tests/trainer_ref.py; logf / powf are the only operations that may differ from NumPy's by an ulp or two.
+//   * forward only: no gradients are produced.
+#include "common.h"
+#include "box_iou.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+namespace tt {
+
+constexpr int TPB = 256;
+constexpr int WAVES = TPB / 64;
+constexpr int GT_TILE = 64;               // ground-truth rows held in LDS at a time
+constexpr int APT = 4;                    // anchors per thread of the best-prior kernel
+constexpr int MAX_BLOCKS = ML_TRAIN_MAX_BLOCKS;
+constexpr int MAX_CLASSES = ML_EVAL_MAX_CLASSES;
+constexpr int MAX_GRID_Y = 65535;
+
+// ----------------------------------------------------------------------------- fixed-order block sum
+// Thread 0 returns the block's sum: lanes by a shuffle tree, waves in index order.  Uniform call sites only.
+__device__ inline double block_sum(double v) {
+    __shared__ double s[WAVES];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();                                   // the previous call's read of s[] is over
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < WAVES; ++w) t += s[w];
+    return t;
+}
+
+__device__ inline int block_min(int v) {
+    __shared__ int s[WAVES];
+    for (int off = 32; off > 0; off >>= 1) {
+        const int o = __shfl_down(v, off, 64);
+        v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int m = s[0];
+    for (int w = 1; w < WAVES; ++w) m = s[w] < m ? s[w] : m;
+    return m;                                          // every thread
+}
+
+// ----------------------------------------------------------------------------- CalculateIOU (the standalone layer)
+__global__ __launch_bounds__(TPB) void iou_matrix_kernel(const float *aa, int sa, int n, const float *bb, int sb, int m, float *out) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= (long long)n * m) return;
+    out[i] = box_iou(aa + (i / m) * sa, bb + (i % m) * sb);
+}
+
+// ----------------------------------------------------------------------------- best prior per ground truth
+// iou[b, g, a] of AssignBoxes: CalculateIOU([gt, pr_boxes[0]]) times (gt cx != -1)
+__device__ inline float masked_gt_iou(const float *g, const float *p) { return box_iou(g, p) * (g[0] != -1.f ? 1.f : 0.f); }
+
+// keys [B, G] zeroed.  key = IoU bits << 32 | ~anchor: IoUs are >= +0, so the integer order of the keys is (IoU, then
+// the LOWER anchor index) and the integer maximum is tf.argmax's first maximum whatever the order of the atomics.
+__global__ __launch_bounds__(TPB) void best_prior_kernel(const float *gt, const int32_t *pr, int G, int A, unsigned long long *keys) {
+    __shared__ float sg[GT_TILE * 4];
+    __shared__ unsigned long long sk[GT_TILE];
+    const int b = blockIdx.y;
+    float p[APT][4];
+    unsigned a[APT];
+    for (int k = 0; k < APT; ++k) {
+        a[k] = (unsigned)blockIdx.x * (TPB * APT) + k * TPB + threadIdx.x;
+        for (int q = 0; q < 4; ++q) p[k][q] = a[k] < (unsigned)A ? (float)pr[4ll * a[k] + q] : 0.f;
+    }
+    for (int g0 = 0; g0 < G; g0 += GT_TILE) {
+        const int n = G - g0 < GT_TILE ? G - g0 : GT_TILE;
+        __syncthreads();
+        for (int i = threadIdx.x; i < n * 4; i += TPB) sg[i] = gt[((long long)b * G + g0 + i / 4) * 6 + i % 4];
+        if (threadIdx.x < n) sk[threadIdx.x] = 0;
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            unsigned long long key = 0;
+            for (int k = 0; k < APT; ++k)
+                if (a[k] < (unsigned)A) {
+                    const unsigned long long c = ((unsigned long long)__float_as_uint(masked_gt_iou(sg + 4 * j, p[k])) << 32) | (0xffffffffu - a[k]);
+                    key = c > key ? c : key;
+                }
+            for (int off = 32; off > 0; off >>= 1) {
+                const unsigned long long o = __shfl_down(key, off, 64);
+                key = o > key ? o : key;
+            }
+            if ((threadIdx.x & 63) == 0 && key) atomicMax(&sk[j], key);
+        }
+        __syncthreads();
+        if (threadIdx.x < n && sk[threadIdx.x]) atomicMax(&keys[(long long)b * G + g0 + threadIdx.x], sk[threadIdx.x]);
+    }
+}
+
+__global__ void best_finish_kernel(const unsigned long long *keys, int n, int A, int32_t *best) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned a = 0xffffffffu - (unsigned)(keys[i] & 0xffffffffu);
+    best[i] = a < (unsigned)A ? (int32_t)a : 0;
+}
+
+// ----------------------------------------------------------------------------- AssignBoxes
+// float32 log of a float32 quotient, rounded once from the float64 logarithm: at most a handful per prior, and loc_true
+// SUMS these terms, so their last bits matter more than their cost
+__device__ inline float log_f32(float x) { return (float)log((double)x); }
+
+// One thread per anchor.  Match entries in the reference's order: every g with IoU >= 0.5 (ascending), then every g
+// with conf > 0 whose best prior this is (ascending).  label = the last entry's class, loc_true = the SUM over entries.
+__global__ __launch_bounds__(TPB) void assign_boxes_kernel(const float *gt, const int32_t *pr, const int32_t *best, int G, int A, int C,
+                                                           float *cls_true, float *loc_true, float *assign_mask) {
+    __shared__ float sg[GT_TILE * 6];
+    __shared__ int32_t sb[GT_TILE];
+    const int b = blockIdx.y;
+    const int a = blockIdx.x * TPB + threadIdx.x;
+    const bool active = a < A;
+    float p[4] = {0.f, 0.f, 1.f, 1.f};
+    if (active)
+        for (int q = 0; q < 4; ++q) p[q] = (float)pr[4ll * a + q];
+    float label = -1.f, loc[4] = {0.f, 0.f, 0.f, 0.f};
+    bool ignore = false;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int g0 = 0; g0 < G; g0 += GT_TILE) {
+            const int n = G - g0 < GT_TILE ? G - g0 : GT_TILE;
+            __syncthreads();
+            for (int i = threadIdx.x; i < n * 6; i += TPB) sg[i] = gt[((long long)b * G + g0) * 6 + i];
+            if (threadIdx.x < n) sb[threadIdx.x] = best[(long long)b * G + g0 + threadIdx.x];
+            __syncthreads();
+            if (!active) continue;
+            for (int j = 0; j < n; ++j) {
+                const float *g = sg + 6 * j;
+                bool entry;
+                if (pass == 0) {
+                    const float iou = masked_gt_iou(g, p);
+                    entry = iou >= 0.5f;
+                    ignore = ignore || (iou < 0.5f && iou >= 0.4f);
+                } else {
+                    entry = g[5] > 0.f && sb[j] == a;
+                }
+                if (entry) {
+                    label = g[4];
+                    loc[0] += (g[0] - p[0]) / p[2];
+                    loc[1] += (g[1] - p[1]) / p[3];
+                    loc[2] += log_f32(g[2] / p[2]);
+                    loc[3] += log_f32(g[3] / p[3]);
+                }
+            }
+        }
+    if (!active) return;
+    const int li = label != -1.f ? (int)label : C;     // tf.one_hot: a class outside [0, C] lights nothing
+    const long long row = (long long)b * A + a;
+    for (int c = 0; c < C; ++c) cls_true[row * C + c] = c == li ? 1.f : 0.f;
+    for (int q = 0; q < 4; ++q) loc_true[row * 4 + q] = loc[q];
+    assign_mask[row] = ignore ? -1.f : li == C ? 1.f : 0.f;
+}
+
+// ----------------------------------------------------------------------------- ClassLoss
+struct FocalArgs { float eps, one_minus_eps, alpha, gamma; };
+
+__device__ inline float focal_term(float t, float pred, const FocalArgs &f) {        // losses.py:204-218
+    const float p = pred < f.eps ? f.eps : pred > f.one_minus_eps ? f.one_minus_eps : pred;
+    const float pt = t == 1.f ? p : 1.f - p;
+    return f.alpha * (-powf(1.f - pt, f.gamma) * logf(pt));
+}
+
+// partial [B, gridDim.x, 2] = (sum of the masked focal terms, #positive + #negative anchors)
+__global__ __launch_bounds__(TPB) void class_loss_kernel(const float *cls_true, const float *cls_pred, const float *mask,
+                                                         const float *exists, int A, int C, FocalArgs f, double *partial) {
+    const int b = blockIdx.y;
+    double sum = 0.0, cnt = 0.0;
+    for (int a = blockIdx.x * TPB + threadIdx.x; a < A; a += gridDim.x * TPB) {
+        const long long row = (long long)b * A + a;
+        const float m = mask[row];
+        cnt += (m == 1.f || m == 0.f) ? 1.0 : 0.0;
+        const float keep = m == -1.f ? 0.f : 1.f;
+        for (int c = 0; c < C; ++c) {
+            const float t = cls_true[row * C + c] != 0.f ? 1.f : 0.f;
+            const float l = focal_term(t, cls_pred[row * C + c], f) * exists[b * C + c];
+            sum += (double)(keep * l);
+        }
+    }
+    const double s = block_sum(sum), n = block_sum(cnt);
+    if (threadIdx.x == 0) {
+        double *o = partial + ((long long)b * gridDim.x + blockIdx.x) * 2;
+        o[0] = s;
+        o[1] = n;
+    }
+}
+
+__global__ void class_loss_finish_kernel(const double *partial, int B, int nblk, float eps, float weight, float *out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s = 0.0, n = 0.0;
+    for (int k = 0; k < nblk; ++k) {
+        s += partial[((long long)b * nblk + k) * 2];
+        n += partial[((long long)b * nblk + k) * 2 + 1];
+    }
+    out[b] = weight * (float)(s / (n + (double)eps));
+}
+
+// ----------------------------------------------------------------------------- BoxLoss
+// STAT 0: sum of offsets = |loc_true - loc_pred| * pos_mask per coordinate; STAT 1: sum of (offsets - mean)^2.
+// partial [gridDim.x, 4] over ALL N = B * A anchors.
+template <int STAT>
+__global__ __launch_bounds__(TPB) void box_stat_kernel(const float *loc_true, const float *loc_pred, const float *mask, long long N,
+                                                       const float *mean, double *partial) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    float mu[4] = {0.f, 0.f, 0.f, 0.f};
+    if (STAT == 1)
+        for (int q = 0; q < 4; ++q) mu[q] = mean[q];
+    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < N; i += (long long)gridDim.x * TPB) {
+        const float pos = mask[i] == 0.f ? 1.f : 0.f;
+        const f32x4 t = *(const f32x4 *)(loc_true + 4 * i), p = *(const f32x4 *)(loc_pred + 4 * i);
+        for (int q = 0; q < 4; ++q) {
+            const float off = fabsf(t[q] - p[q]) * pos;
+            if (STAT == 0) {
+                acc[q] += (double)off;
+            } else {
+                const float d = off - mu[q];
+                acc[q] += (double)(d * d);
+            }
+        }
+    }
+    for (int q = 0; q < 4; ++q) {
+        const double s = block_sum(acc[q]);
+        if (threadIdx.x == 0) partial[(long long)blockIdx.x * 4 + q] = s;
+    }
+}
+
+struct BoxArgs { float momentum, one_minus_momentum, beta, weight, eps; };
+
+// 4 threads.  STAT 0: scratch[q] = mean.  STAT 1: var, the moving values' update, scratch[4 + q] = beta per coordinate.
+template <int STAT>
+__global__ void box_stat_finish_kernel(const double *partial, int nblk, long long N, BoxArgs k, float *state, float *scratch) {
+    const int q = threadIdx.x;
+    if (q >= 4) return;
+    double s = 0.0;
+    for (int i = 0; i < nblk; ++i) s += partial[(long long)i * 4 + q];
+    const float m = (float)(s / (double)N);
+    if (STAT == 0) {
+        scratch[q] = m;
+    } else {
+        const float next_mean = state[q] * k.momentum + scratch[q] * k.one_minus_momentum;
+        const float next_var = state[4 + q] * k.momentum + m * k.one_minus_momentum;
+        state[q] = next_mean;
+        state[4 + q] = next_var;
+        const float beta = next_mean - next_var;
+        scratch[4 + q] = beta < 1e-3f ? 1e-3f : beta > k.beta ? k.beta : beta;
+    }
+}
+
+__global__ void box_fixed_beta_kernel(float beta, float *scratch) {
+    if (threadIdx.x < 4) scratch[4 + threadIdx.x] = beta;
+}
+
+// partial [B, gridDim.x, 2] = (sum over positives of mean_q smooth_l1, #positives)
+__global__ __launch_bounds__(TPB) void box_loss_kernel(const float *loc_true, const float *loc_pred, const float *mask, int A,
+                                                       const float *scratch, double *partial) {
+    const int b = blockIdx.y;
+    float beta[4];
+    for (int q = 0; q < 4; ++q) beta[q] = scratch[4 + q];
+    double sum = 0.0, cnt = 0.0;
+    for (int a = blockIdx.x * TPB + threadIdx.x; a < A; a += gridDim.x * TPB) {
+        const long long row = (long long)b * A + a;
+        if (mask[row] != 0.f) continue;
+        const f32x4 t = *(const f32x4 *)(loc_true + 4 * row), p = *(const f32x4 *)(loc_pred + 4 * row);
+        float l[4];
+        for (int q = 0; q < 4; ++q) {                   // smooth_l1 as written: l2 where l1 < beta (losses.py:221-234)
+            const float d = t[q] - p[q];
+            const float l1 = fabsf(d) - 0.5f * beta[q];
+            const float l2 = 0.5f * (d * d) / beta[q];
+            l[q] = l1 < beta[q] ? l2 : l1;
+        }
+        sum += (double)((((l[0] + l[1]) + l[2]) + l[3]) / 4.f);
+        cnt += 1.0;
+    }
+    const double s = block_sum(sum), n = block_sum(cnt);
+    if (threadIdx.x == 0) {
+        double *o = partial + ((long long)b * gridDim.x + blockIdx.x) * 2;
+        o[0] = s;
+        o[1] = n;
+    }
+}
+
+// ----------------------------------------------------------------------------- AssignMasks
+struct MaskDims { int R, G, H, W, mh, mw, C; float thr; };
+
+// tf.image.crop_and_resize's sampling position along one axis, float32 as oracle/tfops.py::crop_and_resize
+__device__ inline float crop_pos(float lo, float hi, int i, int out, int in) {
+    if (out > 1) {
+        const float step = (hi - lo) * (float)(in - 1) / (float)(out - 1);
+        return lo * (float)(in - 1) + (float)i * step;
+    }
+    return 0.5f * (lo + hi) * (float)(in - 1);
+}
+
+// one block per (image, RoI); out int32 [B, R, mh, mw]
+template <typename T>
+__global__ __launch_bounds__(TPB) void assign_masks_kernel(const float *roi, const float *gt, const T *masks, MaskDims d, int32_t *out) {
+    __shared__ unsigned long long skey;
+    const int b = blockIdx.y, r = blockIdx.x;
+    const float *box = roi + ((long long)b * d.R + r) * 6;
+    const float *G0 = gt + (long long)b * d.G * 6;
+    if (threadIdx.x == 0) skey = 0;
+    __syncthreads();
+    if (threadIdx.x < 64) {                             // argmax over the ground truths: first maximum
+        unsigned long long key = 0;
+        for (int g = threadIdx.x; g < d.G; g += 64) {
+            const float *gb = G0 + 6 * g;
+            const float live = (gb[5] != -1.f && box[5] != -1.f) ? 1.f : 0.f;
+            const float same = gb[4] == box[4] ? 1.f : 0.f;
+            const float iou = box_iou(gb, box) * live * same;
+            const unsigned long long c = ((unsigned long long)__float_as_uint(iou) << 32) | (0xffffffffu - (unsigned)g);
+            key = c > key ? c : key;
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned long long o = __shfl_down(key, off, 64);
+            key = o > key ? o : key;
+        }
+        if (threadIdx.x == 0) skey = key;
+    }
+    __syncthreads();
+    const unsigned long long key = skey;
+    const float best = __uint_as_float((unsigned)(key >> 32));
+    unsigned g = 0xffffffffu - (unsigned)(key & 0xffffffffu);
+    const bool matched = key != 0 && g < (unsigned)d.G && best >= d.thr;
+    int32_t *o = out + ((long long)b * d.R + r) * d.mh * d.mw;
+    if (!matched) {                                     // num_classes everywhere: the crop is skipped
+        for (int i = threadIdx.x; i < d.mh * d.mw; i += TPB) o[i] = d.C;
+        return;
+    }
+    const int cls = (int)G0[6 * g + 4];
+    // NormalizeBoxes(shape = the mask's (H, W)), detection.py:360-375
+    const float cx = box[0], cy = box[1], w = box[2], h = box[3];
+    const float x1 = (cx - w / 2.f) / (float)d.W, y1 = (cy - h / 2.f) / (float)d.H;
+    const float x2 = (cx + w / 2.f) / (float)d.W, y2 = (cy + h / 2.f) / (float)d.H;
+    const T *img = masks + ((long long)b * d.G + g) * d.H * d.W;
+    for (int i = threadIdx.x; i < d.mh * d.mw; i += TPB) {
+        const int oy = i / d.mw, ox = i - oy * d.mw;
+        const float in_y = crop_pos(y1, y2, oy, d.mh, d.H), in_x = crop_pos(x1, x2, ox, d.mw, d.W);
+        float v = 0.f;                                  // extrapolation value
+        if (!(in_y < 0.f || in_y > (float)(d.H - 1) || in_x < 0.f || in_x > (float)(d.W - 1)) && in_y == in_y && in_x == in_x) {
+            const int ty = (int)floorf(in_y), by = (int)ceilf(in_y), lx = (int)floorf(in_x), rx = (int)ceilf(in_x);
+            const float fy = in_y - (float)ty, fx = in_x - (float)lx;
+            const float tl = (float)img[(long long)ty * d.W + lx], tr = (float)img[(long long)ty * d.W + rx];
+            const float bl = (float)img[(long long)by * d.W + lx], br = (float)img[(long long)by * d.W + rx];
+            const float top = tl + (tr - tl) * fx, bot = bl + (br - bl) * fx;
+            v = top + (bot - top) * fy;
+        }
+        o[i] = v > 0.5f ? cls : d.C;
+    }
+}
+
+// ----------------------------------------------------------------------------- MaskLoss
+struct BceArgs { float eps, keep, half_smooth; };         // y = keep * t + half_smooth  (1 - label_smoothing, label_smoothing / 2)
+
+__device__ inline float bce_term(float t, float p, const BceArgs &k) {               // losses.py:237-248
+    const float y = k.keep * t + k.half_smooth;
+    return -(y * logf(p + k.eps) + (1.f - y) * logf(1.f - p + k.eps));
+}
+
+// one block per (image, RoI): roi_loss [B, R] = mean BCE of the RoI's class channel, 0 for an RoI that is not selected
+__global__ __launch_bounds__(TPB) void mask_roi_loss_kernel(const int32_t *target, const float *pred, int R, int hw, int C, BceArgs k,
+                                                            float *roi_loss) {
+    const long long row = (long long)blockIdx.y * R + blockIdx.x;
+    const int32_t *t = target + row * hw;
+    int m = 0x7fffffff;
+    for (int i = threadIdx.x; i < hw; i += TPB) m = t[i] < m ? t[i] : m;
+    const int cls = block_min(m);
+    if (cls >= C || cls < 0) {                          // (a negative class cannot come out of AssignMasks; it would index nothing)
+        if (threadIdx.x == 0) roi_loss[row] = 0.f;
+        return;
+    }
+    const float *p = pred + row * hw * C + cls;
+    double sum = 0.0;
+    for (int i = threadIdx.x; i < hw; i += TPB) sum += (double)bce_term(t[i] == cls ? 1.f : 0.f, p[(long long)i * C], k);
+    const double s = block_sum(sum);
+    if (threadIdx.x == 0) roi_loss[row] = (float)(s / (double)hw);
+}
+
+__global__ void mask_loss_finish_kernel(const float *roi_loss, int B, int R, float weight, float *out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double s = 0.0;
+    int nz = 0;
+    for (int r = 0; r < R; ++r) {
+        const float l = roi_loss[(long long)b * R + r];
+        s += (double)l;
+        nz += l != 0.f;
+    }
+    out[b] = weight * (float)(s / (double)(nz + 1));
+}
+
+// ----------------------------------------------------------------------------- AssignSeg
+struct SegDims { int H, W, C, oh, ow; float sy, sx; };
+
+// round-half-to-even of resize_bilinear(align_corners=True), the arithmetic of oracle/tfops.py::resize_bilinear_align_corners
+template <typename T>
+__global__ __launch_bounds__(TPB) void assign_seg_kernel(const T *gt, SegDims d, long long n, float *out) {
+    const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % d.C);
+    const long long px = i / d.C;
+    const int ox = (int)(px % d.ow), oy = (int)((px / d.ow) % d.oh);
+    const long long b = px / ((long long)d.ow * d.oh);
+    const float fy = (float)oy * d.sy, fx = (float)ox * d.sx;
+    const float fly = floorf(fy), flx = floorf(fx);
+    int ylo = (int)fly, xlo = (int)flx, yhi = (int)ceilf(fy), xhi = (int)ceilf(fx);
+    ylo = ylo < 0 ? 0 : ylo > d.H - 1 ? d.H - 1 : ylo;
+    xlo = xlo < 0 ? 0 : xlo > d.W - 1 ? d.W - 1 : xlo;
+    yhi = yhi > d.H - 1 ? d.H - 1 : yhi < 0 ? 0 : yhi;
+    xhi = xhi > d.W - 1 ? d.W - 1 : xhi < 0 ? 0 : xhi;
+    const float ty = fy - fly, tx = fx - flx;
+    const T *img = gt + b * d.H * d.W * d.C + c;
+    const float tl = (float)img[((long long)ylo * d.W + xlo) * d.C], tr = (float)img[((long long)ylo * d.W + xhi) * d.C];
+    const float bl = (float)img[((long long)yhi * d.W + xlo) * d.C], br = (float)img[((long long)yhi * d.W + xhi) * d.C];
+    const float top = tl + (tr - tl) * tx, bot = bl + (br - bl) * tx;
+    out[i] = rintf(top + (bot - top) * ty);
+}
+
+// ----------------------------------------------------------------------------- SegLoss
+// partial [B, gridDim.x, C]: per class the sum of the BCE terms over the block's pixels
+__global__ __launch_bounds__(TPB) void seg_loss_kernel(const float *seg_true, const float *seg_pred, long long HW, int C, BceArgs k,
+                                                       double *partial) {
+    const int b = blockIdx.y;
+    double acc[MAX_CLASSES];
+#pragma unroll
+    for (int c = 0; c < MAX_CLASSES; ++c) acc[c] = 0.0;
+    for (long long px = (long long)blockIdx.x * TPB + threadIdx.x; px < HW; px += (long long)gridDim.x * TPB) {
+        const long long e = ((long long)b * HW + px) * C;
+#pragma unroll
+        for (int c = 0; c < MAX_CLASSES; ++c)
+            if (c < C) acc[c] += (double)bce_term(seg_true[e + c], seg_pred[e + c], k);
+    }
+#pragma unroll
+    for (int c = 0; c < MAX_CLASSES; ++c)
+        if (c < C) {
+            const double s = block_sum(acc[c]);
+            if (threadIdx.x == 0) partial[((long long)b * gridDim.x + blockIdx.x) * C + c] = s;
+        }
+}
+
+__global__ void seg_loss_finish_kernel(const double *partial, const float *exist, int B, int nblk, long long HW, int C, float weight,
+                                       float *out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double tot = 0.0;
+    for (int c = 0; c < C; ++c) {
+        double s = 0.0;
+        for (int i = 0; i < nblk; ++i) s += partial[((long long)b * nblk + i) * C + c];
+        tot += (double)(exist[b * C + c] * (float)(s / (double)HW));
+    }
+    out[b] = weight * (float)(tot / (double)C);
+}
+
+int blocks_for(long long n) {
+    long long nb = (n + TPB - 1) / TPB;
+    return (int)(nb < 1 ? 1 : nb > MAX_BLOCKS ? MAX_BLOCKS : nb);
+}
+
+}  // namespace tt
+}  // namespace
+
+using namespace tt;
+
+#define ML_HIP_OK(call, what)                                                \
+    do {                                                                     \
+        hipError_t e_ = (call);                                              \
+        if (e_ != hipSuccess) {                                              \
+            ml_set_error("%s: %s", what, hipGetErrorString(e_));             \
+            return ML_E_LAUNCH;                                              \
+        }                                                                    \
+    } while (0)
+
+extern "C" int64_t ml_train_workspace_bytes(int32_t B, int32_t C) {
+    if (B < 1 || C < 1) return 0;
+    const int64_t per = C > 4 ? C : 4;
+    return (int64_t)sizeof(double) * ((int64_t)B * MAX_BLOCKS * per + 16);
+}
+
+extern "C" int ml_train_calculate_iou_f32(const float *aa, int32_t aa_stride, int32_t n, const float *bb, int32_t bb_stride, int32_t m,
+                                          float *out, void *stream) {
+    const char *what = "train_calculate_iou";
+    ML_REQUIRE(aa && bb && out, "%s: null pointer", what);
+    ML_REQUIRE(n >= 1 && m >= 1 && aa_stride >= 4 && bb_stride >= 4 && (long long)n * m < (1ll << 38), "%s: bad dims n=%d m=%d", what, n, m);
+    const long long nb = ((long long)n * m + TPB - 1) / TPB;
+    hipLaunchKernelGGL(iou_matrix_kernel, dim3((unsigned)nb), dim3(TPB), 0, (hipStream_t)stream, aa, aa_stride, n, bb, bb_stride, m, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_best_prior_f32(const float *gt_boxes, const int32_t *pr_boxes, int32_t B, int32_t G, int32_t A, void *keys,
+                                       int32_t *best, void *stream) {
+    const char *what = "train_best_prior";
+    ML_REQUIRE(gt_boxes && pr_boxes && keys && best, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && G >= 1 && A >= 1 && (long long)B * G < (1ll << 31), "%s: bad dims B=%d G=%d A=%d", what, B, G, A);
+    hipStream_t s = (hipStream_t)stream;
+    ML_HIP_OK(hipMemsetAsync(keys, 0, sizeof(unsigned long long) * (size_t)B * G, s), what);
+    hipLaunchKernelGGL(best_prior_kernel, dim3((A + TPB * APT - 1) / (TPB * APT), B), dim3(TPB), 0, s, gt_boxes, pr_boxes, G, A,
+                       (unsigned long long *)keys);
+    hipLaunchKernelGGL(best_finish_kernel, dim3((B * G + TPB - 1) / TPB), dim3(TPB), 0, s, (const unsigned long long *)keys, B * G, A, best);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_assign_boxes_f32(const float *gt_boxes, const int32_t *pr_boxes, const int32_t *best, int32_t B, int32_t G,
+                                         int32_t A, int32_t C, float *cls_true, float *loc_true, float *assign_mask, void *stream) {
+    const char *what = "train_assign_boxes";
+    ML_REQUIRE(gt_boxes && pr_boxes && best && cls_true && loc_true && assign_mask, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && G >= 1 && A >= 1 && C >= 1, "%s: bad dims B=%d G=%d A=%d C=%d", what, B, G, A, C);
+    hipLaunchKernelGGL(assign_boxes_kernel, dim3((A + TPB - 1) / TPB, B), dim3(TPB), 0, (hipStream_t)stream, gt_boxes, pr_boxes, best, G, A,
+                       C, cls_true, loc_true, assign_mask);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_class_loss_f32(const float *cls_true, const float *cls_pred, const float *assign_mask, const float *cls_exists,
+                                       int32_t B, int32_t A, int32_t C, float weight, float alpha, float gamma, void *workspace,
+                                       float *out, void *stream) {
+    const char *what = "train_class_loss";
+    ML_REQUIRE(cls_true && cls_pred && assign_mask && cls_exists && workspace && out, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && A >= 1 && C >= 1, "%s: bad dims B=%d A=%d C=%d", what, B, A, C);
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = blocks_for(A);
+    const float eps = 1e-7f;
+    const FocalArgs f = {eps, 1.f - eps, alpha, gamma};
+    hipLaunchKernelGGL(class_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, cls_true, cls_pred, assign_mask, cls_exists, A, C, f,
+                       (double *)workspace);
+    hipLaunchKernelGGL(class_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)workspace, B, nblk, eps, weight, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_box_loss_f32(const float *loc_true, const float *loc_pred, const float *assign_mask, int32_t B, int32_t A,
+                                     float weight, float momentum, float one_minus_momentum, float beta, int32_t use_adjust,
+                                     float *state, void *workspace, float *out, void *stream) {
+    const char *what = "train_box_loss";
+    ML_REQUIRE(loc_true && loc_pred && assign_mask && workspace && out && (state || !use_adjust), "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && A >= 1, "%s: bad dims B=%d A=%d", what, B, A);
+    ML_REQUIRE(ml_aligned16(loc_true) && ml_aligned16(loc_pred), "%s: loc_true and loc_pred must be 16-byte aligned", what);
+    hipStream_t s = (hipStream_t)stream;
+    double *partial = (double *)workspace;
+    float *scratch = (float *)(partial + (size_t)B * MAX_BLOCKS * 4);        // 8 floats behind the partials
+    const BoxArgs k = {momentum, one_minus_momentum, beta, weight, 1e-7f};
+    const long long N = (long long)B * A;
+    if (use_adjust) {
+        const int nb = blocks_for(N);
+        hipLaunchKernelGGL(box_stat_kernel<0>, dim3(nb), dim3(TPB), 0, s, loc_true, loc_pred, assign_mask, N, (const float *)scratch, partial);
+        hipLaunchKernelGGL(box_stat_finish_kernel<0>, dim3(1), dim3(64), 0, s, (const double *)partial, nb, N, k, state, scratch);
+        hipLaunchKernelGGL(box_stat_kernel<1>, dim3(nb), dim3(TPB), 0, s, loc_true, loc_pred, assign_mask, N, (const float *)scratch, partial);
+        hipLaunchKernelGGL(box_stat_finish_kernel<1>, dim3(1), dim3(64), 0, s, (const double *)partial, nb, N, k, state, scratch);
+    } else {
+        hipLaunchKernelGGL(box_fixed_beta_kernel, dim3(1), dim3(64), 0, s, beta, scratch);
+    }
+    const int nblk = blocks_for(A);
+    hipLaunchKernelGGL(box_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, loc_true, loc_pred, assign_mask, A, (const float *)scratch, partial);
+    hipLaunchKernelGGL(class_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)partial, B, nblk, k.eps, weight, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_assign_masks(const float *roi_boxes, const float *gt_boxes, const void *gt_masks, int32_t mask_dtype, int32_t B,
+                                     int32_t R, int32_t G, int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t C, float threshold,
+                                     int32_t *out, void *stream) {
+    const char *what = "train_assign_masks";
+    ML_REQUIRE(roi_boxes && gt_boxes && gt_masks && out, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && R >= 1 && G >= 1 && H >= 1 && W >= 1 && mh >= 1 && mw >= 1 && C >= 1 &&
+                   (long long)H * W < (1ll << 31) && (long long)mh * mw < (1ll << 24),
+               "%s: bad dims B=%d R=%d G=%d mask %d x %d crop %d x %d C=%d", what, B, R, G, H, W, mh, mw, C);
+    ML_REQUIRE(mask_dtype == ML_TRAIN_MASK_I8 || mask_dtype == ML_TRAIN_MASK_U8, "%s: gt_masks must be int8 or uint8", what);
+    const MaskDims d = {R, G, H, W, mh, mw, C, threshold};
+    hipStream_t s = (hipStream_t)stream;
+    if (mask_dtype == ML_TRAIN_MASK_I8)
+        hipLaunchKernelGGL(assign_masks_kernel<int8_t>, dim3(R, B), dim3(TPB), 0, s, roi_boxes, gt_boxes, (const int8_t *)gt_masks, d, out);
+    else
+        hipLaunchKernelGGL(assign_masks_kernel<uint8_t>, dim3(R, B), dim3(TPB), 0, s, roi_boxes, gt_boxes, (const uint8_t *)gt_masks, d, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_mask_loss_f32(const int32_t *mask_true, const float *mask_pred, int32_t B, int32_t R, int32_t mh, int32_t mw,
+                                      int32_t C, float weight, float keep, float half_smooth, float *roi_loss, float *out, void *stream) {
+    const char *what = "train_mask_loss";
+    ML_REQUIRE(mask_true && mask_pred && roi_loss && out, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= 32 && R >= 1 && mh >= 1 && mw >= 1 && C >= 1 && (long long)mh * mw < (1ll << 24),
+               "%s: bad dims B=%d R=%d crop %d x %d C=%d (B <= 32: MoldBatch)", what, B, R, mh, mw, C);
+    hipStream_t s = (hipStream_t)stream;
+    const BceArgs k = {1e-7f, keep, half_smooth};
+    hipLaunchKernelGGL(mask_roi_loss_kernel, dim3(R, B), dim3(TPB), 0, s, mask_true, mask_pred, R, mh * mw, C, k, roi_loss);
+    hipLaunchKernelGGL(mask_loss_finish_kernel, dim3(1), dim3(64), 0, s, (const float *)roi_loss, B, R, weight, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_assign_seg(const void *gt_seg, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C, int32_t oh, int32_t ow,
+                                   float *out, void *stream) {
+    const char *what = "train_assign_seg";
+    ML_REQUIRE(gt_seg && out, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1 && oh >= 1 && ow >= 1 && (long long)H * W * C < (1ll << 31), "%s: bad dims", what);
+    ML_REQUIRE(dtype == ML_EVAL_F32 || dtype == ML_EVAL_U8, "%s: gt_seg must be float32 or uint8", what);
+    const long long n = (long long)B * oh * ow * C;
+    ML_REQUIRE((n + TPB - 1) / TPB < (1ll << 31), "%s: too many elements for one launch", what);
+    const SegDims d = {H, W, C, oh, ow, oh > 1 ? (float)((double)(H - 1) / (double)(oh - 1)) : 0.f,
+                       ow > 1 ? (float)((double)(W - 1) / (double)(ow - 1)) : 0.f};
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nb = (unsigned)((n + TPB - 1) / TPB);
+    if (dtype == ML_EVAL_F32)
+        hipLaunchKernelGGL(assign_seg_kernel<float>, dim3(nb), dim3(TPB), 0, s, (const float *)gt_seg, d, n, out);
+    else
+        hipLaunchKernelGGL(assign_seg_kernel<uint8_t>, dim3(nb), dim3(TPB), 0, s, (const uint8_t *)gt_seg, d, n, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
+                                     float weight, float keep, float half_smooth, void *workspace, float *out, void *stream) {
+    const char *what = "train_seg_loss";
+    ML_REQUIRE(seg_true && seg_pred && seg_exist && workspace && out, "%s: null pointer", what);
+    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && HW >= 1 && C >= 1 && C <= MAX_CLASSES, "%s: bad dims B=%d HW=%lld C=%d (C <= %d)", what, B,
+               (long long)HW, C, MAX_CLASSES);
+    hipStream_t s = (hipStream_t)stream;
+    const int nblk = blocks_for(HW);
+    const BceArgs k = {1e-7f, keep, half_smooth};
+    hipLaunchKernelGGL(seg_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, seg_true, seg_pred, (long long)HW, C, k, (double *)workspace);
+    hipLaunchKernelGGL(seg_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)workspace, seg_exist, B, nblk,
+                       (long long)HW, C, weight, out);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}

@@ -20,10 +20,12 @@ def get_custom_objects():
              "SegmentationSubNet", "SqueezeExcite", "MobileSeparableConv2D", "DownSampleInput", "UpSampleOutput",
              "TrimInstances", "SemanticSmoothing", "CropAndPadMask", "CrackToInstance", "SummaryOutput",
              "IncludeMyRoad", "CalculateInstanceSize", "DrawSegmentation", "DrawInstance", "DrawBoxes", "EncodeImageContent",
-             "DecodeImageContent"]
+             "DecodeImageContent", "CalculateIOU", "AssignBoxes", "AssignMasks", "AssignSeg"]
     reg = {n: getattr(L, n) for n in names}
     reg["BackBonePreProcess"] = BackBonePreProcess
     reg["GroupNormalization"] = GroupNormalization
     from . import metrics
     reg.update({n: getattr(metrics, n) for n in metrics.__all__})
+    from . import losses
+    reg.update({n: getattr(losses, n) for n in losses.__all__})
     return reg

@@ -183,7 +183,18 @@ SIGNATURES = {
     "ml_eval_detection_metric_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "ml_eval_confusion_f32": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "ml_eval_reference_host": (C.c_int, [_vp] * 4 + [_i32, _vp, _vp] + [_i32] * 8 + [_vp] * 3),
+    "ml_train_workspace_bytes": (_i64, [_i32, _i32]),
+    "ml_train_calculate_iou_f32": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "ml_train_best_prior_f32": (C.c_int, [_vp, _vp] + [_i32] * 3 + [_vp, _vp, _vp]),
+    "ml_train_assign_boxes_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 4 + [_vp] * 4),
+    "ml_train_class_loss_f32": (C.c_int, [_vp] * 4 + [_i32] * 3 + [_f32] * 3 + [_vp] * 3),
+    "ml_train_box_loss_f32": (C.c_int, [_vp] * 3 + [_i32] * 2 + [_f32] * 4 + [_i32] + [_vp] * 4),
+    "ml_train_assign_masks": (C.c_int, [_vp] * 3 + [_i32] * 9 + [_f32, _vp, _vp]),
+    "ml_train_mask_loss_f32": (C.c_int, [_vp, _vp] + [_i32] * 5 + [_f32] * 3 + [_vp] * 3),
+    "ml_train_assign_seg": (C.c_int, [_vp] + [_i32] * 7 + [_vp, _vp]),
+    "ml_train_seg_loss_f32": (C.c_int, [_vp] * 3 + [_i32, _i64, _i32] + [_f32] * 3 + [_vp] * 3),
 }
+TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1                    # ML_TRAIN_MASK_*
 EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3     # ML_EVAL_*
 EVAL_MAX_CLASSES = 16                                  # ML_EVAL_MAX_CLASSES
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*

@@ -377,3 +377,36 @@ class DetectionProposal(Layer):
             "post_iou_threshold": self.post_iou_threshold, "nms_max_output_size": self.nms_max_output_size,
             "max_batch_size": self.max_batch_size})
         return config
+
+
+class CalculateIOU(Layer):
+    """IoU of every pair of two (cx,cy,w,h) box tables (reference :378-422): inputs = [aa_boxes [n, >=4], bb_boxes [m, >=4]]
+    -> float32 [n,m], with the reference's + 1e-5 in the denominator.  AssignBoxes, AssignMasks and DetectionIOUMetric
+    evaluate the same arithmetic inside their own kernels and never build the matrix."""
+
+    def call(self, inputs, **kwargs):
+        aa_boxes, bb_boxes = inputs[0], inputs[1]
+        return ops.calculate_iou(aa_boxes.to(torch.float32).contiguous(), bb_boxes.to(torch.float32).contiguous())
+
+
+class AssignBoxes(Layer):
+    """Ground-truth boxes -> per-prior targets (reference :589-697): inputs = [gt_boxes [B,G,6] (-1 padded), pr_boxes
+    [B,A,4]] -> (cls_true [B,A,C], loc_true [B,A,4], assign_mask [B,A,1]) float32.  The reference's rule, restated per prior
+    (include/masklab_hip.h, "Trainer forward"); pr_boxes[0] serves the whole batch, as in the reference."""
+
+    def __init__(self, num_classes, **kwargs):
+        self.num_classes = num_classes
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        gt_boxes, pr_boxes = inputs[0], inputs[1]
+        priors = pr_boxes[0] if pr_boxes.dim() == 3 else pr_boxes
+        priors = priors.contiguous().to(torch.int32)
+        gt_boxes = gt_boxes.to(torch.float32).contiguous()
+        self.last_best = ops.best_prior(gt_boxes, priors)
+        return ops.assign_boxes(gt_boxes, priors, self.num_classes, best=self.last_best)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"num_classes": self.num_classes})
+        return config

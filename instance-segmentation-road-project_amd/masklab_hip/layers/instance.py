@@ -259,3 +259,26 @@ class TrimInstances(Layer):
         config = super().get_config()
         config.update({"mold": self.mold, "max_batch_size": self.max_batch_size})
         return config
+
+
+class AssignMasks(Layer):
+    """Ground-truth masks -> per-RoI targets (reference :296-386): inputs = [roi_boxes [B,R,6], roi_masks [B,R,h,w,C],
+    gt_boxes [B,G,6], gt_masks [B,G,H,W] int8 / uint8] -> int32 [B,R,h,w]: an RoI is matched to the first ground truth of
+    its class with the highest IoU if that is >= match_iou_threshold; its target is the matched class where the bilinear
+    crop of that ground truth's mask is > 0.5 and num_classes elsewhere; unmatched and padded RoIs are num_classes."""
+
+    def __init__(self, match_iou_threshold=0.5, **kwargs):
+        self.match_iou_threshold = match_iou_threshold
+        kwargs.update({"trainable": False})
+        super().__init__(**kwargs)
+
+    def call(self, inputs, **kwargs):
+        roi_boxes, roi_masks, gt_boxes, gt_masks = inputs[0], inputs[1], inputs[2], inputs[3]
+        return ops.assign_masks(roi_boxes.contiguous(), gt_boxes.to(torch.float32).contiguous(), gt_masks.contiguous(),
+                                (int(roi_masks.shape[2]), int(roi_masks.shape[3])), int(roi_masks.shape[-1]),
+                                self.match_iou_threshold)
+
+    def get_config(self):
+        config = super().get_config()
+        config.update({"match_iou_threshold": self.match_iou_threshold})
+        return config

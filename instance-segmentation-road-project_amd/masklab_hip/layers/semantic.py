@@ -207,3 +207,12 @@ class SemanticSmoothing(Layer):
         config = super().get_config()
         config.update({"kernel_size": self.kernel_size, "weight": self.weight})
         return config
+
+
+class AssignSeg(Layer):
+    """The semantic truth at the prediction's size (reference :304-311): inputs = [seg_true [B,H,W,C] float32 / uint8,
+    seg_pred [B,h,w,C]] -> float32 [B,h,w,C] = tf.round (half to even) of ResizeLike's align_corners bilinear resize."""
+
+    def call(self, inputs, **kwargs):
+        seg_true, seg_pred = inputs[0], inputs[1]
+        return ops.assign_seg(seg_true.contiguous(), (int(seg_pred.shape[1]), int(seg_pred.shape[2])))

@@ -1776,3 +1776,170 @@ def eval_reference_host(det=None, ins=None, gt=None, pairs=None, pr_sem=None, gt
                                                   p(pr_sem), p(gt_sem), B, n, mh, mw, G, H, W, Cc, p(area), p(out_pairs),
                                                   p(out_sem)), "ml_eval_reference_host")
     return area, out_pairs, out_sem
+
+
+# ----------------------------------------------------------------------------- trainer forward (csrc/train_targets.hip)
+def _require_f32(op, *named):
+    for t, name in named:
+        _require_dev(t, name)
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{op}: `{name}` must be float32, got {t.dtype}")
+
+
+def _train_ws(B, Cc, device):
+    """The per-block partial sums of one loss call: a few hundred KiB, written in full before they are read, so a fresh
+    allocation per call (stream-ordered, like the outputs) rather than a cached workspace."""
+    return torch.empty(int(_lib.load().ml_train_workspace_bytes(int(B), int(Cc))), dtype=torch.uint8, device=device)
+
+
+def calculate_iou(aa_boxes, bb_boxes):
+    """ml_train_calculate_iou_f32 (CalculateIOU.call): float32 [n, >=4] and [m, >=4] rows of (cx, cy, w, h, ...) -> float32 [n,m]."""
+    _require_f32("calculate_iou", (aa_boxes, "aa_boxes"), (bb_boxes, "bb_boxes"))
+    if aa_boxes.dim() != 2 or bb_boxes.dim() != 2 or aa_boxes.shape[1] < 4 or bb_boxes.shape[1] < 4:
+        raise ValueError(f"calculate_iou: two [n, >=4] box tables expected, got {tuple(aa_boxes.shape)}, {tuple(bb_boxes.shape)}")
+    n, m = aa_boxes.shape[0], bb_boxes.shape[0]
+    out = torch.empty((n, m), dtype=torch.float32, device=aa_boxes.device)
+    if n and m:
+        _lib.check(_lib.load().ml_train_calculate_iou_f32(_ptr(aa_boxes), aa_boxes.shape[1], n, _ptr(bb_boxes), bb_boxes.shape[1], m,
+                                                          _ptr(out), _stream()), "ml_train_calculate_iou_f32")
+    return out
+
+
+def best_prior(gt_boxes, pr_boxes):
+    """ml_train_best_prior_f32: gt_boxes float32 [B,G,6] (-1 padded), pr_boxes int32 [A,4] -> int32 [B,G], the first index of
+    the maximum of every ground truth's IoU row (0 for a row of zeros)."""
+    _require_f32("best_prior", (gt_boxes, "gt_boxes"))
+    _require_dev(pr_boxes, "pr_boxes")
+    if gt_boxes.dim() != 3 or gt_boxes.shape[2] != 6 or pr_boxes.dtype != torch.int32 or pr_boxes.dim() != 2 or pr_boxes.shape[1] != 4:
+        raise ValueError(f"best_prior: float32 [B,G,6] boxes and an int32 [A,4] prior table expected, got {tuple(gt_boxes.shape)} and "
+                         f"{pr_boxes.dtype} {tuple(pr_boxes.shape)}")
+    B, G, _ = gt_boxes.shape
+    A = pr_boxes.shape[0]
+    if G == 0 or A == 0:
+        raise ValueError("best_prior: no ground-truth rows or no priors")
+    keys = torch.empty((B, G), dtype=torch.int64, device=gt_boxes.device)
+    best = torch.empty((B, G), dtype=torch.int32, device=gt_boxes.device)
+    with _Prof("best_prior", 0, 4 * (gt_boxes.numel() + pr_boxes.numel())):
+        _lib.check(_lib.load().ml_train_best_prior_f32(_ptr(gt_boxes), _ptr(pr_boxes), B, G, A, _ptr(keys), _ptr(best), _stream()),
+                   "ml_train_best_prior_f32")
+    return best
+
+
+def assign_boxes(gt_boxes, pr_boxes, num_classes, best=None):
+    """ml_train_assign_boxes_f32 (AssignBoxes.call) -> (cls_true [B,A,C], loc_true [B,A,4], assign_mask [B,A,1]) float32."""
+    if best is None:
+        best = best_prior(gt_boxes, pr_boxes)
+    B, G, _ = gt_boxes.shape
+    A, Cn = pr_boxes.shape[0], int(num_classes)
+    dev = gt_boxes.device
+    cls_true = torch.empty((B, A, Cn), dtype=torch.float32, device=dev)
+    loc_true = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, A, 1), dtype=torch.float32, device=dev)
+    with _Prof("assign_boxes", 0, 4 * (gt_boxes.numel() + pr_boxes.numel() + cls_true.numel() + loc_true.numel() + mask.numel())):
+        _lib.check(_lib.load().ml_train_assign_boxes_f32(_ptr(gt_boxes), _ptr(pr_boxes), _ptr(best), B, G, A, Cn, _ptr(cls_true),
+                                                         _ptr(loc_true), _ptr(mask), _stream()), "ml_train_assign_boxes_f32")
+    return cls_true, loc_true, mask
+
+
+def class_loss(cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma):
+    """ml_train_class_loss_f32 (ClassLoss.call): [B,A,C], [B,A,C], [B,A(,1)], [B,C] float32 -> float32 [B]."""
+    _require_f32("class_loss", (cls_true, "cls_true"), (cls_pred, "cls_pred"), (assign_mask, "assign_mask"), (cls_exists, "cls_exists"))
+    if cls_true.dim() != 3 or cls_true.shape != cls_pred.shape or assign_mask.numel() * cls_true.shape[2] != cls_true.numel() or \
+            tuple(cls_exists.shape) != (cls_true.shape[0], cls_true.shape[2]):
+        raise ValueError(f"class_loss: shapes {tuple(cls_true.shape)}, {tuple(cls_pred.shape)}, {tuple(assign_mask.shape)}, "
+                         f"{tuple(cls_exists.shape)} do not fit")
+    B, A, Cn = cls_true.shape
+    out = torch.empty((B,), dtype=torch.float32, device=cls_true.device)
+    ws = _train_ws(B, Cn, cls_true.device)
+    with _Prof("class_loss", 0, 4 * (2 * cls_true.numel() + assign_mask.numel())):
+        _lib.check(_lib.load().ml_train_class_loss_f32(_ptr(cls_true), _ptr(cls_pred), _ptr(assign_mask), _ptr(cls_exists), B, A, Cn,
+                                                       float(weight), float(alpha), float(gamma), _ptr(ws), _ptr(out), _stream()),
+                   "ml_train_class_loss_f32")
+    return out
+
+
+def box_loss(loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state=None):
+    """ml_train_box_loss_f32 (BoxLoss.call): [B,A,4], [B,A,4], [B,A(,1)] float32 -> float32 [B].  state: float32 [8] on the
+    device = moving_mean, moving_var, updated in place when use_adjust."""
+    _require_f32("box_loss", (loc_true, "loc_true"), (loc_pred, "loc_pred"), (assign_mask, "assign_mask"))
+    if loc_true.dim() != 3 or loc_true.shape[2] != 4 or loc_true.shape != loc_pred.shape or assign_mask.numel() * 4 != loc_true.numel():
+        raise ValueError(f"box_loss: shapes {tuple(loc_true.shape)}, {tuple(loc_pred.shape)}, {tuple(assign_mask.shape)} do not fit")
+    if use_adjust:
+        _require_f32("box_loss", (state, "state"))
+        if state.numel() != 8:
+            raise ValueError("box_loss: `state` must hold moving_mean[4] and moving_var[4]")
+    B, A, _ = loc_true.shape
+    out = torch.empty((B,), dtype=torch.float32, device=loc_true.device)
+    ws = _train_ws(B, 4, loc_true.device)
+    passes = 3 if use_adjust else 1
+    with _Prof("box_loss", 0, 4 * passes * (2 * loc_true.numel() + assign_mask.numel())):
+        _lib.check(_lib.load().ml_train_box_loss_f32(_ptr(loc_true), _ptr(loc_pred), _ptr(assign_mask), B, A, float(weight), float(momentum),
+                                                     float(1 - momentum), float(beta), int(bool(use_adjust)),
+                                                     _ptr(state if use_adjust else None), _ptr(ws), _ptr(out), _stream()),
+                   "ml_train_box_loss_f32")
+    return out
+
+
+def assign_masks(roi_boxes, gt_boxes, gt_masks, crop_hw, num_classes, threshold=0.5):
+    """ml_train_assign_masks (AssignMasks.call): roi_boxes [B,R,6], gt_boxes [B,G,6] float32, gt_masks [B,G,H,W] int8 / uint8
+    -> int32 [B,R,h,w]."""
+    _require_f32("assign_masks", (roi_boxes, "roi_boxes"), (gt_boxes, "gt_boxes"))
+    _require_bytes(gt_masks, "gt_masks")
+    B, G, H, W = gt_masks.shape
+    if roi_boxes.dim() != 3 or roi_boxes.shape[2] != 6 or roi_boxes.shape[0] != B or tuple(gt_boxes.shape) != (B, G, 6):
+        raise ValueError(f"assign_masks: shapes roi_boxes {tuple(roi_boxes.shape)} gt_boxes {tuple(gt_boxes.shape)} gt_masks "
+                         f"{tuple(gt_masks.shape)} do not fit")
+    R = roi_boxes.shape[1]
+    mh, mw = int(crop_hw[0]), int(crop_hw[1])
+    out = torch.empty((B, R, mh, mw), dtype=torch.int32, device=roi_boxes.device)
+    dt = _lib.TRAIN_MASK_I8 if gt_masks.dtype == torch.int8 else _lib.TRAIN_MASK_U8
+    with _Prof("assign_masks", 0, 4 * out.numel()):
+        _lib.check(_lib.load().ml_train_assign_masks(_ptr(roi_boxes), _ptr(gt_boxes), _ptr(gt_masks), dt, B, R, G, H, W, mh, mw,
+                                                     int(num_classes), float(threshold), _ptr(out), _stream()), "ml_train_assign_masks")
+    return out
+
+
+def mask_loss(mask_true, mask_pred, weight, label_smoothing):
+    """ml_train_mask_loss_f32 (MaskLoss.call): mask_true int32 [B,R,h,w], mask_pred float32 [B,R,h,w,C] -> float32 [B]."""
+    _require_dev(mask_true, "mask_true")
+    _require_f32("mask_loss", (mask_pred, "mask_pred"))
+    if mask_true.dtype != torch.int32 or mask_pred.dim() != 5 or tuple(mask_true.shape) != tuple(mask_pred.shape[:4]):
+        raise ValueError(f"mask_loss: int32 [B,R,h,w] targets and float32 [B,R,h,w,C] predictions expected, got {mask_true.dtype} "
+                         f"{tuple(mask_true.shape)} and {tuple(mask_pred.shape)}")
+    B, R, mh, mw, Cn = mask_pred.shape
+    roi_loss = torch.empty((B, R), dtype=torch.float32, device=mask_pred.device)
+    out = torch.empty((B,), dtype=torch.float32, device=mask_pred.device)
+    with _Prof("mask_loss", 0, 8 * mask_true.numel()):
+        _lib.check(_lib.load().ml_train_mask_loss_f32(_ptr(mask_true), _ptr(mask_pred), B, R, mh, mw, Cn, float(weight),
+                                                      float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(roi_loss), _ptr(out),
+                                                      _stream()), "ml_train_mask_loss_f32")
+    return out
+
+
+def assign_seg(gt_seg, out_hw):
+    """ml_train_assign_seg (AssignSeg.call): gt_seg [B,H,W,C] float32 / uint8 -> float32 [B,oh,ow,C], rounded half to even."""
+    _require_dev(gt_seg, "gt_seg")
+    if gt_seg.dtype not in (torch.float32, torch.uint8) or gt_seg.dim() != 4:
+        raise RuntimeError(f"assign_seg: a float32 or uint8 [B,H,W,C] map expected, got {gt_seg.dtype} {tuple(gt_seg.shape)}")
+    B, H, W, Cn = gt_seg.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    out = torch.empty((B, oh, ow, Cn), dtype=torch.float32, device=gt_seg.device)
+    with _Prof("assign_seg", 0, 4 * out.numel() + gt_seg.numel() * gt_seg.element_size()):
+        _lib.check(_lib.load().ml_train_assign_seg(_ptr(gt_seg), _EVAL_DTYPE[gt_seg.dtype], B, H, W, Cn, oh, ow, _ptr(out), _stream()),
+                   "ml_train_assign_seg")
+    return out
+
+
+def seg_loss(seg_true, seg_pred, seg_exist, weight, label_smoothing):
+    """ml_train_seg_loss_f32 (SegLoss.call): seg_true, seg_pred [B,H,W,C], seg_exist [B,C] float32 -> float32 [B]."""
+    _require_f32("seg_loss", (seg_true, "seg_true"), (seg_pred, "seg_pred"), (seg_exist, "seg_exist"))
+    if seg_true.dim() != 4 or seg_true.shape != seg_pred.shape or tuple(seg_exist.shape) != (seg_true.shape[0], seg_true.shape[3]):
+        raise ValueError(f"seg_loss: shapes {tuple(seg_true.shape)}, {tuple(seg_pred.shape)}, {tuple(seg_exist.shape)} do not fit")
+    B, H, W, Cn = seg_true.shape
+    out = torch.empty((B,), dtype=torch.float32, device=seg_true.device)
+    ws = _train_ws(B, Cn, seg_true.device)
+    with _Prof("seg_loss", 0, 8 * seg_true.numel()):
+        _lib.check(_lib.load().ml_train_seg_loss_f32(_ptr(seg_true), _ptr(seg_pred), _ptr(seg_exist), B, H * W, Cn, float(weight),
+                                                     float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(ws), _ptr(out),
+                                                     _stream()), "ml_train_seg_loss_f32")
+    return out

@@ -3,8 +3,9 @@ build_backbone_network :19-37, build_detection_network :40-112, build_instance_n
 build_semantic_network :160-198, construct_inference_network :420-495, find_layer_name :646-649,
 and the deploy wrapper of load_masklab_inference_model_from_h5 :598-643 (DeployModel below).
 Same function names, argument meaning and return structure; the returned model runs eagerly on
-the MI355X kernels.  Training-only pieces (construct_trainer_network, losses, dataset) are out of
-scope of the accelerated path.
+the MI355X kernels.  construct_trainer_network :223-395 is restated FORWARD ONLY (TrainerModel: target assignment,
+the four losses and the metrics of a batch with ground truth); backward passes, optimizers and the dataset stay out of
+scope.
 """
 import numpy as np
 import torch
@@ -12,7 +13,8 @@ import torch
 from . import backbone
 from . import keras_like as K
 from .config import ModelConfiguration
-from .layers import (ASPPNetwork, BoxRegressionSubNet, ClassificationSubNet, CropAndPadMask, DetectionProposal,
+from .layers import (ASPPNetwork, AssignBoxes, AssignMasks, AssignSeg, BoxRegressionSubNet, ClassificationSubNet, CropAndPadMask,
+                     DetectionProposal,
                      DownSampleInput, DrawBoxes, DrawInstance, DrawSegmentation, EncodeImageContent, SummaryOutput,
                      FeaturePyramid, MaskDistribute, MaskSubNet, PriorLayer, PyramidRoiAlign, ResizeLike,
                      RestoreBoxes, SegmentationSubNet, SemanticSmoothing, TrimInstances, UpSampleOutput)
@@ -94,6 +96,32 @@ def build_semantic_network(configuration: ModelConfiguration):
     return aspp_subnet, seg_subnet
 
 
+def build_network_shapes(configuration, backbone_network, detection_networks, instance_networks, semantic_networks):
+    """Propagate the symbolic shapes through the backbone and the head groups so that every weight spec exists (no GPU
+    involved).  The inference and the trainer model share the layer objects; building them again changes nothing."""
+    bb = backbone_network
+    shapes = bb.output_shapes if bb.built else bb.build((None, None, None, 3))
+    by_name = dict(zip(bb.output_names, shapes))
+    if detection_networks is not None:
+        det_config = configuration.detection
+        _, fpn, cls, loc = detection_networks
+        fpn_in = [by_name[n] for n in bb.output_names if n in det_config.feature_pyramid_inputs]
+        rest = [by_name[n] for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
+        feats = fpn.build(fpn_in) + rest
+        cls.build(feats)
+        loc.build(feats)
+        if instance_networks is not None:
+            ins = configuration.instance
+            mask = instance_networks[3]
+            ch, cw = ins.crop_size
+            mask.build([(None, None, ch, cw, f[-1]) for f in feats[:ins.max_k + 1]])
+    if semantic_networks is not None:
+        seg_config = configuration.semantic
+        aspp, seg = semantic_networks
+        a = aspp.build(by_name[seg_config.aspp_input_name])
+        seg.build([a, by_name[seg_config.skip_input_name]])
+
+
 class InferenceModel(K.Layer):
     """The Keras functional `Model(images -> [cls_pred, loc_pred, roi_boxes, roi_masks, seg_pred])`
     of reference :420-495, executed eagerly.  Output list shrinks like the reference when a head
@@ -167,27 +195,8 @@ class InferenceModel(K.Layer):
         return out
 
     def _build_shapes(self):
-        bb = self.backbone_network
-        shapes = bb.output_shapes if bb.built else bb.build((None, None, None, 3))
-        by_name = dict(zip(bb.output_names, shapes))
-        if self.detection_networks is not None:
-            det_config = self.configuration.detection
-            _, fpn, cls, loc = self.detection_networks
-            fpn_in = [by_name[n] for n in bb.output_names if n in det_config.feature_pyramid_inputs]
-            rest = [by_name[n] for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
-            feats = fpn.build(fpn_in) + rest
-            cls.build(feats)
-            loc.build(feats)
-            if self.instance_networks is not None:
-                ins = self.configuration.instance
-                mask = self.instance_networks[3]
-                ch, cw = ins.crop_size
-                mask.build([(None, None, ch, cw, f[-1]) for f in feats[:ins.max_k + 1]])
-        if self.semantic_networks is not None:
-            seg_config = self.configuration.semantic
-            aspp, seg = self.semantic_networks
-            a = aspp.build(by_name[seg_config.aspp_input_name])
-            seg.build([a, by_name[seg_config.skip_input_name]])
+        build_network_shapes(self.configuration, self.backbone_network, self.detection_networks, self.instance_networks,
+                             self.semantic_networks)
         self.built = True
 
     # ---- weights
@@ -539,21 +548,219 @@ def construct_inference_network(configuration: ModelConfiguration, backbone_netw
                           semantic_networks=semantic_networks, instance_networks=instance_networks)
 
 
+class TrainerModel(K.Layer):
+    """The Keras functional `Model([images, gt_boxes, gt_boxes_exist, gt_masks, gt_seg, gt_seg_exist] -> losses and metrics)`
+    of reference :223-395, FORWARD ONLY and executed eagerly (no hipGraph, no fixed-capacity stage 2): what
+    `fit_generator(validation_data=...)` evaluates to report a checkpoint's validation losses.  The backbone and head layers
+    are the OBJECTS the inference model holds, as in the reference; the assignment, loss and metric layers are the model's
+    own.  Every output is float32 [B]; the lists shrink like the reference's when a head group is None.
+    `last_forward` keeps the intermediate tensors of the last call."""
+
+    METRIC_NAMES = ['other_road_iou_metric', 'my_road_metric', 'crack_iou_metric']
+
+    def __init__(self, configuration, backbone_network, detection_networks=None, semantic_networks=None,
+                 instance_networks=None, name='trainer'):
+        super().__init__(name=name)
+        from .losses import BoxLoss, ClassLoss, MaskLoss, SegLoss
+        from .metrics import ClassBinaryIOU, DetectionIOUMetric
+        config = configuration.loss
+        self.configuration = configuration
+        self.backbone_network = backbone_network
+        self.detection_networks = detection_networks
+        self.semantic_networks = semantic_networks
+        self.instance_networks = instance_networks if detection_networks is not None else None
+        self.input_names = ['images']
+        self.output_names = []
+        own = []
+        if detection_networks is not None:
+            det_config = configuration.detection
+            num_classes = len(configuration.dataset.instance_labels)
+            self.input_names += ['gt_boxes', 'gt_boxes_exist']
+            self.assign_boxes = AssignBoxes(num_classes=num_classes)
+            self.class_loss = ClassLoss(weight=config.cls_loss_weight, alpha=config.cls_loss_alpha,
+                                        gamma=config.cls_loss_gamma, name='class_loss')
+            self.box_loss = BoxLoss(weight=config.box_loss_weight, momentum=config.box_loss_momentum,
+                                    beta=config.box_loss_beta, use_adjust=config.box_loss_use_adjust, name='box_loss')
+            self.metric_restore = RestoreBoxes()
+            self.metric_proposal = DetectionProposal(                                  # config.detection.* (:295-300)
+                min_confidence=det_config.min_confidence, nms_iou_threshold=det_config.nms_iou_threshold,
+                post_iou_threshold=det_config.post_iou_threshold, nms_max_output_size=det_config.nms_max_output_size,
+                max_batch_size=configuration.train.max_batch_size)
+            self.detection_metric = DetectionIOUMetric()
+            self.output_names += ['class_loss', 'box_loss', 'detection_precision_metric', 'detection_recall_metric',
+                                  'detection_fmeasure_metric']
+            own += [self.assign_boxes, self.class_loss, self.box_loss, self.metric_restore, self.metric_proposal,
+                    self.detection_metric]
+            if self.instance_networks is not None:
+                self.input_names.append('gt_masks')
+                self.loss_proposal = DetectionProposal(                                # config.loss.* (:314-319)
+                    min_confidence=config.min_confidence, nms_iou_threshold=config.nms_iou_threshold,
+                    post_iou_threshold=config.post_iou_threshold, nms_max_output_size=config.nms_max_output_size,
+                    max_batch_size=configuration.train.max_batch_size)
+                self.assign_masks = AssignMasks()
+                self.mask_loss = MaskLoss(weight=config.mask_loss_weight,
+                                          label_smoothing=config.mask_loss_label_smoothing, name='mask_loss')
+                self.output_names.append('mask_loss')
+                own += [self.loss_proposal, self.assign_masks, self.mask_loss]
+        if semantic_networks is not None:
+            if len(configuration.dataset.semantic_labels) != len(self.METRIC_NAMES):
+                raise ValueError("the trainer network unpacks ClassBinaryIOU into three metrics (reference :385-391): it needs "
+                                 "three semantic labels")
+            self.input_names += ['gt_seg', 'gt_seg_exist']
+            self.assign_seg = AssignSeg()
+            self.seg_loss = SegLoss(weight=config.seg_loss_weight, label_smoothing=config.seg_loss_label_smoothing,
+                                    name='seg_loss')
+            self.class_iou = ClassBinaryIOU(0.5, name='class_iou_metric')
+            self.output_names += ['seg_loss'] + self.METRIC_NAMES
+            own += [self.assign_seg, self.seg_loss, self.class_iou]
+        self.layers = [backbone_network]
+        for grp in (self.detection_networks, self.instance_networks, self.semantic_networks):
+            if grp is not None:
+                self.layers += list(grp)
+        self.layers += own
+        self.device = None
+        self.last_forward = None
+        build_network_shapes(configuration, backbone_network, self.detection_networks, self.instance_networks,
+                             self.semantic_networks)
+        self.built = True
+
+    # ---- structure and weights (the surface of InferenceModel)
+    def get_layer(self, name):
+        for l in self.layers:
+            if l.name == name:
+                return l
+        raise ValueError(f"No such layer: {name}")
+
+    def children(self):
+        return self.layers
+
+    def weight_specs(self):
+        out = {}
+        for l in self.layers:
+            out.update(l.weight_specs())
+        return out
+
+    def init_weights(self, seed=0):
+        return K.init_weights(self.weight_specs(), seed)
+
+    def load_weights(self, weights, device="cuda"):
+        """Load every layer, the shared ones included.  An inference model built beside this one has its own
+        `load_weights` (it also drops its captured graphs); `box_loss/moving_mean` and `box_loss/moving_var` are optional."""
+        self.device = torch.device(device)
+        for l in self.layers:
+            l.load_weights(weights, self.device)
+        return self
+
+    # ---- forward (reference :233-391)
+    def _named_inputs(self, inputs):
+        if isinstance(inputs, dict):
+            missing = [n for n in self.input_names if n not in inputs]
+            if missing:
+                raise ValueError(f"TrainerModel: inputs {missing} are missing")
+            return {n: inputs[n] for n in self.input_names}
+        inputs = list(inputs)
+        if len(inputs) != len(self.input_names):
+            raise ValueError(f"TrainerModel: {len(self.input_names)} inputs expected ({self.input_names}), got {len(inputs)}")
+        return dict(zip(self.input_names, inputs))
+
+    def _dev(self, t, dtype=None):
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.ascontiguousarray(t))
+        t = t.to(self.device)
+        if dtype is not None and t.dtype != dtype:
+            t = t.to(dtype)
+        return t.contiguous()
+
+    def call(self, inputs, **kwargs):
+        if self.device is None:
+            raise RuntimeError("TrainerModel: call load_weights(weights, device) first")
+        cfg = self.configuration
+        x = self._named_inputs(inputs)
+        images = self._dev(x['images'])
+        bb = self.backbone_network
+        by_name = dict(zip(bb.output_names, bb(images)))
+        fw, outputs = {}, []
+        if self.detection_networks is not None:
+            det_config = cfg.detection
+            prior_subnet, fpn_subnet, cls_subnet, loc_subnet = self.detection_networks
+            pr_boxes = prior_subnet(images)
+            fpn_inputs = [by_name[n] for n in bb.output_names if n in det_config.feature_pyramid_inputs]
+            without_fpn = [by_name[n] for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
+            feature_outputs = fpn_subnet(fpn_inputs) + without_fpn
+            cls_pred = cls_subnet(feature_outputs)
+            loc_pred = loc_subnet(feature_outputs)
+            gt_boxes = self._dev(x['gt_boxes'], torch.float32)
+            gt_boxes_exist = self._dev(x['gt_boxes_exist'], torch.float32)
+            cls_true, loc_true, assign_mask = self.assign_boxes([gt_boxes, pr_boxes])
+            outputs += [self.class_loss([cls_true, cls_pred, assign_mask, gt_boxes_exist]),
+                        self.box_loss([loc_true, loc_pred, assign_mask])]
+            # The metric's proposals stay at capacity (-1 padded): DetectionIOUMetric counts rows, so the reference's
+            # trimmed tensor gives the same numbers, and nothing is read by the host.
+            restored_boxes = self.metric_restore([loc_pred, pr_boxes])
+            proposed, _, _ = self.metric_proposal.propose_fixed(cls_pred, restored_boxes)
+            outputs += list(self.detection_metric([proposed, gt_boxes]))
+            fw.update(cls_pred=cls_pred, loc_pred=loc_pred, pr_boxes=pr_boxes, proposed=proposed, cls_true=cls_true,
+                      loc_true=loc_true, assign_mask=assign_mask, best_prior=self.assign_boxes.last_best)
+            if self.instance_networks is not None:
+                restore_layer, distribute_layer, pyramid_roi_align, mask_subnet = self.instance_networks
+                restored_boxes = restore_layer([loc_pred, pr_boxes])
+                proposed_loss, _, _ = self.loss_proposal.propose_fixed(cls_pred, restored_boxes)
+                # gt_boxes' -1 rows sit in the MIDDLE of this list: the distribute kernel drops every row with cx == -1
+                # wherever it is (csrc/detect.hip), and the crops are taken from the per-level slot lists it writes
+                chosen_boxes = torch.cat([gt_boxes, proposed_loss], dim=1)              # Concatenate(axis=1)
+                dist_boxes = distribute_layer(chosen_boxes)
+                roi_fmaps, roi_boxes = pyramid_roi_align([feature_outputs[:cfg.instance.max_k + 1], dist_boxes, images])
+                roi_masks = mask_subnet(roi_fmaps)
+                gt_masks = self._dev(x['gt_masks'])
+                match_gt_masks = self.assign_masks([roi_boxes, roi_masks, gt_boxes, gt_masks])
+                outputs.append(self.mask_loss([match_gt_masks, roi_masks]))
+                fw.update(proposed_loss=proposed_loss, roi_boxes=roi_boxes, roi_masks=roi_masks, match_gt_masks=match_gt_masks)
+        if self.semantic_networks is not None:
+            sem_config = cfg.semantic
+            aspp_subnet, seg_subnet = self.semantic_networks
+            seg_pred = seg_subnet([aspp_subnet(by_name[sem_config.aspp_input_name]), by_name[sem_config.skip_input_name]])
+            gt_seg = self._dev(x['gt_seg'])
+            gt_seg_exist = self._dev(x['gt_seg_exist'], torch.float32)
+            seg_assigned = self.assign_seg([gt_seg, seg_pred])
+            outputs.append(self.seg_loss([seg_assigned, seg_pred, gt_seg_exist]))
+            outputs += list(self.class_iou([seg_assigned, seg_pred]))
+            fw.update(seg_pred=seg_pred, seg_assigned=seg_assigned)
+        self.last_forward = fw
+        return outputs
+
+    def predict(self, inputs, **kwargs):
+        """Keras `Model.predict` with named outputs: {output name: float32 [B] ndarray}."""
+        outs = self.call(inputs, **kwargs)
+        torch.cuda.synchronize(self.device)
+        return {n: o.cpu().numpy() for n, o in zip(self.output_names, outs)}
+
+
+def construct_trainer_network(configuration: ModelConfiguration, backbone_network, detection_networks=None,
+                              semantic_networks=None, instance_networks=None):
+    """Same signature as reference :223-227; the returned model is forward only."""
+    return TrainerModel(configuration, backbone_network, detection_networks=detection_networks,
+                        semantic_networks=semantic_networks, instance_networks=instance_networks)
+
+
 def construct_masklab_networks(config: ModelConfiguration, with_trainer=False):
-    """Reference :201-220 returns (trainer, inference); the training graph is outside the
-    accelerated path, so the first element is None."""
+    """Reference :201-220 returns (trainer, inference).  The trainer network (forward only: losses and metrics of a
+    batch with ground truth) is built on request; by default the first element is None."""
     K.clear_session()
     backbone_network = build_backbone_network(config)
     detection_networks = build_detection_network(config)
     instance_networks = build_instance_network(config)
     semantic_networks = build_semantic_network(config)
-    if with_trainer:
-        raise NotImplementedError("construct_trainer_network is training-only (out of the hot-path scope)")
     inference = construct_inference_network(configuration=config, backbone_network=backbone_network,
                                             detection_networks=detection_networks,
                                             semantic_networks=semantic_networks,
                                             instance_networks=instance_networks)
-    return None, inference
+    trainer = None
+    if with_trainer:                      # after the inference model, whose automatic layer names stay what they were
+        trainer = construct_trainer_network(configuration=config, backbone_network=backbone_network,
+                                            detection_networks=detection_networks,
+                                            semantic_networks=semantic_networks,
+                                            instance_networks=instance_networks)
+    return trainer, inference
 
 
 class DeployModel(K.Layer):

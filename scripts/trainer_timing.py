@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""The trainer forward's detection tail -- best prior per ground truth, AssignBoxes, ClassLoss, BoxLoss (csrc/train_targets.hip)
+-- at 8 x 1024 x 1024 (A = 327 360 priors, G = 32 ground truths per image, 5 classes), three numbers:
+
+  (a) kernels  the four ops through masklab_hip.ops, predictions and ground truth already on the device;
+  (b) torch    the same arithmetic written with torch tensor ops on the device the way the reference writes it: the
+               [B,G,A] IoU matrix, nonzero() index lists (each a host read, like tf.where's dynamic shape), index_put
+               scatters, one-hot, elementwise losses.  Not the product path: a yardstick only;
+  (c) floor    the bytes the kernels of (a) must read and write (counted from the shapes, pass by pass: BoxLoss with
+               use_adjust reads its inputs three times) over the sustained copy rate of profiles/r03_peaks.json.
+
+(a) and (b) alternate in one process after a warm-up, a device synchronise closing every timing; median, min, max and the
+inter-quartile range as the spread.  The losses of the two must agree to rtol 1e-3 (float32 sums in (b), and index_put leaves the winner among duplicate labels open).  One JSON line.
+
+Usage (GPU box):  timeout 600 python scripts/trainer_timing.py [--steps 20] [--warmup 3] [--batch 8] [--size 1024]"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "instance-segmentation-road-project_amd"), os.path.join(ROOT, "scripts")]
+
+from jpeg_encode_timing import alternate, stats  # noqa: E402
+
+C, G = 5, 32
+LOSS = dict(cls_weight=300., alpha=.25, gamma=2., box_weight=1., momentum=.9, beta=.11)
+
+
+def ground_truth(B, size, pr, rng):
+    import numpy as np
+    gt = np.full((B, G, 6), -1, np.float32)
+    for b in range(B):
+        n = int(rng.integers(G // 2, G + 1))
+        side = np.exp(rng.uniform(np.log(16), np.log(size / 2), (n, 2)))
+        gt[b, :n] = np.concatenate([rng.uniform(0, size, (n, 2)), side, rng.integers(0, C, (n, 1)), np.ones((n, 1))], axis=1)
+        gt[b, 0, :4] = pr[rng.integers(0, len(pr))]                       # an exact hit
+    return gt
+
+
+def torch_tail(gt, pr, cls_pred, loc_pred, exist, state):
+    """AssignBoxes + ClassLoss + BoxLoss(use_adjust) in torch tensor ops, as the reference's graph is written."""
+    import torch
+    B, A = gt.shape[0], pr.shape[0]
+    prf = pr.float()
+    g = gt[..., :4].reshape(-1, 4)
+    areas = (prf[:, 2] * prf[:, 3])[None, :] + (g[:, 2] * g[:, 3])[:, None]
+    gy1, gx1, gy2, gx2 = (g[:, 1] - g[:, 3] / 2)[:, None], (g[:, 0] - g[:, 2] / 2)[:, None], (g[:, 1] + g[:, 3] / 2)[:, None], \
+        (g[:, 0] + g[:, 2] / 2)[:, None]
+    py1, px1, py2, px2 = (prf[:, 1] - prf[:, 3] / 2)[None], (prf[:, 0] - prf[:, 2] / 2)[None], (prf[:, 1] + prf[:, 3] / 2)[None], \
+        (prf[:, 0] + prf[:, 2] / 2)[None]
+    inter = (torch.minimum(px2, gx2) - torch.maximum(px1, gx1)).clamp_min(0) * (torch.minimum(py2, gy2) - torch.maximum(py1, gy1)).clamp_min(0)
+    iou = (inter / (areas - inter + 1e-5)).view(B, G, A) * (gt[..., 0] != -1).float()[..., None]
+    match = torch.nonzero(iou >= 0.5)
+    best = iou.view(-1, A).argmax(dim=1)
+    bs, gs = torch.meshgrid(torch.arange(B, device=gt.device), torch.arange(G, device=gt.device), indexing="ij")
+    best_rows = torch.stack([bs.reshape(-1), gs.reshape(-1), best], dim=1)
+    match = torch.cat([match, best_rows[torch.nonzero(gt[..., 5].reshape(-1) > 0)[:, 0]]], dim=0)
+    b_i, g_i, p_i = match.unbind(1)
+    cls = torch.full((B, A), -1., device=gt.device)
+    cls[b_i, p_i] = gt[b_i, g_i, 4]
+    cls = torch.where(cls != -1, cls, torch.full_like(cls, C))
+    one_hot = torch.nn.functional.one_hot(cls.long(), C + 1).float()
+    ignore = torch.nonzero((iou < 0.5) & (iou >= 0.4))
+    ignore_mask = torch.zeros((B, A), device=gt.device).index_put_((ignore[:, 0], ignore[:, 2]), torch.ones(len(ignore), device=gt.device),
+                                                                   accumulate=True)
+    mask = torch.where(ignore_mask > 0, torch.full_like(ignore_mask, -1), one_hot[..., -1])
+    p, q = prf[p_i], gt[b_i, g_i, :4]
+    hat = torch.stack([(q[:, 0] - p[:, 0]) / p[:, 2], (q[:, 1] - p[:, 1]) / p[:, 3], torch.log(q[:, 2] / p[:, 2]), torch.log(q[:, 3] / p[:, 3])], dim=1)
+    loc_true = torch.zeros((B, A, 4), device=gt.device).index_put_((b_i, p_i), hat, accumulate=True)
+    cls_true = one_hot[..., :C]
+    # ClassLoss
+    neg, pos, keep = (mask == 1).float(), (mask == 0).float(), (mask != -1).float()
+    pc = cls_pred.clamp(1e-7, 1 - 1e-7)
+    pt = torch.where(cls_true == 1, pc, 1 - pc)
+    focal = LOSS["alpha"] * (-torch.pow(1 - pt, LOSS["gamma"]) * torch.log(pt)) * exist[:, None, :]
+    class_loss = LOSS["cls_weight"] * (keep[..., None] * focal).sum(dim=(1, 2)) / ((pos + neg).sum(dim=1) + 1e-7)
+    # BoxLoss, use_adjust
+    offsets = (loc_true - loc_pred).abs() * pos[..., None]
+    mean = offsets.mean(dim=(0, 1))
+    var = ((offsets - mean) ** 2).mean(dim=(0, 1))
+    state[:4] = state[:4] * LOSS["momentum"] + mean * (1 - LOSS["momentum"])
+    state[4:] = state[4:] * LOSS["momentum"] + var * (1 - LOSS["momentum"])
+    beta = (state[:4] - state[4:]).clamp(1e-3, LOSS["beta"])
+    d = loc_true - loc_pred
+    l1, l2 = d.abs() - 0.5 * beta, 0.5 * d ** 2 / beta
+    box = torch.where(l1 < beta, l2, l1).mean(dim=-1)
+    box_loss = LOSS["box_weight"] * (pos * box).sum(dim=1) / (pos.sum(dim=1) + 1e-7)
+    return class_loss, box_loss
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, default=1024)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from masklab_hip import ModelConfiguration, ops
+    from masklab_hip import retinamasklab as R
+    if not torch.cuda.is_available():
+        raise SystemExit("trainer_timing: no GPU -- nothing is measured without one")
+    B, size = args.batch, args.size
+    rng = np.random.default_rng(size)
+    pr_host = R.build_detection_network(ModelConfiguration())[0].prior.anchors(size, size, 'same')
+    A = len(pr_host)
+    gt = torch.from_numpy(ground_truth(B, size, pr_host, rng)).cuda()
+    pr = torch.from_numpy(pr_host).cuda()
+    cls_pred = torch.from_numpy(rng.uniform(0, 1, (B, A, C)).astype(np.float32)).cuda()
+    loc_pred = torch.from_numpy(rng.normal(size=(B, A, 4)).astype(np.float32)).cuda()
+    exist = torch.ones((B, C), device="cuda")
+    fresh = torch.tensor([LOSS["beta"]] * 4 + [0.] * 4, device="cuda")
+    kept = {}
+
+    def kernels():
+        state = fresh.clone()
+        cls_true, loc_true, mask = ops.assign_boxes(gt, pr, C, best=ops.best_prior(gt, pr))
+        kept["kernels"] = (ops.class_loss(cls_true, cls_pred, mask, exist, LOSS["cls_weight"], LOSS["alpha"], LOSS["gamma"]),
+                           ops.box_loss(loc_true, loc_pred, mask, LOSS["box_weight"], LOSS["momentum"], LOSS["beta"], True, state))
+
+    def torch_ops():
+        kept["torch"] = torch_tail(gt, pr, cls_pred, loc_pred, exist, fresh.clone())
+
+    t = alternate({"kernels": kernels, "torch": torch_ops}, args.steps, args.warmup)
+    k, r = stats(t["kernels"]), stats(t["torch"])
+    same = all(torch.allclose(a, b, rtol=1e-3, atol=1e-6) for a, b in zip(kept["kernels"], kept["torch"]))
+    # bytes the kernels must move, pass by pass (gt and the [B,G] tables are negligible and left out)
+    n = B * A
+    passes = {"best_prior": 16 * A, "assign_boxes": 16 * A + 4 * n * (C + 4 + 1), "class_loss": 4 * n * (2 * C + 1),
+              "box_loss (mean, variance, loss)": 3 * 4 * n * (4 + 4 + 1)}
+    with open(os.path.join(ROOT, "profiles", "r03_peaks.json")) as f:
+        rate = json.load(f)["copy_global_x4"]["read_plus_write_GBs"]
+    floor_ms = sum(passes.values()) / (rate * 1e9) * 1e3
+    print(json.dumps({"leg": "best prior + AssignBoxes + ClassLoss + BoxLoss(use_adjust)", "shape": f"{B}x{size}x{size}", "priors": A,
+                      "ground_truths": G, "classes": C, "kernels": k, "torch_ops": r,
+                      "torch_minus_kernels_ms": round(r["ms_median"] - k["ms_median"], 3),
+                      "kernels_faster_by_more_than_the_spread": bool(k["ms_median"] + k["ms_iqr"] < r["ms_median"] - r["ms_iqr"]),
+                      "losses_agree": bool(same), "bytes": passes, "bytes_total": int(sum(passes.values())),
+                      "copy_rate_GBs": rate, "floor_ms": round(floor_ms, 4),
+                      "kernels_over_floor": round(k["ms_median"] / floor_ms, 2)}), flush=True)
+    assert same, "the kernels' losses differ from the torch tensor-op formulation"
+
+
+if __name__ == "__main__":
+    main()
