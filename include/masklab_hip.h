@@ -922,6 +922,36 @@ int ml_train_assign_seg(const void *gt_seg, int32_t dtype, int32_t B, int32_t H,
 int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
                           float weight, float keep, float half_smooth, void *workspace, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Generator resizes: the cv2.resize(x, (ow, oh)) calls of the reference's MaskLabGenerator (engine/utils/generator/
+ * masklab.py), default INTER_LINEAR, on uint8 planes (csrc/cv_resize.hip).  OpenCV parity is unpinned: the arithmetic
+ * below is restated from OpenCV's plain C++ path and held to tests/generator_ref.py, not to a run of OpenCV.
+ *   axis      as in "Evaluation": scale = 1 / (dst / src) in float64; f = float32((d + 0.5) * scale - 0.5); s = floor(f);
+ *             f -= s in float32; s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0; taps (s, min(s + 1, src - 1))
+ *             with float32 weights (1.f - f, f).
+ *   uint8     fixed point: every weight becomes (short)rint(w * 2048), half to even, each on its own; per source row
+ *             r = S[x0] * a0 + S[x1] * a1 in int32; dst = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2.
+ *   float64   weights widened to double; h = S[x0] * wx0 + S[x1] * wx1 per source row, value = h0 * wy0 + h1 * wy1, FP
+ *             contraction off; the kernel reads the uint8 source, applies np.round (rint, half to even) and writes the
+ *             integer 0..255 as float32 or uint8 (both lossless).
+ *   exactly 2x on BOTH axes (H == 2 * oh and W == 2 * ow): cv::resize switches to INTER_AREA -- uint8
+ *             (S00 + S01 + S10 + S11 + 2) >> 2, float64 (S00 + S01 + S10 + S11) * 0.25, then the rounding.
+ * src [planes,H,W,C] -> dst [planes,oh,ow,C], any alignment, plane offsets 64-bit; H*W*C < 2^31, oh*ow*C < 2^31,
+ * oh <= 65535; planes == 0 is a no-op.  No workspace, no atomics, no host read; every output element is written once.
+ * ------------------------------------------------------------------------------------------- */
+enum { ML_CV_RESIZE_U8 = 0, ML_CV_RESIZE_ROUND_U8 = 1, ML_CV_RESIZE_ROUND_F32 = 2 };
+/* The uint8 path.  With skip_minus_one a plane whose first byte is 0xFF (int8 -1, the reference's `mask[0,0] == -1.`) is
+ * filled with 0xFF and nothing else of it is read.                                                                    */
+int ml_cv_resize_linear_u8(const void *src, void *dst, int64_t planes, int32_t H, int32_t W, int32_t C, int32_t oh, int32_t ow,
+                           int32_t skip_minus_one, void *stream);
+/* The float64 path plus np.round; dst is float32 (dst_is_f32, 4-byte aligned) or uint8.                               */
+int ml_cv_resize_linear_round_u8(const void *src, void *dst, int32_t dst_is_f32, int64_t planes, int32_t H, int32_t W, int32_t C,
+                                 int32_t oh, int32_t ow, void *stream);
+/* Host.  The kernels' per-thread code in CPU loops, both pointers in host memory; mode = ML_CV_RESIZE_*.  For checking the
+ * arithmetic without a device, and the generator's device="cpu" path -- not a product path.                           */
+int ml_cv_resize_reference_host(const void *src, void *dst, int32_t mode, int64_t planes, int32_t H, int32_t W, int32_t C,
+                                int32_t oh, int32_t ow, int32_t skip_minus_one);
+
 #ifdef __cplusplus
 }
 #endif

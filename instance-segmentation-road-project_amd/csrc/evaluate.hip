@@ -11,6 +11,7 @@
 //     the mask-area, mask-pair and semantic bodies in CPU loops, so the CPU tests hold this very code to NumPy.
 #include "common.h"
 #include "box_iou.h"
+#include "cv_resize.h"
 
 #pragma clang fp contract(off)
 
@@ -212,19 +213,10 @@ __host__ __device__ inline Box pred_box(const int32_t *d, int H, int W) {
     return {sx, sy, ex - sx, ey - sy};
 }
 
-struct Tap { int s0, s1; float w0, w1; };
-
-__host__ __device__ inline double axis_scale(int dst, int src) { return 1.0 / ((double)dst / (double)src); }
-
-// one axis of cv2.resize(INTER_LINEAR): destination index d -> two source indices and their float32 weights
-__host__ __device__ inline Tap axis_tap(int d, double scale, int src) {
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { s = 0; f = 0.f; }
-    if (s >= src - 1) { s = src - 1; f = 0.f; }
-    return {s, s + 1 < src ? s + 1 : src - 1, 1.f - f, f};
-}
+// one axis of cv2.resize(INTER_LINEAR): cv_resize.h, shared with cv_resize.hip
+using cvr::Tap;
+using cvr::axis_scale;
+using cvr::axis_tap;
 
 // m: the h x w mask, already max(., 0).  Horizontal taps inside each of the two source rows, then the two rows.
 __host__ __device__ inline bool pred_pixel(const int32_t *m, int mw, const Tap &ty, const Tap &tx) {

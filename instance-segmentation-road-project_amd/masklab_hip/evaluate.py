@@ -140,3 +140,29 @@ def evaluate(model, dataset, batch_size=1):
         pr_detections, pr_instances, pr_semantics = model(targets['images'])
         ev.update(pr_detections, pr_instances, pr_semantics, targets['detection'], targets['instance'], targets['semantic'])
     return ev.result()
+
+
+def validate(trainer, generator, steps=None):
+    """What `fit_generator(validation_data=generator)` reports for a trainer network (road_project/train.py:98-101: every
+    output is a metric with aggregation 'mean', every output whose name contains 'loss' is also a loss by its mean).
+    `trainer`: a TrainerModel (anything callable on the generator's dict that returns one [B] tensor per name of its
+    `output_names`); `generator`: a MaskLabGenerator; `steps`: batches to run, None = len(generator).
+    -> {"val_<name>": mean over all samples of all batches} plus "val_loss", the sum of the loss means.  The batches are
+    equal-sized (the generator drops the remainder).  The sums accumulate in float64 on the device and are read once at the
+    end; Keras keeps float32 running totals."""
+    steps = len(generator) if steps is None else int(steps)
+    if steps < 1 or steps > len(generator):
+        raise ValueError(f"validate: {steps} steps asked of a generator of {len(generator)} batches")
+    names = list(trainer.output_names)
+    total, samples = None, 0
+    for i in range(steps):
+        outs = trainer(generator[i][0])
+        if len(outs) != len(names):
+            raise ValueError(f"validate: the trainer returned {len(outs)} outputs for {len(names)} names")
+        batch = torch.stack([o.reshape(-1) for o in outs]).to(torch.float64)        # [names, B]
+        total = batch.sum(dim=1) if total is None else total + batch.sum(dim=1)
+        samples += batch.shape[1]
+    means = (total / samples).cpu().numpy()
+    result = {"val_" + n: float(m) for n, m in zip(names, means)}
+    result["val_loss"] = float(sum(m for n, m in zip(names, means) if "loss" in n))
+    return result

@@ -1778,6 +1778,87 @@ def eval_reference_host(det=None, ins=None, gt=None, pairs=None, pr_sem=None, gt
     return area, out_pairs, out_sem
 
 
+# ----------------------------------------------------------------------------- generator resizes (csrc/cv_resize.hip)
+def _cv_planes(op, x):
+    """x [B,H,W,C] (uint8: images, semantic maps) or [B,n,H,W] (int8: instance masks, planes of one channel)
+    -> (planes, H, W, C, the output's shape but for its two sizes)."""
+    if x.dtype not in (torch.uint8, torch.int8) or x.dim() != 4:
+        raise RuntimeError(f"{op}: a uint8 [B,H,W,C] or int8 [B,n,H,W] tensor expected, got {x.dtype} {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise RuntimeError(f"{op}: `x` must be contiguous")
+    if x.dtype == torch.int8:
+        B, n, H, W = x.shape
+        return B * n, H, W, 1, lambda oh, ow: (B, n, oh, ow)
+    B, H, W, Cc = x.shape
+    return B, H, W, Cc, lambda oh, ow: (B, oh, ow, Cc)
+
+
+def _cv_out(op, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != device or not out.is_contiguous():
+        raise ValueError(f"{op}: `out` must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}")
+    return out
+
+
+def cv_resize_linear(x, oh, ow, skip_minus_one=False, out=None):
+    """ml_cv_resize_linear_u8: cv2.resize(plane, (ow, oh)) of every plane, OpenCV's fixed-point uint8 arithmetic restated
+    (INTER_AREA at exactly 2x on both axes).  x: uint8 [B,H,W,C], or int8 [B,n,H,W] handled as its bytes (the reference's
+    `mask.astype(np.uint8)` and the store back into int8).  skip_minus_one: a plane that starts with -1 is filled with -1
+    unread.  OpenCV parity is unpinned (include/masklab_hip.h, "Generator resizes")."""
+    _require_dev(x, "x")
+    planes, H, W, Cc, shape = _cv_planes("cv_resize_linear", x)
+    oh, ow = int(oh), int(ow)
+    out = _cv_out("cv_resize_linear", out, shape(oh, ow), x.dtype, x.device)
+    with _Prof("cv_resize_linear", 0, x.numel() + out.numel(), f"{planes}x{H}x{W}x{Cc}->{oh}x{ow}"):
+        _lib.check(_lib.load().ml_cv_resize_linear_u8(_ptr(x), _ptr(out), planes, H, W, Cc, oh, ow, int(bool(skip_minus_one)),
+                                                      _stream()), "ml_cv_resize_linear_u8")
+    return out
+
+
+def cv_resize_linear_round(x, oh, ow, dtype=torch.float32, out=None):
+    """ml_cv_resize_linear_round_u8: np.round(cv2.resize(plane.astype(float64), (ow, oh))) of uint8 [B,H,W,C] planes, read
+    as bytes and converted per tap -> float32 or uint8 [B,oh,ow,C] (the value is an integer in 0..255 either way)."""
+    _require_dev(x, "x")
+    if x.dtype != torch.uint8 or dtype not in (torch.float32, torch.uint8):
+        raise RuntimeError(f"cv_resize_linear_round: uint8 input and a float32 or uint8 result expected, got {x.dtype} -> {dtype}")
+    planes, H, W, Cc, shape = _cv_planes("cv_resize_linear_round", x)
+    oh, ow = int(oh), int(ow)
+    out = _cv_out("cv_resize_linear_round", out, shape(oh, ow), dtype, x.device)
+    with _Prof("cv_resize_linear_round", 0, x.numel() + out.numel() * out.element_size(), f"{planes}x{H}x{W}x{Cc}->{oh}x{ow}"):
+        _lib.check(_lib.load().ml_cv_resize_linear_round_u8(_ptr(x), _ptr(out), int(dtype == torch.float32), planes, H, W, Cc, oh, ow,
+                                                            _stream()), "ml_cv_resize_linear_round_u8")
+    return out
+
+
+def cv_resize_reference_host(x, oh, ow, mode="u8", skip_minus_one=False):
+    """ml_cv_resize_reference_host: the per-thread code of the resize kernels in CPU loops over a NumPy array (for tests
+    without a device and the generator's device="cpu" path; not a product path).  mode "u8": cv_resize_linear;
+    "round_f32" / "round_u8": cv_resize_linear_round."""
+    modes = {"u8": (_lib.CV_RESIZE_U8, None), "round_u8": (_lib.CV_RESIZE_ROUND_U8, np.uint8),
+             "round_f32": (_lib.CV_RESIZE_ROUND_F32, np.float32)}
+    if mode not in modes:
+        raise ValueError(f"cv_resize_reference_host: mode must be one of {sorted(modes)}, got {mode!r}")
+    code, out_dtype = modes[mode]
+    x = np.ascontiguousarray(x)
+    if x.dtype not in (np.uint8, np.int8) or x.ndim != 4 or (mode != "u8" and x.dtype != np.uint8):
+        raise TypeError(f"cv_resize_reference_host: a uint8 [B,H,W,C] or (mode 'u8') int8 [B,n,H,W] array expected, got {x.dtype} "
+                        f"{x.shape}")
+    oh, ow = int(oh), int(ow)
+    if x.dtype == np.int8:
+        (B, n, H, W), Cc = x.shape, 1
+        planes, shape = B * n, (B, n, oh, ow)
+    else:
+        B, H, W, Cc = x.shape
+        planes, shape = B, (B, oh, ow, Cc)
+    if oh < 1 or ow < 1:
+        raise ValueError(f"cv_resize_reference_host: bad output size {oh} x {ow}")
+    out = np.empty(shape, out_dtype or x.dtype)
+    _lib.check(_lib.load().ml_cv_resize_reference_host(C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), code, planes, H, W, Cc,
+                                                       oh, ow, int(bool(skip_minus_one))), "ml_cv_resize_reference_host")
+    return out
+
+
 # ----------------------------------------------------------------------------- trainer forward (csrc/train_targets.hip)
 def _require_f32(op, *named):
     for t, name in named:
