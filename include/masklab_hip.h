@@ -102,9 +102,12 @@ typedef struct ml_conv2d_desc {
     int32_t tile;           /* 0 auto, 1 = 128x128, 2 = 128x64, 3 = 128x32, 4 = pipelined 1x1 (128x128), 5 = half 1x1 on 256x256 tiles,
                                6 = Winograd F(2x2,3x3) (conv_wino.hip; ml_conv2d_wino_eligible problems only, every problem of
                                the launch): `wgt` then points to the transformed weights U = G g G^T (fp64, rounded once),
-                               [n_pad / 32][span_pad / 8][8 channels][32 outputs][16 positions] floats (packing.py
-                               pack_winograd); never split along K; gn_partials on even maps whose Wo / 2 divides or is a
-                               multiple of 64 with (Ho / 2)(Wo / 2) % 64 == 0 (slot = 32-channel group)            */
+                               [4][span_pad / 8][8 channels][32 outputs][16 positions] floats (packing.py
+                               pack_winograd; n_pad = 128 says no more than that: four 32-output blocks, rows >= cout zero);
+                               the kernel launches ceil(cout / 64) blocks of 64 channels and a 32-channel half of a block
+                               that lies wholly >= cout issues no MFMA; never split along K; gn_partials on even maps whose
+                               Wo / 2 divides or is a multiple of 64 with (Ho / 2)(Wo / 2) % 64 == 0 (slot = 32-channel
+                               group)                                                                             */
     int32_t math;           /* ML_MATH_F32: v_mfma_f32_32x32x2_f32 (exact fp32 products);
                                ML_MATH_F16: operands rounded to fp16 on their way into LDS,
                                v_mfma_f32_32x32x16_f16 with fp32 accumulation (BASELINE config 5);
@@ -194,6 +197,12 @@ int ml_conv2d_launch_splits(const ml_conv2d_desc *descs, int32_t n, int64_t work
  * padding (pad 1, Ho = H, Wo = W), dense input (no row-span / grouped windows), no shuffle2x2 / residual / half
  * output, span % 32 == 0, n_pad == 128.  Per-problem geometry and math mode only (never the batch or the launch).    */
 int ml_conv2d_wino_eligible(const ml_conv2d_desc *d);
+/* 1 iff the problem fails that rule ONLY on n_pad: cout <= n_pad, n_pad in {32, 64, 96} (the automatic packing of a conv of
+ * at most 96 output channels), cout not 32 or 64 (kept on the direct kernel beside their `live` launches), no `live`, no
+ * gn_partials.  Such a problem runs on the Winograd kernel when the caller sets
+ * tile = 6, n_pad = 128 and points `wgt` to the transformed weights padded with zero rows to four 32-output blocks.  Per-
+ * problem geometry only.                                                                                              */
+int ml_conv2d_wino_narrow(const ml_conv2d_desc *d);
 /* Smallest launch, in 128 x 128 tiles over all its problems, that ml_conv2d_multi_f32 neither narrows to 128 x 64 / 128 x 32
  * tiles nor cuts along K on the current device: the size from which ml_conv2d_desc.gn_partials may be set. */
 int64_t ml_conv2d_gn_min_launch_tiles(void);

@@ -8,7 +8,7 @@
 //   GEMMs  M_p[tiles, Cout] = V_p[tiles, Cin] . U_p[Cin, Cout], accumulated over the whole K loop (no split-K).
 //
 //   Block = 512 threads = 8 waves, one block per CU; block tile = 64 Winograd tiles (flattened over image, tile row, tile
-//   column) x 64 output channels (two 32-channel blocks of the host layout).  Wave w owns tile group tg = w & 3 (tiles
+//   column) x 64 output channels (two 32-channel blocks of the host layout); ceil(cout / 64) such channel blocks per tile block.  Wave w owns tile group tg = w & 3 (tiles
 //   16 tg .. 16 tg + 15) x channel half h = w >> 2 (32 channels) x all 16 positions: 2 x 16 accumulators of the 16x16x4
 //   MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of its 4 tiles x 1
 //   channel per 16-wide half).  The patches of a tile group are staged once and read by both channel halves.
@@ -63,11 +63,30 @@
 //   Against the direct kernel (conv_mfma.hip, 9 x 128 / 32 = 36 chunks of 64 32x32x2 MFMAs per 128 x 128 tile): the
 //   same output takes 16 / 36 of the MFMA cycles.
 //
+//   Channel blocks and the dead half (profiles/r14_wino_narrow.md).  The weight layout is always four 32-output blocks
+//   (n_pad = 128, rows >= cout zero), but a problem is given NB = ceil(cout / 64) channel blocks per 64-tile block, not
+//   n_pad / 64: a block whose 64 channels are all >= cout is never launched.  In a launched block whose second 32-channel
+//   half lies wholly >= cout (cout <= 32, or 65..96: the 75-channel class output of the towers), waves 4-7 run a second
+//   copy of the K loop, chosen once before the loop by a wave-uniform branch: their 4 patch DMA instructions per
+//   iteration (the patches serve both halves), their 4 weight DMA instructions through an empty resource, the same
+//   s_waitcnt and s_barrier -- so the rings, the counted waits and the barriers per iteration are those of the live
+//   loop for all eight waves -- and no B-fragment or patch read, no transform, no MFMA, no epilogue.  Their DMAs are
+//   s_sleep 3 (~192 cycles, the live loop's 6 MFMAs) apart, not a burst.  Wave w + 4 shares a SIMD with wave w, so a
+//   dead half leaves that SIMD 1024 instead of 2048 cycles of MFMA per K step.  The live loop is the same instruction
+//   sequence as before, and every cout = 128 launch gives the same bits.  Which narrow classes run here instead of on the
+//   direct kernel is decided per cout class by measurement and written as cout ranges in ml_conv2d_wino_narrow below,
+//   never as a launch-size heuristic.  Measured, the towers' five-level output launch of 8 x 1024^2 alone on the chip, direct
+//   kernel -> this one, two runs each: cout 32 (one block, dead half) 152-154 -> 108-109 us; 60 (one block) 258-261 ->
+//   156-159; 75 (two blocks, the second half-dead, sigmoid) 412-414 -> 290-295; 96 393-397 -> 277-278; the full 128 -> 128
+//   tower launch takes 280-290.  So a half-dead block costs 0.69 of a full one (0.65 was the estimate from 1024 of 2048 MFMA
+//   cycles plus the step's 0.20-0.36 us beyond them), and all three classes (<= 32, 33..64, 65..96) are faster here; the
+//   predicate leaves out only cout = 32 and 64 themselves, for the reason given there.
+//
 //   Epilogue: Y = A^T M A per (tile, channel), bias + activation, scalar stores (16 lanes = 64 contiguous bytes) with the
 //   generic addressing: out_coff / out_cstride / out_bstride.  gn_partials: on the geometries where a block covers
 //   exactly two whole 128-pixel flattened tiles (host check wino_gn_ok), slots 2 nt2 + h (the block's two 32-channel
 //   groups) of each of them get that group's (sum, sum of squares) in fp64, its 4 waves added in tile-group order; the
-//   2 blocks of n_pad = 128 fill all 4 slots.  Output addressing is 64-bit.  Several problems (pyramid levels) per
+//   2 blocks of cout = 128 fill all 4 slots.  Output addressing is 64-bit.  Several problems (pyramid levels) per
 //   launch; no host reads, no allocation: capturable in a hipGraph.  Fixed-capacity RoI batches (`live`): blocks that hold
 //   only non-existing images return at once, so a mask-head conv runs on the same kernel (same bits) with or without
 //   `live`.
@@ -210,15 +229,20 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     float *dst_p = lds + (wave >> 1) * 2048 + (wave & 1) * 1024;
     float *dst_w = lds + RING_W + (wave >> 2) * WSTEP + (wave & 3) * 512;
     const int nch = P.nchunks, nsteps = 2 * P.nchunks;
+    // A half whose 32 channels are all >= cout (only h = 1: blocks are launched for ceil(cout / 64) channel blocks, so a
+    // launched block's first half is live) is dead: its waves stage their share of the patches and go through every wait
+    // and barrier of the loop, and do nothing else.  Wave-uniform.
+    const bool dead = (2 * nt2 + h) * 32 >= p.cout;
 
     // resources of patch chunk j (8 channels) and of the weights of K step s; past the end empty (nothing lands, nothing
-    // of it is used), so the loop body is one basic block
+    // of it is used), so the loop body is one basic block.  The weights of a dead half: empty too (this wave's weight DMAs
+    // fill the rows of its own half h, which nobody reads)
     auto rsrc_p = [&](int j) __attribute__((always_inline)) {
         const bool real = j < nch && !(WINO_EXP & 1);
         return __builtin_amdgcn_make_buffer_rsrc((void *)(pin + j * 8), 0, real ? (int)OOB : 0, 0x00020000);
     };
     auto rsrc_w = [&](int s) __attribute__((always_inline)) {
-        const bool real = s < nsteps && !(WINO_EXP & 2);
+        const bool real = s < nsteps && !dead && !(WINO_EXP & 2);
         return __builtin_amdgcn_make_buffer_rsrc((void *)(wsrc + (size_t)s * WSTEP), 0, real ? WSTEP * 4 : 0, 0x00020000);
     };
 
@@ -298,9 +322,38 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         dma16(rw2, dst_w + 2 * SLOT_W, voff_w);
         dma16(rw2, dst_w + 2 * SLOT_W + 256, voff_w + 1024);
     }
-    Ops oa, ob;
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+
+    // ---- the dead half's K loop: the waits, the barrier and the 8 DMA instructions of the live loop below (same slots, same
+    // resources, so the rings, the counted waits and the barriers per iteration are the same for all eight waves), and no
+    // LDS read, no transform, no MFMA; then no epilogue.  The branch is wave-uniform and taken once, here.  The DMAs keep
+    // about the live loop's distance (6 MFMAs of the live wave that shares the SIMD = 192 cycles = s_sleep 3) instead of
+    // queueing at the texture path in one burst, and the sleeping wave leaves the SIMD's issue slots to the live one.  All 8
+    // are out after ~1500 cycles of an iteration of >= 2048, so a dead wave is never the last one at the barrier.
+    // (gn_partials needs cout = 128: no dead half there, so the block-wide barriers of its exchange see all 8 waves.)
+    if (dead) {
+        int ps2 = 2 * SLOT_P;                          // patch slot of chunk j + 2
+        for (int j = 0; j < nch; ++j) {
+            const int w0 = (2 * j) & 3;
+            const int wa = ((w0 ^ 2) + 1) * SLOT_W, wb = w0 * SLOT_W;
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            const __amdgpu_buffer_rsrc_t rp = rsrc_p(j + 2), rwa = rsrc_w(2 * j + 3), rwb = rsrc_w(2 * j + 4);
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (q < 4) dma16(rp, dst_p + ps2 + q * 256, voff_p[q]);
+                else if (q < 6) dma16(rwa, dst_w + wa + (q - 4) * 256, voff_w + (q - 4) * 1024);
+                else dma16(rwb, dst_w + wb + (q - 6) * 256, voff_w + (q - 6) * 1024);
+                __builtin_amdgcn_s_sleep(3);
+            }
+            ps2 = ps2 == 2 * SLOT_P ? 0 : ps2 + SLOT_P;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+    }
+
+    Ops oa, ob;
     read_ops(pa_lane0, pb_lane, oa);
 #pragma unroll
     for (int k = 0; k < 32; ++k) bt_d_b_op(k, oa.d, oa.t, oa.v);
@@ -437,6 +490,25 @@ extern "C" int ml_conv2d_wino_eligible(const ml_conv2d_desc *d) {
            d->cout <= 128 && d->n_pad == 128;
 }
 
+// The narrow case: a problem that fails the rule above ONLY on n_pad -- a conv of at most 96 output channels in its
+// automatic packing of 32, 64 or 96 rows (ml_conv2d_ntile), the last conv of the class and box towers -- without `live` and
+// without gn_partials.  The host hands such a problem to the kernel with n_pad = 128 and weights padded to four 32-output
+// blocks (packing.py pack_winograd); the kernel launches ceil(cout / 64) channel blocks and runs a dead half without
+// MFMAs, so the padding costs no matrix work.  Per-problem geometry only, like the rule itself.  Which cout classes are
+// taken is a measured, per-class decision (kernel header), written as cout ranges here and never as a launch-size heuristic:
+// 1..32, 33..64 and 65..96 were each faster here than on the direct kernel.  Taken: cout 1..31, 33..63 and 65..96.  cout = 32
+// and cout = 64 stay on the direct kernel: the fixed-capacity RoI batches of these two widths (`live`, not taken here) are
+// held to the bits and the K slices of their `live`-less launch (tests/test_gpu_live_slots.py
+// test_conv3x3_split_k_with_live), so that launch keeps the kernel its `live` twin runs on.
+extern "C" int ml_conv2d_wino_narrow(const ml_conv2d_desc *d) {
+    if (!d || d->live || d->gn_partials) return 0;
+    if (d->n_pad != 32 && d->n_pad != 64 && d->n_pad != 96) return 0;
+    if (d->cout < 1 || d->cout > d->n_pad || d->cout == 32 || d->cout == 64) return 0;
+    ml_conv2d_desc w = *d;
+    w.n_pad = 128;
+    return ml_conv2d_wino_eligible(&w);
+}
+
 // gn_partials on the Winograd path: every 64-tile block must cover exactly two whole 128-pixel flattened tiles of one image
 // (even Ho / Wo; a block is whole tile rows, or a 128-column piece of one), 4 channel groups of 32 = the 4 slots.
 int ml_conv2d_wino_gn_ok(const ml_conv2d_desc &d) {
@@ -468,7 +540,7 @@ int ml_conv2d_wino_launch(const ml_conv2d_desc *descs, int n, hipStream_t s) {
         ML_REQUIRE(T < (1ll << 30), "conv2d (winograd): too many tiles");
         P.T = (int)T;
         P.MB = (int)((T + WT - 1) / WT);
-        P.NB = d.n_pad / WN;
+        P.NB = (d.cout + WN - 1) / WN;                 // channel blocks that hold a channel < cout: a dead block is never launched
         P.nchunks = d.span_pad / WK;
         // a block's patch offsets are 32-bit from its first tap row: its 64 tiles cover at most 64 / TW + 2 flattened tile
         // rows, i.e. 2 (64 / TW + 2) + 2 pixel rows with the taps above and below

@@ -98,6 +98,7 @@ SIGNATURES = {
     "ml_conv2d_launch_mtile": (C.c_int, [C.POINTER(ConvDesc), _i32, _i32]),
     "ml_conv2d_launch_splits": (C.c_int, [C.POINTER(ConvDesc), _i32, _i64, C.POINTER(C.c_int32)]),
     "ml_conv2d_wino_eligible": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ml_conv2d_wino_narrow": (C.c_int, [C.POINTER(ConvDesc)]),
     "ml_conv2d_gn_min_launch_tiles": (_i64, []),
     "ml_conv2d_workspace_bytes": (_i64, []),
     "ml_conv2d_multi_f32": (C.c_int, [C.POINTER(ConvDesc), _i32, _vp, _i64, _vp]),

@@ -138,8 +138,9 @@ class DeviceConv:
 
     @property
     def wgt_wino(self):
-        """The Winograd F(2x2,3x3) weights U = G g G^T (packing.pack_winograd: fp64, rounded once) of a dense 3x3 conv with
-        n_pad = 128 -- what ml_conv2d_desc.tile = 6 reads; made on first use."""
+        """The Winograd F(2x2,3x3) weights U = G g G^T (packing.pack_winograd: fp64, rounded once) of a dense 3x3 conv, four
+        32-output blocks (a packing narrower than 128 rows is padded with zero blocks) -- what ml_conv2d_desc.tile = 6 reads
+        with n_pad = 128; made on first use."""
         if self._wgt_wino is None:
             self._wgt_wino = torch.from_numpy(pack_winograd(self.p)).to(self.wgt.device)
         return self._wgt_wino
@@ -328,17 +329,23 @@ def _launch_conv(descs, problems, flops, nbytes, shapes, multi):
 
 
 def _wino_select(descs, n, problems):
-    """Move a launch onto the Winograd F(2x2,3x3) kernel (tile = 6) when the conv math is "f32", every problem holds fp32
-    tensors, was packed for the automatic tile choice and passes the library's one eligibility rule
-    (ml_conv2d_wino_eligible); a mixed launch stays on the direct kernel.  -> True if it was moved."""
+    """Move a launch onto the Winograd F(2x2,3x3) kernel (tile = 6) when the conv math is "f32" and every problem holds fp32
+    tensors, was packed for the automatic tile choice and passes one of the library's two predicates: the eligibility rule
+    (ml_conv2d_wino_eligible: n_pad = 128) or the narrow case (ml_conv2d_wino_narrow: the same rule failed on n_pad alone --
+    the 75- and 60-channel output convs of the towers, packed 96 and 64 wide).  A narrow problem is handed over with
+    n_pad = 128 and DeviceConv.wgt_wino, which pads its weights to four 32-output blocks; the kernel launches
+    ceil(cout / 64) channel blocks and runs no MFMA for a 32-channel half past cout.  The direct-path weights (dc.wgt, wgt_x3,
+    wgt_h) are untouched.  A mixed launch stays on the direct kernel.  -> True if it was moved."""
     if CONV_MATH != "f32":
         return False
     lib = _lib.load()
     for i, (x, dc) in enumerate(problems):
-        if x.dtype != torch.float32 or dc.p.tile != 0 or not lib.ml_conv2d_wino_eligible(C.byref(descs[i])):
+        if x.dtype != torch.float32 or dc.p.tile != 0:
+            return False
+        if not (lib.ml_conv2d_wino_eligible(C.byref(descs[i])) or lib.ml_conv2d_wino_narrow(C.byref(descs[i]))):
             return False
     for i, (x, dc) in enumerate(problems):
-        descs[i].tile = 6
+        descs[i].tile, descs[i].n_pad = 6, 128
         descs[i].wgt = dc.wgt_wino.data_ptr()
     return True
 

@@ -230,11 +230,15 @@ def winograd_transform(g):
 def pack_winograd(packed: PackedConv):
     """The weights of the Winograd kernel (ml_conv2d_desc.tile = 6) from a dense 3x3 packing: U = G g G^T in fp64, rounded
     once to fp32, laid out [n_pad / 32][span_pad / 8][8 channels][32 outputs][16 positions p = 4a + b] -- one contiguous
-    16 KB block per (32-output block, 8-channel chunk), the order conv_wino.hip stages it in."""
+    16 KB block per (32-output block, 8-channel chunk), the order conv_wino.hip stages it in.  The kernel takes n_pad = 128
+    only: a narrower packing (n_pad = 32 / 64 / 96, the automatic choice for cout <= 96) is padded with zero blocks to four
+    32-output blocks, so it equals the packing of the same kernel packed 128 wide."""
     p = packed
     if (p.KH, p.KW) != (3, 3) or p.cpp_shift != NO_PIX_SPAN or p.group_cin_step or p.shuffle2x2 or p.n_pad % 32 or p.span_pad % 8:
         raise ValueError("winograd packing needs a dense 3x3 conv (n_pad % 32 == 0)")
     g = p.wgt.reshape(p.n_pad, 3, 3, p.span_pad).transpose(0, 3, 1, 2)              # [n][c][3][3]
     u = winograd_transform(g).reshape(p.n_pad, p.span_pad, 16).astype(np.float32)    # [n][c][p]
     u = u.reshape(p.n_pad // 32, 32, p.span_pad // 8, 8, 16).transpose(0, 2, 3, 1, 4)  # [nb][chunk][k][n][p]
+    if u.shape[0] < 4:
+        u = np.concatenate([u, np.zeros((4 - u.shape[0],) + u.shape[1:], np.float32)])
     return np.ascontiguousarray(u)

@@ -7,6 +7,11 @@ Shapes (8 x 1024^2 ResNeXt-50 bench step):
   decoder : the 128^2 semantic / decoder conv, 8 images, 160 -> 128, relu
   mask    : the 14 x 14 mask-head launch, `multi x3`: 800 RoIs (100 per image) over three levels (400 / 250 / 150), 128 -> 128
   level128: the decoder's grid at 128 -> 128: with `decoder` (the same 1024 blocks, 8 K steps more) the time per K step
+  cls_out : the class tower's output launch, `multi x5` like `tower`, 128 -> 75, sigmoid (two channel blocks, the second half dead)
+  box_out : the box tower's output launch, 128 -> 60, no activation (one channel block)
+  out32 / out96: the same launch at 128 -> 32 (one block, dead half) and 128 -> 96 (the widest of the 65..96 class)
+--direct packs with the explicit tile code of the automatic choice (same packing, same direct kernel as without the Winograd
+path), so a narrow shape can be timed on both kernels from one build;
 --lib loads another build of the library (the product path has no override), so the parent's build and this one can be
 timed in alternating processes; --save writes the sha256 of each output tensor's bytes to DIR/<shape>.sha256 (compare two builds
 bit for bit); --time prints
@@ -28,20 +33,26 @@ SHAPES = {
     "decoder": (160, 128, [(8, 128)]),
     "mask": (128, 128, [(400, 14), (250, 14), (150, 14)]),
     "level128": (128, 128, [(8, 128)]),
+    "cls_out": (128, 75, [(8, 128), (8, 64), (8, 32), (8, 16), (8, 8)]),
+    "box_out": (128, 60, [(8, 128), (8, 64), (8, 32), (8, 16), (8, 8)]),
+    "out32": (128, 32, [(8, 128), (8, 64), (8, 32), (8, 16), (8, 8)]),
+    "out96": (128, 96, [(8, 128), (8, 64), (8, 32), (8, 16), (8, 8)]),
 }
+ACTS = {"cls_out": _lib.ACT_SIGMOID, "box_out": _lib.ACT_NONE}
 
 
-def setup(name, seed=0):
+def setup(name, seed=0, direct=False):
     cin, cout, levels = SHAPES[name]
     rng = np.random.default_rng(seed)
     w = (rng.normal(size=(3, 3, cin, cout)) / np.sqrt(9 * cin)).astype(np.float32)
     b = rng.normal(size=cout).astype(np.float32)
-    dc = ops.DeviceConv(packing.pack_dense(w, b), "cuda")
+    tile = {128: 1, 64: 2, 32: 3}[packing.ntile_for(cout)] if direct else 0
+    dc = ops.DeviceConv(packing.pack_dense(w, b, tile=tile), "cuda")
     probs, flops = [], 0.0
     for B, hw in levels:
         x = torch.from_numpy(rng.normal(size=(B, hw, hw, cin)).astype(np.float32)).cuda()
         out = torch.empty((B, hw, hw, cout), device="cuda")
-        probs.append(dict(x=x, dc=dc, padding="same", act=_lib.ACT_RELU, out=out))
+        probs.append(dict(x=x, dc=dc, padding="same", act=ACTS.get(name, _lib.ACT_RELU), out=out))
         flops += 2.0 * B * ((hw + 1) // 2) ** 2 * 16 * cin * cout
     return probs, flops
 
@@ -53,6 +64,7 @@ def main():
     ap.add_argument("--lib", default=None, help="an experiment build of the library")
     ap.add_argument("--save", default=None, metavar="DIR", help="write the sha256 of each output to DIR/<shape>.sha256")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--direct", action="store_true", help="the direct kernel: pack with the automatic choice's explicit tile code")
     args = ap.parse_args()
     if args.lib:
         _lib.LIB_PATH = os.path.abspath(args.lib)
@@ -61,13 +73,13 @@ def main():
     if any(n not in SHAPES for n in names):
         ap.error("--shape: all or names out of " + ", ".join(SHAPES))
     for name in names:
-        probs, flops = setup(name)
+        probs, flops = setup(name, direct=args.direct)
         ops.PROFILE = []
         ops.conv2d_multi(probs)
         torch.cuda.synchronize()
         kernels = {rec["kernel"] for rec in ops.PROFILE}
         ops.PROFILE = None
-        assert kernels == {"conv_wino_f32"}, (name, kernels)
+        assert (kernels == {"conv_wino_f32"}) != args.direct, (name, kernels)
         times = []
         for _ in range(3):                          # back-to-back launches between two events: the per-launch mean
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,7 +96,7 @@ def main():
                     f.write("%d %s\n" % (i, hashlib.sha256(pr["out"].cpu().numpy().tobytes()).hexdigest()))
         if args.time:
             ms = float(np.median(times))
-            print(f"{name:8s} {1e3 * ms:8.1f} us  {flops / ms / 1e9:6.1f} TF executed  (median of 3 x {args.reps} launches)", flush=True)
+            print(f"{name:8s} {1e3 * ms:8.1f} us  {flops / ms / 1e9:6.1f} TF executed  (median of 3 x {args.reps} launches)  {'/'.join(sorted(kernels))}", flush=True)
     print("done")
 
 
