@@ -961,6 +961,46 @@ int ml_cv_resize_linear_round_u8(const void *src, void *dst, int32_t dst_is_f32,
 int ml_cv_resize_reference_host(const void *src, void *dst, int32_t mode, int64_t planes, int32_t H, int32_t W, int32_t C,
                                 int32_t oh, int32_t ow, int32_t skip_minus_one);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dataset polygons: the polygon labels of the reference's dataset (road_project/setup/process.py draws each with
+ * skimage.draw.polygon into a PNG; engine/utils/dataset/masklab.py reads the PNGs back) rasterised straight into the
+ * batch's instance planes and semantic maps (csrc/polygon.hip).  skimage parity is unpinned: the rule below was written
+ * down from memory of skimage's 2019 releases (later releases also count pixels lying exactly on an edge or vertex) and
+ * is held to its NumPy restatement in tests/polygon_ref.py, not to a run of skimage.
+ *   clip      every vertex (xp, yp), float64, first becomes (min(max(xp, 0), W - 1), min(max(yp, 0), H - 1)), as the
+ *             reference clips before it draws; the library does it, on the device and on the host.
+ *   inside    pixel (x, y), integer column and row taken as float64, is inside iff an odd number of edges (j -> i),
+ *             j = i - 1 cyclically, satisfy both
+ *                 (yp[i] <= y and y < yp[j]) or (yp[j] <= y and y < yp[i])
+ *                 x < (xp[j] - xp[i]) * (y - yp[i]) / (yp[j] - yp[i]) + xp[i]
+ *             in float64, evaluated in that order (multiply, divide, add), FP contraction off.
+ * verts float64 [total,2] (x, y), total < 2^31; every offsets array is int32, starts at >= 0 and never decreases.  One
+ * launch per call on `stream` (per 65 535 planes / images), no workspace, no atomics to global memory, no host read; every
+ * output byte is written exactly once, zeros and -1 planes included; `out` needs no alignment, plane offsets are 64-bit,
+ * H*W < 2^31; any vertex count per polygon.  The device entries cannot read their offsets (device memory) before the
+ * launch: the kernels clamp every range to the array it indexes, so wrong offsets give wrong masks and never a read out
+ * of bounds; the host entry and the Python wrappers refuse offsets that decrease or point past the end.
+ * ------------------------------------------------------------------------------------------- */
+enum { ML_POLYGON_INSTANCE = 0, ML_POLYGON_SEMANTIC = 1 };
+/* Instance planes.  plane_offsets [B*n+1] into verts, windows [B*n,4] = (x1, y1, x2, y2) inclusive -> out int8 [B,n,H,W]:
+ * a plane with an empty vertex range is padding, every byte -1; any other is 1 where the pixel is inside its polygon and
+ * x1 <= x <= min(x2, W-1) and y1 <= y <= min(y2, H-1), 0 elsewhere.  B == 0 or n == 0 is a no-op.                     */
+int ml_polygon_instance_masks(const double *verts, int64_t total, const int32_t *plane_offsets, const int32_t *windows, int32_t B,
+                              int32_t n, int32_t H, int32_t W, void *out, void *stream);
+/* Semantic maps.  poly_offsets [P+1] into verts; group_offsets [B*(S+1)+1] into the polygons, group (b, s) for s < S is
+ * label s of image b and group (b, S) its "except" group -> out uint8 [B,H,W,S]: channel s is 1 where the pixel is inside
+ * ANY polygon of group s (a union across polygons, even-odd within one) and inside NO polygon of the except group, else
+ * 0.  S <= ML_EVAL_MAX_CLASSES; B == 0 or S == 0 is a no-op.                                                            */
+int ml_polygon_semantic_maps(const double *verts, int64_t total, const int32_t *poly_offsets, int32_t P, const int32_t *group_offsets,
+                             int32_t B, int32_t S, int32_t H, int32_t W, void *out, void *stream);
+/* Host.  The kernels' edge, scan and store functions in CPU loops, every pointer in host memory; kind = ML_POLYGON_*:
+ * INSTANCE takes offsets = plane_offsets, windows and n_or_S = n (P and group_offsets unused), SEMANTIC takes offsets =
+ * poly_offsets, P, group_offsets and n_or_S = S (windows unused).  For checking the arithmetic without a device and the
+ * dataset's device="cpu" path -- not a product path.                                                                   */
+int ml_polygon_reference_host(int32_t kind, const double *verts, int64_t total, const int32_t *offsets, int32_t P,
+                              const int32_t *group_offsets, const int32_t *windows, int32_t B, int32_t n_or_S, int32_t H, int32_t W,
+                              void *out);
+
 #ifdef __cplusplus
 }
 #endif

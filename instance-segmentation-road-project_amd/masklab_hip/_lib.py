@@ -197,7 +197,11 @@ SIGNATURES = {
     "ml_cv_resize_linear_u8": (C.c_int, [_vp, _vp, _i64] + [_i32] * 6 + [_vp]),
     "ml_cv_resize_linear_round_u8": (C.c_int, [_vp, _vp, _i32, _i64] + [_i32] * 5 + [_vp]),
     "ml_cv_resize_reference_host": (C.c_int, [_vp, _vp, _i32, _i64] + [_i32] * 6),
+    "ml_polygon_instance_masks": (C.c_int, [_vp, _i64, _vp, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "ml_polygon_semantic_maps": (C.c_int, [_vp, _i64, _vp, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
+    "ml_polygon_reference_host": (C.c_int, [_i32, _vp, _i64, _vp, _i32, _vp, _vp] + [_i32] * 4 + [_vp]),
 }
+POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1                           # ML_POLYGON_*
 CV_RESIZE_U8, CV_RESIZE_ROUND_U8, CV_RESIZE_ROUND_F32 = 0, 1, 2     # ML_CV_RESIZE_*
 TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1                    # ML_TRAIN_MASK_*
 EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3     # ML_EVAL_*

@@ -98,15 +98,20 @@ class Evaluator:
     def update(self, pr_detection, pr_instance, pr_semantic, gt_detection, gt_instance, gt_semantic):
         """One batch.  Predictions: the deploy model's outputs, device tensors or arrays -- [B,n,6] int32, [B,n,h,w] int32,
         [B,H,W,C] int32.  Ground truth in the reference dataset's layout: [B,G,6] float, [B,G,H,W] int8 or uint8,
-        [B,H,W,C] uint8."""
-        gt_instance = np.asarray(gt_instance)
+        [B,H,W,C] uint8; masks and maps that are device tensors already (a MaskLabDataset batch) are not copied to the host."""
+        on_device = isinstance(gt_instance, torch.Tensor) and gt_instance.is_cuda    # a MaskLabDataset batch: the masks stay there
+        if not on_device:
+            gt_instance = np.asarray(gt_instance)
         B = gt_instance.shape[0]
         if len(pr_detection) != B or len(pr_instance) != B or len(pr_semantic) != B or len(gt_detection) != B or len(gt_semantic) != B:
             raise ValueError("Evaluator.update: the batch sizes differ")
         if pr_semantic.shape[-1] > len(self.semantic_labels):
             raise ValueError(f"Evaluator.update: {pr_semantic.shape[-1]} semantic classes, {len(self.semantic_labels)} labels")
         # train.py:206, on the host array as stored (an int8 mask holds -1 where a 0 / 255 mask was set)
-        has_instances = [bool(np.any(gt_instance[b][..., -1] != -1)) for b in range(B)]
+        if on_device:                                                                # the last column alone, B flags read back
+            has_instances = (gt_instance[..., -1] != -1).reshape(B, -1).any(dim=1).cpu().tolist()
+        else:
+            has_instances = [bool(np.any(gt_instance[b][..., -1] != -1)) for b in range(B)]
         det_host, pairs, pair_counts, sem_counts = self._counts(pr_detection, pr_instance, pr_semantic, gt_detection, gt_instance,
                                                                 gt_semantic)
         at = 0

@@ -1866,6 +1866,159 @@ def cv_resize_reference_host(x, oh, ow, mode="u8", skip_minus_one=False):
     return out
 
 
+# ----------------------------------------------------------------------------- dataset polygons (csrc/polygon.hip)
+def _poly_host(op, a, name, dtype, cols=None):
+    """A host array (NumPy or a CPU tensor) -> contiguous NumPy of `dtype`, 1-d or [rows, cols]."""
+    if isinstance(a, torch.Tensor):
+        if a.is_cuda:
+            raise TypeError(f"{op}: `{name}` must be in host memory")
+        a = a.numpy()
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        raise TypeError(f"{op}: `{name}` must be {np.dtype(dtype).name}, got {a.dtype}")
+    if (a.ndim != 1) if cols is None else (a.ndim != 2 or a.shape[1] != cols):
+        raise ValueError(f"{op}: `{name}` must be {'1-d' if cols is None else f'[rows, {cols}]'}, got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _poly_offsets(op, a, name, count, limit):
+    """An offsets array in host memory: int32 [count + 1], from >= 0, never decreasing, to <= limit."""
+    a = _poly_host(op, a, name, np.int32)
+    if a.shape[0] != count + 1:
+        raise ValueError(f"{op}: `{name}` must have {count + 1} entries, got {a.shape[0]}")
+    if a[0] < 0 or a[-1] > limit or (np.diff(a) < 0).any():
+        raise ValueError(f"{op}: `{name}` must start at >= 0, never decrease and end at <= {limit}")
+    return a
+
+
+def _poly_sizes(op, H, W, **counts):
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"{op}: bad plane size {H} x {W} (H, W >= 1, H*W < 2^31)")
+    for name, v in counts.items():
+        if int(v) < 0:
+            raise ValueError(f"{op}: `{name}` must be >= 0, got {v}")
+    return (H, W) + tuple(int(v) for v in counts.values())
+
+
+def _poly_dev(op, a, name, dtype, device, check):
+    """A device tensor as it is (its offsets are trusted: the kernels clamp them), or a host array checked and uploaded."""
+    if isinstance(a, torch.Tensor) and a.is_cuda:
+        if a.dtype != dtype or not a.is_contiguous() or a.device != device:
+            raise TypeError(f"{op}: `{name}` on the device must be a contiguous {dtype} tensor on {device}")
+        return a
+    return torch.from_numpy(check(a)).to(device)
+
+
+def _poly_device(device, out):
+    if out is not None:
+        return out.device
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"masklab_hip: the polygon kernels run only on the device, got {device} (the host loops are "
+                           f"polygon_reference_host)")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def polygon_instance_masks(verts, plane_offsets, windows, B, n, H, W, device=None, out=None):
+    """ml_polygon_instance_masks: polygons -> the int8 [B,n,H,W] instance planes of a batch in one launch.  verts float64
+    [total,2] (x, y); plane_offsets int32 [B*n+1] into verts (an empty range: a padding plane of -1); windows int32 [B*n,4]
+    = (x1, y1, x2, y2) inclusive: a plane is 1 inside its polygon (even-odd; include/masklab_hip.h, "Dataset polygons")
+    and inside its window, 0 elsewhere.  Host arrays are checked and uploaded; device tensors are taken as they are.
+    skimage parity is unpinned."""
+    op = "polygon_instance_masks"
+    H, W, B, n = _poly_sizes(op, H, W, B=B, n=n)
+    device = _poly_device(device, out)
+    out = _cv_out(op, out, (B, n, H, W), torch.int8, device)
+    if B == 0 or n == 0:
+        return out
+    verts = _poly_dev(op, verts, "verts", torch.float64, device, lambda a: _poly_host(op, a, "verts", np.float64, 2))
+    if verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError(f"{op}: `verts` must be [total, 2], got {tuple(verts.shape)}")
+    total = int(verts.shape[0])
+    plane_offsets = _poly_dev(op, plane_offsets, "plane_offsets", torch.int32, device,
+                              lambda a: _poly_offsets(op, a, "plane_offsets", B * n, total))
+    windows = _poly_dev(op, windows, "windows", torch.int32, device, lambda a: _poly_host(op, a, "windows", np.int32, 4))
+    if plane_offsets.numel() != B * n + 1 or tuple(windows.shape) != (B * n, 4):
+        raise ValueError(f"{op}: plane_offsets {tuple(plane_offsets.shape)} / windows {tuple(windows.shape)} do not fit B*n = {B * n}")
+    with torch.cuda.device(device), _Prof(op, 0, out.numel() + verts.numel() * 8, f"{B}x{n}x{H}x{W}"):
+        _lib.check(_lib.load().ml_polygon_instance_masks(_ptr(verts), total, _ptr(plane_offsets), _ptr(windows), B, n, H, W, _ptr(out),
+                                                         _stream()), "ml_polygon_instance_masks")
+    return out
+
+
+def polygon_semantic_maps(verts, poly_offsets, group_offsets, B, S, H, W, device=None, out=None):
+    """ml_polygon_semantic_maps: polygons -> the uint8 [B,H,W,S] semantic maps of a batch in one launch.  poly_offsets int32
+    [P+1] into verts; group_offsets int32 [B*(S+1)+1] into the polygons: group (b, s) is label s of image b, group (b, S) the
+    except group.  Channel s is 1 inside any polygon of its group and outside every except polygon.  S <= 16."""
+    op = "polygon_semantic_maps"
+    H, W, B, S = _poly_sizes(op, H, W, B=B, S=S)
+    if S > _lib.EVAL_MAX_CLASSES:
+        raise ValueError(f"{op}: {S} semantic labels, at most {_lib.EVAL_MAX_CLASSES}")
+    device = _poly_device(device, out)
+    out = _cv_out(op, out, (B, H, W, S), torch.uint8, device)
+    if B == 0 or S == 0:
+        return out
+    verts = _poly_dev(op, verts, "verts", torch.float64, device, lambda a: _poly_host(op, a, "verts", np.float64, 2))
+    if verts.dim() != 2 or verts.shape[1] != 2:
+        raise ValueError(f"{op}: `verts` must be [total, 2], got {tuple(verts.shape)}")
+    total = int(verts.shape[0])
+    P = int(poly_offsets.shape[0]) - 1 if hasattr(poly_offsets, "shape") and len(poly_offsets.shape) == 1 else len(poly_offsets) - 1
+    if P < 0:
+        raise ValueError(f"{op}: `poly_offsets` must have at least one entry")
+    poly_offsets = _poly_dev(op, poly_offsets, "poly_offsets", torch.int32, device, lambda a: _poly_offsets(op, a, "poly_offsets", P, total))
+    group_offsets = _poly_dev(op, group_offsets, "group_offsets", torch.int32, device,
+                              lambda a: _poly_offsets(op, a, "group_offsets", B * (S + 1), P))
+    if poly_offsets.numel() != P + 1 or group_offsets.numel() != B * (S + 1) + 1:
+        raise ValueError(f"{op}: poly_offsets {tuple(poly_offsets.shape)} / group_offsets {tuple(group_offsets.shape)} do not fit")
+    with torch.cuda.device(device), _Prof(op, 0, out.numel() + verts.numel() * 8, f"{B}x{H}x{W}x{S}"):
+        _lib.check(_lib.load().ml_polygon_semantic_maps(_ptr(verts), total, _ptr(poly_offsets), P, _ptr(group_offsets), B, S, H, W,
+                                                        _ptr(out), _stream()), "ml_polygon_semantic_maps")
+    return out
+
+
+def polygon_reference_host(kind, verts, offsets, B, n_or_S, H, W, windows=None, group_offsets=None):
+    """ml_polygon_reference_host: the polygon kernels' edge, scan and store code in CPU loops over NumPy arrays (for tests
+    without a device and the dataset's device="cpu" path; not a product path).  kind "instance": offsets = plane_offsets,
+    `windows`, n_or_S = n -> int8 [B,n,H,W]; kind "semantic": offsets = poly_offsets, `group_offsets`, n_or_S = S -> uint8
+    [B,H,W,S]."""
+    op = "polygon_reference_host"
+    if kind not in ("instance", "semantic"):
+        raise ValueError(f"{op}: kind must be 'instance' or 'semantic', got {kind!r}")
+    H, W, B, k = _poly_sizes(op, H, W, B=B, n_or_S=n_or_S)
+    verts = _poly_host(op, verts, "verts", np.float64, 2)
+    total = verts.shape[0]
+    vp = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else C.c_void_p(0)
+    if kind == "instance":
+        out = np.empty((B, k, H, W), np.int8)
+        if B == 0 or k == 0:
+            return out
+        if windows is None:
+            raise ValueError(f"{op}: kind 'instance' needs `windows`")
+        offsets = _poly_offsets(op, offsets, "plane_offsets", B * k, total)
+        windows = _poly_host(op, windows, "windows", np.int32, 4)
+        if windows.shape[0] != B * k:
+            raise ValueError(f"{op}: `windows` must be [{B * k}, 4], got {windows.shape}")
+        _lib.check(_lib.load().ml_polygon_reference_host(_lib.POLYGON_INSTANCE, vp(verts), total, vp(offsets), 0, None, vp(windows), B, k,
+                                                         H, W, vp(out)), "ml_polygon_reference_host")
+        return out
+    if k > _lib.EVAL_MAX_CLASSES:
+        raise ValueError(f"{op}: {k} semantic labels, at most {_lib.EVAL_MAX_CLASSES}")
+    out = np.empty((B, H, W, k), np.uint8)
+    if B == 0 or k == 0:
+        return out
+    if group_offsets is None:
+        raise ValueError(f"{op}: kind 'semantic' needs `group_offsets`")
+    P = len(offsets) - 1
+    if P < 0:
+        raise ValueError(f"{op}: `poly_offsets` must have at least one entry")
+    offsets = _poly_offsets(op, offsets, "poly_offsets", P, total)
+    group_offsets = _poly_offsets(op, group_offsets, "group_offsets", B * (k + 1), P)
+    _lib.check(_lib.load().ml_polygon_reference_host(_lib.POLYGON_SEMANTIC, vp(verts), total, vp(offsets), P, vp(group_offsets), None, B, k,
+                                                     H, W, vp(out)), "ml_polygon_reference_host")
+    return out
+
+
 # ----------------------------------------------------------------------------- trainer forward (csrc/train_targets.hip)
 def _require_f32(op, *named):
     for t, name in named:

@@ -4,8 +4,8 @@ build_semantic_network :160-198, construct_inference_network :420-495, find_laye
 and the deploy wrapper of load_masklab_inference_model_from_h5 :598-643 (DeployModel below).
 Same function names, argument meaning and return structure; the returned model runs eagerly on
 the MI355X kernels.  construct_trainer_network :223-395 is restated FORWARD ONLY (TrainerModel: target assignment,
-the four losses and the metrics of a batch with ground truth); backward passes, optimizers and the dataset stay out of
-scope.
+the four losses and the metrics of a batch with ground truth); construct_masklabdataset :398-417 builds the file-reading
+datasets (masklab_hip/utils/dataset).  Backward passes and optimizers stay out of scope.
 """
 import numpy as np
 import torch
@@ -26,6 +26,21 @@ VERBOSE = False
 def _say(*lines):
     if VERBOSE:
         print("\n".join(lines))
+
+
+def construct_masklabdataset(configuration: ModelConfiguration, device="cuda"):
+    """reference :398-417: (trainset, validset) from `configuration.dataset`; `except_semantic_labels` goes along, since
+    the masks are drawn per batch and not read from a `processed/` tree."""
+    from .utils import MaskLabDataset
+    d_config = configuration.dataset
+    trainset, validset = (MaskLabDataset(cases, min_area=d_config.min_area, data_dir=d_config.data_dir,
+                                         instance_labels=d_config.instance_labels, semantic_labels=d_config.semantic_labels,
+                                         except_semantic_labels=d_config.except_semantic_labels, device=device)
+                          for cases in (d_config.train_cases, d_config.valid_cases))
+    _say("Dataset Summary", "-------------------------------", f"* Num of Train Images : {len(d_config.train_cases)}",
+         f"* Num of Valid Images : {len(d_config.valid_cases)}",
+         f"* Num of Images : {len(d_config.train_cases) + len(d_config.valid_cases)}", "-------------------------------\n")
+    return trainset, validset
 
 
 def build_backbone_network(configuration: ModelConfiguration):

@@ -10,8 +10,9 @@ the reference on purpose:
   * `images`, `gt_seg` and `gt_masks` are torch tensors on `device`; `gt_seg` is float32 (or uint8 with
     `seg_dtype=torch.uint8`) where the reference returns float64 -- the values are integers in 0..255 either way;
   * the boxes are scaled on a float64 COPY; the reference scales the dataset's own array in place;
-  * a dict for `dataset` (from which the reference builds its file-reading MaskLabDataset, with cv2 and pandas) raises
-    NotImplementedError; a target size of zero raises ValueError (the reference fails inside cv2.resize);
+  * a dict for `dataset` (from which the reference builds its MaskLabDataset) raises NotImplementedError: build the
+    `masklab_hip.utils.MaskLabDataset` yourself and pass the object; a target size of zero raises ValueError (the
+    reference fails inside cv2.resize);
   * `rng` (a np.random.Generator) draws the scale; None is the global np.random, as in the reference;
   * `device="cpu"` runs the library's host reference loops: slow, for machines without a GPU.
 """
