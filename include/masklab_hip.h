@@ -877,10 +877,11 @@ int ml_eval_reference_host(const int32_t *det, const int32_t *ins, const void *g
 /* ---------------------------------------------------------------------------------------------
  * Trainer forward: the reference's target assignment (AssignBoxes engine/layers/detection.py:589-697, AssignMasks
  * instance.py:296-386, AssignSeg semantic.py:304-311) and its four loss layers (engine/losses.py), forward only
- * (csrc/train_targets.hip).  All on `stream`, no host read.  No float atomics: a sum is float64 partials per block in
+ * (csrc/train_targets.hip; the losses' gradients are the next block).  All on `stream`, no host read.  No float atomics: a sum is float64 partials per block in
  * `workspace` (ml_train_workspace_bytes) added in block order by a finishing kernel -- the same bits run to run.  Per-element
  * terms are float32 with FP contraction off, as tests/trainer_ref.py evaluates them; sums are float64.
- * NOT supported: gradients; predictions or truths in float16 (cast first); more than ML_EVAL_MAX_CLASSES semantic classes;
+ * Gradients stop at the head outputs ("Trainer backward: the losses").  NOT supported: predictions or truths in float16
+ * (cast first); more than ML_EVAL_MAX_CLASSES semantic classes;
  * more than 32 images in ml_train_mask_loss_f32 (MoldBatch); gt_masks other than int8 / uint8; NaN boxes (a NaN IoU orders
  * above every number in the packed maximum, where tf.argmax leaves it unspecified).
  * The reference's quirks are kept: a ground truth whose best prior also has IoU >= 0.5 enters that prior twice (loc_true
@@ -930,6 +931,48 @@ int ml_train_assign_seg(const void *gt_seg, int32_t dtype, int32_t B, int32_t H,
 /* SegLoss.call (losses.py:179-193): seg_true, seg_pred [B,HW,C], seg_exist [B,C] float32 (C <= ML_EVAL_MAX_CLASSES) -> out [B]. */
 int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
                           float weight, float keep, float half_smooth, void *workspace, float *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Trainer backward: the losses (csrc/train_grads.hip).  Each call is its forward twin above -- the same arguments, the same
+ * `workspace`, the same loss in `out`, BIT FOR BIT -- plus
+ *   upstream         float32 [B] on the device: d(scalar) / d(loss[b]); 1 / B for the scalar the reference compiles
+ *                    (add_loss(K.mean(loss)) per loss layer);
+ *   through_sigmoid  non-zero: the gradient is additionally multiplied by pred * (1 - pred), which makes it the gradient at
+ *                    the pre-activation of the sigmoid the 1x1 output convs fuse (BoxLoss has no such argument);
+ *   grad             float32, shaped like the prediction: d(sum_b upstream[b] * loss[b]) / d(prediction).  EVERY element is
+ *                    written in the pass that sums the loss, the zeros included (ignored anchors, non-positive anchors of
+ *                    the box gradient, RoIs that are not selected, the other class channels of a selected RoI).
+ * These are the gradients TensorFlow gives for the reference's expressions.  Whatever reaches a loss only through a count, a
+ * comparison or an assigned variable is a CONSTANT: num_tot, num_pos, MaskLoss's count_nonzero + 1, the branch of the clip
+ * and of smooth-L1, and BoxLoss's beta (the read of an assigned variable).  With c_b = weight * upstream[b]:
+ *   ClassLoss  p = clip(pred, eps, 1 - eps), t = (cls_true != 0), pt = t ? p : 1 - p;
+ *              grad = c_b / (num_tot_b + eps) * keep * cls_exists[b,c] * (t ? 1 : -1)
+ *                     * alpha * (gamma * (1 - pt)^(gamma - 1) * log pt - (1 - pt)^gamma / pt),
+ *              and 0 where pred < eps or pred > 1 - eps (equality passes, as tf.clip_by_value's gradient does);
+ *   BoxLoss    d = true - pred on positive anchors; grad = c_b / (num_pos_b + eps) / 4 * (|d| - beta/2 < beta ? -d / beta
+ *              : -sign(d)); zeros elsewhere, so an image without a positive anchor gets exact zeros.  With use_adjust the
+ *              moving statistics move ONCE per call, as by one forward call, and beta is this call's;
+ *   MaskLoss   for an RoI whose class cls = min(target) < C, channel cls only:
+ *              grad = c_b / (nz_b + 1) / (mh * mw) * dBCE, nz_b = the image's RoIs with a non-zero loss;
+ *   SegLoss    grad = c_b * seg_exist[b,c] / (C * HW) * dBCE;
+ *   dBCE/dp = -(y / (p + eps) - (1 - y) / (1 - p + eps)), y = keep * t + half_smooth.
+ * No float atomics, float32 terms with FP contraction off, float64 partial sums in block order; on `stream`, no host read.
+ * ------------------------------------------------------------------------------------------- */
+int ml_train_class_loss_grad_f32(const float *cls_true, const float *cls_pred, const float *assign_mask, const float *cls_exists,
+                                 int32_t B, int32_t A, int32_t C, float weight, float alpha, float gamma, void *workspace, float *out,
+                                 const float *upstream, int32_t through_sigmoid, float *grad, void *stream);
+/* grad [B,A,4], 16-byte aligned like loc_true and loc_pred                                                            */
+int ml_train_box_loss_grad_f32(const float *loc_true, const float *loc_pred, const float *assign_mask, int32_t B, int32_t A, float weight,
+                               float momentum, float one_minus_momentum, float beta, int32_t use_adjust, float *state, void *workspace,
+                               float *out, const float *upstream, float *grad, void *stream);
+/* grad [B,R,mh,mw,C]; B <= 32 as in the forward call                                                                  */
+int ml_train_mask_loss_grad_f32(const int32_t *mask_true, const float *mask_pred, int32_t B, int32_t R, int32_t mh, int32_t mw, int32_t C,
+                                float weight, float keep, float half_smooth, float *roi_loss, float *out, const float *upstream,
+                                int32_t through_sigmoid, float *grad, void *stream);
+/* grad [B,HW,C]                                                                                                       */
+int ml_train_seg_loss_grad_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
+                               float weight, float keep, float half_smooth, void *workspace, float *out, const float *upstream,
+                               int32_t through_sigmoid, float *grad, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Generator resizes: the cv2.resize(x, (ow, oh)) calls of the reference's MaskLabGenerator (engine/utils/generator/

@@ -194,6 +194,10 @@ SIGNATURES = {
     "ml_train_mask_loss_f32": (C.c_int, [_vp, _vp] + [_i32] * 5 + [_f32] * 3 + [_vp] * 3),
     "ml_train_assign_seg": (C.c_int, [_vp] + [_i32] * 7 + [_vp, _vp]),
     "ml_train_seg_loss_f32": (C.c_int, [_vp] * 3 + [_i32, _i64, _i32] + [_f32] * 3 + [_vp] * 3),
+    "ml_train_class_loss_grad_f32": (C.c_int, [_vp] * 4 + [_i32] * 3 + [_f32] * 3 + [_vp] * 3 + [_i32, _vp, _vp]),
+    "ml_train_box_loss_grad_f32": (C.c_int, [_vp] * 3 + [_i32] * 2 + [_f32] * 4 + [_i32] + [_vp] * 6),
+    "ml_train_mask_loss_grad_f32": (C.c_int, [_vp, _vp] + [_i32] * 5 + [_f32] * 3 + [_vp] * 3 + [_i32, _vp, _vp]),
+    "ml_train_seg_loss_grad_f32": (C.c_int, [_vp] * 3 + [_i32, _i64, _i32] + [_f32] * 3 + [_vp] * 3 + [_i32, _vp, _vp]),
     "ml_cv_resize_linear_u8": (C.c_int, [_vp, _vp, _i64] + [_i32] * 6 + [_vp]),
     "ml_cv_resize_linear_round_u8": (C.c_int, [_vp, _vp, _i32, _i64] + [_i32] * 5 + [_vp]),
     "ml_cv_resize_reference_host": (C.c_int, [_vp, _vp, _i32, _i64] + [_i32] * 6),
@@ -204,6 +208,7 @@ SIGNATURES = {
 POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1                           # ML_POLYGON_*
 CV_RESIZE_U8, CV_RESIZE_ROUND_U8, CV_RESIZE_ROUND_F32 = 0, 1, 2     # ML_CV_RESIZE_*
 TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1                    # ML_TRAIN_MASK_*
+TRAIN_MAX_BLOCKS = 512                                  # ML_TRAIN_MAX_BLOCKS
 EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3     # ML_EVAL_*
 EVAL_MAX_CLASSES = 16                                  # ML_EVAL_MAX_CLASSES
 JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*

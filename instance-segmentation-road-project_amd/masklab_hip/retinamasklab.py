@@ -3,9 +3,10 @@ build_backbone_network :19-37, build_detection_network :40-112, build_instance_n
 build_semantic_network :160-198, construct_inference_network :420-495, find_layer_name :646-649,
 and the deploy wrapper of load_masklab_inference_model_from_h5 :598-643 (DeployModel below).
 Same function names, argument meaning and return structure; the returned model runs eagerly on
-the MI355X kernels.  construct_trainer_network :223-395 is restated FORWARD ONLY (TrainerModel: target assignment,
-the four losses and the metrics of a batch with ground truth); construct_masklabdataset :398-417 builds the file-reading
-datasets (masklab_hip/utils/dataset).  Backward passes and optimizers stay out of scope.
+the MI355X kernels.  construct_trainer_network :223-395 is restated forward (TrainerModel: target assignment, the four
+losses and the metrics of a batch with ground truth) plus the losses' gradients at the head outputs
+(TrainerModel.loss_and_gradients); construct_masklabdataset :398-417 builds the file-reading datasets
+(masklab_hip/utils/dataset).  The backward of the heads and the backbone and the optimizers stay out of scope.
 """
 import numpy as np
 import torch
@@ -565,8 +566,9 @@ def construct_inference_network(configuration: ModelConfiguration, backbone_netw
 
 class TrainerModel(K.Layer):
     """The Keras functional `Model([images, gt_boxes, gt_boxes_exist, gt_masks, gt_seg, gt_seg_exist] -> losses and metrics)`
-    of reference :223-395, FORWARD ONLY and executed eagerly (no hipGraph, no fixed-capacity stage 2): what
-    `fit_generator(validation_data=...)` evaluates to report a checkpoint's validation losses.  The backbone and head layers
+    of reference :223-395, executed eagerly (no hipGraph, no fixed-capacity stage 2): what
+    `fit_generator(validation_data=...)` evaluates to report a checkpoint's validation losses.  `loss_and_gradients` adds the
+    gradients of the compiled scalar at the four head outputs; they stop there (the heads have no backward pass yet).  The backbone and head layers
     are the OBJECTS the inference model holds, as in the reference; the assignment, loss and metric layers are the model's
     own.  Every output is float32 [B]; the lists shrink like the reference's when a head group is None.
     `last_forward` keeps the intermediate tensors of the last call."""
@@ -686,7 +688,41 @@ class TrainerModel(K.Layer):
             t = t.to(dtype)
         return t.contiguous()
 
+    GRAD_OF = {"class_loss": "cls_pred", "box_loss": "loc_pred", "mask_loss": "roi_masks", "seg_loss": "seg_pred"}
+
     def call(self, inputs, **kwargs):
+        return self._forward(inputs, None)
+
+    def loss_and_gradients(self, inputs, upstream=None, wrt="predictions"):
+        """The forward of `call`, metrics included, with every loss layer run as `call_with_grad` -> (outputs, grads):
+        the outputs of `call` bit for bit, and grads = {"cls_pred", "loc_pred", "roi_masks", "seg_pred"} (those whose head
+        group is present), each shaped like that tensor of `last_forward`: the gradient of sum over the losses of
+        sum_b upstream[loss][b] * loss[b].  upstream None is 1 / B everywhere -- the scalar engine/train.py compiles,
+        add_loss(K.mean(loss)) per loss; a dict {loss name: float32 [B]} overrides single losses.  wrt="pre_activation"
+        gives the class, mask and seg gradients at the pre-activation of their output convs' fused sigmoid (loc_pred is
+        linear).  The gradients stop here: the heads have no backward pass yet.  Also kept in last_forward["grads"]."""
+        if wrt not in ("predictions", "pre_activation"):
+            raise ValueError(f"TrainerModel.loss_and_gradients: wrt must be 'predictions' or 'pre_activation', got {wrt!r}")
+        unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
+        if unknown:
+            raise ValueError(f"TrainerModel.loss_and_gradients: upstream names {unknown} are not losses ({sorted(self.GRAD_OF)})")
+        grads = {}
+        outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=wrt == "pre_activation", grads=grads))
+        self.last_forward["grads"] = grads
+        return outputs, grads
+
+    def _loss(self, layer, inputs, want):
+        """One loss layer: its forward, or with `want` its fused loss + gradient, the gradient filed under the prediction's name."""
+        if want is None:
+            return layer(inputs)
+        up = want["upstream"].get(layer.name)
+        if up is not None:
+            up = self._dev(up, torch.float32)
+        sig = want["through_sigmoid"] and layer.name != "box_loss"
+        loss, want["grads"][self.GRAD_OF[layer.name]] = layer.call_with_grad(inputs, upstream=up, through_sigmoid=sig)
+        return loss
+
+    def _forward(self, inputs, want):
         if self.device is None:
             raise RuntimeError("TrainerModel: call load_weights(weights, device) first")
         cfg = self.configuration
@@ -707,8 +743,8 @@ class TrainerModel(K.Layer):
             gt_boxes = self._dev(x['gt_boxes'], torch.float32)
             gt_boxes_exist = self._dev(x['gt_boxes_exist'], torch.float32)
             cls_true, loc_true, assign_mask = self.assign_boxes([gt_boxes, pr_boxes])
-            outputs += [self.class_loss([cls_true, cls_pred, assign_mask, gt_boxes_exist]),
-                        self.box_loss([loc_true, loc_pred, assign_mask])]
+            outputs += [self._loss(self.class_loss, [cls_true, cls_pred, assign_mask, gt_boxes_exist], want),
+                        self._loss(self.box_loss, [loc_true, loc_pred, assign_mask], want)]
             # The metric's proposals stay at capacity (-1 padded): DetectionIOUMetric counts rows, so the reference's
             # trimmed tensor gives the same numbers, and nothing is read by the host.
             restored_boxes = self.metric_restore([loc_pred, pr_boxes])
@@ -728,7 +764,7 @@ class TrainerModel(K.Layer):
                 roi_masks = mask_subnet(roi_fmaps)
                 gt_masks = self._dev(x['gt_masks'])
                 match_gt_masks = self.assign_masks([roi_boxes, roi_masks, gt_boxes, gt_masks])
-                outputs.append(self.mask_loss([match_gt_masks, roi_masks]))
+                outputs.append(self._loss(self.mask_loss, [match_gt_masks, roi_masks], want))
                 fw.update(proposed_loss=proposed_loss, roi_boxes=roi_boxes, roi_masks=roi_masks, match_gt_masks=match_gt_masks)
         if self.semantic_networks is not None:
             sem_config = cfg.semantic
@@ -737,7 +773,7 @@ class TrainerModel(K.Layer):
             gt_seg = self._dev(x['gt_seg'])
             gt_seg_exist = self._dev(x['gt_seg_exist'], torch.float32)
             seg_assigned = self.assign_seg([gt_seg, seg_pred])
-            outputs.append(self.seg_loss([seg_assigned, seg_pred, gt_seg_exist]))
+            outputs.append(self._loss(self.seg_loss, [seg_assigned, seg_pred, gt_seg_exist], want))
             outputs += list(self.class_iou([seg_assigned, seg_pred]))
             fw.update(seg_pred=seg_pred, seg_assigned=seg_assigned)
         self.last_forward = fw
@@ -752,14 +788,14 @@ class TrainerModel(K.Layer):
 
 def construct_trainer_network(configuration: ModelConfiguration, backbone_network, detection_networks=None,
                               semantic_networks=None, instance_networks=None):
-    """Same signature as reference :223-227; the returned model is forward only."""
+    """Same signature as reference :223-227; the returned model's gradients stop at the head outputs."""
     return TrainerModel(configuration, backbone_network, detection_networks=detection_networks,
                         semantic_networks=semantic_networks, instance_networks=instance_networks)
 
 
 def construct_masklab_networks(config: ModelConfiguration, with_trainer=False):
-    """Reference :201-220 returns (trainer, inference).  The trainer network (forward only: losses and metrics of a
-    batch with ground truth) is built on request; by default the first element is None."""
+    """Reference :201-220 returns (trainer, inference).  The trainer network (losses and metrics of a batch with
+    ground truth, gradients at the head outputs) is built on request; by default the first element is None."""
     K.clear_session()
     backbone_network = build_backbone_network(config)
     detection_networks = build_detection_network(config)

@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""The four loss layers' backward (csrc/train_grads.hip) at the default configuration's 8 x 1024 x 1024 shapes -- A = 327 360
+priors and 5 classes for ClassLoss / BoxLoss(use_adjust), 132 RoIs (32 ground truths + 100 proposals) of 28 x 28 x 5 for
+MaskLoss, the 128 x 128 x 3 map of the skip level for SegLoss -- per loss four numbers:
+
+  (a) forward   the forward-only op (ops.class_loss, ...): what a validation step pays;
+  (b) fused     the fused "loss + gradient" op (ops.class_loss_grad, ...), upstream 1 / B;
+  (c) autograd  torch autograd on the device over a float32 tensor-op restatement of the same loss: forward + backward,
+                the gradient with respect to the prediction.  Not a product path: a yardstick only;
+  (d) floor     the bytes of (a)'s reads plus ONE write of the gradient, over the sustained copy rate of
+                profiles/r03_peaks.json.  A separate backward pass would read everything again; (b) should cost (a) plus that
+                one write.  ClassLoss and BoxLoss also read the [B,A] mask once more for the count their gradient is divided
+                by (`count_pass_bytes`, not part of the floor).
+
+Each number is the HIP-event time of `--inner` back-to-back calls divided by their number, `--steps` such windows after a
+warm-up; median, min, max.  The calls of a window rotate through enough copies of the inputs that their footprint exceeds
+`--footprint-mb` (default 768): the 256 MiB last-level cache cannot hold an input from one call to the next.  The outputs come
+from torch's caching allocator, as in the product path.  The calls are enqueued from Python, so for the small shapes
+(MaskLoss, SegLoss) the event time is an upper bound set by the host; `enqueue_ms` says when.  One JSON line per loss;
+the gradients of (b) and (c) must agree to 1e-3 of the largest gradient, nothing else is asserted.
+
+Usage (GPU box):  timeout 900 python scripts/loss_grad_timing.py [--steps 7] [--inner 10] [--warmup 2]"""
+import argparse
+import json
+import math
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "instance-segmentation-road-project_amd"), os.path.join(ROOT, "scripts")]
+
+from generator_timing import time_launch  # noqa: E402
+
+C, G, ROIS, CROP, SEG_C = 5, 32, 132, 28, 3
+LOSS = dict(cls_weight=300., alpha=.25, gamma=2., box_weight=1., momentum=.9, beta=.11, mask_weight=1e-2, seg_weight=.5)
+EPS = 1e-7
+
+
+# ----------------------------------------------------------------------------- (c): the losses in torch tensor ops, float32
+def torch_class_loss(cls_true, cls_pred, mask, exist):
+    import torch
+    neg, pos, keep = (mask == 1).float(), (mask == 0).float(), (mask != -1).float()
+    pc = cls_pred.clamp(EPS, 1 - EPS)
+    pt = torch.where(cls_true != 0, pc, 1 - pc)
+    focal = LOSS["alpha"] * (-torch.pow(1 - pt, LOSS["gamma"]) * torch.log(pt)) * exist[:, None, :]
+    return LOSS["cls_weight"] * (keep * focal).sum(dim=(1, 2)) / ((pos + neg).sum(dim=(1, 2)) + EPS)
+
+
+def torch_box_loss(loc_true, loc_pred, mask, state):
+    import torch
+    pos = (mask == 0).float()
+    with torch.no_grad():                                            # the statistics and beta carry no gradient
+        offsets = (loc_true - loc_pred).abs() * pos
+        mean = offsets.mean(dim=(0, 1))
+        var = ((offsets - mean) ** 2).mean(dim=(0, 1))
+        state[:4] = state[:4] * LOSS["momentum"] + mean * (1 - LOSS["momentum"])
+        state[4:] = state[4:] * LOSS["momentum"] + var * (1 - LOSS["momentum"])
+        beta = (state[:4] - state[4:]).clamp(1e-3, LOSS["beta"])
+    d = loc_true - loc_pred
+    l1, l2 = d.abs() - 0.5 * beta, 0.5 * d ** 2 / beta
+    box = torch.where(l1 < beta, l2, l1).mean(dim=-1)
+    return LOSS["box_weight"] * (pos[..., 0] * box).sum(dim=1) / (pos.sum(dim=(1, 2)) + EPS)
+
+
+def torch_bce(y, p):
+    import torch
+    return -(y * torch.log(p + EPS) + (1 - y) * torch.log(1 - p + EPS))
+
+
+def torch_mask_loss(mask_true, mask_pred):
+    import torch
+    classes = mask_true.amin(dim=(2, 3))
+    chosen = classes < C
+    idx = classes.clamp(max=C - 1).long()[..., None, None, None].expand(-1, -1, CROP, CROP, 1)
+    p = torch.gather(mask_pred, 4, idx)[..., 0]
+    y = (mask_true == classes[..., None, None]).float()
+    roi = torch_bce(y, p).mean(dim=(2, 3)) * chosen.float()
+    return LOSS["mask_weight"] * roi.sum(dim=1) / (torch.count_nonzero(roi.detach(), dim=1) + 1).float()
+
+
+def torch_seg_loss(seg_true, seg_pred, exist):
+    return LOSS["seg_weight"] * (exist * torch_bce(seg_true, seg_pred).mean(dim=(1, 2))).mean(dim=1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, default=1024)
+    ap.add_argument("--footprint-mb", type=int, default=768)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from masklab_hip import ModelConfiguration, ops
+    from masklab_hip import retinamasklab as R
+    if not torch.cuda.is_available():
+        raise SystemExit("loss_grad_timing: no GPU -- nothing is measured without one")
+    B, size = args.batch, args.size
+    gen = torch.Generator(device="cuda").manual_seed(size)
+    A = len(R.build_detection_network(ModelConfiguration())[0].prior.anchors(size, size, 'same'))
+    with open(os.path.join(ROOT, "profiles", "r03_peaks.json")) as f:
+        rate = json.load(f)["copy_global_x4"]["read_plus_write_GBs"]
+    rand = lambda *shape: torch.rand(shape, device="cuda", generator=gen)
+    up = torch.full((B,), 1.0 / B, device="cuda")
+    fresh = torch.tensor([LOSS["beta"]] * 4 + [0.] * 4, device="cuda")
+    n, sh = B * A, size // 8
+
+    def class_inputs():
+        mask = torch.randint(-1, 2, (B, A, 1), device="cuda", generator=gen).float()
+        true = (torch.randint(0, C + 1, (B, A, 1), device="cuda", generator=gen) == torch.arange(C, device="cuda")).float()
+        return true, rand(B, A, C).clamp(1e-4, 1 - 1e-4), mask, torch.ones((B, C), device="cuda")
+
+    def box_inputs():
+        mask = (torch.rand((B, A, 1), device="cuda", generator=gen) < 0.002).float() * -1 + 1      # ~0.2 % positives (mask 0)
+        return torch.randn((B, A, 4), device="cuda", generator=gen) * (mask == 0), torch.randn((B, A, 4), device="cuda", generator=gen), mask
+
+    def mask_inputs():
+        cls = torch.randint(0, C + 1, (B, ROIS, 1, 1), device="cuda", generator=gen, dtype=torch.int32)   # C: not selected
+        inside = torch.rand((B, ROIS, CROP, CROP), device="cuda", generator=gen) < 0.5
+        return torch.where(inside, cls.expand(-1, -1, CROP, CROP), torch.full_like(cls, C)).contiguous(), \
+            rand(B, ROIS, CROP, CROP, C).clamp(1e-4, 1 - 1e-4)
+
+    def seg_inputs():
+        return (rand(B, sh, sh, SEG_C) < 0.5).float(), rand(B, sh, sh, SEG_C).clamp(1e-4, 1 - 1e-4), torch.ones((B, SEG_C), device="cuda")
+
+    legs = {
+        "class_loss": dict(inputs=class_inputs, pred=1, bytes=dict(forward_reads=4 * n * (2 * C + 1), grad_write=4 * n * C),
+                           count_pass_bytes=4 * n,
+                           forward=lambda x: ops.class_loss(*x, LOSS["cls_weight"], LOSS["alpha"], LOSS["gamma"]),
+                           fused=lambda x: ops.class_loss_grad(*x, LOSS["cls_weight"], LOSS["alpha"], LOSS["gamma"], upstream=up),
+                           torch=lambda x, p: torch_class_loss(x[0], p, x[2], x[3])),
+        "box_loss(use_adjust)": dict(inputs=box_inputs, pred=1, bytes=dict(forward_reads=3 * 4 * n * 9, grad_write=4 * n * 4),
+                                     count_pass_bytes=4 * n,
+                                     forward=lambda x: ops.box_loss(*x, LOSS["box_weight"], LOSS["momentum"], LOSS["beta"], True, fresh.clone()),
+                                     fused=lambda x: ops.box_loss_grad(*x, LOSS["box_weight"], LOSS["momentum"], LOSS["beta"], True,
+                                                                       fresh.clone(), upstream=up),
+                                     torch=lambda x, p: torch_box_loss(x[0], p, x[2], fresh.clone())),
+        "mask_loss": dict(inputs=mask_inputs, pred=1,
+                          bytes=dict(forward_reads=8 * B * ROIS * CROP * CROP + 4 * B * ROIS * CROP * CROP,
+                                     grad_write=4 * B * ROIS * CROP * CROP * C),
+                          count_pass_bytes=0, forward=lambda x: ops.mask_loss(*x, LOSS["mask_weight"], 0.),
+                          fused=lambda x: ops.mask_loss_grad(*x, LOSS["mask_weight"], 0., upstream=up),
+                          torch=lambda x, p: torch_mask_loss(x[0], p)),
+        "seg_loss": dict(inputs=seg_inputs, pred=1, bytes=dict(forward_reads=8 * B * sh * sh * SEG_C, grad_write=4 * B * sh * sh * SEG_C),
+                         count_pass_bytes=0, forward=lambda x: ops.seg_loss(*x, LOSS["seg_weight"], 0.),
+                         fused=lambda x: ops.seg_loss_grad(*x, LOSS["seg_weight"], 0., upstream=up),
+                         torch=lambda x, p: torch_seg_loss(x[0], p, x[2])),
+    }
+    for name, leg in legs.items():
+        first = leg["inputs"]()
+        per_copy = sum(t.numel() * t.element_size() for t in first)
+        copies = min(64, max(1, math.ceil(args.footprint_mb * 2 ** 20 / per_copy)))
+        sets = [first] + [tuple(t.clone() for t in first) for _ in range(copies - 1)]
+        kept = {}
+
+        def autograd(k):
+            p = sets[k][leg["pred"]].detach().requires_grad_(True)
+            (leg["torch"](sets[k], p) * up).sum().backward()
+            kept["autograd"] = p.grad
+
+        def fused(k):
+            kept["fused"] = leg["fused"](sets[k])
+
+        line = {"loss": name, "shape": f"{B}x{size}x{size}", "prediction": list(first[leg["pred"]].shape), "copies_rotated": copies}
+        for path, fn in (("forward", lambda k: leg["forward"](sets[k])), ("fused", fused), ("autograd", autograd)):
+            ms, enq = time_launch(fn, copies, args.steps, args.inner, args.warmup)
+            line[path] = {"ms_median": round(float(np.median(ms)), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+                          "enqueue_ms": round(float(np.median(enq)), 4)}
+        fused(0), autograd(0)
+        torch.cuda.synchronize()
+        got, want = kept["fused"][1], kept["autograd"]
+        agree = bool((got - want).abs().max() <= 1e-3 * want.abs().max())
+        floor_ms = sum(leg["bytes"].values()) / (rate * 1e9) * 1e3
+        a, b, c = (line[p]["ms_median"] for p in ("forward", "fused", "autograd"))
+        line.update(bytes=leg["bytes"], count_pass_bytes=leg["count_pass_bytes"], copy_rate_GBs=rate, floor_ms=round(floor_ms, 4),
+                    fused_over_floor=round(b / floor_ms, 2), fused_over_forward=round(b / a, 2),
+                    fused_over_forward_plus_autograd=round(b / (a + c), 3), fused_faster_than_forward_plus_autograd=bool(b < a + c),
+                    gradients_agree=agree)
+        print(json.dumps(line), flush=True)
+        assert agree, f"{name}: the fused gradient differs from torch autograd's"
+        del sets, first, kept
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
