@@ -64,7 +64,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             _entropy / _workspace_bytes / _u8 / _reference_host;
                                             (additive, same version) ml_jpeg_entropy_geometry / _plan_bytes /
                                             _plan / _workspace_bytes / _device / _reference_host;
-                                            (additive, same version) ml_conv1x1_dual_f32 / _f16             */
+                                            (additive, same version) ml_conv1x1_dual_f32 / _f16;
+                                            (additive, same version) ml_gn_grad_desc, ml_groupnorm_chunk_grad_f32 /
+                                            _grad_multi_f32 / _grad_workspace_bytes, ml_groupnorm_chunk_stats_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -364,6 +366,47 @@ typedef struct ml_gn_desc {
 } ml_gn_desc;
 #define ML_GN_MAX_PROBLEMS 8
 int ml_groupnorm_multi_f32(const ml_gn_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------- GroupNormalization, backward (fp32 only)
+ * TensorFlow's gradient of the expression above.  For the chunk (n, g) with values x_i, i < L = HWC/G:
+ *   j_i = g*(C/G) + (i mod C/G)    (= the forward's index: chunks start at multiples of C/G)
+ *   xhat_i = (x_i - mean) * r,  r = 1/sqrt(var + eps)  (biased statistics of the chunk),  y_i = xhat_i*gamma[j_i] + beta[j_i]
+ *   d_i  = dy_i * [y_i > 0]   if relu (the forward's fused ReLU; strict), else dy_i;      g_i = d_i * gamma[j_i]
+ *   dx_i = r * (g_i - mean_i(g) - xhat_i * mean_i(g * xhat))                              (* [x_i > 0] if input_relu)
+ *   dbeta[j] = sum d_i,  dgamma[j] = sum d_i * xhat_i   over all samples, chunks and positions with j_i = j.
+ * input_relu: x is the ReLU output of the layer below (the towers' Conv3x3 + ReLU -> GroupNormalization) and dx is wanted
+ * at that layer's pre-activation.
+ * gamma == NULL: ones (scale=False).  beta is read only when relu (NULL: zeros).  dgamma / dbeta: [C] or NULL (skipped; both
+ * are written in full otherwise).  dx may be dy itself (in place on the gradient buffer); it may not overlap x.
+ * stats: NULL, or the [N*G][2] (sum x, sum x^2) of ml_groupnorm_chunk_stats_f32 -- with relu and chunks of more than 4096
+ * floats the mask needs them before anything is summed, and without `stats` a statistics pass over x runs first.  The results
+ * have the same bits with and without `stats`.
+ * All sums are fp64, reduced in a fixed order; no atomics: two launches give the same bits.
+ * workspace: >= ml_groupnorm_grad_workspace_bytes(N, G, C) bytes; nothing in it needs initialising. */
+int64_t ml_groupnorm_grad_workspace_bytes(int32_t N, int32_t G, int32_t C);
+int ml_groupnorm_chunk_grad_f32(const float *x, const float *dy, const float *gamma, const float *beta, float *dx,
+                                float *dgamma, float *dbeta, const double *stats, int32_t N, int64_t HWC,
+                                int32_t C, int32_t G, float eps, int32_t relu, int32_t input_relu,
+                                void *workspace, void *stream);
+/* (sum x, sum x^2) of every chunk in fp64, stats[(n*G + g)*2 + {0, 1}]: the forward's statistics pass on its own.
+ * workspace: >= ml_groupnorm_workspace_bytes(N, G) bytes. */
+int ml_groupnorm_chunk_stats_f32(const float *x, double *stats, int32_t N, int64_t HWC, int32_t C, int32_t G,
+                                 void *workspace, void *stream);
+/* Several backward problems in one launch set (the five pyramid levels of a tower depth), as ml_groupnorm_multi_f32: up to
+ * ML_GN_MAX_PROBLEMS problems, each with 16-byte aligned tensors and HWC/G and C multiples of 4; the same bits as the
+ * single calls.  workspace_bytes >= the sum over the problems of ml_groupnorm_grad_workspace_bytes(N, G, C). */
+typedef struct ml_gn_grad_desc {
+    const float *x, *dy;           /* the layer's input, the gradient at its output                */
+    const float *gamma, *beta;     /* [C] or NULL                                                  */
+    float *dx;                     /* like x; may be dy                                            */
+    float *dgamma, *dbeta;         /* [C] or NULL                                                  */
+    const double *stats;           /* [N*G][2] or NULL                                             */
+    int64_t HWC;                   /* floats per sample                                            */
+    int32_t N, C, G, relu, input_relu;
+    float eps;
+} ml_gn_grad_desc;
+int ml_groupnorm_grad_multi_f32(const ml_gn_grad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
+                                void *stream);
 
 /* ---------------------------------------------------------------- resampling / reductions
  * tf.compat.v1.image.resize_bilinear(align_corners=True) (engine/layers/misc.py:306), with the

@@ -12,103 +12,9 @@
 //   pass 2: grid (S2, N*G): each block folds the S partials, then normalises its slice.
 // Storage type T: float, or IEEE half (the heads of the fp16 path: x and y are half, 8 per 16-byte access; statistics
 // are fp64 sums of the stored values, the normalisation runs in fp32 and is rounded ONCE at the store).
-#include <type_traits>
-#include "common.h"
+#include "gn_common.h"
 
 namespace {
-
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
-
-// one 16-byte access = VW<T> elements, handled as floats
-template <class T> struct VW { static constexpr int value = 16 / sizeof(T); };
-template <class T>
-__device__ __forceinline__ void vload(const T *p, float (&v)[VW<T>::value]) {
-    if constexpr (std::is_same<T, float>::value) {
-        const f32x4 x = *reinterpret_cast<const f32x4 *>(p);
-        v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-    } else {
-        const f16x8g x = *reinterpret_cast<const f16x8g *>(p);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
-    }
-}
-template <class T>
-__device__ __forceinline__ void vstore(T *p, const float (&v)[VW<T>::value]) {
-    if constexpr (std::is_same<T, float>::value) {
-        const f32x4 x = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4 *>(p) = x;
-    } else {
-        const f16x8g x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
-                          (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
-        *reinterpret_cast<f16x8g *>(p) = x;
-    }
-}
-
-constexpr int GN_TPB = 256;
-constexpr int GN_MAX_SPLIT = 64;
-// Largest chunk the one-pass (register-resident) kernel takes.  Measured on MI355X: one block per chunk wins
-// while the chunk is small (8x8 .. 32x32 maps, 14x14 RoI maps: 6.3 vs 9.8 us, 8.0 vs 10.2 us); from 64x64x128
-// maps up (chunk 32 768 floats, 128 fat blocks) the sliced two-pass form has the parallelism and is faster
-// (19.8 vs 23.7 us), even though it reads x twice.
-constexpr int GN_ONEPASS_MAX = 4096;
-
-struct GnPlan { int S; long long slice; };
-
-// slices are multiples of vw*GN_TPB elements (vw = 4 floats / 8 halves per access) so every block runs whole sweeps
-static GnPlan gn_plan(long long L, int NG, int vw = 4) {
-    long long want = (2048 + NG - 1) / NG;            // aim at >= 2048 blocks on the chip
-    if (want < 1) want = 1;
-    if (want > GN_MAX_SPLIT) want = GN_MAX_SPLIT;
-    const long long unit = (long long)vw * GN_TPB;
-    long long slice = ((L + want - 1) / want + unit - 1) / unit * unit;
-    int S = (int)((L + slice - 1) / slice);
-    return {S, slice};
-}
-
-template <class T, bool VEC4 = true>
-__device__ __forceinline__ void gn_stats_body(const T *__restrict__ x, double *__restrict__ ws, long long L,
-                                              long long slice, int S, int ng, int s) {
-    constexpr int W = VW<T>::value;
-    const T *p = x + (long long)ng * L;
-    const long long lo = (long long)s * slice;
-    const long long hi = min(lo + slice, L);
-    double sum = 0.0, sq = 0.0;
-    if (VEC4) {
-        // a vector is folded in fp32 first (3 adds, 4 fma per 4 values), then joins the fp64 running sums: the kernel
-        // was bound by its fp64 instruction count (12 per float4), not by HBM
-        for (long long i = lo + threadIdx.x * W; i < hi; i += GN_TPB * W) {
-            float v[W];
-            vload<T>(p + i, v);
-            float s4 = (v[0] + v[1]) + (v[2] + v[3]);
-            float q4 = fmaf(v[3], v[3], fmaf(v[2], v[2], fmaf(v[1], v[1], v[0] * v[0])));
-            if constexpr (W == 8) {
-                s4 += (v[4] + v[5]) + (v[6] + v[7]);
-                q4 += fmaf(v[7], v[7], fmaf(v[6], v[6], fmaf(v[5], v[5], v[4] * v[4])));
-            }
-            sum += (double)s4;
-            sq += (double)q4;
-        }
-    } else {
-        for (long long i = lo + threadIdx.x; i < hi; i += GN_TPB) { const double d = (double)(float)p[i]; sum += d; sq += d * d; }
-    }
-    // wave reduce (64 lanes) then across the 4 waves
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sum += __shfl_down(sum, off, 64);
-        sq += __shfl_down(sq, off, 64);
-    }
-    __shared__ double red[2][GN_TPB / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { red[0][wave] = sum; red[1][wave] = sq; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double a = 0, b = 0;
-#pragma unroll
-        for (int w = 0; w < GN_TPB / 64; ++w) { a += red[0][w]; b += red[1][w]; }
-        ws[((long long)ng * S + s) * 2 + 0] = a;
-        ws[((long long)ng * S + s) * 2 + 1] = b;
-    }
-}
 
 template <class T, bool VEC4>
 __global__ void gn_stats_kernel(const T *__restrict__ x, double *__restrict__ ws, long long L, long long slice,
@@ -125,16 +31,8 @@ __device__ __forceinline__ void gn_apply_body(const T *x, T *y, const float *__r
     const int g = ng % G;
     const int cg = C / G;
     if (Sp < 0) Sp = S;
-    double sum = 0, sq = 0;
-    for (int i = 0; i < Sp; ++i) {  // uniform, L2-resident, fixed order
-        sum += ws[((long long)ng * Sp + i) * 2 + 0];
-        sq += ws[((long long)ng * Sp + i) * 2 + 1];
-    }
-    const double meand = sum / (double)L;
-    double vard = sq / (double)L - meand * meand;
-    if (vard < 0) vard = 0;
-    const float mean = (float)meand;
-    const float rstd = (float)(1.0 / sqrt(vard + (double)eps));
+    const GnMoments m = gn_moments(ws, ng, Sp, L, eps);
+    const float mean = m.mean, rstd = m.rstd;
     const T *p = x + (long long)ng * L;
     const bool dense = (out_cs == C);
     // dense: y has x's layout.  sliced: element f of the sample -> y[n][f / C][out_co + f % C]
@@ -198,9 +96,7 @@ __device__ __forceinline__ void gn_apply_body(const T *x, T *y, const float *__r
                 int c = c0 + e;
                 if (c >= C) c -= C;
                 const int j = g * cg + (c % cg);
-                float t = (v[e] - mean) * rstd;
-                if (gamma) t *= gamma[j];
-                if (beta) t += beta[j];
+                const float t = gn_y(v[e], mean, rstd, gamma, beta, j);
                 o[e] = relu ? fmaxf(t, 0.f) : t;
             }
             if (dense) vstore<T>(q + i, o);
@@ -210,9 +106,7 @@ __device__ __forceinline__ void gn_apply_body(const T *x, T *y, const float *__r
         for (long long i = lo + threadIdx.x; i < hi; i += GN_TPB) {
             const int c = (int)((gbase + i) % C);
             const int j = g * cg + (c % cg);
-            float t = ((float)p[i] - mean) * rstd;
-            if (gamma) t *= gamma[j];
-            if (beta) t += beta[j];
+            const float t = gn_y((float)p[i], mean, rstd, gamma, beta, j);
             const float r = relu ? fmaxf(t, 0.f) : t;
             if (dense) q[i] = (T)r;
             else q[((gbase + i) / C) * out_cs + c] = (T)r;
@@ -228,20 +122,6 @@ __global__ void gn_apply_kernel(const T *x, T *y, const float *__restrict__ gamm
 }
 
 // ---- one-pass form: the chunk lives in registers.  Block (TPB threads) = one (sample, chunk).
-template <int TPB>
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();                       // `red` may still be read from the previous reduction
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double t = 0;
-#pragma unroll
-    for (int w = 0; w < TPB / 64; ++w) t += red[w];
-    return t;
-}
-
 template <class T, int TPB, int VPT>
 __device__ __forceinline__ void gn_onepass_body(const T *__restrict__ x, T *__restrict__ y,
                                                 const float *__restrict__ gamma, const float *__restrict__ beta, int L,
@@ -292,9 +172,7 @@ __device__ __forceinline__ void gn_onepass_body(const T *__restrict__ x, T *__re
             int c = c0 + e;
             if (c >= C) c -= C;
             const int j = g * cg + (c % cg);
-            float t = (v[k][e] - mean) * rstd;
-            if (gamma) t *= gamma[j];
-            if (beta) t += beta[j];
+            const float t = gn_y(v[k][e], mean, rstd, gamma, beta, j);
             o[e] = relu ? fmaxf(t, 0.f) : t;
         }
         if (dense) vstore<T>(q + i, o);

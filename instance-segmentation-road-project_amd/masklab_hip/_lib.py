@@ -49,6 +49,14 @@ class GnDesc(C.Structure):
                 ("partials", C.c_void_p), ("n_partials", C.c_int32), ("reserved2", C.c_int32)]
 
 
+class GnGradDesc(C.Structure):
+    """Mirror of `ml_gn_grad_desc` (include/masklab_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("dx", C.c_void_p),
+                ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("stats", C.c_void_p), ("HWC", C.c_int64),
+                ("N", C.c_int32), ("C", C.c_int32), ("G", C.c_int32), ("relu", C.c_int32), ("input_relu", C.c_int32),
+                ("eps", C.c_float)]
+
+
 class DeconvOutProblem(C.Structure):
     """Mirror of `ml_deconv_out_problem` (include/masklab_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("wd", C.c_void_p), ("bd", C.c_void_p), ("wo_table", C.c_void_p),
@@ -125,6 +133,10 @@ SIGNATURES = {
     "ml_groupnorm_workspace_bytes": (_i64, [_i32, _i32]),
     "ml_groupnorm_multi_f32": (C.c_int, [C.POINTER(GnDesc), _i32, _vp, _i64, _vp]),
     "ml_groupnorm_chunk_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _f32, _i32, _i32, _i32, _vp, _vp]),
+    "ml_groupnorm_grad_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "ml_groupnorm_chunk_grad_f32": (C.c_int, [_vp] * 8 + [_i32, _i64, _i32, _i32, _f32, _i32, _i32, _vp, _vp]),
+    "ml_groupnorm_chunk_stats_f32": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]),
+    "ml_groupnorm_grad_multi_f32": (C.c_int, [C.POINTER(GnGradDesc), _i32, _vp, _i64, _vp]),
     "ml_resize_bilinear_ac_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 12 + [_vp]),
     "ml_global_mean_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ml_scale_channels_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),

@@ -1,5 +1,5 @@
 """GroupNormalization -- drop-in for reference engine/normalization.py (the Keras layer),
-running the chunk-norm HIP kernel (csrc/groupnorm.hip).
+running the chunk-norm HIP kernel (csrc/groupnorm.hip) and its backward (csrc/groupnorm_grad.hip).
 
 The reference layer with axis=-1 on NHWC does NOT group channels: it reshapes [N,H,W,C]
 row-major to [N,G,H,W,C/G] and normalises over axes (2,3,4) (normalization.py:123-143), i.e.
@@ -90,6 +90,42 @@ class GroupNormalization(Layer):
             probs.append(dict(x=x, gamma=layer.gamma, beta=layer.beta, groups=layer.groups, eps=layer.epsilon,
                               out=x if inplace else None, live=live, partials=part))
         return ops.groupnorm_chunk_multi(probs)
+
+    def _check_loaded(self, shape):
+        if not self.built:
+            self.build(tuple(shape))
+        if (self.scale and self.gamma is None) or (self.center and self.beta is None):
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+
+    def _grads(self, dgamma, dbeta):
+        """the weights this layer has (`scale` / `center`)"""
+        return {k: v for k, v, has in (("gamma", dgamma, self.scale), ("beta", dbeta, self.center)) if has}
+
+    def backward(self, inputs, grad_outputs, fuse_relu=False, input_relu=False, inplace=False, stats=None):
+        """The layer's backward (ops.groupnorm_chunk_grad), float32 only.
+        inputs: what the layer was CALLED on.  The inference forward normalises in place and so destroys it: a caller that
+        wants gradients calls the layer with inplace=False and keeps `inputs`.  grad_outputs: the gradient at the layer's
+        output; fuse_relu: as in that call.  input_relu: `inputs` is a ReLU's output and the gradient is wanted in front of
+        that ReLU (the tower unit Conv3x3 + ReLU -> GroupNormalization).  inplace: write the result over grad_outputs.
+        -> (grad_inputs, {"gamma": ..., "beta": ...}) with the weights the layer has."""
+        self._check_loaded(inputs.shape)
+        dx, dgamma, dbeta = ops.groupnorm_chunk_grad(inputs, grad_outputs, self.gamma, self.beta, self.groups, self.epsilon,
+                                                     relu=fuse_relu, input_relu=input_relu, stats=stats,
+                                                     out=grad_outputs if inplace else None)
+        return dx, self._grads(dgamma, dbeta)
+
+    @staticmethod
+    def backward_multi(layers, inputs, grad_outputs, fuse_relu=False, input_relu=False, inplace=False):
+        """backward() of several layers on their own inputs in ONE launch set (the counterpart of call_multi: the towers run
+        depth-major over five pyramid levels): results identical to calling each.  With a problem that is not vectorisable
+        in the list the single calls run, as in call_multi (ops.groupnorm_chunk_grad_multi).  -> list of (grad_inputs, {...})"""
+        probs = []
+        for layer, x, dy in zip(layers, inputs, grad_outputs):
+            layer._check_loaded(x.shape)
+            probs.append(dict(x=x, dy=dy, gamma=layer.gamma, beta=layer.beta, groups=layer.groups, eps=layer.epsilon,
+                              relu=fuse_relu, input_relu=input_relu, out=dy if inplace else None))
+        return [(dx, layer._grads(dgamma, dbeta))
+                for layer, (dx, dgamma, dbeta) in zip(layers, ops.groupnorm_chunk_grad_multi(probs))]
 
     def get_config(self):
         config = {

@@ -714,6 +714,113 @@ def groupnorm_chunk_multi(problems):
     return outs
 
 
+def groupnorm_chunk_stats(x, groups):
+    """(sum x, sum x^2) of every chunk of the chunk-wise GroupNormalization, float64 [N*groups, 2]: the forward's statistics
+    pass on its own.  Accepted as `stats=` by groupnorm_chunk_grad, whose relu=True form then needs no pass of its own."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 2:
+        raise ValueError("groupnorm_stats: x must be a float32 tensor [N, ..., C]")
+    N, Cc = x.shape[0], x.shape[-1]
+    if groups < 1 or Cc % groups:
+        raise ValueError(f"groupnorm_stats: Number of groups ({groups}) must be a multiple of the number of channels ({Cc}).")
+    _require_dev(x, "x")
+    lib = _lib.load()
+    stats = torch.empty((N * groups, 2), dtype=torch.float64, device=x.device)
+    ws = workspace(lib.ml_groupnorm_workspace_bytes(N, groups), x.device, "gn")
+    with _Prof("groupnorm_stats", 0, x.element_size() * x.numel(), f"N={N} HWC={x.numel() // N} G={groups}"):
+        _lib.check(lib.ml_groupnorm_chunk_stats_f32(_ptr(x), _ptr(stats), N, x.numel() // N, Cc, groups, _ptr(ws), _stream()),
+                   "ml_groupnorm_chunk_stats_f32")
+    return stats
+
+
+def _gn_grad_problem(x, dy, gamma, beta, groups, eps=1e-5, relu=False, input_relu=False, stats=None, out=None,
+                     want_param_grads=True):
+    """The argument checks of one backward problem (shapes and dtypes first: they need no device), and its outputs.
+    -> (dx, dgamma, dbeta)"""
+    for name, t in (("x", x), ("dy", dy)):
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise ValueError(f"groupnorm_grad: `{name}` must be a tensor [N, ..., C]")
+        if t.dtype != torch.float32:
+            raise TypeError(f"groupnorm_grad: `{name}` is {t.dtype}; the backward is float32 only")
+    if tuple(dy.shape) != tuple(x.shape):
+        raise ValueError(f"groupnorm_grad: dy {tuple(dy.shape)} must have x's shape {tuple(x.shape)}")
+    N, Cc = x.shape[0], x.shape[-1]
+    if groups < 1 or groups > Cc or Cc % groups:
+        raise ValueError(f"groupnorm_grad: Number of groups ({groups}) must be a multiple of the number of channels ({Cc}).")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (Cc,)):
+            raise ValueError(f"groupnorm_grad: `{name}` must be float32 [{Cc}]")
+    if stats is not None and (stats.dtype != torch.float64 or tuple(stats.shape) != (N * groups, 2)):
+        raise ValueError(f"groupnorm_grad: `stats` must be float64 [{N * groups}, 2] (groupnorm_chunk_stats)")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape)):
+        raise ValueError("groupnorm_grad: `out` must be a float32 tensor of x's shape (dy itself: in place)")
+    for name, t in (("x", x), ("dy", dy), ("gamma", gamma), ("beta", beta), ("stats", stats), ("out", out)):
+        if t is not None:
+            _require_dev(t, name)
+    if out is not None and out.data_ptr() == x.data_ptr():
+        raise ValueError("groupnorm_grad: `out` may be dy, not x (the layer's input is read while dx is written)")
+    dx = torch.empty_like(x) if out is None else out
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device) if want_param_grads else None
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device) if want_param_grads else None
+    return dx, dgamma, dbeta
+
+
+def groupnorm_chunk_grad(x, dy, gamma, beta, groups, eps=1e-5, relu=False, input_relu=False, stats=None, out=None,
+                         want_param_grads=True):
+    """Backward of groupnorm_chunk (csrc/groupnorm_grad.hip), float32: x is the layer's INPUT (the inference forward
+    normalises in place and destroys it: run it with out=None and keep x), dy the gradient at its output.
+    relu: the forward fused a ReLU behind the normalisation; input_relu: x is a ReLU's output and the gradient is wanted in
+    front of that ReLU (the towers' Conv3x3 + ReLU -> GroupNormalization).  gamma=None: ones.  stats: groupnorm_chunk_stats(x,
+    groups), saves the statistics pass of relu=True on large chunks.  out: None, or dy (in place on the gradient buffer).
+    -> (dx, dgamma, dbeta); the last two are None unless want_param_grads."""
+    dx, dgamma, dbeta = _gn_grad_problem(x, dy, gamma, beta, groups, eps, relu, input_relu, stats, out, want_param_grads)
+    lib = _lib.load()
+    N, Cc = x.shape[0], x.shape[-1]
+    hwc = x.numel() // N
+    ws = workspace(lib.ml_groupnorm_grad_workspace_bytes(N, groups, Cc), x.device, "gn")
+    with _Prof("groupnorm_chunk_grad", 0, 3 * x.element_size() * x.numel(), f"N={N} HWC={hwc} G={groups}"):
+        _lib.check(lib.ml_groupnorm_chunk_grad_f32(_ptr(x), _ptr(dy), _ptr(gamma), _ptr(beta), _ptr(dx), _ptr(dgamma),
+                                                   _ptr(dbeta), _ptr(stats), N, hwc, Cc, groups, float(eps), int(relu),
+                                                   int(input_relu), _ptr(ws), _stream()), "ml_groupnorm_chunk_grad_f32")
+    return dx, dgamma, dbeta
+
+
+def groupnorm_chunk_grad_multi(problems):
+    """ml_groupnorm_grad_multi_f32: several backward problems in one launch set.  problems: list of dicts with
+    groupnorm_chunk_grad's arguments (x, dy, gamma, beta, groups, ...) -> list of (dx, dgamma, dbeta), the bits of the
+    single calls.  The launch takes vectorisable problems only (chunk and channel counts multiples of 4): with another one
+    in the list the single calls run instead, as GroupNormalization.call_multi does for the forward."""
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.GN_MAX_PROBLEMS:
+        return (groupnorm_chunk_grad_multi(problems[:_lib.GN_MAX_PROBLEMS]) +
+                groupnorm_chunk_grad_multi(problems[_lib.GN_MAX_PROBLEMS:]))
+    for pr in problems:                  # the multi launch takes vectorisable problems only: single calls otherwise
+        x = pr["x"]
+        if isinstance(x, torch.Tensor) and x.dim() >= 2 and x.numel() and pr["groups"] >= 1 and (
+                (x.numel() // x.shape[0] // pr["groups"]) % 4 or x.shape[-1] % 4):
+            return [groupnorm_chunk_grad(**p) for p in problems]
+    outs = [_gn_grad_problem(**pr) for pr in problems]
+    lib = _lib.load()
+    arr = (_lib.GnGradDesc * n)()
+    nbytes, ws_bytes = 0, 0
+    for d, pr, (dx, dgamma, dbeta) in zip(arr, problems, outs):
+        x = pr["x"]
+        N, Cc = x.shape[0], x.shape[-1]
+        d.x, d.dy, d.dx = x.data_ptr(), pr["dy"].data_ptr(), dx.data_ptr()
+        for name, t in (("gamma", pr.get("gamma")), ("beta", pr.get("beta")), ("dgamma", dgamma), ("dbeta", dbeta),
+                        ("stats", pr.get("stats"))):
+            setattr(d, name, t.data_ptr() if t is not None else None)
+        d.HWC, d.N, d.C, d.G = x.numel() // N, N, Cc, pr["groups"]
+        d.relu, d.input_relu, d.eps = int(pr.get("relu", False)), int(pr.get("input_relu", False)), float(pr.get("eps", 1e-5))
+        ws_bytes += int(lib.ml_groupnorm_grad_workspace_bytes(N, pr["groups"], Cc))
+        nbytes += 3 * x.element_size() * x.numel()
+    ws = workspace(ws_bytes, problems[0]["x"].device, "gn_multi")
+    with _Prof("groupnorm_chunk_grad", 0, nbytes, f"multi x{n}"):
+        _lib.check(lib.ml_groupnorm_grad_multi_f32(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_groupnorm_grad_multi_f32")
+    return outs
+
+
 def resize_bilinear_ac(x, oh, ow, add=None, out=None, out_coff=0):
     lib = _lib.load()
     _require_dev(x, "x")

@@ -6,7 +6,8 @@ Same function names, argument meaning and return structure; the returned model r
 the MI355X kernels.  construct_trainer_network :223-395 is restated forward (TrainerModel: target assignment, the four
 losses and the metrics of a batch with ground truth) plus the losses' gradients at the head outputs
 (TrainerModel.loss_and_gradients); construct_masklabdataset :398-417 builds the file-reading datasets
-(masklab_hip/utils/dataset).  The backward of the heads and the backbone and the optimizers stay out of scope.
+(masklab_hip/utils/dataset).  GroupNormalization has its backward as a layer method (normalization.py), not yet wired in: the
+conv, resize and RoI-align backward of the heads, the backbone's backward and the optimizers stay out of scope.
 """
 import numpy as np
 import torch

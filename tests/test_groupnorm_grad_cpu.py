@@ -1,0 +1,98 @@
+"""CPU tests of GroupNormalization's backward: the closed form the kernels implement (include/masklab_hip.h) against torch
+autograd over the float64 restatement of the reference layer, the index rule, the argument checks of the ops, and the
+C ABI's new symbols."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+import groupnorm_grad_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FLAGS = [(False, False), (False, True), (True, False), (True, True)]
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_closed_form_equals_autograd_over_the_restatement(name):
+    inp = R.inputs(name)
+    assert R.mask_margin(inp["x"], inp["gamma"], inp["beta"], inp["groups"]) >= R.GUARD
+    assert 0.3 < (inp["x"] == 0).mean() < 0.45                      # exact zeros: the strictness of x > 0 is exercised
+    for relu, input_relu in FLAGS:
+        for gamma in (inp["gamma"], None):
+            args = (inp["x"], inp["dy"], gamma, inp["beta"], inp["groups"], relu, input_relu)
+            want = R.autograd(inp["x"], inp["dy"], np.ones_like(inp["gamma"]) if gamma is None else gamma, *args[3:])
+            R.check(R.closed_form(*args), want, R.scale(*args), f"{name} relu={relu} input_relu={input_relu} "
+                    f"gamma={'None' if gamma is None else 'given'}", bar=1e-10)
+
+
+def test_mask_margin_holds_for_the_seeds_the_gpu_test_could_use():
+    for name in R.CASES:
+        for seed in range(3):
+            inp = R.inputs(name, seed)
+            assert R.mask_margin(inp["x"], inp["gamma"], inp["beta"], inp["groups"]) >= R.GUARD, (name, seed)
+
+
+def test_index_rule_is_the_chunk_not_the_channel_group():
+    """Case B: chunks of 200 values start mid-row (200 mod 32 = 8).  The reference's dgamma differs from the dgamma of group
+    norm proper (what torch.nn.functional.group_norm computes: channels grouped, gamma[c]) on the same tensors."""
+    inp = R.inputs("B")
+    N, H, W, C, G = R.CASES["B"]
+    _, dgamma, dbeta = R.closed_form(inp["x"], inp["dy"], inp["gamma"], inp["beta"], G)
+    # group norm proper, by hand: channel c belongs to group c // (C/G), statistics over (H, W, C/G), gamma[c] / beta[c]
+    xg = inp["x"].astype(np.float64).reshape(N, H * W, G, C // G)
+    xhat = (xg - xg.mean(axis=(1, 3), keepdims=True)) / np.sqrt(xg.var(axis=(1, 3), keepdims=True) + R.EPS)
+    dyc = inp["dy"].astype(np.float64).reshape(N, H * W, C)
+    proper_dgamma, proper_dbeta = (dyc * xhat.reshape(N, H * W, C)).sum(axis=(0, 1)), dyc.sum(axis=(0, 1))
+    assert np.abs(proper_dgamma - dgamma).max() > 0.1 * np.abs(dgamma).max()
+    # beta[j] is met by channels c with c mod 8 = j mod 8 of chunk j // 8, not by channel j alone
+    assert np.abs(proper_dbeta - dbeta).max() > 0.1 * np.abs(dbeta).max()
+    # and the rule itself, spelled out for one index: j = 9 collects chunk 1, positions i with (200 + i) mod 32 mod 8 = 1
+    d = inp["dy"].astype(np.float64).reshape(N, G, -1)
+    i = np.arange(200)
+    assert np.isclose(dbeta[9], d[:, 1, ((200 + i) % 32) % 8 == 1].sum(), rtol=1e-12)
+
+
+def test_argument_checks_raise_on_the_host():
+    from masklab_hip import ops
+    x, dy = torch.zeros(2, 3, 5, 8), torch.zeros(2, 3, 5, 8)
+    gamma, beta = torch.ones(8), torch.zeros(8)
+    ok = dict(x=x, dy=dy, gamma=gamma, beta=beta, groups=4)
+    for bad, err in ((dict(dy=torch.zeros(2, 3, 5, 4)), ValueError), (dict(groups=3), ValueError), (dict(groups=16), ValueError),
+                     (dict(x=x.half()), TypeError), (dict(dy=dy.half()), TypeError), (dict(gamma=torch.ones(4)), ValueError),
+                     (dict(beta=beta.double()), ValueError), (dict(stats=torch.zeros(8, 2)), ValueError),
+                     (dict(stats=torch.zeros(4, 2, dtype=torch.float64)), ValueError), (dict(out=torch.zeros(2, 3, 5, 4)), ValueError),
+                     (dict(), RuntimeError)):                          # all shapes right, but host tensors: no CPU fallback
+        with pytest.raises(err):
+            ops.groupnorm_chunk_grad(**{**ok, **bad})
+        with pytest.raises(err):
+            ops.groupnorm_chunk_grad_multi([{**ok, **bad}])
+    assert ops.groupnorm_chunk_grad_multi([]) == []
+    with pytest.raises(ValueError):
+        ops.groupnorm_chunk_stats(x, 3)
+    with pytest.raises(ValueError):
+        ops.groupnorm_chunk_stats(x.half(), 4)
+    with pytest.raises(RuntimeError):
+        ops.groupnorm_chunk_stats(x, 4)
+
+
+def test_new_symbols_are_declared_and_bound_with_matching_arity():
+    from masklab_hip import _lib
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "masklab_hip.h")).read(), flags=re.S)
+    lib = _lib.load()
+    for name in ("ml_groupnorm_grad_workspace_bytes", "ml_groupnorm_chunk_grad_f32", "ml_groupnorm_chunk_stats_f32",
+                 "ml_groupnorm_grad_multi_f32"):
+        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
+        assert decl is not None, f"{name} is not declared in masklab_hip.h"
+        assert name in _lib.SIGNATURES and hasattr(lib, name), name
+        assert len(_lib.SIGNATURES[name][1]) == len(decl.group(1).split(",")), name
+    # the descriptor: 8 pointers, one int64, 5 int32, one float, padded to 8
+    fields = re.search(r"typedef struct ml_gn_grad_desc \{(.*?)\} ml_gn_grad_desc;", header, flags=re.S).group(1)
+    names = [n.strip(" *") for decl in fields.split(";") if decl.strip() for n in decl.split(",")]
+    names = [n.split()[-1].lstrip("*") for n in names]
+    assert names == [f[0] for f in _lib.GnGradDesc._fields_], names
+    assert ctypes.sizeof(_lib.GnGradDesc) == 8 * 8 + 8 + 5 * 4 + 4 and _lib.GnGradDesc.HWC.offset == 64
+    assert lib.ml_groupnorm_grad_workspace_bytes(8, 16, 256) >= 8 * 64 * 2 * (16 + 256) * 8
