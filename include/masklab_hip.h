@@ -920,7 +920,7 @@ int ml_eval_reference_host(const int32_t *det, const int32_t *ins, const void *g
 /* ---------------------------------------------------------------------------------------------
  * Trainer forward: the reference's target assignment (AssignBoxes engine/layers/detection.py:589-697, AssignMasks
  * instance.py:296-386, AssignSeg semantic.py:304-311) and its four loss layers (engine/losses.py), forward only
- * (csrc/train_targets.hip; the losses' gradients are the next block).  All on `stream`, no host read.  No float atomics: a sum is float64 partials per block in
+ * (assignment: csrc/train_targets.hip; losses: csrc/train_losses.hip; the losses' gradients are the next block).  All on `stream`, no host read.  No float atomics: a sum is float64 partials per block in
  * `workspace` (ml_train_workspace_bytes) added in block order by a finishing kernel -- the same bits run to run.  Per-element
  * terms are float32 with FP contraction off, as tests/trainer_ref.py evaluates them; sums are float64.
  * Gradients stop at the head outputs ("Trainer backward: the losses").  NOT supported: predictions or truths in float16
@@ -976,7 +976,7 @@ int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const fl
                           float weight, float keep, float half_smooth, void *workspace, float *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Trainer backward: the losses (csrc/train_grads.hip).  Each call is its forward twin above -- the same arguments, the same
+ * Trainer backward: the losses (csrc/train_losses.hip, the forward's own kernel source).  Each call is its forward twin above -- the same arguments, the same
  * `workspace`, the same loss in `out`, BIT FOR BIT -- plus
  *   upstream         float32 [B] on the device: d(scalar) / d(loss[b]); 1 / B for the scalar the reference compiles
  *                    (add_loss(K.mean(loss)) per loss layer);

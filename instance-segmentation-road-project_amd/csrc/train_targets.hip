@@ -1,14 +1,13 @@
-// The trainer network's forward tail: the reference's target assignment (AssignBoxes detection.py:589-697, AssignMasks
-// instance.py:296-386, AssignSeg semantic.py:304-311) and its four loss layers (engine/losses.py).  The contract is in
-// include/masklab_hip.h ("Trainer forward"); what matters here:
+// The trainer network's target assignment: the reference's CalculateIOU, AssignBoxes (detection.py:589-697), AssignMasks
+// (instance.py:296-386) and AssignSeg (semantic.py:304-311).  The contract is in include/masklab_hip.h ("Trainer
+// forward"); what matters here:
 //
-//   * no float atomics.  A sum is per-thread float64 -> wave shuffle tree -> one LDS word per wave -> one float64 partial
-//     per block in the workspace, and a finishing kernel adds the partials of an image in block order: the same bits run
-//     to run.  Integer atomics appear only where the order cannot matter (the packed (IoU, index) maximum).
+//   * no float atomics, and integer atomics only where the order cannot matter (the packed (IoU, index) maximum): the same
+//     bits run to run.
 //   * per-element terms are float32 with FP contraction OFF, operation by operation as NumPy evaluates
-//     tests/trainer_ref.py; logf / powf are the only operations that may differ from NumPy's by an ulp or two.
-//   * forward only.  The losses' gradients are in train_grads.hip; what the two files share (block_sum, the focal and
-//     cross-entropy terms, BoxLoss's statistics, the finishing kernels) is in train_terms.h.
+//     tests/trainer_ref.py.
+//   * the four losses these targets feed, forward and backward, are in train_losses.hip; train_terms.h holds the launch
+//     constants the two files share.
 #include "common.h"
 #include "box_iou.h"
 #include "train_terms.h"
@@ -129,61 +128,6 @@ __global__ __launch_bounds__(TPB) void assign_boxes_kernel(const float *gt, cons
     assign_mask[row] = ignore ? -1.f : li == C ? 1.f : 0.f;
 }
 
-// ----------------------------------------------------------------------------- ClassLoss
-// partial [B, gridDim.x, 2] = (sum of the masked focal terms, #positive + #negative anchors)
-__global__ __launch_bounds__(TPB) void class_loss_kernel(const float *cls_true, const float *cls_pred, const float *mask,
-                                                         const float *exists, int A, int C, FocalArgs f, double *partial) {
-    const int b = blockIdx.y;
-    double sum = 0.0, cnt = 0.0;
-    for (int a = blockIdx.x * TPB + threadIdx.x; a < A; a += gridDim.x * TPB) {
-        const long long row = (long long)b * A + a;
-        const float m = mask[row];
-        cnt += (m == 1.f || m == 0.f) ? 1.0 : 0.0;
-        const float keep = m == -1.f ? 0.f : 1.f;
-        for (int c = 0; c < C; ++c) {
-            const float t = cls_true[row * C + c] != 0.f ? 1.f : 0.f;
-            const float l = focal_term(t, cls_pred[row * C + c], f) * exists[b * C + c];
-            sum += (double)(keep * l);
-        }
-    }
-    const double s = block_sum(sum), n = block_sum(cnt);
-    if (threadIdx.x == 0) {
-        double *o = partial + ((long long)b * gridDim.x + blockIdx.x) * 2;
-        o[0] = s;
-        o[1] = n;
-    }
-}
-
-// ----------------------------------------------------------------------------- BoxLoss (beta: train_terms.h)
-// partial [B, gridDim.x, 2] = (sum over positives of mean_q smooth_l1, #positives)
-__global__ __launch_bounds__(TPB) void box_loss_kernel(const float *loc_true, const float *loc_pred, const float *mask, int A,
-                                                       const float *scratch, double *partial) {
-    const int b = blockIdx.y;
-    float beta[4];
-    for (int q = 0; q < 4; ++q) beta[q] = scratch[4 + q];
-    double sum = 0.0, cnt = 0.0;
-    for (int a = blockIdx.x * TPB + threadIdx.x; a < A; a += gridDim.x * TPB) {
-        const long long row = (long long)b * A + a;
-        if (mask[row] != 0.f) continue;
-        const f32x4 t = *(const f32x4 *)(loc_true + 4 * row), p = *(const f32x4 *)(loc_pred + 4 * row);
-        float l[4];
-        for (int q = 0; q < 4; ++q) {                   // smooth_l1 as written: l2 where l1 < beta (losses.py:221-234)
-            const float d = t[q] - p[q];
-            const float l1 = fabsf(d) - 0.5f * beta[q];
-            const float l2 = 0.5f * (d * d) / beta[q];
-            l[q] = l1 < beta[q] ? l2 : l1;
-        }
-        sum += (double)((((l[0] + l[1]) + l[2]) + l[3]) / 4.f);
-        cnt += 1.0;
-    }
-    const double s = block_sum(sum), n = block_sum(cnt);
-    if (threadIdx.x == 0) {
-        double *o = partial + ((long long)b * gridDim.x + blockIdx.x) * 2;
-        o[0] = s;
-        o[1] = n;
-    }
-}
-
 // ----------------------------------------------------------------------------- AssignMasks
 struct MaskDims { int R, G, H, W, mh, mw, C; float thr; };
 
@@ -280,38 +224,10 @@ __global__ __launch_bounds__(TPB) void assign_seg_kernel(const T *gt, SegDims d,
     out[i] = rintf(top + (bot - top) * ty);
 }
 
-// ----------------------------------------------------------------------------- SegLoss
-// partial [B, gridDim.x, C]: per class the sum of the BCE terms over the block's pixels
-__global__ __launch_bounds__(TPB) void seg_loss_kernel(const float *seg_true, const float *seg_pred, long long HW, int C, BceArgs k,
-                                                       double *partial) {
-    const int b = blockIdx.y;
-    double acc[MAX_CLASSES];
-#pragma unroll
-    for (int c = 0; c < MAX_CLASSES; ++c) acc[c] = 0.0;
-    for (long long px = (long long)blockIdx.x * TPB + threadIdx.x; px < HW; px += (long long)gridDim.x * TPB) {
-        const long long e = ((long long)b * HW + px) * C;
-#pragma unroll
-        for (int c = 0; c < MAX_CLASSES; ++c)
-            if (c < C) acc[c] += (double)bce_term(seg_true[e + c], seg_pred[e + c], k);
-    }
-#pragma unroll
-    for (int c = 0; c < MAX_CLASSES; ++c)
-        if (c < C) {
-            const double s = block_sum(acc[c]);
-            if (threadIdx.x == 0) partial[((long long)b * gridDim.x + blockIdx.x) * C + c] = s;
-        }
-}
-
 }  // namespace tt
 }  // namespace
 
 using namespace tt;
-
-extern "C" int64_t ml_train_workspace_bytes(int32_t B, int32_t C) {
-    if (B < 1 || C < 1) return 0;
-    const int64_t per = C > 4 ? C : 4;
-    return (int64_t)sizeof(double) * ((int64_t)B * MAX_BLOCKS * per + 16);
-}
 
 extern "C" int ml_train_calculate_iou_f32(const float *aa, int32_t aa_stride, int32_t n, const float *bb, int32_t bb_stride, int32_t m,
                                           float *out, void *stream) {
@@ -349,42 +265,6 @@ extern "C" int ml_train_assign_boxes_f32(const float *gt_boxes, const int32_t *p
     return ML_OK;
 }
 
-extern "C" int ml_train_class_loss_f32(const float *cls_true, const float *cls_pred, const float *assign_mask, const float *cls_exists,
-                                       int32_t B, int32_t A, int32_t C, float weight, float alpha, float gamma, void *workspace,
-                                       float *out, void *stream) {
-    const char *what = "train_class_loss";
-    ML_REQUIRE(cls_true && cls_pred && assign_mask && cls_exists && workspace && out, "%s: null pointer", what);
-    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && A >= 1 && C >= 1, "%s: bad dims B=%d A=%d C=%d", what, B, A, C);
-    hipStream_t s = (hipStream_t)stream;
-    const int nblk = blocks_for(A);
-    const float eps = 1e-7f;
-    const FocalArgs f = {eps, 1.f - eps, alpha, gamma};
-    hipLaunchKernelGGL(class_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, cls_true, cls_pred, assign_mask, cls_exists, A, C, f,
-                       (double *)workspace);
-    hipLaunchKernelGGL(class_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)workspace, B, nblk, eps, weight, out);
-    ML_CHECK_LAUNCH(what);
-    return ML_OK;
-}
-
-extern "C" int ml_train_box_loss_f32(const float *loc_true, const float *loc_pred, const float *assign_mask, int32_t B, int32_t A,
-                                     float weight, float momentum, float one_minus_momentum, float beta, int32_t use_adjust,
-                                     float *state, void *workspace, float *out, void *stream) {
-    const char *what = "train_box_loss";
-    ML_REQUIRE(loc_true && loc_pred && assign_mask && workspace && out && (state || !use_adjust), "%s: null pointer", what);
-    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && A >= 1, "%s: bad dims B=%d A=%d", what, B, A);
-    ML_REQUIRE(ml_aligned16(loc_true) && ml_aligned16(loc_pred), "%s: loc_true and loc_pred must be 16-byte aligned", what);
-    hipStream_t s = (hipStream_t)stream;
-    double *partial = (double *)workspace;
-    const BoxArgs k = {momentum, one_minus_momentum, beta, weight, 1e-7f};
-    launch_box_beta(loc_true, loc_pred, assign_mask, B, A, k, use_adjust, state, partial, s);
-    const int nblk = blocks_for(A);
-    hipLaunchKernelGGL(box_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, loc_true, loc_pred, assign_mask, A,
-                       (const float *)box_scratch(partial, B), partial);
-    hipLaunchKernelGGL(class_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)partial, B, nblk, k.eps, weight, out);
-    ML_CHECK_LAUNCH(what);
-    return ML_OK;
-}
-
 extern "C" int ml_train_assign_masks(const float *roi_boxes, const float *gt_boxes, const void *gt_masks, int32_t mask_dtype, int32_t B,
                                      int32_t R, int32_t G, int32_t H, int32_t W, int32_t mh, int32_t mw, int32_t C, float threshold,
                                      int32_t *out, void *stream) {
@@ -400,20 +280,6 @@ extern "C" int ml_train_assign_masks(const float *roi_boxes, const float *gt_box
         hipLaunchKernelGGL(assign_masks_kernel<int8_t>, dim3(R, B), dim3(TPB), 0, s, roi_boxes, gt_boxes, (const int8_t *)gt_masks, d, out);
     else
         hipLaunchKernelGGL(assign_masks_kernel<uint8_t>, dim3(R, B), dim3(TPB), 0, s, roi_boxes, gt_boxes, (const uint8_t *)gt_masks, d, out);
-    ML_CHECK_LAUNCH(what);
-    return ML_OK;
-}
-
-extern "C" int ml_train_mask_loss_f32(const int32_t *mask_true, const float *mask_pred, int32_t B, int32_t R, int32_t mh, int32_t mw,
-                                      int32_t C, float weight, float keep, float half_smooth, float *roi_loss, float *out, void *stream) {
-    const char *what = "train_mask_loss";
-    ML_REQUIRE(mask_true && mask_pred && roi_loss && out, "%s: null pointer", what);
-    ML_REQUIRE(B >= 1 && B <= 32 && R >= 1 && mh >= 1 && mw >= 1 && C >= 1 && (long long)mh * mw < (1ll << 24),
-               "%s: bad dims B=%d R=%d crop %d x %d C=%d (B <= 32: MoldBatch)", what, B, R, mh, mw, C);
-    hipStream_t s = (hipStream_t)stream;
-    const BceArgs k = {1e-7f, keep, half_smooth};
-    hipLaunchKernelGGL(mask_roi_loss_kernel, dim3(R, B), dim3(TPB), 0, s, mask_true, mask_pred, R, mh * mw, C, k, roi_loss);
-    hipLaunchKernelGGL(mask_loss_finish_kernel, dim3(1), dim3(64), 0, s, (const float *)roi_loss, B, R, weight, out);
     ML_CHECK_LAUNCH(what);
     return ML_OK;
 }
@@ -434,22 +300,6 @@ extern "C" int ml_train_assign_seg(const void *gt_seg, int32_t dtype, int32_t B,
         hipLaunchKernelGGL(assign_seg_kernel<float>, dim3(nb), dim3(TPB), 0, s, (const float *)gt_seg, d, n, out);
     else
         hipLaunchKernelGGL(assign_seg_kernel<uint8_t>, dim3(nb), dim3(TPB), 0, s, (const uint8_t *)gt_seg, d, n, out);
-    ML_CHECK_LAUNCH(what);
-    return ML_OK;
-}
-
-extern "C" int ml_train_seg_loss_f32(const float *seg_true, const float *seg_pred, const float *seg_exist, int32_t B, int64_t HW, int32_t C,
-                                     float weight, float keep, float half_smooth, void *workspace, float *out, void *stream) {
-    const char *what = "train_seg_loss";
-    ML_REQUIRE(seg_true && seg_pred && seg_exist && workspace && out, "%s: null pointer", what);
-    ML_REQUIRE(B >= 1 && B <= MAX_GRID_Y && HW >= 1 && C >= 1 && C <= MAX_CLASSES, "%s: bad dims B=%d HW=%lld C=%d (C <= %d)", what, B,
-               (long long)HW, C, MAX_CLASSES);
-    hipStream_t s = (hipStream_t)stream;
-    const int nblk = blocks_for(HW);
-    const BceArgs k = {1e-7f, keep, half_smooth};
-    hipLaunchKernelGGL(seg_loss_kernel, dim3(nblk, B), dim3(TPB), 0, s, seg_true, seg_pred, (long long)HW, C, k, (double *)workspace);
-    hipLaunchKernelGGL(seg_loss_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, (const double *)workspace, seg_exist, B, nblk,
-                       (long long)HW, C, weight, out);
     ML_CHECK_LAUNCH(what);
     return ML_OK;
 }

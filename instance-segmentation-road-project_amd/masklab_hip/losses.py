@@ -1,8 +1,8 @@
 """Drop-in for the reference's engine/losses.py: ClassLoss, BoxLoss, MaskLoss and SegLoss with the same constructor
 arguments and get_config keys.  Inputs are float32 device tensors; every term and every sum runs in the kernels of
-csrc/train_targets.hip (through masklab_hip.ops): float32 terms as the reference writes them, float64 sums in a fixed
+csrc/train_losses.hip (through masklab_hip.ops): float32 terms as the reference writes them, float64 sums in a fixed
 order, so two calls give the same bits.  `call` is the forward.  `call_with_grad(inputs, upstream=None,
-through_sigmoid=False)` returns (loss [B], grad): the same loss bit for bit and, from the same pass (csrc/train_grads.hip),
+through_sigmoid=False)` returns (loss [B], grad): the same loss bit for bit and, from the same pass of the same kernel,
 the gradient of sum_b upstream[b] * loss[b] with respect to the layer's prediction -- upstream None is 1 / B, the K.mean the
 reference compiles; through_sigmoid gives the gradient at the output conv's pre-activation.  The gradients stop there: the
 heads and the backbone have no backward pass yet.  No CPU fallback."""
@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import keras_like as K
+from . import ops
 
 
 class ClassLoss(K.Layer):
@@ -23,17 +24,16 @@ class ClassLoss(K.Layer):
         self.gamma = gamma
         super().__init__(**kwargs)
 
-    def call(self, inputs, **kwargs):
-        from . import ops
+    def _op_args(self, inputs):
         cls_true, cls_pred, mask, cls_exists = inputs
-        return ops.class_loss(cls_true, cls_pred, mask, cls_exists.to(torch.float32), self.weight, self.alpha, self.gamma)
+        return cls_true, cls_pred, mask, cls_exists.to(torch.float32), self.weight, self.alpha, self.gamma
+
+    def call(self, inputs, **kwargs):
+        return ops.class_loss(*self._op_args(inputs))
 
     def call_with_grad(self, inputs, upstream=None, through_sigmoid=False):
         """-> (loss [B], d / d cls_pred [B,A,C]); ignored anchors and classes that do not exist get zeros."""
-        from . import ops
-        cls_true, cls_pred, mask, cls_exists = inputs
-        return ops.class_loss_grad(cls_true, cls_pred, mask, cls_exists.to(torch.float32), self.weight, self.alpha, self.gamma,
-                                   upstream=upstream, through_sigmoid=through_sigmoid)
+        return ops.class_loss_grad(*self._op_args(inputs), upstream=upstream, through_sigmoid=through_sigmoid)
 
     def get_config(self):
         return {**super().get_config(), "weight": self.weight, "alpha": self.alpha, "gamma": self.gamma}
@@ -75,24 +75,21 @@ class BoxLoss(K.Layer):
     def moving_var(self):
         return None if self.state is None else self.state[4:]
 
-    def call(self, inputs, **kwargs):
-        from . import ops
+    def _op_args(self, inputs):
         loc_true, loc_pred, mask = inputs
         if self.state is None or self.state.device != loc_true.device:
             self._load_own({}, loc_true.device)
-        return ops.box_loss(loc_true, loc_pred, mask, self.weight, self.momentum, self.beta, self.use_adjust, self.state)
+        return loc_true, loc_pred, mask, self.weight, self.momentum, self.beta, self.use_adjust, self.state
+
+    def call(self, inputs, **kwargs):
+        return ops.box_loss(*self._op_args(inputs))
 
     def call_with_grad(self, inputs, upstream=None, through_sigmoid=False):
         """-> (loss [B], d / d loc_pred [B,A,4]), zeros off the positive anchors.  The moving statistics move once, as by
         `call`; beta is a constant of the gradient.  loc_pred is a linear output: through_sigmoid must stay False."""
-        from . import ops
         if through_sigmoid:
             raise ValueError("BoxLoss: loc_pred is not a sigmoid output, there is no through_sigmoid gradient")
-        loc_true, loc_pred, mask = inputs
-        if self.state is None or self.state.device != loc_true.device:
-            self._load_own({}, loc_true.device)
-        return ops.box_loss_grad(loc_true, loc_pred, mask, self.weight, self.momentum, self.beta, self.use_adjust, self.state,
-                                 upstream=upstream)
+        return ops.box_loss_grad(*self._op_args(inputs), upstream=upstream)
 
     def get_config(self):
         return {**super().get_config(), "momentum": self.momentum, "weight": self.weight, "beta": self.beta,
@@ -110,21 +107,18 @@ class MaskLoss(K.Layer):
         self.max_batch_size = max_batch_size
         super().__init__(**kwargs)
 
-    def call(self, inputs, **kwargs):
-        from . import ops
+    def _op_args(self, inputs):
         mask_true, mask_pred = inputs
         if mask_pred.shape[0] > 32:
             raise ValueError("MaskLoss: MoldBatch supports at most 32 images per call (reference misc.py:275)")
-        return ops.mask_loss(mask_true, mask_pred, self.weight, self.label_smoothing)
+        return mask_true, mask_pred, self.weight, self.label_smoothing
+
+    def call(self, inputs, **kwargs):
+        return ops.mask_loss(*self._op_args(inputs))
 
     def call_with_grad(self, inputs, upstream=None, through_sigmoid=False):
         """-> (loss [B], d / d mask_pred [B,R,h,w,C]): non-zero in the class channel of the selected RoIs only."""
-        from . import ops
-        mask_true, mask_pred = inputs
-        if mask_pred.shape[0] > 32:
-            raise ValueError("MaskLoss: MoldBatch supports at most 32 images per call (reference misc.py:275)")
-        return ops.mask_loss_grad(mask_true, mask_pred, self.weight, self.label_smoothing, upstream=upstream,
-                                  through_sigmoid=through_sigmoid)
+        return ops.mask_loss_grad(*self._op_args(inputs), upstream=upstream, through_sigmoid=through_sigmoid)
 
     def get_config(self):
         return {**super().get_config(), "weight": self.weight, "label_smoothing": self.label_smoothing,
@@ -140,17 +134,16 @@ class SegLoss(K.Layer):
         self.label_smoothing = label_smoothing
         super().__init__(**kwargs)
 
-    def call(self, inputs, **kwargs):
-        from . import ops
+    def _op_args(self, inputs):
         mask_true, mask_pred, mask_exists = inputs
-        return ops.seg_loss(mask_true, mask_pred, mask_exists.to(torch.float32), self.weight, self.label_smoothing)
+        return mask_true, mask_pred, mask_exists.to(torch.float32), self.weight, self.label_smoothing
+
+    def call(self, inputs, **kwargs):
+        return ops.seg_loss(*self._op_args(inputs))
 
     def call_with_grad(self, inputs, upstream=None, through_sigmoid=False):
         """-> (loss [B], d / d mask_pred [B,H,W,C])."""
-        from . import ops
-        mask_true, mask_pred, mask_exists = inputs
-        return ops.seg_loss_grad(mask_true, mask_pred, mask_exists.to(torch.float32), self.weight, self.label_smoothing,
-                                 upstream=upstream, through_sigmoid=through_sigmoid)
+        return ops.seg_loss_grad(*self._op_args(inputs), upstream=upstream, through_sigmoid=through_sigmoid)
 
     def get_config(self):
         return {**super().get_config(), "weight": self.weight, "label_smoothing": self.label_smoothing}

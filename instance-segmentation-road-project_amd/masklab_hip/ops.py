@@ -2126,18 +2126,12 @@ def polygon_reference_host(kind, verts, offsets, B, n_or_S, H, W, windows=None, 
     return out
 
 
-# ----------------------------------------------------------------------------- trainer forward (csrc/train_targets.hip)
+# ----------------------------------------------------------------------------- trainer: target assignment (csrc/train_targets.hip)
 def _require_f32(op, *named):
     for t, name in named:
         _require_dev(t, name)
         if t.dtype != torch.float32:
             raise RuntimeError(f"{op}: `{name}` must be float32, got {t.dtype}")
-
-
-def _train_ws(B, Cc, device):
-    """The per-block partial sums of one loss call: a few hundred KiB, written in full before they are read, so a fresh
-    allocation per call (stream-ordered, like the outputs) rather than a cached workspace."""
-    return torch.empty(int(_lib.load().ml_train_workspace_bytes(int(B), int(Cc))), dtype=torch.uint8, device=device)
 
 
 def calculate_iou(aa_boxes, bb_boxes):
@@ -2189,45 +2183,6 @@ def assign_boxes(gt_boxes, pr_boxes, num_classes, best=None):
     return cls_true, loc_true, mask
 
 
-def class_loss(cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma):
-    """ml_train_class_loss_f32 (ClassLoss.call): [B,A,C], [B,A,C], [B,A(,1)], [B,C] float32 -> float32 [B]."""
-    _require_f32("class_loss", (cls_true, "cls_true"), (cls_pred, "cls_pred"), (assign_mask, "assign_mask"), (cls_exists, "cls_exists"))
-    if cls_true.dim() != 3 or cls_true.shape != cls_pred.shape or assign_mask.numel() * cls_true.shape[2] != cls_true.numel() or \
-            tuple(cls_exists.shape) != (cls_true.shape[0], cls_true.shape[2]):
-        raise ValueError(f"class_loss: shapes {tuple(cls_true.shape)}, {tuple(cls_pred.shape)}, {tuple(assign_mask.shape)}, "
-                         f"{tuple(cls_exists.shape)} do not fit")
-    B, A, Cn = cls_true.shape
-    out = torch.empty((B,), dtype=torch.float32, device=cls_true.device)
-    ws = _train_ws(B, Cn, cls_true.device)
-    with _Prof("class_loss", 0, 4 * (2 * cls_true.numel() + assign_mask.numel())):
-        _lib.check(_lib.load().ml_train_class_loss_f32(_ptr(cls_true), _ptr(cls_pred), _ptr(assign_mask), _ptr(cls_exists), B, A, Cn,
-                                                       float(weight), float(alpha), float(gamma), _ptr(ws), _ptr(out), _stream()),
-                   "ml_train_class_loss_f32")
-    return out
-
-
-def box_loss(loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state=None):
-    """ml_train_box_loss_f32 (BoxLoss.call): [B,A,4], [B,A,4], [B,A(,1)] float32 -> float32 [B].  state: float32 [8] on the
-    device = moving_mean, moving_var, updated in place when use_adjust."""
-    _require_f32("box_loss", (loc_true, "loc_true"), (loc_pred, "loc_pred"), (assign_mask, "assign_mask"))
-    if loc_true.dim() != 3 or loc_true.shape[2] != 4 or loc_true.shape != loc_pred.shape or assign_mask.numel() * 4 != loc_true.numel():
-        raise ValueError(f"box_loss: shapes {tuple(loc_true.shape)}, {tuple(loc_pred.shape)}, {tuple(assign_mask.shape)} do not fit")
-    if use_adjust:
-        _require_f32("box_loss", (state, "state"))
-        if state.numel() != 8:
-            raise ValueError("box_loss: `state` must hold moving_mean[4] and moving_var[4]")
-    B, A, _ = loc_true.shape
-    out = torch.empty((B,), dtype=torch.float32, device=loc_true.device)
-    ws = _train_ws(B, 4, loc_true.device)
-    passes = 3 if use_adjust else 1
-    with _Prof("box_loss", 0, 4 * passes * (2 * loc_true.numel() + assign_mask.numel())):
-        _lib.check(_lib.load().ml_train_box_loss_f32(_ptr(loc_true), _ptr(loc_pred), _ptr(assign_mask), B, A, float(weight), float(momentum),
-                                                     float(1 - momentum), float(beta), int(bool(use_adjust)),
-                                                     _ptr(state if use_adjust else None), _ptr(ws), _ptr(out), _stream()),
-                   "ml_train_box_loss_f32")
-    return out
-
-
 def assign_masks(roi_boxes, gt_boxes, gt_masks, crop_hw, num_classes, threshold=0.5):
     """ml_train_assign_masks (AssignMasks.call): roi_boxes [B,R,6], gt_boxes [B,G,6] float32, gt_masks [B,G,H,W] int8 / uint8
     -> int32 [B,R,h,w]."""
@@ -2247,23 +2202,6 @@ def assign_masks(roi_boxes, gt_boxes, gt_masks, crop_hw, num_classes, threshold=
     return out
 
 
-def mask_loss(mask_true, mask_pred, weight, label_smoothing):
-    """ml_train_mask_loss_f32 (MaskLoss.call): mask_true int32 [B,R,h,w], mask_pred float32 [B,R,h,w,C] -> float32 [B]."""
-    _require_dev(mask_true, "mask_true")
-    _require_f32("mask_loss", (mask_pred, "mask_pred"))
-    if mask_true.dtype != torch.int32 or mask_pred.dim() != 5 or tuple(mask_true.shape) != tuple(mask_pred.shape[:4]):
-        raise ValueError(f"mask_loss: int32 [B,R,h,w] targets and float32 [B,R,h,w,C] predictions expected, got {mask_true.dtype} "
-                         f"{tuple(mask_true.shape)} and {tuple(mask_pred.shape)}")
-    B, R, mh, mw, Cn = mask_pred.shape
-    roi_loss = torch.empty((B, R), dtype=torch.float32, device=mask_pred.device)
-    out = torch.empty((B,), dtype=torch.float32, device=mask_pred.device)
-    with _Prof("mask_loss", 0, 8 * mask_true.numel()):
-        _lib.check(_lib.load().ml_train_mask_loss_f32(_ptr(mask_true), _ptr(mask_pred), B, R, mh, mw, Cn, float(weight),
-                                                      float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(roi_loss), _ptr(out),
-                                                      _stream()), "ml_train_mask_loss_f32")
-    return out
-
-
 def assign_seg(gt_seg, out_hw):
     """ml_train_assign_seg (AssignSeg.call): gt_seg [B,H,W,C] float32 / uint8 -> float32 [B,oh,ow,C], rounded half to even."""
     _require_dev(gt_seg, "gt_seg")
@@ -2278,22 +2216,15 @@ def assign_seg(gt_seg, out_hw):
     return out
 
 
-def seg_loss(seg_true, seg_pred, seg_exist, weight, label_smoothing):
-    """ml_train_seg_loss_f32 (SegLoss.call): seg_true, seg_pred [B,H,W,C], seg_exist [B,C] float32 -> float32 [B]."""
-    _require_f32("seg_loss", (seg_true, "seg_true"), (seg_pred, "seg_pred"), (seg_exist, "seg_exist"))
-    if seg_true.dim() != 4 or seg_true.shape != seg_pred.shape or tuple(seg_exist.shape) != (seg_true.shape[0], seg_true.shape[3]):
-        raise ValueError(f"seg_loss: shapes {tuple(seg_true.shape)}, {tuple(seg_pred.shape)}, {tuple(seg_exist.shape)} do not fit")
-    B, H, W, Cn = seg_true.shape
-    out = torch.empty((B,), dtype=torch.float32, device=seg_true.device)
-    ws = _train_ws(B, Cn, seg_true.device)
-    with _Prof("seg_loss", 0, 8 * seg_true.numel()):
-        _lib.check(_lib.load().ml_train_seg_loss_f32(_ptr(seg_true), _ptr(seg_pred), _ptr(seg_exist), B, H * W, Cn, float(weight),
-                                                     float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(ws), _ptr(out),
-                                                     _stream()), "ml_train_seg_loss_f32")
-    return out
+# ----------------------------------------------------------------------------- trainer: the four losses (csrc/train_losses.hip)
+# Each loss has one body, _x_loss(want_grad, ...): the checks, the allocations and the arguments of its forward op `x_loss`
+# and of its fused op `x_loss_grad`, which adds d(sum_b upstream[b] * loss[b]) / d(prediction) from the same pass.
+def _train_ws(B, Cc, device):
+    """The per-block partial sums of one loss call: a few hundred KiB, written in full before they are read, so a fresh
+    allocation per call (stream-ordered, like the outputs) rather than a cached workspace."""
+    return torch.empty(int(_lib.load().ml_train_workspace_bytes(int(B), int(Cc))), dtype=torch.uint8, device=device)
 
 
-# ----------------------------------------------------------------------------- trainer backward: the losses (csrc/train_grads.hip)
 def _upstream(op, upstream, B, device):
     """d(scalar) / d(loss[b]) as float32 [B] on the device; None = 1 / B, the K.mean the reference compiles per loss."""
     if upstream is None:
@@ -2304,85 +2235,146 @@ def _upstream(op, upstream, B, device):
     return upstream
 
 
+def _class_loss(want_grad, cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma, upstream=None, through_sigmoid=False):
+    op = "class_loss_grad" if want_grad else "class_loss"
+    _require_f32(op, (cls_true, "cls_true"), (cls_pred, "cls_pred"), (assign_mask, "assign_mask"), (cls_exists, "cls_exists"))
+    if cls_true.dim() != 3 or cls_true.shape != cls_pred.shape or assign_mask.numel() * cls_true.shape[2] != cls_true.numel() or \
+            tuple(cls_exists.shape) != (cls_true.shape[0], cls_true.shape[2]):
+        raise ValueError(f"{op}: shapes {tuple(cls_true.shape)}, {tuple(cls_pred.shape)}, {tuple(assign_mask.shape)}, "
+                         f"{tuple(cls_exists.shape)} do not fit")
+    B, A, Cn = cls_true.shape
+    dev = cls_true.device
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    ws = _train_ws(B, Cn, dev)
+    args = (_ptr(cls_true), _ptr(cls_pred), _ptr(assign_mask), _ptr(cls_exists), B, A, Cn, float(weight), float(alpha), float(gamma),
+            _ptr(ws), _ptr(out))
+    if not want_grad:
+        with _Prof(op, 0, 4 * (2 * cls_true.numel() + assign_mask.numel())):
+            _lib.check(_lib.load().ml_train_class_loss_f32(*args, _stream()), "ml_train_class_loss_f32")
+        return out
+    upstream = _upstream(op, upstream, B, dev)
+    grad = torch.empty((B, A, Cn), dtype=torch.float32, device=dev)
+    with _Prof(op, 0, 4 * (3 * cls_true.numel() + 2 * assign_mask.numel())):
+        _lib.check(_lib.load().ml_train_class_loss_grad_f32(*args, _ptr(upstream), int(bool(through_sigmoid)), _ptr(grad), _stream()),
+                   "ml_train_class_loss_grad_f32")
+    return out, grad
+
+
+def class_loss(cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma):
+    """ml_train_class_loss_f32 (ClassLoss.call): [B,A,C], [B,A,C], [B,A(,1)], [B,C] float32 -> float32 [B]."""
+    return _class_loss(False, cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma)
+
+
 def class_loss_grad(cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma, upstream=None, through_sigmoid=False):
     """ml_train_class_loss_grad_f32: class_loss plus d(sum_b upstream[b] * loss[b]) / d(cls_pred) -> (loss [B], grad [B,A,C]).
     through_sigmoid: times cls_pred * (1 - cls_pred), the gradient at the output conv's pre-activation."""
-    _require_f32("class_loss_grad", (cls_true, "cls_true"), (cls_pred, "cls_pred"), (assign_mask, "assign_mask"), (cls_exists, "cls_exists"))
-    if cls_true.dim() != 3 or cls_true.shape != cls_pred.shape or assign_mask.numel() * cls_true.shape[2] != cls_true.numel() or \
-            tuple(cls_exists.shape) != (cls_true.shape[0], cls_true.shape[2]):
-        raise ValueError(f"class_loss_grad: shapes {tuple(cls_true.shape)}, {tuple(cls_pred.shape)}, {tuple(assign_mask.shape)}, "
-                         f"{tuple(cls_exists.shape)} do not fit")
-    B, A, Cn = cls_true.shape
-    upstream = _upstream("class_loss_grad", upstream, B, cls_true.device)
-    out = torch.empty((B,), dtype=torch.float32, device=cls_true.device)
-    grad = torch.empty((B, A, Cn), dtype=torch.float32, device=cls_true.device)
-    ws = _train_ws(B, Cn, cls_true.device)
-    with _Prof("class_loss_grad", 0, 4 * (3 * cls_true.numel() + 2 * assign_mask.numel())):
-        _lib.check(_lib.load().ml_train_class_loss_grad_f32(_ptr(cls_true), _ptr(cls_pred), _ptr(assign_mask), _ptr(cls_exists), B, A, Cn,
-                                                            float(weight), float(alpha), float(gamma), _ptr(ws), _ptr(out), _ptr(upstream),
-                                                            int(bool(through_sigmoid)), _ptr(grad), _stream()),
-                   "ml_train_class_loss_grad_f32")
+    return _class_loss(True, cls_true, cls_pred, assign_mask, cls_exists, weight, alpha, gamma, upstream, through_sigmoid)
+
+
+def _box_loss(want_grad, loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state, upstream=None):
+    op = "box_loss_grad" if want_grad else "box_loss"
+    _require_f32(op, (loc_true, "loc_true"), (loc_pred, "loc_pred"), (assign_mask, "assign_mask"))
+    if loc_true.dim() != 3 or loc_true.shape[2] != 4 or loc_true.shape != loc_pred.shape or assign_mask.numel() * 4 != loc_true.numel():
+        raise ValueError(f"{op}: shapes {tuple(loc_true.shape)}, {tuple(loc_pred.shape)}, {tuple(assign_mask.shape)} do not fit")
+    if use_adjust:
+        _require_f32(op, (state, "state"))
+        if state.numel() != 8:
+            raise ValueError(f"{op}: `state` must hold moving_mean[4] and moving_var[4]")
+    B, A, _ = loc_true.shape
+    dev = loc_true.device
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    ws = _train_ws(B, 4, dev)
+    nbytes = 4 * (3 if use_adjust else 1) * (2 * loc_true.numel() + assign_mask.numel())           # with use_adjust, three passes
+    args = (_ptr(loc_true), _ptr(loc_pred), _ptr(assign_mask), B, A, float(weight), float(momentum), float(1 - momentum), float(beta),
+            int(bool(use_adjust)), _ptr(state if use_adjust else None), _ptr(ws), _ptr(out))
+    if not want_grad:
+        with _Prof(op, 0, nbytes):
+            _lib.check(_lib.load().ml_train_box_loss_f32(*args, _stream()), "ml_train_box_loss_f32")
+        return out
+    upstream = _upstream(op, upstream, B, dev)
+    grad = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+    with _Prof(op, 0, nbytes + 4 * (assign_mask.numel() + loc_true.numel())):
+        _lib.check(_lib.load().ml_train_box_loss_grad_f32(*args, _ptr(upstream), _ptr(grad), _stream()),
+                   "ml_train_box_loss_grad_f32")
     return out, grad
+
+
+def box_loss(loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state=None):
+    """ml_train_box_loss_f32 (BoxLoss.call): [B,A,4], [B,A,4], [B,A(,1)] float32 -> float32 [B].  state: float32 [8] on the
+    device = moving_mean, moving_var, updated in place when use_adjust."""
+    return _box_loss(False, loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state)
 
 
 def box_loss_grad(loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state=None, upstream=None):
     """ml_train_box_loss_grad_f32: box_loss plus d(sum_b upstream[b] * loss[b]) / d(loc_pred) -> (loss [B], grad [B,A,4]).
     `state` moves once, as by one box_loss call; beta is a constant of the gradient."""
-    _require_f32("box_loss_grad", (loc_true, "loc_true"), (loc_pred, "loc_pred"), (assign_mask, "assign_mask"))
-    if loc_true.dim() != 3 or loc_true.shape[2] != 4 or loc_true.shape != loc_pred.shape or assign_mask.numel() * 4 != loc_true.numel():
-        raise ValueError(f"box_loss_grad: shapes {tuple(loc_true.shape)}, {tuple(loc_pred.shape)}, {tuple(assign_mask.shape)} do not fit")
-    if use_adjust:
-        _require_f32("box_loss_grad", (state, "state"))
-        if state.numel() != 8:
-            raise ValueError("box_loss_grad: `state` must hold moving_mean[4] and moving_var[4]")
-    B, A, _ = loc_true.shape
-    upstream = _upstream("box_loss_grad", upstream, B, loc_true.device)
-    out = torch.empty((B,), dtype=torch.float32, device=loc_true.device)
-    grad = torch.empty((B, A, 4), dtype=torch.float32, device=loc_true.device)
-    ws = _train_ws(B, 4, loc_true.device)
-    passes = 3 if use_adjust else 1
-    with _Prof("box_loss_grad", 0, 4 * (passes * (2 * loc_true.numel() + assign_mask.numel()) + assign_mask.numel() + loc_true.numel())):
-        _lib.check(_lib.load().ml_train_box_loss_grad_f32(_ptr(loc_true), _ptr(loc_pred), _ptr(assign_mask), B, A, float(weight),
-                                                          float(momentum), float(1 - momentum), float(beta), int(bool(use_adjust)),
-                                                          _ptr(state if use_adjust else None), _ptr(ws), _ptr(out), _ptr(upstream),
-                                                          _ptr(grad), _stream()), "ml_train_box_loss_grad_f32")
+    return _box_loss(True, loc_true, loc_pred, assign_mask, weight, momentum, beta, use_adjust, state, upstream)
+
+
+def _mask_loss(want_grad, mask_true, mask_pred, weight, label_smoothing, upstream=None, through_sigmoid=False):
+    op = "mask_loss_grad" if want_grad else "mask_loss"
+    _require_dev(mask_true, "mask_true")
+    _require_f32(op, (mask_pred, "mask_pred"))
+    if mask_true.dtype != torch.int32 or mask_pred.dim() != 5 or tuple(mask_true.shape) != tuple(mask_pred.shape[:4]):
+        raise ValueError(f"{op}: int32 [B,R,h,w] targets and float32 [B,R,h,w,C] predictions expected, got {mask_true.dtype} "
+                         f"{tuple(mask_true.shape)} and {tuple(mask_pred.shape)}")
+    B, R, mh, mw, Cn = mask_pred.shape
+    dev = mask_pred.device
+    roi_loss = torch.empty((B, R), dtype=torch.float32, device=dev)
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    args = (_ptr(mask_true), _ptr(mask_pred), B, R, mh, mw, Cn, float(weight), float(1 - label_smoothing), float(label_smoothing / 2.),
+            _ptr(roi_loss), _ptr(out))
+    if not want_grad:
+        with _Prof(op, 0, 8 * mask_true.numel()):
+            _lib.check(_lib.load().ml_train_mask_loss_f32(*args, _stream()), "ml_train_mask_loss_f32")
+        return out
+    upstream = _upstream(op, upstream, B, dev)
+    grad = torch.empty((B, R, mh, mw, Cn), dtype=torch.float32, device=dev)
+    with _Prof(op, 0, 4 * (4 * mask_true.numel() + mask_pred.numel())):
+        _lib.check(_lib.load().ml_train_mask_loss_grad_f32(*args, _ptr(upstream), int(bool(through_sigmoid)), _ptr(grad), _stream()),
+                   "ml_train_mask_loss_grad_f32")
     return out, grad
+
+
+def mask_loss(mask_true, mask_pred, weight, label_smoothing):
+    """ml_train_mask_loss_f32 (MaskLoss.call): mask_true int32 [B,R,h,w], mask_pred float32 [B,R,h,w,C] -> float32 [B]."""
+    return _mask_loss(False, mask_true, mask_pred, weight, label_smoothing)
 
 
 def mask_loss_grad(mask_true, mask_pred, weight, label_smoothing, upstream=None, through_sigmoid=False):
     """ml_train_mask_loss_grad_f32: mask_loss plus d(sum_b upstream[b] * loss[b]) / d(mask_pred) -> (loss [B], grad
     [B,R,h,w,C]): non-zero only in the class channel of the selected RoIs."""
-    _require_dev(mask_true, "mask_true")
-    _require_f32("mask_loss_grad", (mask_pred, "mask_pred"))
-    if mask_true.dtype != torch.int32 or mask_pred.dim() != 5 or tuple(mask_true.shape) != tuple(mask_pred.shape[:4]):
-        raise ValueError(f"mask_loss_grad: int32 [B,R,h,w] targets and float32 [B,R,h,w,C] predictions expected, got {mask_true.dtype} "
-                         f"{tuple(mask_true.shape)} and {tuple(mask_pred.shape)}")
-    B, R, mh, mw, Cn = mask_pred.shape
-    upstream = _upstream("mask_loss_grad", upstream, B, mask_pred.device)
-    roi_loss = torch.empty((B, R), dtype=torch.float32, device=mask_pred.device)
-    out = torch.empty((B,), dtype=torch.float32, device=mask_pred.device)
-    grad = torch.empty((B, R, mh, mw, Cn), dtype=torch.float32, device=mask_pred.device)
-    with _Prof("mask_loss_grad", 0, 4 * (4 * mask_true.numel() + mask_pred.numel())):
-        _lib.check(_lib.load().ml_train_mask_loss_grad_f32(_ptr(mask_true), _ptr(mask_pred), B, R, mh, mw, Cn, float(weight),
-                                                           float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(roi_loss), _ptr(out),
-                                                           _ptr(upstream), int(bool(through_sigmoid)), _ptr(grad), _stream()),
-                   "ml_train_mask_loss_grad_f32")
+    return _mask_loss(True, mask_true, mask_pred, weight, label_smoothing, upstream, through_sigmoid)
+
+
+def _seg_loss(want_grad, seg_true, seg_pred, seg_exist, weight, label_smoothing, upstream=None, through_sigmoid=False):
+    op = "seg_loss_grad" if want_grad else "seg_loss"
+    _require_f32(op, (seg_true, "seg_true"), (seg_pred, "seg_pred"), (seg_exist, "seg_exist"))
+    if seg_true.dim() != 4 or seg_true.shape != seg_pred.shape or tuple(seg_exist.shape) != (seg_true.shape[0], seg_true.shape[3]):
+        raise ValueError(f"{op}: shapes {tuple(seg_true.shape)}, {tuple(seg_pred.shape)}, {tuple(seg_exist.shape)} do not fit")
+    B, H, W, Cn = seg_true.shape
+    dev = seg_true.device
+    out = torch.empty((B,), dtype=torch.float32, device=dev)
+    ws = _train_ws(B, Cn, dev)
+    args = (_ptr(seg_true), _ptr(seg_pred), _ptr(seg_exist), B, H * W, Cn, float(weight), float(1 - label_smoothing),
+            float(label_smoothing / 2.), _ptr(ws), _ptr(out))
+    if not want_grad:
+        with _Prof(op, 0, 8 * seg_true.numel()):
+            _lib.check(_lib.load().ml_train_seg_loss_f32(*args, _stream()), "ml_train_seg_loss_f32")
+        return out
+    upstream = _upstream(op, upstream, B, dev)
+    grad = torch.empty((B, H, W, Cn), dtype=torch.float32, device=dev)
+    with _Prof(op, 0, 12 * seg_true.numel()):
+        _lib.check(_lib.load().ml_train_seg_loss_grad_f32(*args, _ptr(upstream), int(bool(through_sigmoid)), _ptr(grad), _stream()),
+                   "ml_train_seg_loss_grad_f32")
     return out, grad
+
+
+def seg_loss(seg_true, seg_pred, seg_exist, weight, label_smoothing):
+    """ml_train_seg_loss_f32 (SegLoss.call): seg_true, seg_pred [B,H,W,C], seg_exist [B,C] float32 -> float32 [B]."""
+    return _seg_loss(False, seg_true, seg_pred, seg_exist, weight, label_smoothing)
 
 
 def seg_loss_grad(seg_true, seg_pred, seg_exist, weight, label_smoothing, upstream=None, through_sigmoid=False):
     """ml_train_seg_loss_grad_f32: seg_loss plus d(sum_b upstream[b] * loss[b]) / d(seg_pred) -> (loss [B], grad [B,H,W,C])."""
-    _require_f32("seg_loss_grad", (seg_true, "seg_true"), (seg_pred, "seg_pred"), (seg_exist, "seg_exist"))
-    if seg_true.dim() != 4 or seg_true.shape != seg_pred.shape or tuple(seg_exist.shape) != (seg_true.shape[0], seg_true.shape[3]):
-        raise ValueError(f"seg_loss_grad: shapes {tuple(seg_true.shape)}, {tuple(seg_pred.shape)}, {tuple(seg_exist.shape)} do not fit")
-    B, H, W, Cn = seg_true.shape
-    upstream = _upstream("seg_loss_grad", upstream, B, seg_true.device)
-    out = torch.empty((B,), dtype=torch.float32, device=seg_true.device)
-    grad = torch.empty((B, H, W, Cn), dtype=torch.float32, device=seg_true.device)
-    ws = _train_ws(B, Cn, seg_true.device)
-    with _Prof("seg_loss_grad", 0, 12 * seg_true.numel()):
-        _lib.check(_lib.load().ml_train_seg_loss_grad_f32(_ptr(seg_true), _ptr(seg_pred), _ptr(seg_exist), B, H * W, Cn, float(weight),
-                                                          float(1 - label_smoothing), float(label_smoothing / 2.), _ptr(ws), _ptr(out),
-                                                          _ptr(upstream), int(bool(through_sigmoid)), _ptr(grad), _stream()),
-                   "ml_train_seg_loss_grad_f32")
-    return out, grad
+    return _seg_loss(True, seg_true, seg_pred, seg_exist, weight, label_smoothing, upstream, through_sigmoid)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The four loss layers' backward (csrc/train_grads.hip) at the default configuration's 8 x 1024 x 1024 shapes -- A = 327 360
+"""The four loss layers' backward (csrc/train_losses.hip) at the default configuration's 8 x 1024 x 1024 shapes -- A = 327 360
 priors and 5 classes for ClassLoss / BoxLoss(use_adjust), 132 RoIs (32 ground truths + 100 proposals) of 28 x 28 x 5 for
 MaskLoss, the 128 x 128 x 3 map of the skip level for SegLoss -- per loss four numbers:
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The trainer forward's detection tail -- best prior per ground truth, AssignBoxes, ClassLoss, BoxLoss (csrc/train_targets.hip)
+"""The trainer forward's detection tail -- best prior per ground truth, AssignBoxes, ClassLoss, BoxLoss (csrc/train_targets.hip, csrc/train_losses.hip)
 -- at 8 x 1024 x 1024 (A = 327 360 priors, G = 32 ground truths per image, 5 classes), three numbers:
 
   (a) kernels  the four ops through masklab_hip.ops, predictions and ground truth already on the device;

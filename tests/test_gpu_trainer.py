@@ -1,4 +1,4 @@
-"""GPU tests of the trainer forward: the assignment and loss kernels (csrc/train_targets.hip), their layers and the trainer
+"""GPU tests of the trainer forward: the assignment and loss kernels (csrc/train_targets.hip, csrc/train_losses.hip), their layers and the trainer
 model against the NumPy restatement tests/trainer_ref.py.  Assigned targets are compared for exact equality (the log columns
 of loc_true within 4 float32 ulp), losses to rtol 1e-5 / atol 1e-6 * weight: with FP contraction off every term is the
 restatement's up to the few-ulp difference of log / pow (2^-24 each) and the sums are float64 on both sides, which leaves

@@ -1,4 +1,4 @@
-"""GPU tests of the losses' backward (csrc/train_grads.hip): the four fused "loss + gradient" ops, the layers'
+"""GPU tests of the losses' backward (csrc/train_losses.hip): the four fused "loss + gradient" ops, the layers'
 call_with_grad and TrainerModel.loss_and_gradients against torch autograd over the float64 restatement of
 tests/trainer_grad_ref.py.  The bar is |got - want| <= 1e-5 * S, S the uncancelled magnitude (trainer_grad_ref.check): a term
 is about a dozen float32 operations plus logf / powf, each within a couple of ulp, about 1e-6 of S.  Every case also holds:

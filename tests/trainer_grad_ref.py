@@ -6,7 +6,7 @@
     assigned variable carry no gradient in TensorFlow, and none here: tf.where / torch.where select, sums of masks do not
     depend on the prediction, and BoxLoss's beta is detached.
 2.  The closed forms of include/masklab_hip.h ("Trainer backward: the losses") in float32 NumPy, the way the kernels of
-    csrc/train_grads.hip evaluate them, and in float64 the magnitude S every comparison is scaled by: the same expression
+    csrc/train_losses.hip evaluate them, and in float64 the magnitude S every comparison is scaled by: the same expression
     with the two cross-entropy terms ADDED in absolute value (for the focal and the smooth-L1 gradient nothing cancels and S
     is |gradient|).
 
