@@ -10,8 +10,9 @@
 //   Block = 512 threads = 8 waves, one block per CU; block tile = 64 Winograd tiles (flattened over image, tile row, tile
 //   column) x 64 output channels (two 32-channel blocks of the host layout); ceil(cout / 64) such channel blocks per tile block.  Wave w owns tile group tg = w & 3 (tiles
 //   16 tg .. 16 tg + 15) x channel half h = w >> 2 (32 channels) x all 16 positions: 2 x 16 accumulators of the 16x16x4
-//   MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of its 4 tiles x 1
-//   channel per 16-wide half).  The patches of a tile group are staged once and read by both channel halves.
+//   MFMA = 128 registers, so the output transform runs in registers (a lane holds all 16 positions of 1 tile x 4
+//   channels per 16-wide half: the B fragment is the MFMA's first operand, see Epilogue).  The patches of a tile group are
+//   staged once and read by both channel halves.
 //   K step = 4 input channels = 32 MFMAs per wave.  Staging is by LDS DMA (buffer_load_dwordx4 ... lds, 16 B per lane, 1 KB
 //   per wave instruction) straight from global memory into two rings, with ONE barrier per two K steps:
 //     * patches in chunks of 8 channels (two K steps), 3 slots of 32 KB, 4 DMA instructions per wave and chunk.  A slot holds
@@ -82,11 +83,25 @@
 //   cycles plus the step's 0.20-0.36 us beyond them), and all three classes (<= 32, 33..64, 65..96) are faster here; the
 //   predicate leaves out only cout = 32 and 64 themselves, for the reason given there.
 //
-//   Epilogue: Y = A^T M A per (tile, channel), bias + activation, scalar stores (16 lanes = 64 contiguous bytes) with the
-//   generic addressing: out_coff / out_cstride / out_bstride.  gn_partials: on the geometries where a block covers
-//   exactly two whole 128-pixel flattened tiles (host check wino_gn_ok), slots 2 nt2 + h (the block's two 32-channel
-//   groups) of each of them get that group's (sum, sum of squares) in fp64, its 4 waves added in tile-group order; the
-//   2 blocks of cout = 128 fill all 4 slots.  Output addressing is 64-bit.  Several problems (pyramid levels) per
+//   Epilogue (profiles/r18_wino_epilogue.md).  v_mfma_f32_16x16x4_f32 takes one float per lane for each operand with the
+//   same lane map [l & 15][l >> 4], so with the B fragment as its FIRST operand and the transformed patch value as its
+//   second the 16 x 16 tile comes out transposed -- the same products in the same k order, the same bits -- and lane
+//   (r, kq) owns tile 16 tg + r and channels 16 t + 4 kq .. + 3 of its half as the four floats of each accumulator.  So: one
+//   set of tile-to-address arithmetic per lane (it was four), Y = A^T M A on f32x4 values, bias as one 16-byte load, and per
+//   half and output pixel one 16-byte store with the generic addressing (out_coff / out_cstride / out_bstride): 8 store
+//   instructions per lane where the tile-major accumulators needed 32 dword stores.  The 16-byte accesses are dword-aligned
+//   (f32x4d: the hardware's global_store_dwordx4 asks no more), so the class tower's output at a channel stride of 75 and
+//   an out_view offset that is no multiple of 4 take the same path as a dense 128-wide tensor.  Only a quad that reaches
+//   past cout (cout % 4 != 0: 72..74 of 75) is stored channel by channel; a quad wholly past cout stores nothing.
+//   Measured against the dword epilogue, alternating in one job: the 128^2 launch 204-206 -> 194-197 us, the tower launch
+//   287-291 -> 278-280, cout 75 293-296 -> 282-285, cout 60 157-159 -> 151; with the stores sent through an empty resource
+//   (make wino-exp, bit 3) either epilogue loses another 4-8 us per launch, so what the rewrite saved is issue and address
+//   work, not bytes.
+//   gn_partials: on the geometries where a block covers exactly two whole 128-pixel flattened tiles (host check
+//   wino_gn_ok), slots 2 nt2 + h (the block's two 32-channel groups) of each of them get that group's (sum, sum of
+//   squares) in fp64: a lane adds the 2 halves x 4 channels x 4 pixels it stores, each value widened first, the wave folds
+//   its lanes, and the group's 4 waves are added in tile-group order; the 2 blocks of cout = 128 fill all 4 slots.  About
+//   6 us of a tower launch (bit 4 of WINO_EXP skips it).  Output addressing is 64-bit.  Several problems (pyramid levels) per
 //   launch; no host reads, no allocation: capturable in a hipGraph.  Fixed-capacity RoI batches (`live`): blocks that hold
 //   only non-existing images return at once, so a mask-head conv runs on the same kernel (same bits) with or without
 //   `live`.
@@ -109,7 +124,9 @@ constexpr int LDS_BYTES = (RING_W + NSLOT_W * SLOT_W) * 4;   // 160 KB: all of a
 static_assert(LDS_BYTES == 160 * 1024, "the two rings fill the CU's LDS");
 // Experiment builds (make wino-exp; never the default library): WINO_EXP bit 0 sends the patch DMAs, bit 1 the weight
 // DMAs through empty resources (same instructions, no line fetched, WRONG outputs: for timing only); WINO_EXP = 4 issues
-// a step's DMAs in one burst at the step's head instead of spread through its MFMAs.
+// a step's DMAs in one burst at the step's head instead of spread through its MFMAs.  Two bits split the time outside the
+// K loop: bit 3 (8) sends the epilogue's stores through an empty buffer resource (the same count and width of store
+// instructions, no byte written), bit 4 (16) skips the gn_partials sums and their exchange.
 #ifndef WINO_EXP
 #define WINO_EXP 0
 #endif
@@ -134,6 +151,30 @@ struct WArgs {
 __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, float *dst, int voff) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, 0, 0, 0);
+#endif
+}
+
+// Four consecutive channels of one pixel at a dword-aligned address: a channel stride or offset that is no multiple of 4
+// (the 75 classes written into cls_pred) takes the same 16-byte global instruction as an aligned destination.
+typedef f32x4 f32x4d __attribute__((aligned(4)));
+
+// One store of the epilogue (a float, or the four channels of a lane).  WINO_EXP bit 3: as a buffer store through
+// an empty resource, which the hardware drops.
+__device__ __forceinline__ void out_store(float *base, float *ptr, float val) {
+#if (WINO_EXP & 8) && defined(__HIP_DEVICE_COMPILE__)
+    const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), none, (int)((ptr - base) * 4), 0, 0);
+#else
+    *ptr = val;
+#endif
+}
+__device__ __forceinline__ void out_store(float *base, float *ptr, f32x4 val) {
+#if (WINO_EXP & 8) && defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), none, (int)((ptr - base) * 4), 0, 0);
+#else
+    *reinterpret_cast<f32x4d *>(ptr) = val;
 #endif
 }
 
@@ -287,7 +328,7 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         for (int m = 0; m < 32; ++m) {
             const int t = m >> 4, pq = (m >> 2) & 3, e = m & 3;
             acc[t][4 * pq + e] =
-                __builtin_amdgcn_mfma_f32_16x16x4f32(cur.v[4 * pq + e], cur.b[t][pq][e], acc[t][4 * pq + e], 0, 0, 0);
+                __builtin_amdgcn_mfma_f32_16x16x4f32(cur.b[t][pq][e], cur.v[4 * pq + e], acc[t][4 * pq + e], 0, 0, 0);
             if (m == 3) {
                 __builtin_amdgcn_sched_barrier(0);
                 read_ops(pa, pb, nxt);
@@ -385,9 +426,11 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the empty DMAs past the last chunk
 
-    // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1]; lane holds tiles tg*16 + kq*4 + i, channel 16t + r
+    // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1], on the four channels of a lane at once.  The B fragment is the
+    // MFMA's first operand, so the tile comes out transposed: lane (r, kq) holds tile tg * 16 + r and channels
+    // 16 t + 4 kq .. + 3 of its half as the four floats of acc[t][position].
     const int nt = 2 * nt2 + h;                        // this wave's 32-channel group
-    const bool gn = p.gn_partials != nullptr;      // (block-uniform; host: wino_gn_ok)
+    const bool gn = p.gn_partials != nullptr && !(WINO_EXP & 16);   // (block-uniform; host: wino_gn_ok)
     double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
     long long f0 = 0;
     if (gn) {
@@ -396,51 +439,59 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     }
     const float lo = 0.f, hi = (p.act == ML_ACT_RELU6) ? 6.f : 3.402823466e38f;
     const bool clampv = p.act == ML_ACT_RELU || p.act == ML_ACT_RELU6;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int gt = gt0 + tg * 16 + kq * 4 + i;
-        if (gt >= P.T) continue;
+    const int gt = gt0 + tg * 16 + r;
+    if (gt < P.T) {
         const int bi = gt / tpi, rem = gt - bi * tpi;
         const int ty = rem / P.TW, tx = rem - ty * P.TW;
         const int oy = 2 * ty, ox = 2 * tx;
         const bool y1 = oy + 1 < p.Ho, x1 = ox + 1 < p.Wo;
         const size_t img = p.out_bstride ? (size_t)bi * (size_t)p.out_bstride : (size_t)bi * p.Ho * p.Wo * p.out_cstride;
         const size_t pix0 = (size_t)oy * p.Wo + ox;
+        const long long m_flat0 = (long long)(bi * p.Ho + oy) * p.Wo + ox;
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const int n = nt * 32 + 16 * t + r;
+            const int n = nt * 32 + 16 * t + 4 * kq;   // the lane's first channel of this half
             if (n >= p.cout) continue;
-            float m[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) m[q] = acc[t][q][i];
-            float u[8];                            // A^T M: rows 0, 1 x 4 columns
+            const bool quad = n + 4 <= p.cout;         // else cout % 4 of the four are live: stored one by one
+            f32x4 u[8];                                // A^T M: rows 0, 1 x 4 columns
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                u[j] = m[0 * 4 + j] + m[1 * 4 + j] + m[2 * 4 + j];
-                u[4 + j] = m[1 * 4 + j] - m[2 * 4 + j] - m[3 * 4 + j];
+                u[j] = acc[t][0 * 4 + j] + acc[t][1 * 4 + j] + acc[t][2 * 4 + j];
+                u[4 + j] = acc[t][1 * 4 + j] - acc[t][2 * 4 + j] - acc[t][3 * 4 + j];
             }
-            float yv[4];
+            f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+            if (p.bias) {
+                if (quad) bv = *reinterpret_cast<const f32x4d *>(p.bias + n);
+                else
 #pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                yv[2 * a] = u[4 * a + 0] + u[4 * a + 1] + u[4 * a + 2];
-                yv[2 * a + 1] = u[4 * a + 1] - u[4 * a + 2] - u[4 * a + 3];
+                    for (int c = 0; c < 3; ++c)
+                        if (n + c < p.cout) bv[c] = p.bias[n + c];
             }
-            const float bv = p.bias ? p.bias[n] : 0.f;
             float *o = p.out + img + p.out_coff + n;
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2) {
                     if ((a && !y1) || (c2 && !x1)) continue;
-                    float val = yv[2 * a + c2] + bv;
-                    if (clampv) val = __builtin_amdgcn_fmed3f(val, lo, hi);
-                    else if (p.act != ML_ACT_NONE) val = ml_apply_act(val, p.act);
-                    o[(pix0 + (size_t)a * p.Wo + c2) * p.out_cstride] = val;
-                    if (gn) {
-                        const long long m_flat = ((long long)(bi * p.Ho + oy + a) * p.Wo + ox + c2);
-                        const int f = (m_flat >> 7) != f0;
-                        gs[f] += (double)val;
-                        gq[f] += (double)val * (double)val;
+                    f32x4 val = (c2 ? u[4 * a + 1] - u[4 * a + 2] - u[4 * a + 3] : u[4 * a + 0] + u[4 * a + 1] + u[4 * a + 2]) + bv;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (clampv) val[c] = __builtin_amdgcn_fmed3f(val[c], lo, hi);
+                        else if (p.act != ML_ACT_NONE) val[c] = ml_apply_act(val[c], p.act);
+                    }
+                    float *op = o + (pix0 + (size_t)a * p.Wo + c2) * p.out_cstride;
+                    if (quad) out_store(p.out, op, val);
+                    else
+#pragma unroll
+                        for (int c = 0; c < 3; ++c)
+                            if (n + c < p.cout) out_store(p.out, op + c, val[c]);
+                    if (gn) {                          // (cout = 128: every channel of the quad is stored)
+                        const int f = ((m_flat0 + (long long)a * p.Wo + c2) >> 7) != f0;
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            gs[f] += (double)val[c];
+                            gq[f] += (double)val[c] * (double)val[c];
+                        }
                     }
                 }
         }
