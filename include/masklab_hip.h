@@ -66,7 +66,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             _plan / _workspace_bytes / _device / _reference_host;
                                             (additive, same version) ml_conv1x1_dual_f32 / _f16;
                                             (additive, same version) ml_gn_grad_desc, ml_groupnorm_chunk_grad_f32 /
-                                            _grad_multi_f32 / _grad_workspace_bytes, ml_groupnorm_chunk_stats_f32 */
+                                            _grad_multi_f32 / _grad_workspace_bytes, ml_groupnorm_chunk_stats_f32;
+                                            (additive, same version) ml_opt_tensor / _state / _scalars,
+                                            ml_optimizer_plan / _scalars / _apply_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -1086,6 +1088,60 @@ int ml_polygon_semantic_maps(const double *verts, int64_t total, const int32_t *
 int ml_polygon_reference_host(int32_t kind, const double *verts, int64_t total, const int32_t *offsets, int32_t P,
                               const int32_t *group_offsets, const int32_t *windows, int32_t B, int32_t n_or_S, int32_t H, int32_t W,
                               void *out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Optimizers: the reference's RectifiedAdam and AdamW (engine/optimizers.py) as one step over any number of float32
+ * tensors (csrc/optimizer.hip).  A step is two launches on `stream`, no workspace, no atomics, no host read:
+ *   scalars   one thread reads `state` (iterations and lr live on the device, so a captured step replays with the values
+ *             of its replay), forms the step's scalars in float64, writes them as floats into `scalars`, then adds 1 to
+ *             state->iterations.  With it = iterations before the add, t = it + 1, lr' = lr / (1 + decay * it) if decay > 0:
+ *               RectifiedAdam  N_max = 2 / (1 - beta_2) - 1,  N = N_max - 2 t beta_2^t / (1 - beta_2^t),  rectified = N > 5,
+ *                              step = lr' sqrt((1 - beta_2^t) (N - 4) / (N_max - 4) (N - 2) / N N_max / (N_max - 2)) / (1 - beta_1^t)
+ *                              if rectified, else lr' / (1 - beta_1^t);  wd_lr = weight_decay lr'
+ *               AdamW          lr_t = lr' sqrt(1 - beta_2^t) / (1 - beta_1^t),  eta_wd = (lr' / init_lr) weight_decay
+ *   apply     per element, float32, one rounding per operation in this order (FP contraction off, correctly rounded
+ *             divide and square root):
+ *               m' = beta_1 m + (1 - beta_1) g,   v' = beta_2 v + (1 - beta_2) (g g)
+ *               RectifiedAdam  p_ = p - wd_lr p (only if weight_decay != 0, else p_ = p)
+ *                              p' = p_ - step (m' / (sqrt(v') + epsilon)) if rectified, else p' = p_ - step m'
+ *               AdamW          p' = p - lr_t m' / (sqrt(v') + epsilon) - eta_wd p
+ *             One launch for every tensor of the device table: the elements are cut into chunks of ML_OPT_CHUNK, a block
+ *             finds its chunk's tensor by a search over `first_chunk` and grid-strides over the chunks.  16-byte accesses
+ *             where p, g, m, v of a tensor are all 16-byte aligned, scalar ones otherwise and for the last n mod 4 elements.
+ *             Every element is read and written by one lane; n = 0 is legal.  The kernel clamps every chunk to its tensor's
+ *             n, so a wrong `total_chunks` skips or repeats nothing out of bounds.
+ * ------------------------------------------------------------------------------------------- */
+enum { ML_OPT_RADAM = 0, ML_OPT_ADAMW = 1 };
+#define ML_OPT_CHUNK 4096
+typedef struct ml_opt_tensor {
+    float *p;                      /* the weights, updated in place                                 */
+    const float *g;                /* their gradient                                                */
+    float *m, *v;                  /* first and second moment, updated in place                     */
+    int64_t n;                     /* floats in each of the four                                    */
+    int64_t first_chunk;           /* chunks of the tensors in front (ml_optimizer_plan fills it)   */
+} ml_opt_tensor;
+typedef struct ml_opt_state {
+    int64_t iterations;            /* steps taken                                                   */
+    float lr;                      /* the learning rate the next step reads                         */
+    int32_t reserved;
+} ml_opt_state;
+typedef struct ml_opt_scalars {
+    float beta_1, one_minus_beta_1, beta_2, one_minus_beta_2, epsilon;
+    float lr;                      /* lr' (after `decay`)                                           */
+    float step, wd_lr;             /* RectifiedAdam (0 for AdamW)                                   */
+    float lr_t, eta_wd;            /* AdamW (0 for RectifiedAdam)                                   */
+    int32_t rectified;             /* RectifiedAdam: N > 5; AdamW: 1                                */
+    int32_t decays;                /* weight_decay != 0                                             */
+} ml_opt_scalars;
+/* Host.  Fills first_chunk of the n entries of a table in HOST memory -> the number of chunks, or ML_E_BADARG for a null
+ * pointer with n > 0 elements or a negative count.                                                                       */
+int64_t ml_optimizer_plan(ml_opt_tensor *host_table, int32_t n);
+/* state, scalars: device memory.  kind = ML_OPT_*; init_lr is read by AdamW only.                                       */
+int ml_optimizer_scalars(int32_t kind, ml_opt_state *state, ml_opt_scalars *scalars, double beta_1, double beta_2, double epsilon,
+                         double decay, double weight_decay, double init_lr, void *stream);
+/* table [n] and scalars: device memory; total_chunks as ml_optimizer_plan returned it for this table.                   */
+int ml_optimizer_apply_f32(int32_t kind, const ml_opt_tensor *table, int32_t n, int64_t total_chunks, const ml_opt_scalars *scalars,
+                           void *stream);
 
 #ifdef __cplusplus
 }

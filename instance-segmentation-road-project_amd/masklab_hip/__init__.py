@@ -28,4 +28,6 @@ def get_custom_objects():
     reg.update({n: getattr(metrics, n) for n in metrics.__all__})
     from . import losses
     reg.update({n: getattr(losses, n) for n in losses.__all__})
+    from . import optimizers
+    reg.update({n: getattr(optimizers, n) for n in optimizers.__all__})
     return reg

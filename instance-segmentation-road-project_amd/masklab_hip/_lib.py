@@ -88,11 +88,29 @@ class SeBottleneckDesc(C.Structure):
                 ("B", C.c_int32), ("HW", C.c_int32), ("C", C.c_int32), ("Hd", C.c_int32)]
 
 
+class OptTensor(C.Structure):
+    """Mirror of `ml_opt_tensor` (include/masklab_hip.h)."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("first_chunk", C.c_int64)]
+
+
+class OptState(C.Structure):
+    """Mirror of `ml_opt_state` (include/masklab_hip.h)."""
+    _fields_ = [("iterations", C.c_int64), ("lr", C.c_float), ("reserved", C.c_int32)]
+
+
+class OptScalars(C.Structure):
+    """Mirror of `ml_opt_scalars` (include/masklab_hip.h)."""
+    _fields_ = [("beta_1", C.c_float), ("one_minus_beta_1", C.c_float), ("beta_2", C.c_float), ("one_minus_beta_2", C.c_float),
+                ("epsilon", C.c_float), ("lr", C.c_float), ("step", C.c_float), ("wd_lr", C.c_float), ("lr_t", C.c_float),
+                ("eta_wd", C.c_float), ("rectified", C.c_int32), ("decays", C.c_int32)]
+
+
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
 DECONV_OUT_MAX_PROBLEMS = 4
-_i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
+_i32, _i64, _f32, _f64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
 # name -> (restype, argtypes); every symbol include/masklab_hip.h declares
 SIGNATURES = {
@@ -216,7 +234,12 @@ SIGNATURES = {
     "ml_polygon_instance_masks": (C.c_int, [_vp, _i64, _vp, _vp] + [_i32] * 4 + [_vp, _vp]),
     "ml_polygon_semantic_maps": (C.c_int, [_vp, _i64, _vp, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
     "ml_polygon_reference_host": (C.c_int, [_i32, _vp, _i64, _vp, _i32, _vp, _vp] + [_i32] * 4 + [_vp]),
+    "ml_optimizer_plan": (_i64, [_vp, _i32]),
+    "ml_optimizer_scalars": (C.c_int, [_i32, _vp, _vp] + [_f64] * 6 + [_vp]),
+    "ml_optimizer_apply_f32": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _vp]),
 }
+OPT_RADAM, OPT_ADAMW = 0, 1                                         # ML_OPT_*
+OPT_CHUNK = 4096                                                    # ML_OPT_CHUNK
 POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1                           # ML_POLYGON_*
 CV_RESIZE_U8, CV_RESIZE_ROUND_U8, CV_RESIZE_ROUND_F32 = 0, 1, 2     # ML_CV_RESIZE_*
 TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1                    # ML_TRAIN_MASK_*

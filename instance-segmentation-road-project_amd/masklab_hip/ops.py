@@ -2378,3 +2378,165 @@ def seg_loss(seg_true, seg_pred, seg_exist, weight, label_smoothing):
 def seg_loss_grad(seg_true, seg_pred, seg_exist, weight, label_smoothing, upstream=None, through_sigmoid=False):
     """ml_train_seg_loss_grad_f32: seg_loss plus d(sum_b upstream[b] * loss[b]) / d(seg_pred) -> (loss [B], grad [B,H,W,C])."""
     return _seg_loss(True, seg_true, seg_pred, seg_exist, weight, label_smoothing, upstream, through_sigmoid)
+
+
+# ----------------------------------------------------------------------------- optimizers (csrc/optimizer.hip)
+OPTIMIZER_KINDS = {"RectifiedAdam": _lib.OPT_RADAM, "AdamW": _lib.OPT_ADAMW}
+_OPT_ROLES = ("p", "g", "m", "v")
+
+
+def _optimizer_refuse(i, quad):
+    """Words the TypeError / ValueError of tensor i, whose quick checks failed."""
+    if len(quad) != 4:
+        raise ValueError(f"optimizer_step: tensor {i} must be a (p, g, m, v) tuple")
+    for role, t in zip(_OPT_ROLES, quad):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"optimizer_step: `{role}` of tensor {i} is a {type(t).__name__}, not a torch tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"optimizer_step: `{role}` of tensor {i} is {t.dtype}; the step is float32 only")
+    n = quad[0].numel()
+    for role, t in zip(_OPT_ROLES, quad):
+        if not t.is_contiguous():
+            raise ValueError(f"optimizer_step: `{role}` of tensor {i} must be contiguous")
+        if t.numel() != n:
+            raise ValueError(f"optimizer_step: `{role}` of tensor {i} has {t.numel()} elements, `p` has {n}")
+    ptrs = [t.data_ptr() for t in quad]
+    order = sorted(range(4), key=ptrs.__getitem__)
+    for a, b in zip(order, order[1:]):
+        if ptrs[b] - ptrs[a] < 4 * n:
+            raise ValueError(f"optimizer_step: `{_OPT_ROLES[a]}` and `{_OPT_ROLES[b]}` of tensor {i} overlap")
+    raise AssertionError("optimizer_step: a tensor was refused for no reason")
+
+
+def optimizer_check(tensors):
+    """The argument checks of a step, all on the host: float32 (TypeError); contiguous, equal numel, the four buffers of a
+    tensor apart from each other (ValueError); and only when all of that holds: all on one device, none on the host
+    (RuntimeError).  tensors: list of (p, g, m, v).  -> the table's key: a tuple of (p, g, m, v addresses, numel) per tensor.
+    Runs every step over every tensor (an address may change under the same object), so the passing path is kept short."""
+    f32, key, device, misplaced = torch.float32, [], None, None
+    for i, quad in enumerate(tensors):
+        try:
+            p, g, m, v = quad
+            fine = (p.dtype is f32 and g.dtype is f32 and m.dtype is f32 and v.dtype is f32 and
+                    p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous())
+            n = p.numel()
+            fine = fine and g.numel() == n and m.numel() == n and v.numel() == n
+        except (AttributeError, TypeError, ValueError):
+            fine = False
+        if not fine:
+            _optimizer_refuse(i, quad)
+        a, b, c, d = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
+        if n:
+            w, x, y, z = sorted((a, b, c, d))
+            if x - w < 4 * n or y - x < 4 * n or z - y < 4 * n:
+                _optimizer_refuse(i, quad)
+        key.append((a, b, c, d, n))
+        if misplaced is None:
+            at = p.get_device()                              # -1: the host
+            if device is None and at >= 0:
+                device = at
+            if not (at == device and g.get_device() == at and m.get_device() == at and v.get_device() == at):
+                role, t = next((r, t) for r, t in zip(_OPT_ROLES, quad) if t.get_device() != device)
+                misplaced = (role, i, t.device)
+    if misplaced is not None:
+        role, i, where = misplaced
+        if where.type != "cuda":
+            raise RuntimeError(f"optimizer_step: `{role}` of tensor {i} is on {where}: the step runs only on the MI355X kernels "
+                               f"(no CPU fallback)")
+        raise RuntimeError(f"optimizer_step: `{role}` of tensor {i} is on {where}, the tensors before it on cuda:{device}")
+    return tuple(key)
+
+
+class OptimizerTable:
+    """The device table of a step (`ml_opt_tensor` per tensor) and its pinned staging memory.  update() uploads the table
+    only when an address or a size in it differs from the last upload: a stream-ordered copy from pinned memory on the current
+    stream, never a device synchronise.  A captured step holds the table's address, so the table cannot change during a
+    capture: take one eager step with the same tensors first."""
+
+    def __init__(self):
+        self.key = None
+        self.table = None
+        self.n = 0
+        self.chunks = 0
+        self.uploads = 0            # how many times the table went up (tests, timing)
+        self._staging = _Staging()
+        self._retired = []          # outgrown tables: a graph captured earlier may replay with their address
+
+    def update(self, key, device):
+        """key: what optimizer_check returned for the step's tensors."""
+        if key == self.key and (self.table is None or self.table.device == device):
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("optimizer_step: the tensors differ from the last eager step's, and the device table cannot be "
+                               "uploaded while a graph is captured: take one eager step with these tensors first")
+        lib = _lib.load()
+        n = len(key)
+        nbytes = n * C.sizeof(_lib.OptTensor)
+        chunks = 0
+        if n:
+            slot = self._staging.take(nbytes)
+            host = slot[0]
+            arr = (_lib.OptTensor * n).from_address(host.data_ptr())
+            for e, (p, g, m, v, numel) in zip(arr, key):
+                e.p, e.g, e.m, e.v, e.n, e.first_chunk = p, g, m, v, numel, 0
+            chunks = int(lib.ml_optimizer_plan(C.c_void_p(host.data_ptr()), n))
+            if chunks < 0:
+                _lib.check(chunks, "ml_optimizer_plan")
+            if self.table is None or self.table.numel() < nbytes or self.table.device != device:
+                if self.table is not None:
+                    self._retired.append(self.table)
+                self.table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self.table[:nbytes].copy_(host[:nbytes], non_blocking=True)
+            slot[1] = torch.cuda.Event()
+            slot[1].record()
+            self.uploads += 1
+        self.key, self.n, self.chunks = key, n, chunks
+
+
+def optimizer_state(device, iterations=0, lr=0.001):
+    """`ml_opt_state` on the device: int64 iterations, float32 lr (and 4 bytes of padding), as an int64 [2] tensor."""
+    host = np.zeros(1, dtype=np.dtype([("iterations", "<i8"), ("lr", "<f4"), ("reserved", "<i4")]))
+    host["iterations"], host["lr"] = int(iterations), float(lr)
+    return torch.from_numpy(host.view(np.int64).copy()).to(device)
+
+
+def optimizer_state_lr(state):
+    """The float32 [1] view of a state's lr: fill_() sets it in stream order, .item() reads it."""
+    return state.view(torch.float32)[2:3]
+
+
+def optimizer_scalars_buffer(device):
+    """`ml_opt_scalars` on the device, zeroed: what the scalars launch of a step writes and its apply launch reads."""
+    return torch.zeros(C.sizeof(_lib.OptScalars), dtype=torch.uint8, device=device)
+
+
+def optimizer_scalars_read(scalars):
+    """A host copy of the device's `ml_opt_scalars` (a device-to-host read: for tests and logging, not part of a step)."""
+    return _lib.OptScalars.from_buffer_copy(scalars.cpu().numpy().tobytes())
+
+
+def optimizer_step(kind, tensors, table, state, scalars, beta_1, beta_2, epsilon, decay=0., weight_decay=0., init_lr=1.):
+    """One step of the reference's RectifiedAdam / AdamW (kind: a key of OPTIMIZER_KINDS) over every (p, g, m, v) of `tensors`
+    in two launches on the current stream: ml_optimizer_scalars reads `state` (optimizer_state: iterations and lr stay on the
+    device), writes `scalars` (optimizer_scalars_buffer) and adds 1 to the iterations; ml_optimizer_apply_f32 updates p, m, v
+    of every tensor in place.  table: the OptimizerTable of this parameter set.  Nothing is read on the host, so a step can be
+    captured into a graph (after one eager step, which uploads the table).  An empty `tensors` still counts a step."""
+    if kind not in OPTIMIZER_KINDS:
+        raise ValueError(f"optimizer_step: kind must be one of {sorted(OPTIMIZER_KINDS)}, got {kind!r}")
+    key = optimizer_check(tensors)
+    for name, t in (("state", state), ("scalars", scalars)):
+        _require_dev(t, name)
+    if state.dtype != torch.int64 or state.numel() != 2 or scalars.dtype != torch.uint8 or scalars.numel() != C.sizeof(_lib.OptScalars):
+        raise ValueError("optimizer_step: `state` must come from optimizer_state() and `scalars` from optimizer_scalars_buffer()")
+    if key and tensors[0][0].device != state.device:
+        raise RuntimeError(f"optimizer_step: the tensors are on {tensors[0][0].device}, the optimizer's state on {state.device}")
+    lib = _lib.load()
+    code = OPTIMIZER_KINDS[kind]
+    with torch.cuda.device(state.device):
+        table.update(key, state.device)
+        nelem = sum(k[4] for k in key)
+        with _Prof("optimizer_step", 12 * nelem, 28 * nelem, f"{kind} x{len(key)}"):
+            _lib.check(lib.ml_optimizer_scalars(code, _ptr(state), _ptr(scalars), float(beta_1), float(beta_2), float(epsilon),
+                                                float(decay), float(weight_decay), float(init_lr), _stream()), "ml_optimizer_scalars")
+            _lib.check(lib.ml_optimizer_apply_f32(code, _ptr(table.table), table.n, table.chunks, _ptr(scalars), _stream()),
+                       "ml_optimizer_apply_f32")

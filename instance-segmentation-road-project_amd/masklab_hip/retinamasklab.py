@@ -7,7 +7,8 @@ the MI355X kernels.  construct_trainer_network :223-395 is restated forward (Tra
 losses and the metrics of a batch with ground truth) plus the losses' gradients at the head outputs
 (TrainerModel.loss_and_gradients); construct_masklabdataset :398-417 builds the file-reading datasets
 (masklab_hip/utils/dataset).  GroupNormalization has its backward as a layer method (normalization.py), not yet wired in: the
-conv, resize and RoI-align backward of the heads, the backbone's backward and the optimizers stay out of scope.
+conv, resize and RoI-align backward of the heads and the backbone's backward stay out of scope; the optimizers
+(masklab_hip/optimizers.py) wait for their gradients.
 """
 import numpy as np
 import torch
