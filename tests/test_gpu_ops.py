@@ -50,20 +50,23 @@ def conv_math(request):
 
 
 # ------------------------------------------------------------------ conv family
+# (what each shape runs on today, asked of the library's planning entries: a launch this small is narrowed to 128 x 32 tiles
+# whatever it was packed for; "wino" = the Winograd kernel under "f32", where "f32x3" runs 128 x 32 tiles cut along K.  The
+# wide tiles are tested kernel by kernel in tests/test_gpu_conv_instantiations.py.)
 @pytest.mark.parametrize("k,cin,cout,stride,padding,dil,act,hw", [
-    (1, 64, 256, 1, "valid", 1, "relu", (40, 24)),        # backbone 1x1, N tile 128
-    (3, 128, 128, 1, "same", 1, "relu", (33, 35)),        # tower conv, ragged M
-    (3, 128, 75, 1, "same", 1, "sigmoid", (16, 16)),      # cls output, N tile 32 x3
-    (3, 128, 60, 1, "same", 1, None, (8, 8)),             # loc output, N tile 64
-    (1, 512, 32, 1, "valid", 1, None, (16, 16)),          # skip projection
-    (1, 640, 128, 1, "valid", 1, None, (4, 4)),           # concat projection
-    (3, 2048, 128, 2, "same", 1, "relu", (4, 4)),         # P6 conv (stride 2, same)
-    (3, 128, 128, 2, ((0, 1), (0, 1)), 1, "relu", (7, 9)),  # mobilenet P7 style explicit pad
-    (1, 128, 5, 1, "same", 1, "sigmoid", (28, 28)),       # mask output
-    (1, 256, 512, 2, "valid", 1, None, (16, 16)),         # strided shortcut
-    (3, 160, 128, 1, "same", 1, "relu", (16, 16)),        # decoder conv (cin 160)
-    (1, 8, 128, 1, "valid", 1, "sigmoid", (1, 1)),        # SE dense (cin 8 < 32)
-    (3, 32, 96, 1, "same", 3, "relu6", (12, 12)),         # dilation 3
+    (1, 64, 256, 1, "valid", 1, "relu", (40, 24)),        # backbone 1x1: 128x32 tiles, one K slice
+    (3, 128, 128, 1, "same", 1, "relu", (33, 35)),        # tower conv, ragged M: wino | 128x32, 4 K slices
+    (3, 128, 75, 1, "same", 1, "sigmoid", (16, 16)),      # cls output: wino (narrow) | 128x32, 4 K slices, scalar stores
+    (3, 128, 60, 1, "same", 1, None, (8, 8)),             # loc output: wino (narrow) | 128x32, 4 K slices
+    (1, 512, 32, 1, "valid", 1, None, (16, 16)),          # skip projection: 128x32, 2 K slices
+    (1, 640, 128, 1, "valid", 1, None, (4, 4)),           # concat projection: 128x32, 2 K slices
+    (3, 2048, 128, 2, "same", 1, "relu", (4, 4)),         # P6 conv (stride 2, same): 128x32, 64 K slices
+    (3, 128, 128, 2, ((0, 1), (0, 1)), 1, "relu", (7, 9)),  # mobilenet P7 style explicit pad: 128x32, 4 K slices
+    (1, 128, 5, 1, "same", 1, "sigmoid", (28, 28)),       # mask output: 128x32, one K slice, scalar stores
+    (1, 256, 512, 2, "valid", 1, None, (16, 16)),         # strided shortcut: 128x32, one K slice
+    (3, 160, 128, 1, "same", 1, "relu", (16, 16)),        # decoder conv (cin 160): wino | 128x32, 5 K slices
+    (1, 8, 128, 1, "valid", 1, "sigmoid", (1, 1)),        # SE dense (cin 8 < 32): 128x32, one K slice
+    (3, 32, 96, 1, "same", 3, "relu6", (12, 12)),         # dilation 3: 128x32, one K slice (no value here reaches ReLU6's 6)
 ])
 def test_conv2d_dense(k, cin, cout, stride, padding, dil, act, hw, conv_math):
     from masklab_hip import _lib, packing
@@ -362,6 +365,8 @@ def test_deconv2x2_out1x1_rejects_bad_shapes():
                                    3, _lib.ACT_RELU, _lib.ACT_SIGMOID)
 
 
+# (every case runs on 128 x 32 tiles in both maths -- the stride-1 ones carry a residual, which the Winograd kernel does not
+# take -- cut into 64, 8, 8, 4, 2 and 9 K slices; split-K on the 128-wide tile: tests/test_gpu_conv_instantiations.py)
 @pytest.mark.parametrize("k,cin,cout,hw,stride", [(3, 2048, 128, (6, 6), 2), (1, 2048, 128, (16, 16), 1),
                                                   (1, 2048, 128, (1, 1), 1), (3, 128, 128, (8, 8), 1),
                                                   (1, 640, 128, (32, 32), 1), (3, 256, 75, (4, 4), 1)])

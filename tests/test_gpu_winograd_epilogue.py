@@ -15,10 +15,10 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from oracle import tfops as T
+from sentinel_dest import SENT, Dest
 
 RNG = np.random.default_rng(181)
 ATOL = 2e-5
-SENT = -7.25
 ACT = {None: lambda v: v, "relu": T.relu, "sigmoid": T.sigmoid}
 
 
@@ -62,27 +62,6 @@ def _names(fn):
         return r, [rec["kernel"] for rec in ops.PROFILE]
     finally:
         ops.PROFILE = None
-
-
-class Dest:
-    """A flat sentinel buffer and the `out_view` of a [B, H, W, cout] conv output inside it: `head` floats, then per pixel
-    `cstride` floats of which [coff, coff + cout) are the conv's, then `tail` floats."""
-
-    def __init__(self, shape, cout, cstride, coff=0, head=0, tail=8):
-        self.B, self.H, self.W = shape
-        self.cout, self.cstride, self.coff, self.head = cout, cstride, coff, head
-        assert coff + cout <= cstride
-        self.npix = self.B * self.H * self.W
-        self.buf = torch.full((head + self.npix * cstride + tail,), SENT, device="cuda")
-        self.view = (self.buf, head + coff, cstride, self.H * self.W * cstride)
-
-    def read(self):
-        """-> the conv's values [B, H, W, cout]; asserts that every other float still holds the sentinel."""
-        flat = host(self.buf)
-        body = flat[self.head:self.head + self.npix * self.cstride].reshape(self.npix, self.cstride)
-        assert (flat[:self.head] == SENT).all() and (flat[self.head + self.npix * self.cstride:] == SENT).all()
-        assert (body[:, :self.coff] == SENT).all() and (body[:, self.coff + self.cout:] == SENT).all()
-        return body[:, self.coff:self.coff + self.cout].reshape(self.B, self.H, self.W, self.cout).copy()
 
 
 def _wino(x, dc, dest, act=None, **kw):
