@@ -68,7 +68,10 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_gn_grad_desc, ml_groupnorm_chunk_grad_f32 /
                                             _grad_multi_f32 / _grad_workspace_bytes, ml_groupnorm_chunk_stats_f32;
                                             (additive, same version) ml_opt_tensor / _state / _scalars,
-                                            ml_optimizer_plan / _scalars / _apply_f32 */
+                                            ml_optimizer_plan / _scalars / _apply_f32;
+                                            (additive, same version) ml_roi_grad_level, ml_roi_crop_resize_grad_f32,
+                                            ml_resize_bilinear_ac_grad_f32 / _grad_workspace_bytes,
+                                            ml_global_mean_grad_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -421,6 +424,26 @@ int ml_resize_bilinear_ac_f32(const float *in, const float *add, float *out,
 /* tf.reduce_mean over H,W (semantic.py:149; GlobalAveragePooling2D misc.py:43): [B,HW,C]->[B,C] */
 int ml_global_mean_f32(const float *in, float *out, int32_t B, int32_t HW, int32_t C, void *stream);
 
+/* ---------------------------------------------------------------- resampling, backward (fp32 only, C % 4 == 0)
+ * The three layers are linear: their backward needs shapes and the RoI tables, no saved activation.  Every kernel is a
+ * GATHER: a thread owns 4 channels of one pixel of the input-side gradient and adds the output samples that reach it in a
+ * fixed order.  No float atomics and no zero-fill: every element of dx is written, exact zeros where no sample reaches, and
+ * two launches give the same bits whatever dx and the workspace held.  The sample coordinates are the forward kernels'
+ * expressions evaluated in float32, one rounding per operation.  `add` (NULL, or like dx): dx = add + gradient; dx may be
+ * add itself (in place), it may not overlap dy.
+ *
+ * ml_resize_bilinear_ac_grad_f32: dy [B,Ho,Wo,dy_cstride], read at channels dy_coff .. dy_coff + C (the forward writes
+ * concat slices) -> dx [B,H,W,C]; per element oy ascending, then ox.  A 1x1 source (every output pixel is that pixel) is
+ * summed in fp64 over slices of the pixels and folded in slice order; only this form needs the workspace
+ * (ml_resize_bilinear_ac_grad_workspace_bytes, 0 otherwise; nothing in it needs initialising).                        */
+int64_t ml_resize_bilinear_ac_grad_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t C, int32_t Ho, int32_t Wo);
+int ml_resize_bilinear_ac_grad_f32(const float *dy, const float *add, float *dx, int32_t B, int32_t H, int32_t W,
+                                   int32_t C, int32_t Ho, int32_t Wo, int32_t dy_cstride, int32_t dy_coff,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+/* dx[b,p,c] = dpool[b,c] / HW (+ add): dpool [B,C] -> dx [B,HW,C] */
+int ml_global_mean_grad_f32(const float *dpool, const float *add, float *dx, int32_t B, int32_t HW, int32_t C,
+                            void *stream);
+
 /* x[b,h,w,c] *= s[b,c]  (SqueezeExcite scale, misc.py:46-47)                                 */
 int ml_scale_channels_f32(float *x, const float *s, int32_t B, int32_t HW, int32_t C, void *stream);
 
@@ -581,6 +604,24 @@ int ml_roi_crop_resize_f16(const void *fmap, const float *rows, int32_t row_stri
                            int32_t level, int32_t n_l, int32_t ch, int32_t cw,
                            float img_h, float img_w, int32_t box_off, int32_t box_rows, const int32_t *live,
                            void *stream);
+
+/* Backward of ml_roi_crop_resize_f32 for ALL levels in one launch: levels[l] is pyramid level l (l < n_levels <= L), dy the
+ * gradient at its molded crops [B, n_l, ch, cw, C] (n_l: the host-sized value, or cap from a fixed-capacity forward), dx the
+ * gradient at its feature map [B, Hf, Wf, C].  rows / level_slots / level_counts: what the forward read.  The boxes carry no
+ * gradient (DetectionProposal ends in tf.stop_gradient).  Rows j >= level_counts[b, l] are MoldBatch padding: their dy is
+ * never read.  Per element the sum runs over slot j ascending, then oy, then ox; a sample outside [0, Hf-1] x [0, Wf-1]
+ * was the extrapolation value and contributes nothing.  See "resampling, backward" above for add / dx and the guarantees. */
+#define ML_RESAMPLE_MAX_LEVELS 8
+typedef struct ml_roi_grad_level {
+    const float *dy;               /* [B, n_l, ch, cw, C]                                          */
+    const float *add;              /* [B, Hf, Wf, C] or NULL                                       */
+    float *dx;                     /* [B, Hf, Wf, C]; may be add                                   */
+    int32_t Hf, Wf, n_l, reserved;
+} ml_roi_grad_level;
+int ml_roi_crop_resize_grad_f32(const ml_roi_grad_level *levels, int32_t n_levels, const float *rows, int32_t row_stride,
+                                int32_t row_off, const int32_t *level_slots, const int32_t *level_counts, int32_t B,
+                                int32_t C, int32_t cap, int32_t L, int32_t ch, int32_t cw, float img_h, float img_w,
+                                void *stream);
 
 /* MoldBatch + Concatenate(axis=1) of a fixed-capacity stage 2 (instance.py:222-225, misc.py:231-286): src [B, L*cap, E]
  * holds level l's RoIs at rows l*cap ..; dst [B, sum n_l, E] receives rows [l*cap, l*cap + n_l) of every image, the

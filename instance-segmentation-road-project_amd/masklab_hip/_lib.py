@@ -57,6 +57,12 @@ class GnGradDesc(C.Structure):
                 ("eps", C.c_float)]
 
 
+class RoiGradLevel(C.Structure):
+    """Mirror of `ml_roi_grad_level` (include/masklab_hip.h)."""
+    _fields_ = [("dy", C.c_void_p), ("add", C.c_void_p), ("dx", C.c_void_p), ("Hf", C.c_int32), ("Wf", C.c_int32),
+                ("n_l", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DeconvOutProblem(C.Structure):
     """Mirror of `ml_deconv_out_problem` (include/masklab_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("wd", C.c_void_p), ("bd", C.c_void_p), ("wo_table", C.c_void_p),
@@ -109,6 +115,7 @@ class OptScalars(C.Structure):
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
+RESAMPLE_MAX_LEVELS = 8                                             # ML_RESAMPLE_MAX_LEVELS
 DECONV_OUT_MAX_PROBLEMS = 4
 _i32, _i64, _f32, _f64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
@@ -156,6 +163,9 @@ SIGNATURES = {
     "ml_groupnorm_chunk_stats_f32": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "ml_groupnorm_grad_multi_f32": (C.c_int, [C.POINTER(GnGradDesc), _i32, _vp, _i64, _vp]),
     "ml_resize_bilinear_ac_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 12 + [_vp]),
+    "ml_resize_bilinear_ac_grad_workspace_bytes": (_i64, [_i32] * 6),
+    "ml_resize_bilinear_ac_grad_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 8 + [_vp, _i64, _vp]),
+    "ml_global_mean_grad_f32": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "ml_global_mean_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ml_scale_channels_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "ml_squeeze_excite_workspace_bytes": (_i64, [_i32, _i32, _i32]),
@@ -173,6 +183,8 @@ SIGNATURES = {
     "ml_detection_proposal_f32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _vp, _vp]),
     "ml_mask_distribute_i32": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "ml_roi_crop_resize_f32": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp] + [_i32] * 10 + [_f32, _f32, _i32, _i32, _vp, _vp]),
+    "ml_roi_crop_resize_grad_f32": (C.c_int, [C.POINTER(RoiGradLevel), _i32, _vp, _i32, _i32, _vp, _vp] + [_i32] * 6 +
+                                    [_f32, _f32, _vp]),
     "ml_mold_levels_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, C.POINTER(C.c_int32), _vp]),
     "ml_mold_levels_dev_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp]),
     "ml_add_f32": (C.c_int, [_vp, _vp, _i64, _vp]),

@@ -68,6 +68,15 @@ class FeaturePyramid(Layer):
                 t.record_stream(main)
         return pyramid_outputs[::-1]
 
+    def backward_top_down(self, d_merged):
+        """Backward of the top-down chain of `call`.  d_merged: the gradients at the merged maps, finest first (what the 3x3
+        output convs' data gradient delivers).  merged[l] = lateral[l] + resize(merged[l+1]), so the gradient at
+        merged[l+1] also receives resize^T of the full gradient at merged[l]: d_merged[l+1] += resize^T(d_merged[l]), finest
+        to coarsest, IN PLACE.  -> the same tensors, now the gradients at the lateral convs' outputs."""
+        for fine, coarse in zip(d_merged[:-1], d_merged[1:]):
+            ops.resize_bilinear_ac_grad(fine, coarse.shape[1], coarse.shape[2], add=coarse, out=coarse)
+        return list(d_merged)
+
     def get_config(self):
         config = super().get_config()
         config.update({"strides": self.strides, "num_features": self.num_features})

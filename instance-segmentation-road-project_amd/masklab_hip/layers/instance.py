@@ -81,6 +81,14 @@ class PyramidRoiAlign(Layer):
         slots, lcounts, lmax = self.distribute(len(fmap_outputs), rows, has_k, base_size)
         return self.crop_distributed(fmap_outputs, rows, image_hw, slots, lcounts, lmax)
 
+    def backward(self, grad_roi_fmaps, fmap_shapes, rows, image_hw, slots, lcounts, add=None, out=None):
+        """The gradient at the pyramid levels from the gradients at the molded crops of crop_distributed (sized) or
+        crop_capacity ([B,cap,...]): one launch for all levels (ops.roi_crop_resize_grad).  rows / slots / lcounts: what
+        the forward used; the boxes carry no gradient.  add / out: per level, out = add + gradient (a level also
+        receives the gradients of the two towers)."""
+        return ops.roi_crop_resize_grad(grad_roi_fmaps, fmap_shapes, rows, slots, lcounts, tuple(self.crop_size), image_hw,
+                                        add=add, out=out)
+
     def call(self, inputs, **kwargs):
         fmap_outputs, dist_boxes, images = inputs[0], inputs[1], inputs[2]
         image_hw = (int(images.shape[1]), int(images.shape[2]))

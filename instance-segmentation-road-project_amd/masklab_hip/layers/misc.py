@@ -44,6 +44,12 @@ class ResizeLike(Layer):
                                       add=kwargs.get('add'), out=kwargs.get('out'),
                                       out_coff=kwargs.get('out_coff', 0))
 
+    def backward(self, grad, input_shape, **kwargs):
+        """The gradient at the resized tensor ([B,H,W,C] = input_shape) from the gradient at the output; kwargs: dy_coff
+        (the forward wrote a concat slice: the gradient is read from it), add, out (ops.resize_bilinear_ac_grad)."""
+        return ops.resize_bilinear_ac_grad(grad, int(input_shape[1]), int(input_shape[2]), int(input_shape[3]),
+                                           dy_coff=kwargs.get('dy_coff', 0), add=kwargs.get('add'), out=kwargs.get('out'))
+
     def compute_output_shape(self, input_shapes):
         input_shape, target_shape = input_shapes
         return input_shape[0], target_shape[1], target_shape[2], input_shape[-1]

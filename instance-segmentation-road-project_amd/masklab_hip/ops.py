@@ -854,6 +854,76 @@ def global_mean(x):
     return out
 
 
+def _grad_tensor(what, name, t, shape=None):
+    """The checks every gradient tensor of the resampling backward passes: a float32 tensor (of `shape`)."""
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: `{name}` must be a tensor")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: `{name}` is {t.dtype}; the backward is float32 only")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what}: `{name}` is {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _grad_out(what, shape, device, add, out):
+    """add / out of a resampling backward (out = add + gradient; out may be add itself) -> the tensor to write"""
+    if shape[-1] % 4:
+        raise ValueError(f"{what}: the channel count ({shape[-1]}) must be a multiple of 4 (16-byte accesses)")
+    for name, t in (("add", add), ("out", out)):
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+            _require_dev(t, name)
+    return torch.empty(tuple(shape), dtype=torch.float32, device=device) if out is None else out
+
+
+def resize_bilinear_ac_grad(dy, H, W, C=None, dy_coff=0, add=None, out=None):
+    """Backward of resize_bilinear_ac (csrc/resample_grad.hip), float32: dy [B,Ho,Wo,Cs] is the gradient at the resize's
+    output, read at channels dy_coff : dy_coff + C (the forward writes concat slices; C=None: all Cs) -> the gradient
+    [B,H,W,C] at its input.  add / out: out = add + gradient, in place if they are the same tensor (the FPN top-down merge).
+    A gather with a fixed summation order: two launches give the same bits; a 1x1 source takes a block reduction in fp64."""
+    what = "resize_bilinear_ac_grad"
+    _grad_tensor(what, "dy", dy)
+    if dy.dim() != 4:
+        raise ValueError(f"{what}: `dy` must be [B, Ho, Wo, C], got {tuple(dy.shape)}")
+    B, Ho, Wo, Cs = dy.shape
+    Cc = Cs - dy_coff if C is None else int(C)
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or Cc < 1 or dy_coff < 0 or dy_coff + Cc > Cs:
+        raise ValueError(f"{what}: channels {dy_coff} : {dy_coff + Cc} of {Cs} at {H} x {W} is no slice of dy")
+    if Cs % 4 or dy_coff % 4:
+        raise ValueError(f"{what}: dy's channel count ({Cs}) and the offset ({dy_coff}) must each be a multiple of 4 "
+                         f"(16-byte accesses)")
+    dx = _grad_out(what, (B, H, W, Cc), dy.device, add, out)
+    _require_dev(dy, "dy")
+    lib = _lib.load()
+    ws_bytes = int(lib.ml_resize_bilinear_ac_grad_workspace_bytes(B, H, W, Cc, Ho, Wo))
+    # (the slice sums of a 1x1 source, a few hundred KiB: from the caching allocator like the output, not a grow-only buffer)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device) if ws_bytes else None
+    with _Prof("resize_bilinear_grad", 0, 4 * (B * Ho * Wo * Cc + dx.numel() * (2 if add is not None else 1)),
+               f"{Ho}x{Wo}->{H}x{W} C={Cc}"):
+        _lib.check(lib.ml_resize_bilinear_ac_grad_f32(_ptr(dy), _ptr(add), _ptr(dx), B, H, W, Cc, Ho, Wo, Cs, dy_coff,
+                                                      _ptr(ws), ws_bytes, _stream()), "ml_resize_bilinear_ac_grad_f32")
+    return dx
+
+
+def global_mean_grad(dpool, H, W, add=None, out=None):
+    """Backward of global_mean: dpool [B,1,1,C] float32 -> dx[b,y,x,c] = dpool[b,0,0,c] / (H W) (+ add), one streaming launch."""
+    what = "global_mean_grad"
+    _grad_tensor(what, "dpool", dpool)
+    if dpool.dim() != 4 or dpool.shape[1] != 1 or dpool.shape[2] != 1:
+        raise ValueError(f"{what}: `dpool` must be [B, 1, 1, C], got {tuple(dpool.shape)}")
+    B, Cc = dpool.shape[0], dpool.shape[3]
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: bad size {H} x {W}")
+    dx = _grad_out(what, (B, H, W, Cc), dpool.device, add, out)
+    _require_dev(dpool, "dpool")
+    lib = _lib.load()
+    with _Prof("global_mean_grad", 0, 4 * (dpool.numel() + dx.numel() * (2 if add is not None else 1)), f"{H}x{W} C={Cc}"):
+        _lib.check(lib.ml_global_mean_grad_f32(_ptr(dpool), _ptr(add), _ptr(dx), B, H * W, Cc, _stream()),
+                   "ml_global_mean_grad_f32")
+    return dx
+
+
 def scale_channels_(x, s):
     lib = _lib.load()
     if x.dtype != torch.float32 or s.dtype != torch.float32:
@@ -1179,6 +1249,57 @@ def roi_crop_resize(fmap, rows, slots, lcounts, level, n_l, crop_size, img_hw, r
                   _ptr(roi_boxes), B, Hf, Wf, Cc, cap, L, level, n_l, ch, cw,
                   float(img_hw[0]), float(img_hw[1]), box_off, roi_boxes.shape[1], _ptr(live), _stream()), "ml_roi_crop_resize")
     return out
+
+
+def roi_crop_resize_grad(dys, fmap_shapes, rows, slots, lcounts, crop_size, img_hw, add=None, out=None):
+    """Backward of roi_crop_resize for every level in ONE launch (csrc/resample_grad.hip), float32.  dys[l]: the gradient
+    [B,n_l,ch,cw,C] at level l's molded crops (n_l the host-sized value, or cap from a fixed-capacity forward: the same
+    bits); fmap_shapes[l]: that level's (B,Hf,Wf,C); rows / slots / lcounts: what mask_distribute and the forward used.
+    Rows j >= lcounts[b,l] are MoldBatch padding: their dy is never read.  The boxes carry no gradient (tf.stop_gradient
+    behind DetectionProposal).  add[l] / out[l]: out = add + gradient, in place if they are the same tensor.
+    -> one [B,Hf,Wf,C] gradient per level; a gather over slot j, then oy, then ox: two launches give the same bits."""
+    what = "roi_crop_resize_grad"
+    n = len(dys)
+    if n == 0 or n != len(fmap_shapes) or n > _lib.RESAMPLE_MAX_LEVELS:
+        raise ValueError(f"{what}: {n} gradients for {len(fmap_shapes)} feature maps (1..{_lib.RESAMPLE_MAX_LEVELS} levels)")
+    for name, t, dt in (("rows", rows, torch.float32), ("slots", slots, torch.int32), ("lcounts", lcounts, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise ValueError(f"{what}: `{name}` must be a {dt} tensor")
+    if rows.dim() != 3 or rows.shape[2] < 6 or slots.dim() != 3 or tuple(slots.shape[::2]) != tuple(rows.shape[:2]):
+        raise ValueError(f"{what}: rows {tuple(rows.shape)} / slots {tuple(slots.shape)} are not [B,cap,>=6] / [B,L,cap]")
+    B, cap, rs = rows.shape
+    L = slots.shape[1]
+    if tuple(lcounts.shape) != (B, L) or n > L:
+        raise ValueError(f"{what}: lcounts {tuple(lcounts.shape)} must be [{B}, {L}] and cover the {n} levels")
+    ch, cw = int(crop_size[0]), int(crop_size[1])
+    adds = [None] * n if add is None else list(add)
+    outs = [None] * n if out is None else list(out)
+    if len(adds) != n or len(outs) != n:
+        raise ValueError(f"{what}: add / out must have one entry per level")
+    Cc = int(fmap_shapes[0][-1])
+    arr = (_lib.RoiGradLevel * n)()
+    dxs, nbytes = [], 0
+    for l, (d, dy, shape) in enumerate(zip(arr, dys, fmap_shapes)):
+        shape = tuple(int(v) for v in shape)
+        _grad_tensor(what, f"dys[{l}]", dy)
+        if len(shape) != 4 or shape[0] != B or shape[3] != Cc:
+            raise ValueError(f"{what}: fmap_shapes[{l}] = {shape} is not [{B}, Hf, Wf, {Cc}]")
+        if dy.dim() != 5 or tuple(dy.shape[0:1] + dy.shape[2:]) != (B, ch, cw, Cc) or not 1 <= dy.shape[1] <= cap:
+            raise ValueError(f"{what}: dys[{l}] is {tuple(dy.shape)}, expected [{B}, n_l <= {cap}, {ch}, {cw}, {Cc}]")
+        dx = _grad_out(what, shape, dy.device, adds[l], outs[l])
+        _require_dev(dy, f"dys[{l}]")
+        d.dy, d.dx, d.add = dy.data_ptr(), dx.data_ptr(), None if adds[l] is None else adds[l].data_ptr()
+        d.Hf, d.Wf, d.n_l = shape[1], shape[2], dy.shape[1]
+        nbytes += 4 * (dy.numel() + dx.numel() * (2 if adds[l] is not None else 1))
+        dxs.append(dx)
+    for name, t in (("rows", rows), ("slots", slots), ("lcounts", lcounts)):
+        _require_dev(t, name)
+    lib = _lib.load()
+    with _Prof("roi_crop_resize_grad", 0, nbytes, f"levels={n} crop={ch}x{cw} C={Cc}"):
+        _lib.check(lib.ml_roi_crop_resize_grad_f32(arr, n, _ptr(rows), rs, rs - 6, _ptr(slots), _ptr(lcounts), B, Cc, cap, L, ch,
+                                                   cw, float(img_hw[0]), float(img_hw[1]), _stream()),
+                   "ml_roi_crop_resize_grad_f32")
+    return dxs
 
 
 def mold_levels(src, n_l, cap):
