@@ -5,10 +5,17 @@
 #include <stdio.h>
 #include "masklab_hip.h"
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 void ml_set_error(const char *fmt, ...);
 
@@ -42,8 +49,6 @@ __device__ __forceinline__ float ml_apply_act(float v, int act) {
 // Inf / NaN -- loud, as in the fp16-storage mode).  16 VALU instructions: 4 packed multiplies (x * 2^11), 4 packed converts,
 // 8 v_fma_mix (f16 hi * -2^11 + the scaled x, result stored as f16).
 __device__ __forceinline__ void split_hi_lo(const f32x4 x0, const f32x4 x1, const float neg_scale, f16x8 &hi, f16x8 &lo) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     const f32x4 s0 = x0 * 2048.f, s1 = x1 * 2048.f;
     unsigned hw[4], lw[4];
     hw[0] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){x0[0], x0[1]}, f16x2));
@@ -57,7 +62,6 @@ __device__ __forceinline__ void split_hi_lo(const f32x4 x0, const f32x4 x1, cons
         asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
             : "+v"(lw[i]) : "v"(hw[i]), "s"(neg_scale), "v"(sv[2 * i + 1]));
     }
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 H = {hw[0], hw[1], hw[2], hw[3]}, L = {lw[0], lw[1], lw[2], lw[3]};
     hi = __builtin_bit_cast(f16x8, H);
     lo = __builtin_bit_cast(f16x8, L);
@@ -65,8 +69,6 @@ __device__ __forceinline__ void split_hi_lo(const f32x4 x0, const f32x4 x1, cons
 
 // the same split for two values (packed halves in one register each)
 __device__ __forceinline__ void split_hi_lo_pair(const float xa, const float xb, const float neg_scale, unsigned &hi, unsigned &lo) {
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
     const f32x2 x = {xa, xb};
     const f32x2 sc = x * 2048.f;
     hi = __builtin_bit_cast(unsigned, __builtin_convertvector(x, f16x2));

@@ -18,7 +18,7 @@
 // the 16-byte fragment reads (row = lane & 31, 16 (lane >> 5) bytes into each 32-byte k-step) and the 16-byte staging
 // writes are both conflict-free at that pitch.  Rows past M read pixel M - 1 and are not stored.  No atomics, no split K:
 // the same bits run to run, under graph replay and for image k of any batch.
-#include "common.h"
+#include "gfx_mem.h"
 
 namespace {
 
@@ -26,10 +26,6 @@ constexpr int DU_TM = 128, DU_TN = 128, DU_TPB = 256;
 constexpr int DU_CHUNK = 128;                  // bytes of K per row and chunk
 constexpr int DU_ROWB = DU_CHUNK + 16;         // LDS row pitch
 constexpr int DU_TILEB = DU_TM * DU_ROWB;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 struct DualArgs {
     const void *a, *x, *wgt;
@@ -59,10 +55,10 @@ __global__ void __launch_bounds__(DU_TPB, 2) conv1x1_dual_kernel(const DualArgs 
     const int tile = xcd_contiguous(blockIdx.x, gridDim.x);
     const int n0 = (tile % A.tiles_n) * DU_TN, m0 = (tile / A.tiles_n) * DU_TM;
 
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)A.a, 0, A.a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)A.x, 0, A.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void *)A.wgt, 0, A.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(A.out, 0, A.out_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ra = rsrc_bytes(A.a, A.a_bytes);
+    const __amdgpu_buffer_rsrc_t rx = rsrc_bytes(A.x, A.x_bytes);
+    const __amdgpu_buffer_rsrc_t rw = rsrc_bytes(A.wgt, A.w_bytes);
+    const __amdgpu_buffer_rsrc_t ro = rsrc_bytes(A.out, A.out_bytes);
 
     // staging: thread t moves 16-byte piece t & 7 of rows (t >> 3) + 32 i, i = 0..3, of both tiles
     const int piece = (t & 7) * 16, row0 = t >> 3;

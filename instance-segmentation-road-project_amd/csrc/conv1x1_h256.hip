@@ -40,8 +40,7 @@
 // changes nothing (not an L2-channel effect).
 // Numerics: fp16 products are exact in fp32, fp32 accumulation in k order per output, bias / residual / clamp in fp32 --
 // the same arithmetic as conv1x1_pipe_kernel<_Float16> (which chains 64-deep chunks the same way).
-#include <type_traits>
-#include "common.h"
+#include "gfx_mem.h"
 
 namespace {
 
@@ -63,9 +62,15 @@ constexpr int SCR_LD = 36;                         // floats per row of a wave's
 constexpr int SCRB = 16 * SCR_LD * 4;              // (8 waves x 2 304 B: lives in the A slot the tile's last chunk freed)
 constexpr int H256_LDS = 3 * ABUF + 2 * BBUF;      // 163 840 B = all of a CU's LDS: a ring of 3 A slots + 2 B slots
 static_assert(8 * SCRB <= ABUF, "the epilogue scratch must fit an A slot");
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// What a wave issues, in vector-memory operations -- the counted waits of begin_chunk are sums of these.  A request moves
+// 8 rows (64 lanes x 16 B of 128-byte rows) and the 8 waves share a slot's rows; the epilogue stores one 16-row x 32-column
+// piece per instruction, EPI_GROUPS groups of EPI_PIECES pieces cover the wave's 128 x 64 part of the tile.
+constexpr int A_REQ = TM / (8 * 8), B_REQ = TN / (8 * 8);     // requests per wave and staged A slot / B slot
+static_assert(A_REQ * 64 == TM && B_REQ * 64 == TN, "request i of wave w covers rows 64 i + 8 w .. + 7 (stage_a, stage_b, send_piece)");
+constexpr int EPI_GROUPS = TM / 2 / 32;                       // the wave's rows of 32 x 32 accumulators (mi)
+constexpr int EPI_PIECES = TN / 4 / 32 * 2;                   // per group: its accumulators (ni) x their 16-row halves (hs)
+constexpr int TILE_STORES = EPI_GROUPS * EPI_PIECES;          // stores per wave and tile
+static_assert(TILE_STORES * 16 * 32 == (TM / 2) * (TN / 4), "the epilogue's pieces cover the wave's 128 x 64 part exactly once");
 
 struct H256Args {
     const void *in, *wgt, *res;
@@ -82,51 +87,6 @@ struct H256Args {
     int clamp;
 };
 
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, char *dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ unsigned records_left(long long off, long long total) {
-    const unsigned long long left = (unsigned long long)(total - off);
-    const unsigned hi = (unsigned)(left >> 32), lo = (unsigned)left;
-    return (hi & 0x80000000u) ? 0u : (hi ? 0xffffffffu : lo);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_at(const void *ptr, long long off, long long total) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)ptr + off), 0, (int)records_left(off, total), 0x00020000);
-}
-// `nbytes` bytes from ptr + off (the rows of ONE tile: anything past them reads zeros / is not stored, no traffic)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_span(const void *ptr, long long off, int nbytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)ptr + off), 0, nbytes, 0x00020000);
-}
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// the same descriptor as four plain dwords, for inline-asm operands
-__device__ __forceinline__ i32x4 rsrc_words(const void *ptr, long long off, long long total) {
-    const unsigned long long base = (unsigned long long)((const char *)ptr + off);
-    const i32x4 w = {(int)(unsigned)base, (int)((unsigned)(base >> 32) & 0xffffu), (int)records_left(off, total), 0x00020000};
-    return w;
-}
-// Register-destination load hipcc must not see: beside LDS-direct loads in flight it would wait vmcnt(0) before every
-// use of an ordinary load's result -- i.e. for the previous piece's STORES too.  Completion is waited for by hand.
-__device__ __forceinline__ f32x4 buf_load16_asm(i32x4 rsrc, int voff) {
-    f32x4 v;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v) : "v"(voff), "s"(rsrc) : "memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_loaded4(f32x4 &a, f32x4 &b, f32x4 &c, f32x4 &d) {
-    asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N));
-}
-
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, E>(f);
-    }
-}
-
 template <bool HAS_RES>
 __global__ void __launch_bounds__(512, 2)
 conv1x1_h256_kernel(const H256Args A) {
@@ -141,9 +101,10 @@ conv1x1_h256_kernel(const H256Args A) {
     // lane -> row lane >> 3, 16-byte group (lane & 7) ^ swizzle key of that row
     const int ld_r = 8 * wave + (lane >> 3);                   // + 64 i
     const int ld_g = (lane & 7) ^ ((ld_r >> 1) & 7);           // (64 i does not change the key)
-    int a_voff[4], b_voff[4];
+    static_assert(A_REQ == B_REQ, "one loop sets both operands' request offsets");
+    int a_voff[A_REQ], b_voff[B_REQ];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < A_REQ; ++i) {
         a_voff[i] = ((ld_r + 64 * i) * A.in_cs + A.in_coff) * 2 + ld_g * 16;
         b_voff[i] = (ld_r + 64 * i) * A.K * 2 + ld_g * 16;
     }
@@ -162,11 +123,8 @@ conv1x1_h256_kernel(const H256Args A) {
     // ---- which rows: one N tile for the block's life and ONE contiguous range of rows, cut at multiples of 32 so that
     // all ranges of a launch differ by at most 32 rows (a 1x1 conv's rows are independent: where the cut falls changes no
     // result).  The range is walked in 256-row tiles; the last may be short (rows past it read zeros and are not stored).
-    const int bid = (int)blockIdx.x;
-    const int gmask = A.G - 1;
-    const int slot = bid >> 3, ppx = A.nb >> 3;
-    const int nt = A.xcd_map ? (slot & gmask) : (bid & gmask);
-    const int ri = A.xcd_map ? (bid & 7) * ppx + (slot >> A.gshift) : (bid >> A.gshift);
+    int nt, ri;                                                // the block's N tile and row range (the row units of xcd_group_map)
+    xcd_group_map((int)blockIdx.x, A.nb, A.G, A.gshift, A.xcd_map, nt, ri);
     const int g0 = ri * A.g_base + min(ri, A.g_rem);
     const int gcnt = A.g_base + (ri < A.g_rem ? 1 : 0);
     long long row = (long long)g0 * 32;
@@ -177,15 +135,17 @@ conv1x1_h256_kernel(const H256Args A) {
     const __amdgpu_buffer_rsrc_t rb = rsrc_at(A.wgt, (long long)nt * TN * A.K * 2, w_total);
     const __amdgpu_buffer_rsrc_t r_none = rsrc_at(A.wgt, 0, 0);         // empty extent: the request is counted, nothing moves
     auto res_a = [&](long long r0, int nrows) {              // rows r0 .. r0 + nrows - 1 of the input (nrows = 0: empty)
-        return rsrc_span(A.in, nrows > 0 ? r0 * A.in_cs * 2 : 0, nrows * A.in_cs * 2);
+        const long long off = nrows > 0 ? r0 * A.in_cs * 2 : 0;
+        const int nbytes = nrows * A.in_cs * 2;              // anything past the rows reads zeros, no traffic
+        return rsrc_bytes((const char *)A.in + off, nbytes);
     };
     auto stage_a = [&](__amdgpu_buffer_rsrc_t ra, char *dst, int soff) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(ra, dst + (64 * i + 8 * wave) * ROWB, a_voff[i], soff);
+        for (int i = 0; i < A_REQ; ++i) lds_dma16(ra, dst + (64 * i + 8 * wave) * ROWB, a_voff[i], soff);
     };
     auto stage_b = [&](__amdgpu_buffer_rsrc_t rbb, char *dst, int soff) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) lds_dma16(rbb, dst + (64 * i + 8 * wave) * ROWB, b_voff[i], soff);
+        for (int i = 0; i < B_REQ; ++i) lds_dma16(rbb, dst + (64 * i + 8 * wave) * ROWB, b_voff[i], soff);
     };
 
     // bias of this wave's 64 columns, in the epilogue's column ownership: 2 sub-tiles x 8 floats
@@ -227,9 +187,10 @@ conv1x1_h256_kernel(const H256Args A) {
         //   chunk 2 of a later tile needs B(c), which is YOUNGER than the stores: the store drain of a tile overlaps
         //   the next tile's first two chunks and no more.
         // (with a residual the epilogue's own waits have retired everything older than its stores: the counts hold)
-        if (!first_tile && kc == 0) asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-        else if (!first_tile && kc == 1) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        static_assert(A_REQ + B_REQ + TILE_STORES == 24 && TILE_STORES + A_REQ == 20 && A_REQ == 4, "the table above");
+        if (!first_tile && kc == 0) wait_vmcnt<A_REQ + B_REQ + TILE_STORES>();
+        else if (!first_tile && kc == 1) wait_vmcnt<TILE_STORES + A_REQ>();
+        else wait_vmcnt<A_REQ>();
         __builtin_amdgcn_s_barrier();                               // ... everyone's; and chunk c - 1's slots are free
         Chunk C;
         C.rd_a = lds + sa * ABUF;
@@ -248,10 +209,11 @@ conv1x1_h256_kernel(const H256Args A) {
     };
     auto send_piece = [&](const Chunk &C, auto pc) __attribute__((always_inline)) {     // piece 0..7: B first (needed first)
         constexpr int p = decltype(pc)::value;
-        if constexpr (p < 4) {
+        static_assert(p < B_REQ + A_REQ, "a chunk's requests are one B slot and one A slot");
+        if constexpr (p < B_REQ) {
             if (C.send_b) lds_dma16(H256_ABL_B ? r_none : C.rb_nx, C.wr_b + (64 * p + 8 * wave) * ROWB, b_voff[p], C.soff_b);
         } else {
-            lds_dma16(H256_ABL_A ? r_none : C.ra_nx, C.wr_a + (64 * (p - 4) + 8 * wave) * ROWB, a_voff[p - 4], C.soff_a);
+            lds_dma16(H256_ABL_A ? r_none : C.ra_nx, C.wr_a + (64 * (p - B_REQ) + 8 * wave) * ROWB, a_voff[p - B_REQ], C.soff_a);
         }
     };
     auto end_chunk = [&]() __attribute__((always_inline)) {
@@ -296,14 +258,13 @@ conv1x1_h256_kernel(const H256Args A) {
         }
         const f16x8 o = {(_Float16)v0[0], (_Float16)v0[1], (_Float16)v0[2], (_Float16)v0[3],
                          (_Float16)v1[0], (_Float16)v1[1], (_Float16)v1[2], (_Float16)v1[3]};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ro, voff, 0, 0);
+        buf_store16(__builtin_bit_cast(f32x4, o), ro, voff, 0);
     };
     auto out_rsrc = [&](long long r0, int nrows, __amdgpu_buffer_rsrc_t &ro, i32x4 &rr) __attribute__((always_inline)) {
         const long long tile_off = (r0 * A.out_cs + A.out_coff + (long long)nt * TN) * 2;
         const int tile_bytes = nrows * A.out_cs * 2 - (A.out_coff + nt * TN) * 2;
-        ro = rsrc_span(A.out, tile_off, tile_bytes);
-        const unsigned long long rbase = (unsigned long long)((const char *)A.res + (HAS_RES ? tile_off : 0));
-        rr = i32x4{(int)(unsigned)rbase, (int)((unsigned)(rbase >> 32) & 0xffffu), HAS_RES ? tile_bytes : 0, 0x00020000};
+        ro = rsrc_bytes((const char *)A.out + tile_off, tile_bytes);
+        rr = rsrc_words((const char *)A.res + (HAS_RES ? tile_off : 0), HAS_RES ? tile_bytes : 0);
     };
 
     // ---- whole tiles (and short last tiles of more than 128 rows, which run the same stream on zero-filled rows)
@@ -342,7 +303,7 @@ conv1x1_h256_kernel(const H256Args A) {
                 if constexpr ((idx & 7) == 2 && ks < 3) read_frags(ks + 1, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
                 const f16x8 a = __builtin_bit_cast(f16x8, fa[ks & 1][mi]), b = __builtin_bit_cast(f16x8, fb[ks & 1][ni]);
                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[mi][ni], 0, 0, 0);
-                if constexpr (idx % H256_DMA_STRIDE == 0 && idx / H256_DMA_STRIDE < 8) {
+                if constexpr (idx % H256_DMA_STRIDE == 0 && idx / H256_DMA_STRIDE < B_REQ + A_REQ) {
                     __builtin_amdgcn_sched_barrier(0);
                     send_piece(C, std::integral_constant<int, idx / H256_DMA_STRIDE>{});
                     __builtin_amdgcn_sched_barrier(0);
@@ -352,7 +313,7 @@ conv1x1_h256_kernel(const H256Args A) {
         }
         char *scratch = between_tiles();
 
-        // ---- epilogue of this tile.  Four groups (mi) of four 16-row x 32-column pieces; the residual of group g + 1 is
+        // ---- epilogue of this tile.  EPI_GROUPS groups (mi) of EPI_PIECES 16-row x 32-column pieces; the residual of group g + 1 is
         // fetched (inline asm, counted waits) before group g's stores are issued, so no load ever waits for a store.  Rows
         // past the tile's own are neither read nor stored (resource extents).
         __amdgpu_buffer_rsrc_t ro;
@@ -361,22 +322,23 @@ conv1x1_h256_kernel(const H256Args A) {
         auto voff_of = [&](int mi, int ni, int hs) {
             return ((wr * 128 + mi * 32 + hs * 16 + t_row) * A.out_cs + wc * 64 + ni * 32 + t_col) * 2;
         };
-        f32x4 rq[2][4];
-        auto load_group = [&](int mi, f32x4 (&q)[4]) __attribute__((always_inline)) {
+        f32x4 rq[2][EPI_PIECES];
+        auto load_group = [&](int mi, f32x4 (&q)[EPI_PIECES]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) q[k] = buf_load16_asm(rr, voff_of(mi, k >> 1, k & 1));
+            for (int k = 0; k < EPI_PIECES; ++k) q[k] = buf_load16_asm(rr, voff_of(mi, k >> 1, k & 1));
         };
         if constexpr (HAS_RES) load_group(0, rq[0]);
-        static_for<0, 4>([&](auto mc) {
+        static_for<0, EPI_GROUPS>([&](auto mc) {
             constexpr int mi = decltype(mc)::value;
             if constexpr (HAS_RES) {
-                if constexpr (mi < 3) load_group(mi + 1, rq[(mi + 1) & 1]);
-                // younger than this group's loads: the next group's 4 loads and the previous group's 4 stores
-                constexpr int younger = (mi < 3 ? 4 : 0) + (mi > 0 ? 4 : 0);
-                wait_loaded4<younger>(rq[mi & 1][0], rq[mi & 1][1], rq[mi & 1][2], rq[mi & 1][3]);
+                if constexpr (mi + 1 < EPI_GROUPS) load_group(mi + 1, rq[(mi + 1) & 1]);
+                // younger than this group's loads: the next group's loads and the previous group's stores
+                constexpr int younger = (mi + 1 < EPI_GROUPS ? EPI_PIECES : 0) + (mi > 0 ? EPI_PIECES : 0);
+                static_assert(EPI_PIECES == 4, "wait_loaded takes the group's four values");
+                wait_loaded<younger>(rq[mi & 1][0], rq[mi & 1][1], rq[mi & 1][2], rq[mi & 1][3]);
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
+            for (int k = 0; k < EPI_PIECES; ++k) {       // one store each: TILE_STORES per wave and tile
                 const int ni = k >> 1, hs = k & 1;
                 finish_piece(scratch, acc[mi][ni], hs, rq[mi & 1][k], bias[ni][0], bias[ni][1], ro, voff_of(mi, ni, hs));
             }
@@ -419,7 +381,7 @@ conv1x1_h256_kernel(const H256Args A) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) acc_t[m][e] = 0.f;
             }
-            static_for<0, 8>([&](auto pc) { send_piece(C, pc); });
+            static_for<0, B_REQ + A_REQ>([&](auto pc) { send_piece(C, pc); });
             static_for<0, 4>([&](auto kc4) {
                 constexpr int ks = decltype(kc4)::value;
                 if constexpr (ks < 3) read_frags(ks + 1, fa[(ks + 1) & 1], fb[(ks + 1) & 1]);
@@ -448,7 +410,7 @@ conv1x1_h256_kernel(const H256Args A) {
                 f32x4 res8 = {0.f, 0.f, 0.f, 0.f};
                 if constexpr (HAS_RES) {
                     res8 = buf_load16_asm(rr, voff);
-                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(res8));
+                    wait_loaded<0>(res8);
                 }
                 finish_piece(scratch, acc_t[m], hs, res8, bt[0], bt[1], ro, voff);
             }
@@ -460,7 +422,7 @@ conv1x1_h256_kernel(const H256Args A) {
         case 4: tail(std::integral_constant<int, 4>{}); break;
         default: break;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
 }
 
 template <bool HAS_RES>

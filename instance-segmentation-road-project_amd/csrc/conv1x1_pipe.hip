@@ -35,8 +35,7 @@
 //     also means no 2 GiB tensor limit on this path.
 // Numerics (float): exact fp32 products, k-ordered fma chain per output like conv_mfma.hip (which starts the chain
 // from the bias; here bias and residual are added after it: one rounding placed differently, ~1e-7 relative).
-#include <type_traits>
-#include "common.h"
+#include "gfx_mem.h"
 
 namespace {
 
@@ -55,9 +54,6 @@ constexpr int PIPE_MAX_NBG = 8;                    // N tiles one block walks (i
 
 struct f32x3_t { float v; };                       // storage type tag of ML_MATH_F32X3 (fp32 tensors, split-operand products)
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 struct PipeArgs {
     const void *in, *wgt, *res;
     const float *bias;
@@ -71,65 +67,10 @@ struct PipeArgs {
     float lo, hi;                            // activation as a clamp
 };
 
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, char *dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ void buf_store16(f32x4 v, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, voff, soff, 0);
-#endif
-}
-
-// resource over [ptr + off, ptr + total): num_records saturates at 2^32 - 1 (a tile only ever reaches 128 rows in).
-// (32-bit halves: 64-bit signed compares have no scalar form and would be evaluated on the VALU)
-__device__ __forceinline__ unsigned records_left(long long off, long long total) {
-    const unsigned long long left = (unsigned long long)(total - off);
-    const unsigned hi = (unsigned)(left >> 32), lo = (unsigned)left;
-    return (hi & 0x80000000u) ? 0u : (hi ? 0xffffffffu : lo);      // negative -> empty, >= 4 GiB -> saturate
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_at(const void *ptr, long long off, long long total) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)ptr + off), 0, (int)records_left(off, total), 0x00020000);
-}
-// the same descriptor as four plain dwords, for inline-asm operands (V# of a raw buffer: base, stride 0, num_records, flags)
-__device__ __forceinline__ i32x4 rsrc_words(const void *ptr, long long off, long long total) {
-    const unsigned long long base = (unsigned long long)((const char *)ptr + off);
-    const i32x4 w = {(int)(unsigned)base, (int)((unsigned)(base >> 32) & 0xffffu), (int)records_left(off, total), 0x00020000};
-    return w;
-}
-
 // which tile a cursor points at; advanced with scalar adds only
 struct Cursor {
     int u, nt;           // M panel and N tile; u >= panels: past the end (all its resources are empty)
 };
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, E>(f);
-    }
-}
-
-// Register-destination buffer load as inline asm: hipcc must not see it -- beside LDS-direct loads in flight it waits
-// vmcnt(0) before every use of an ordinary load's result (cdna_hip_programming.md, "Pipelining across barriers"),
-// which would drain the epilogue's stores again and again.  Its completion is waited for by hand (wait_loaded).
-__device__ __forceinline__ f32x4 buf_load16_asm(i32x4 rsrc, int voff, int soff) {
-    f32x4 v;
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    return v;
-}
-// wait until at most N vector-memory operations younger than the loads of a, b are outstanding; ties the values to the wait
-template <int N>
-__device__ __forceinline__ void wait_loaded(f32x4 &a, f32x4 &b) {
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void wait_loaded(f32x4 &a) {
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(a) : "n"(N));
-}
 
 struct PipeState {
     // lane-constant offsets (bytes)
@@ -431,21 +372,11 @@ conv1x1_pipe_kernel(const PipeArgs A) {
     const long long in_total = A.M * (long long)A.in_cs * ES;
     const long long out_total = A.M * (long long)A.out_cs * ES;
     const long long w_total = (long long)A.N * A.K * ES;
-    // Which (panel, N-tile group) this block works on.  A block keeps ONE group for its whole life and walks panels
-    // panel0, panel0 + step, ...  Two maps, the same work either way:
-    //   plain   : block b -> group b & gmask, panel0 = b >> gshift (adjacent blocks = adjacent groups of one panel, which
-    //             the dispatcher deals to DIFFERENT XCDs);
-    //   xcd_map : blocks with equal b & 7 share an XCD and its L2 -- slot j = b >> 3 of XCD x = b & 7 takes group j & gmask
-    //             of panel x * ppx + (j >> gshift): the 2^gshift groups of a panel run side by side on ONE XCD, so the
-    //             panel's activations come from beyond L2 once and from L2 for the other groups.  (Measured before: one
-    //             block walking a panel's N tiles one after the other re-fetched the panel for EVERY tile -- 64 blocks per
-    //             XCD stream 12+ MB through its 4 MB L2 between two tiles; gpurun_out/shape_pmc)
-    const int gmask = (1 << A.gshift) - 1;
+    // Which (panel, N-tile group) this block works on (xcd_group_map): a block keeps ONE group for its whole life and walks
+    // panels panel0, panel0 + step, ...
     const int step = A.grid >> A.gshift;                       // panels in flight per round
-    const int bid = (int)blockIdx.x;
-    const int slot = bid >> 3, ppx = step >> 3;
-    const int group = A.xcd_map ? (slot & gmask) : (bid & gmask);
-    const int panel0 = A.xcd_map ? (bid & 7) * ppx + (slot >> A.gshift) : (bid >> A.gshift);
+    int group, panel0;
+    xcd_group_map((int)blockIdx.x, step, 1 << A.gshift, A.gshift, A.xcd_map, group, panel0);
     auto panel_of = [&](Cursor c) { return c.u; };
     auto res_a = [&](Cursor c) { return rsrc_at(A.in, (long long)panel_of(c) * BM * A.in_cs * ES, c.u < A.panels ? in_total : 0); };
     auto res_b = [&](Cursor c) { return rsrc_at(A.wgt, (long long)c.nt * BN * A.K * ES, c.u < A.panels ? w_total : 0); };
@@ -502,7 +433,7 @@ conv1x1_pipe_kernel(const PipeArgs A) {
         ++kc_nx;
         if (kc_nx == nk) { kc_nx = 0; nx = advance(nx); }
     }
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NSTAGE - 2)) : "memory");      // chunk 0 has landed
+    wait_vmcnt<8 * (NSTAGE - 2)>();      // chunk 0 has landed
     __builtin_amdgcn_s_barrier();
 
     Cursor prev = {A.panels, 0};          // nothing to store yet: empty resource
@@ -527,8 +458,8 @@ conv1x1_pipe_kernel(const PipeArgs A) {
             if (kc_nx == nk) { kc_nx = 0; nx = advance(nx); }
             buf = buf + 1 == NSTAGE ? 0 : buf + 1;
             // the next chunk has landed: younger than its requests are only the 16 stores of a first chunk (see run_tile)
-            if constexpr (first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NSTAGE - 2) + 16) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NSTAGE - 2)) : "memory");
+            if constexpr (first) wait_vmcnt<8 * (NSTAGE - 2) + 16>();
+            else wait_vmcnt<8 * (NSTAGE - 2)>();
             __builtin_amdgcn_s_barrier();
         };
         chunk(std::true_type{});
@@ -560,8 +491,8 @@ conv1x1_pipe_kernel(const PipeArgs A) {
             // residual loads were waited for inside it): vector-memory operations complete in order, so allowing
             // exactly that many to stay outstanding waits for nothing else.  (Short tiles with more than one first
             // chunk in that window only make the wait stricter.)
-            if (kc <= NSTAGE - 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NSTAGE - 2) + (F32 ? 16 : 8)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(8 * (NSTAGE - 2)) : "memory");
+            if (kc <= NSTAGE - 2) wait_vmcnt<8 * (NSTAGE - 2) + (F32 ? 16 : 8)>();
+            else wait_vmcnt<8 * (NSTAGE - 2)>();
             __builtin_amdgcn_s_barrier();
         }
         prev = cur;

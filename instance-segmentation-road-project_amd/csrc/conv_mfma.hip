@@ -30,8 +30,7 @@
 //   CONTIGUOUS range of panels, so the halo rows two neighbouring panels share are fetched into one L2.
 //   1x1 convs with K <= 512 on maps of >= 64x64 pixels go to the persistent pipelined kernel (conv1x1_pipe.hip)
 //   instead; activations >= 2 GiB are cut into image groups (split_by_image_groups below).
-#include "common.h"
-
+#include "gfx_mem.h"
 
 namespace {
 
@@ -39,8 +38,6 @@ constexpr int LDS_LD = 32;   // f32 math: floats per staged row.  No padding: ro
                              // (64 lanes x 16 B land contiguously); bank conflicts are avoided by an XOR swizzle
                              // of the 16-byte k-groups inside a row: slot = kgroup ^ ((row >> 1) & 7)
 constexpr int LDS_LD_H = 40; // f16 math: halves per staged row (32 + 8 pad: 80-byte rows, conflict-free b128 reads)
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // (out-of-image taps: the buffer loads below return zeros for out-of-range offsets -- no post-load select,
 // which would force an s_waitcnt vmcnt before the MFMA block)
@@ -80,15 +77,6 @@ struct MultiArgs {
     int start[MAXP + 1];      // prefix sum of blocks per problem
     Problem p[MAXP];
 };
-
-// buffer_load_dwordx4 ... lds: 16 bytes per lane from (resource + voff + soff) straight into LDS at
-// dst + lane * 16 (dst is wave-uniform and travels in M0); out-of-range lanes write zeros.  Counted in vmcnt.
-// (The builtin only exists in the device pass.)
-__device__ __forceinline__ void load_b128_to_lds(__amdgpu_buffer_rsrc_t rsrc, float *dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 // ---- shared epilogue math: bias + residual + activation + addressing for 4 consecutive channels
 __device__ __forceinline__ void store_out4(const ml_conv2d_desc &p, int HoWo, int m, int n, f32x4 v, bool vec_ok,
@@ -346,8 +334,8 @@ conv_mfma_kernel(const MultiArgs args) {                                        
     // resources with num_records = 0: every lane is out of range, nothing is fetched (it used to re-read the last
     // chunk: +50 % loads on K = 64 convs, +25 % on K = 128).  One s_cselect per chunk.
     const int in_bytes = (int)P.in_bytes, wgt_bytes = (int)P.wgt_bytes;
-    __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)pin, 0, in_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wgt, 0, wgt_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsrc_a = rsrc_bytes(pin, in_bytes);
+    __amdgpu_buffer_rsrc_t rsrc_b = rsrc_bytes(p.wgt, wgt_bytes);
     int b_voff[B_LD];
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) b_voff[i] = ((n0 + ld_row + RPP * i) * ktot + ld_c) * ES;
@@ -363,14 +351,14 @@ conv_mfma_kernel(const MultiArgs args) {                                        
             areg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_a, vo, 0, 0));
         } else {
             // global -> LDS without a register round trip: this wave's 64 x 16 B = rows 32i + 8w .. +7 of the tile
-            load_b128_to_lds(rsrc_a, lds + dst_buf * BUF + (RPP * i + 8 * wave_u) * LDS_LD, vo, 0);
+            lds_dma16(rsrc_a, (char *)(lds + dst_buf * BUF + (RPP * i + 8 * wave_u) * LDS_LD), vo, 0);
         }
     };
     auto piece_b = [&](int i, int kc) {
         if constexpr (F16) {
             breg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_b, b_voff[i], ((kh * pKW + kw) * ncpt + cc) * 128, 0));
         } else {
-            load_b128_to_lds(rsrc_b, lds + dst_buf * BUF + (BM + RPP * i + 8 * wave_u) * LDS_LD, b_voff[i], ((kh * pKW + kw) * ncpt + cc) * 128);
+            lds_dma16(rsrc_b, (char *)(lds + dst_buf * BUF + (BM + RPP * i + 8 * wave_u) * LDS_LD), b_voff[i], ((kh * pKW + kw) * ncpt + cc) * 128);
         }
     };
     auto piece_end = [&]() {                     // advance (kh, kw, cc) and the running offsets with selects
@@ -409,7 +397,7 @@ conv_mfma_kernel(const MultiArgs args) {                                        
             return;
         }
         // f32 math: the data is already on its way into LDS; it has landed when vmcnt reaches 0
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
     };
 
     const int r = lane & 31;
@@ -446,11 +434,11 @@ conv_mfma_kernel(const MultiArgs args) {                                        
         load_chunk(kc_begin);
         if constexpr (NSTAGE == 3) {
             const bool two = kc_begin + 1 < kc_end;
-            rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)pin, 0, two ? in_bytes : 0, 0x00020000);
-            rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wgt, 0, two ? wgt_bytes : 0, 0x00020000);
+            rsrc_a = rsrc_bytes(pin, two ? in_bytes : 0);
+            rsrc_b = rsrc_bytes(p.wgt, two ? wgt_bytes : 0);
             dst_buf = 1;
             load_chunk(two ? kc_begin + 1 : kc_begin);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLOADS) : "memory");
+            wait_vmcnt<NLOADS>();
         } else {
             store_chunk(0);
         }
@@ -472,7 +460,6 @@ conv_mfma_kernel(const MultiArgs args) {                                        
         f16x8 ahA, alA, ahB, alB, bhA[TN], bhB[TN], bl[TN];
         f32x4 rx0, rx1;                                       // the next step's A fragment as staged (fp32)
         unsigned hw[4], lw[4];
-        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         auto ld_a_raw = [&](const float *b, int ks) {
             const float *row = b + a_off;
             rx0 = *reinterpret_cast<const f32x4 *>(row + (((ks * 4 + 2 * h) ^ swz) * 4));
@@ -545,8 +532,8 @@ conv_mfma_kernel(const MultiArgs args) {                                        
         for (int kc = kc_begin; kc < kc_end; ++kc) {
             const bool more = kc + 2 < kc_end;
             const int kc_next = more ? kc + 2 : kc;
-            rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)pin, 0, more ? in_bytes : 0, 0x00020000);
-            rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wgt, 0, more ? wgt_bytes : 0, 0x00020000);
+            rsrc_a = rsrc_bytes(pin, more ? in_bytes : 0);
+            rsrc_b = rsrc_bytes(p.wgt, more ? wgt_bytes : 0);
             const float *base = lds + buf * BUF;
             const int nbuf = buf == 2 ? 0 : buf + 1;
             dst_buf = buf == 0 ? 2 : buf - 1;
@@ -555,7 +542,7 @@ conv_mfma_kernel(const MultiArgs args) {                                        
             step(ahA, alA, bhA, base, 1, ahB, alB, bhB, 0, NPA, kc_next);
             // the chunk after this one has landed (requested during the previous iteration; only this iteration's NPA
             // requests may still be in flight) -- and every wave is past its last read of the buffer being refilled
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPA) : "memory");
+            wait_vmcnt<NPA>();
             __builtin_amdgcn_s_barrier();
             step(ahB, alB, bhB, lds + nbuf * BUF, 0, ahA, alA, bhA, NPA, NLOADS + 1, kc_next);
             buf = nbuf;
@@ -566,8 +553,8 @@ conv_mfma_kernel(const MultiArgs args) {                                        
         const bool more = kc + AHEAD < kc_end;
         // Unconditional prefetch, no branch: on the last iteration(s) it goes through empty resources (no traffic).
         const int kc_next = more ? kc + AHEAD : kc;
-        rsrc_a = __builtin_amdgcn_make_buffer_rsrc((void *)pin, 0, more ? in_bytes : 0, 0x00020000);
-        rsrc_b = __builtin_amdgcn_make_buffer_rsrc((void *)p.wgt, 0, more ? wgt_bytes : 0, 0x00020000);
+        rsrc_a = rsrc_bytes(pin, more ? in_bytes : 0);
+        rsrc_b = rsrc_bytes(p.wgt, more ? wgt_bytes : 0);
         const float *base = lds + buf * BUF;
         dst_buf = NSTAGE == 3 ? (buf == 0 ? 2 : buf - 1) : (buf ^ 1);
         piece_begin();
@@ -720,7 +707,7 @@ conv_mfma_kernel(const MultiArgs args) {                                        
         if constexpr (F16) {
             if (more) store_chunk(buf ^ 1);
         } else if constexpr (NSTAGE == 3) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NLOADS) : "memory");      // the NEXT chunk's rows have landed
+            wait_vmcnt<NLOADS>();      // the NEXT chunk's rows have landed
         } else {
             store_chunk(buf ^ 1);        // always: the (dropped) last prefetch must have landed before the epilogue re-uses the LDS
         }
@@ -733,7 +720,7 @@ conv_mfma_kernel(const MultiArgs args) {                                        
     }
     }
     if constexpr (NSTAGE == 3) {         // (the dropped last prefetches: nothing may still be writing when the epilogue re-uses the LDS)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
     }
 

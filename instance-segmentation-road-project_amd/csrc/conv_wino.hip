@@ -105,7 +105,7 @@
 //   launch; no host reads, no allocation: capturable in a hipGraph.  Fixed-capacity RoI batches (`live`): blocks that hold
 //   only non-existing images return at once, so a mask-head conv runs on the same kernel (same bits) with or without
 //   `live`.
-#include "common.h"
+#include "gfx_mem.h"
 
 namespace {
 
@@ -145,15 +145,6 @@ struct WArgs {
     WProblem p[WMAXP];
 };
 
-// buffer_load_dwordx4 ... lds: 16 bytes per lane from (resource + voff) straight into LDS at dst + lane * 16 (dst is
-// wave-uniform and travels in M0); out-of-range lanes write zeros.  Counted in vmcnt.  (No immediate offset: the
-// instruction adds it to the LDS address as well.)
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, float *dst, int voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, 0, 0, 0);
-#endif
-}
-
 // Four consecutive channels of one pixel at a dword-aligned address: a channel stride or offset that is no multiple of 4
 // (the 75 classes written into cls_pred) takes the same 16-byte global instruction as an aligned destination.
 typedef f32x4 f32x4d __attribute__((aligned(4)));
@@ -162,7 +153,7 @@ typedef f32x4 f32x4d __attribute__((aligned(4)));
 // an empty resource, which the hardware drops.
 __device__ __forceinline__ void out_store(float *base, float *ptr, float val) {
 #if (WINO_EXP & 8) && defined(__HIP_DEVICE_COMPILE__)
-    const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t none = rsrc_bytes(base, 0);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val), none, (int)((ptr - base) * 4), 0, 0);
 #else
     *ptr = val;
@@ -170,8 +161,7 @@ __device__ __forceinline__ void out_store(float *base, float *ptr, float val) {
 }
 __device__ __forceinline__ void out_store(float *base, float *ptr, f32x4 val) {
 #if (WINO_EXP & 8) && defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t none = rsrc_bytes(base, 0);
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), none, (int)((ptr - base) * 4), 0, 0);
 #else
     *reinterpret_cast<f32x4d *>(ptr) = val;
@@ -280,11 +270,11 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
     // fill the rows of its own half h, which nobody reads)
     auto rsrc_p = [&](int j) __attribute__((always_inline)) {
         const bool real = j < nch && !(WINO_EXP & 1);
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(pin + j * 8), 0, real ? (int)OOB : 0, 0x00020000);
+        return rsrc_bytes(pin + j * 8, real ? (int)OOB : 0);
     };
     auto rsrc_w = [&](int s) __attribute__((always_inline)) {
         const bool real = s < nsteps && !dead && !(WINO_EXP & 2);
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(wsrc + (size_t)s * WSTEP), 0, real ? WSTEP * 4 : 0, 0x00020000);
+        return rsrc_bytes(wsrc + (size_t)s * WSTEP, real ? WSTEP * 4 : 0);
     };
 
     f32x4 acc[2][16];
@@ -349,21 +339,23 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         }
     };
 
-    // prologue: chunk 0 and K step 0 first, then what iteration 0's barrier needs
+    // prologue: chunk 0 and K step 0 first, then what iteration 0's barrier needs.  (Everywhere below the second half of a
+    // weight step goes through voff + 1024, not through the instruction's immediate offset: that is added to the LDS
+    // address as well.)
     {
         const __amdgpu_buffer_rsrc_t rp0 = rsrc_p(0), rp1 = rsrc_p(1), rw0 = rsrc_w(0), rw1 = rsrc_w(1), rw2 = rsrc_w(2);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rp0, dst_p + i * 256, voff_p[i]);
-        dma16(rw0, dst_w, voff_w);
-        dma16(rw0, dst_w + 256, voff_w + 1024);
+        for (int i = 0; i < 4; ++i) lds_dma16(rp0, (char *)(dst_p + i * 256), voff_p[i], 0);
+        lds_dma16(rw0, (char *)dst_w, voff_w, 0);
+        lds_dma16(rw0, (char *)(dst_w + 256), voff_w + 1024, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) dma16(rp1, dst_p + SLOT_P + i * 256, voff_p[i]);
-        dma16(rw1, dst_w + SLOT_W, voff_w);
-        dma16(rw1, dst_w + SLOT_W + 256, voff_w + 1024);
-        dma16(rw2, dst_w + 2 * SLOT_W, voff_w);
-        dma16(rw2, dst_w + 2 * SLOT_W + 256, voff_w + 1024);
+        for (int i = 0; i < 4; ++i) lds_dma16(rp1, (char *)(dst_p + SLOT_P + i * 256), voff_p[i], 0);
+        lds_dma16(rw1, (char *)(dst_w + SLOT_W), voff_w, 0);
+        lds_dma16(rw1, (char *)(dst_w + SLOT_W + 256), voff_w + 1024, 0);
+        lds_dma16(rw2, (char *)(dst_w + 2 * SLOT_W), voff_w, 0);
+        lds_dma16(rw2, (char *)(dst_w + 2 * SLOT_W + 256), voff_w + 1024, 0);
     }
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+    wait_vmcnt<8>();
     __builtin_amdgcn_s_barrier();
 
     // ---- the dead half's K loop: the waits, the barrier and the 8 DMA instructions of the live loop below (same slots, same
@@ -383,14 +375,14 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
             const __amdgpu_buffer_rsrc_t rp = rsrc_p(j + 2), rwa = rsrc_w(2 * j + 3), rwb = rsrc_w(2 * j + 4);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
-                if (q < 4) dma16(rp, dst_p + ps2 + q * 256, voff_p[q]);
-                else if (q < 6) dma16(rwa, dst_w + wa + (q - 4) * 256, voff_w + (q - 4) * 1024);
-                else dma16(rwb, dst_w + wb + (q - 6) * 256, voff_w + (q - 6) * 1024);
+                if (q < 4) lds_dma16(rp, (char *)(dst_p + ps2 + q * 256), voff_p[q], 0);
+                else if (q < 6) lds_dma16(rwa, (char *)(dst_w + wa + (q - 4) * 256), voff_w + (q - 4) * 1024, 0);
+                else lds_dma16(rwb, (char *)(dst_w + wb + (q - 6) * 256), voff_w + (q - 6) * 1024, 0);
                 __builtin_amdgcn_s_sleep(3);
             }
             ps2 = ps2 == 2 * SLOT_P ? 0 : ps2 + SLOT_P;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         return;
     }
 
@@ -413,9 +405,9 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         const __amdgpu_buffer_rsrc_t rp = rsrc_p(j + 2), rwa = rsrc_w(2 * j + 3), rwb = rsrc_w(2 * j + 4);
         // the 8 DMA instructions of the iteration: 5 in its first step (the patches first: they may miss L2), 3 in its second
         auto dma = [&](int q) __attribute__((always_inline)) {
-            if (q < 4) dma16(rp, dst_p + ps2 + q * 256, voff_p[q]);
-            else if (q < 6) dma16(rwa, dst_w + wa + (q - 4) * 256, voff_w + (q - 4) * 1024);
-            else dma16(rwb, dst_w + wb + (q - 6) * 256, voff_w + (q - 6) * 1024);
+            if (q < 4) lds_dma16(rp, (char *)(dst_p + ps2 + q * 256), voff_p[q], 0);
+            else if (q < 6) lds_dma16(rwa, (char *)(dst_w + wa + (q - 4) * 256), voff_w + (q - 4) * 1024, 0);
+            else lds_dma16(rwb, (char *)(dst_w + wb + (q - 6) * 256), voff_w + (q - 6) * 1024, 0);
         };
         step(oa, ob, pa_lane1 + ps0, pb_lane + (w0 + 1) * SLOT_W, 5, dma);
         step(ob, oa, pa_lane0 + ps1, pb_lane + (w0 ^ 2) * SLOT_W, 3, [&](int q) __attribute__((always_inline)) { dma(q + 5); });
@@ -424,7 +416,7 @@ __global__ void __launch_bounds__(512, 1) conv_wino_kernel(const WArgs args) {
         ps1 = ps2;
         ps2 = ps;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the empty DMAs past the last chunk
+    wait_vmcnt<0>();   // the empty DMAs past the last chunk
 
     // ---- epilogue: Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1], on the four channels of a lane at once.  The B fragment is the
     // MFMA's first operand, so the tile comes out transposed: lane (r, kq) holds tile tg * 16 + r and channels

@@ -14,8 +14,7 @@
 // rows of the 1x1 kernel (a lane table prepared by the host, see masklab_hip.h).
 // Numerics: exact fp32 products; the 1x1 conv sums its channels in the order (t, e, lane half), not 0 .. C_mid-1
 // (~1e-7 relative).
-#include <type_traits>
-#include "common.h"
+#include "gfx_mem.h"
 
 namespace {
 
@@ -39,25 +38,6 @@ struct DoArgs {
     float mid_lo, mid_hi, out_lo, out_hi;      // activations as clamps (the output one unless out_sigmoid)
 };
 
-template <int I, int E, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < E) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, E>(f);
-    }
-}
-
-__device__ __forceinline__ void lds_dma16(__amdgpu_buffer_rsrc_t rsrc, char *dst, int voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)dst, 16, voff, soff, 0, 0);
-#endif
-}
-// resource over [ptr, ptr + bytes).  Extents are kept in 32 bits (a tile's 128 rows; the launcher checks they fit): 64-bit
-// compares / selects have no scalar form, and a descriptor that went through the VALU makes the compiler wrap every
-// load using it in a readfirstlane loop
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const void *ptr, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)ptr, 0, (int)bytes, 0x00020000);
-}
 // n / d for 0 <= n < 2^24 (exact in float), d >= 1: one multiply and a two-sided correction
 __device__ __forceinline__ int div_small(int n, int d, float rd) {
     int q = (int)((float)n * rd);
@@ -70,12 +50,11 @@ __device__ __forceinline__ int div_small(int n, int d, float rd) {
 struct Loc {
     int pi;                      // problem index, -1 = no such unit
     const char *x;               // first pixel row of the tile
-    unsigned x_bytes;            // bytes of the tile's rows that exist (rows past the problem's end read as zeros)
+    unsigned x_bytes;            // bytes of the tile's rows that exist (rows past the problem's end read as zeros); 32 bits,
+                                 // so the descriptor is built on the SALU: the launcher checks that a tile's 128 rows fit
     const char *w;               // Wd[pos]
     int m0;                      // first pixel of the tile inside its problem
 };
-
-typedef _Float16 f16x8o __attribute__((ext_vector_type(8)));
 
 // One K chunk of HALF tensors (64 deep = the same 128 bytes per row): 4 k-steps of v_mfma_f32_32x32x16_f16, the lane's
 // ds_read_b128 holding the 8 halves it feeds; staging, swizzle and look-ahead loads as below.
@@ -97,7 +76,7 @@ __device__ __forceinline__ void do_chunk_h(f32x16 (&acc)[NT], const char *rd, ch
         constexpr int t = idx % NT, ks = idx / NT;
         if constexpr (t == NT / 2 && ks < 3) read_frags(ks + 1, fx[(ks + 1) & 1], fw[(ks + 1) & 1]);
         const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const f16x8o a = __builtin_bit_cast(f16x8o, fw[ks & 1][t]), b = __builtin_bit_cast(f16x8o, fx[ks & 1]);
+        const f16x8 a = __builtin_bit_cast(f16x8, fw[ks & 1][t]), b = __builtin_bit_cast(f16x8, fx[ks & 1]);
         if constexpr (FIRST && ks == 0) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, zero, 0, 0, 0);
         else acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc[t], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -222,7 +201,7 @@ deconv_out_kernel(const DoArgs A) {
     Loc cur = locate(u);
     if (cur.pi < 0) return;
     {   // chunk 0 of the first unit
-        const __amdgpu_buffer_rsrc_t rx = rsrc_of(cur.x, cur.x_bytes), rw = rsrc_of(cur.w, w_bytes);
+        const __amdgpu_buffer_rsrc_t rx = rsrc_bytes(cur.x, cur.x_bytes), rw = rsrc_bytes(cur.w, w_bytes);
 #pragma unroll
         for (int i = 0; i < 4; ++i) lds_dma16(rx, lds + (32 * i + 8 * wave) * ROWB, x_voff[i], 0);
 #pragma unroll
@@ -243,8 +222,8 @@ deconv_out_kernel(const DoArgs A) {
             if (tid < 32) lds_bo[tid] = (P.bo && tid < A.ncls) ? P.bo[tid] : 0.f;
             tab_pi = cur.pi;                          // (visible after the next chunk barrier, which every unit has)
         }
-        const __amdgpu_buffer_rsrc_t rx = rsrc_of(cur.x, cur.x_bytes), rw = rsrc_of(cur.w, w_bytes);
-        const __amdgpu_buffer_rsrc_t rx_n = rsrc_of(nxt.x, nxt.x_bytes), rw_n = rsrc_of(nxt.w, nxt.pi >= 0 ? w_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t rx = rsrc_bytes(cur.x, cur.x_bytes), rw = rsrc_bytes(cur.w, w_bytes);
+        const __amdgpu_buffer_rsrc_t rx_n = rsrc_bytes(nxt.x, nxt.x_bytes), rw_n = rsrc_bytes(nxt.w, nxt.pi >= 0 ? w_bytes : 0u);
         f32x16 acc[NT];
         for (int kc = 0; kc < nk; ++kc) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // this chunk has landed (my share; and my table writes)
@@ -315,7 +294,7 @@ deconv_out_kernel(const DoArgs A) {
         cur = nxt;
         u = u_nx;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the last chunk's look-ahead loads were empty, but are counted)
+    wait_vmcnt<0>();     // (the last chunk's look-ahead loads were empty, but are counted)
 }
 
 template <int NT, bool HALF>

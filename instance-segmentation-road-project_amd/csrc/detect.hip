@@ -726,7 +726,6 @@ __global__ void mask_distribute_kernel(const float *__restrict__ rows, int rs, i
 // ------------------------------------------------------------------ crop_and_resize + MoldBatch(-1)
 // T = float, or _Float16 (feature maps and crops of the fp16-storage heads: same fp32 arithmetic on the stored values,
 // one rounding at the store; the RoI BOXES stay fp32 either way)
-typedef _Float16 f16x8d __attribute__((ext_vector_type(8)));
 template <class T>
 __global__ void __launch_bounds__(256)
 roi_crop_resize_kernel(const T *__restrict__ fmap, const float *__restrict__ rows, int rs, int roff,
@@ -750,7 +749,7 @@ roi_crop_resize_kernel(const T *__restrict__ fmap, const float *__restrict__ row
             const f32x4 x = *reinterpret_cast<const f32x4 *>(p);
             v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
         } else {
-            const f16x8d x = *reinterpret_cast<const f16x8d *>(p);
+            const f16x8 x = *reinterpret_cast<const f16x8 *>(p);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
         }
@@ -760,9 +759,9 @@ roi_crop_resize_kernel(const T *__restrict__ fmap, const float *__restrict__ row
             const f32x4 x = {v[0], v[1], v[2], v[3]};
             *reinterpret_cast<f32x4 *>(p) = x;
         } else {
-            const f16x8d x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
-                              (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
-            *reinterpret_cast<f16x8d *>(p) = x;
+            const f16x8 x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                             (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+            *reinterpret_cast<f16x8 *>(p) = x;
         }
     };
     if (j >= cnt) {  // MoldBatch padding (misc.py:276-282): -1 for features AND boxes

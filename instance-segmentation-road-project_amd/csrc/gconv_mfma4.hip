@@ -21,13 +21,12 @@ namespace {
 
 // tensor element type TIO: float, or _Float16 for the fp16-STORAGE mode (BASELINE config 5): 4 channels are then an
 // 8-byte load / store, the halo tile in LDS, the weights and all arithmetic stay fp32, the result is rounded once.
-typedef _Float16 f16x4g __attribute__((ext_vector_type(4)));
 template <class TIO>
 __device__ __forceinline__ f32x4 load4(const TIO *p) {
     if constexpr (sizeof(TIO) == 4) {
         return *reinterpret_cast<const f32x4 *>(p);
     } else {
-        const f16x4g h = *reinterpret_cast<const f16x4g *>(p);
+        const f16x4 h = *reinterpret_cast<const f16x4 *>(p);
         return f32x4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
     }
 }
@@ -36,14 +35,13 @@ __device__ __forceinline__ void store4(TIO *p, f32x4 v) {
     if constexpr (sizeof(TIO) == 4) {
         *reinterpret_cast<f32x4 *>(p) = v;
     } else {
-        *reinterpret_cast<f16x4g *>(p) = f16x4g{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+        *reinterpret_cast<f16x4 *>(p) = f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
     }
 }
 
 // staging: every thread moves 16 bytes per load -- 4 fp32 or 8 fp16 channels of one halo pixel
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
 template <class TIO> struct Stage16 { typedef f32x4 type; };
-template <> struct Stage16<_Float16> { typedef f16x8g type; };
+template <> struct Stage16<_Float16> { typedef f16x8 type; };
 template <class TIO>
 __device__ __forceinline__ void stage_to_lds(float *dst, const typename Stage16<TIO>::type &v) {
     if constexpr (sizeof(TIO) == 4) {
@@ -220,7 +218,7 @@ gconv_mfma4h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ w
     const int lane = tid & 63, wave = tid >> 6;
     const int blk = lane >> 2, sub = lane & 3;
 
-    f16x8g stage[NLD];
+    f16x8 stage[NLD];
     const int cN = (tid % TPP) * 8;
     auto fetch = [&](int ty) __attribute__((always_inline)) {
         const int iy0 = ty * TH * STRIDE - pad_t;
@@ -231,20 +229,20 @@ gconv_mfma4h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ w
             const int p = tl / TPP + PPP * i;
             const int py = p / TWIN, px = p - py * TWIN;
             const int iy = iy0 + py, ix = ix0 + px;
-            f16x8g v = {};
+            f16x8 v = {};
             if (p < NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                v = *reinterpret_cast<const f16x8g *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + (tl % TPP) * 8);
+                v = *reinterpret_cast<const f16x8 *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + (tl % TPP) * 8);
             stage[i] = v;
         }
     };
     fetch(ty_begin);
-    f16x4g wv[WV];
+    f16x4 wv[WV];
     {
         const float *wrow = wgt + (long long)(cs0 + blk * 4 + sub) * 9 * c;
 #pragma unroll
         for (int i = 0; i < WV; ++i) {
             const f32x4 w = *reinterpret_cast<const f32x4 *>(wrow + 4 * i);
-            wv[i] = f16x4g{(_Float16)w[0], (_Float16)w[1], (_Float16)w[2], (_Float16)w[3]};
+            wv[i] = f16x4{(_Float16)w[0], (_Float16)w[1], (_Float16)w[2], (_Float16)w[3]};
         }
     }
     const int gch = ((cs0 + blk * 4) / c) * c - cs0;
@@ -264,7 +262,7 @@ gconv_mfma4h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ w
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int p = tid / TPP + PPP * i;
-            if (p < NPIX) *reinterpret_cast<f16x8g *>(tileh + p * PSH + cN) = stage[i];
+            if (p < NPIX) *reinterpret_cast<f16x8 *>(tileh + p * PSH + cN) = stage[i];
         }
         __syncthreads();
         if (ty + 1 < ty_end) fetch(ty + 1);               // flies under this tile's MFMAs
@@ -277,10 +275,10 @@ gconv_mfma4h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ w
             const int toff = ((t / 3) * TWIN + (t % 3)) * PSH;
 #pragma unroll
             for (int i0 = 0; i0 < c; i0 += 4) {
-                const f16x4g w4 = wv[(t * c + i0) / 4];
+                const f16x4 w4 = wv[(t * c + i0) / 4];
 #pragma unroll
                 for (int q = 0; q < QPW; ++q) {
-                    const f16x4g xv = *reinterpret_cast<const f16x4g *>(tileh + qbase[q] + toff + i0);
+                    const f16x4 xv = *reinterpret_cast<const f16x4 *>(tileh + qbase[q] + toff + i0);
                     acc[q] = __builtin_amdgcn_mfma_f32_4x4x4f16(w4, xv, acc[q], 0, 0, 0);
                 }
             }
@@ -442,7 +440,7 @@ gconv16h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
     const int lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, q = lane >> 4;
 
-    f16x8g stage[NLD];
+    f16x8 stage[NLD];
     const int cN = (tid % TPP) * 8;
     auto fetch = [&](int ty) __attribute__((always_inline)) {
         const int iy0 = ty * TH * STRIDE - pad_t;
@@ -453,20 +451,20 @@ gconv16h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
             const int p = tl / TPP + PPP * i;
             const int py = p / TWIN, px = p - py * TWIN;
             const int iy = iy0 + py, ix = ix0 + px;
-            f16x8g v = {};
+            f16x8 v = {};
             if (p < NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                v = *reinterpret_cast<const f16x8g *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + (tl % TPP) * 8);
+                v = *reinterpret_cast<const f16x8 *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + (tl % TPP) * 8);
             stage[i] = v;
         }
     };
     fetch(ty_begin);
-    f16x4g wv[9];
+    f16x4 wv[9];
     {
         const float *wrow = wgt + (long long)(cs0 + wave * 16 + j) * 9 * 16 + 4 * q;
 #pragma unroll
         for (int t = 0; t < 9; ++t) {
             const f32x4 w = *reinterpret_cast<const f32x4 *>(wrow + t * 16);
-            wv[t] = f16x4g{(_Float16)w[0], (_Float16)w[1], (_Float16)w[2], (_Float16)w[3]};
+            wv[t] = f16x4{(_Float16)w[0], (_Float16)w[1], (_Float16)w[2], (_Float16)w[3]};
         }
     }
     int pbase[SETS];
@@ -484,7 +482,7 @@ gconv16h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int p = tid / TPP + PPP * i;
-            if (p < NPIX) *reinterpret_cast<f16x8g *>(tileh + p * PS16H + cN) = stage[i];
+            if (p < NPIX) *reinterpret_cast<f16x8 *>(tileh + p * PS16H + cN) = stage[i];
         }
         __syncthreads();
         if (ty + 1 < ty_end) fetch(ty + 1);               // flies under this tile's MFMAs
@@ -497,7 +495,7 @@ gconv16h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
             const int toff = ((t / 3) * TWIN + (t % 3)) * PS16H;
 #pragma unroll
             for (int s = 0; s < SETS; ++s) {
-                const f16x4g xv = *reinterpret_cast<const f16x4g *>(tileh + pbase[s] + toff);
+                const f16x4 xv = *reinterpret_cast<const f16x4 *>(tileh + pbase[s] + toff);
                 acc[s] = __builtin_amdgcn_mfma_f32_16x16x16f16(wv[t], xv, acc[s], 0, 0, 0);
             }
         }
@@ -524,7 +522,6 @@ gconv16h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
 // Block = a COLUMN of 8 x 8-pixel tiles x one 64-channel slab (two groups): wave w multiplies group w & 1 by the 32 pixels of
 // tile rows 4 (w >> 1) .. + 3, tile after tile, its weights staying in registers.  (Round 3 ran this stage through an fp32 copy of the input on the dense kernel's 32-wide
 // block-diagonal tiles: a cast launch + a conv on operands converted in registers.)
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
 
 template <int STRIDE>
 __global__ void __launch_bounds__(256)
@@ -552,7 +549,7 @@ gconv32h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
     const int grp = wave & 1, half = wave >> 1;
 
     // weights of group `grp` of the slab: out channel cs0 + 32 grp + p32, tap t, in channels 16 kh + 8 q .. + 7
-    f16x8h wv[9][2];
+    f16x8 wv[9][2];
     {
         const float *wrow = wgt + (long long)(cs0 + grp * 32 + p32) * 9 * 32 + 8 * q;
 #pragma unroll
@@ -561,8 +558,8 @@ gconv32h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
             for (int kh = 0; kh < 2; ++kh) {
                 const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wrow + t * 32 + kh * 16);
                 const f32x4 w1 = *reinterpret_cast<const f32x4 *>(wrow + t * 32 + kh * 16 + 4);
-                wv[t][kh] = f16x8h{(_Float16)w0[0], (_Float16)w0[1], (_Float16)w0[2], (_Float16)w0[3],
-                                   (_Float16)w1[0], (_Float16)w1[1], (_Float16)w1[2], (_Float16)w1[3]};
+                wv[t][kh] = f16x8{(_Float16)w0[0], (_Float16)w0[1], (_Float16)w0[2], (_Float16)w0[3],
+                                  (_Float16)w1[0], (_Float16)w1[1], (_Float16)w1[2], (_Float16)w1[3]};
             }
     }
     f32x4 bv[4];
@@ -576,22 +573,22 @@ gconv32h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
     for (int ty = 0; ty < tiles_y; ++ty) {
         const int oy0 = ty * TH;
         const int iy0 = oy0 * STRIDE - pad_t;
-        f16x8g stage[NLD];
+        f16x8 stage[NLD];
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int p = tid / TPP + PPP * i;
             const int ppy = p / TWIN, ppx = p - ppy * TWIN;
             const int iy = iy0 + ppy, ix = ix0 + ppx;
-            f16x8g v = {};
+            f16x8 v = {};
             if (p < NPIX && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                v = *reinterpret_cast<const f16x8g *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + cN);
+                v = *reinterpret_cast<const f16x8 *>(in + ((long long)(b * H + iy) * W + ix) * C + cs0 + cN);
             stage[i] = v;
         }
         if (ty > 0) __syncthreads();                                // every wave is done reading the previous tile
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             const int p = tid / TPP + PPP * i;
-            if (p < NPIX) *reinterpret_cast<f16x8g *>(tileh + p * PS16H + cN) = stage[i];
+            if (p < NPIX) *reinterpret_cast<f16x8 *>(tileh + p * PS16H + cN) = stage[i];
         }
         __syncthreads();
 
@@ -603,7 +600,7 @@ gconv32h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
             const int toff = ((t / 3) * TWIN + (t % 3)) * PS16H;
 #pragma unroll
             for (int kh = 0; kh < 2; ++kh) {
-                const f16x8h xv = *reinterpret_cast<const f16x8h *>(tileh + pbase + toff + kh * 16);
+                const f16x8 xv = *reinterpret_cast<const f16x8 *>(tileh + pbase + toff + kh * 16);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wv[t][kh], xv, acc, 0, 0, 0);
             }
         }

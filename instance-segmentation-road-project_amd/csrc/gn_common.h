@@ -8,8 +8,6 @@
 
 namespace {
 
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
-
 // one 16-byte access = VW<T> elements, handled as floats
 template <class T> struct VW { static constexpr int value = 16 / sizeof(T); };
 template <class T>
@@ -18,7 +16,7 @@ __device__ __forceinline__ void vload(const T *p, float (&v)[VW<T>::value]) {
         const f32x4 x = *reinterpret_cast<const f32x4 *>(p);
         v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
     } else {
-        const f16x8g x = *reinterpret_cast<const f16x8g *>(p);
+        const f16x8 x = *reinterpret_cast<const f16x8 *>(p);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
     }
@@ -29,9 +27,9 @@ __device__ __forceinline__ void vstore(T *p, const float (&v)[VW<T>::value]) {
         const f32x4 x = {v[0], v[1], v[2], v[3]};
         *reinterpret_cast<f32x4 *>(p) = x;
     } else {
-        const f16x8g x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
-                          (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
-        *reinterpret_cast<f16x8g *>(p) = x;
+        const f16x8 x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                         (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+        *reinterpret_cast<f16x8 *>(p) = x;
     }
 }
 

@@ -6,7 +6,6 @@
 
 namespace {
 
-typedef _Float16 f16x8h __attribute__((ext_vector_type(8)));
 constexpr int TPB = 256;
 
 // out[b, oy, ox, :] = in[b, 2 oy, 2 ox, :]: the sampling of a 1x1 stride-2 convolution ('same' and 'valid' agree for
@@ -21,14 +20,14 @@ __global__ void subsample2_h_kernel(const _Float16 *__restrict__ in, _Float16 *_
     const int oy = (int)(pix % Ho);
     const int b = (int)(pix / Ho);
     const int C = C8 * 8;
-    *reinterpret_cast<f16x8h *>(out + ((long long)(b * Ho + oy) * Wo + ox) * C + c8 * 8) =
-        *reinterpret_cast<const f16x8h *>(in + ((long long)(b * H + 2 * oy) * W + 2 * ox) * C + c8 * 8);
+    *reinterpret_cast<f16x8 *>(out + ((long long)(b * Ho + oy) * Wo + ox) * C + c8 * 8) =
+        *reinterpret_cast<const f16x8 *>(in + ((long long)(b * H + 2 * oy) * W + 2 * ox) * C + c8 * 8);
 }
 
 __global__ void cast_h2f_kernel(const _Float16 *__restrict__ in, float *__restrict__ out, long long n8) {
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
     if (i >= n8) return;
-    const f16x8h x = *reinterpret_cast<const f16x8h *>(in + i * 8);
+    const f16x8 x = *reinterpret_cast<const f16x8 *>(in + i * 8);
     f32x4 lo = {(float)x[0], (float)x[1], (float)x[2], (float)x[3]};
     f32x4 hi = {(float)x[4], (float)x[5], (float)x[6], (float)x[7]};
     *reinterpret_cast<f32x4 *>(out + i * 8) = lo;
@@ -36,13 +35,13 @@ __global__ void cast_h2f_kernel(const _Float16 *__restrict__ in, float *__restri
 }
 
 // 8 halves <-> floats (add_h: fp32 arithmetic on the converted values, ONE rounding at the store)
-__device__ __forceinline__ void h8_to_f(const f16x8h x, float (&v)[8]) {
+__device__ __forceinline__ void h8_to_f(const f16x8 x, float (&v)[8]) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (float)x[e];
 }
-__device__ __forceinline__ f16x8h f_to_h8(const float (&v)[8]) {
-    const f16x8h x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
-                      (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+__device__ __forceinline__ f16x8 f_to_h8(const float (&v)[8]) {
+    const f16x8 x = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                     (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
     return x;
 }
 
@@ -51,9 +50,9 @@ __global__ void cast_f2h_kernel(const float *__restrict__ in, _Float16 *__restri
     if (i >= n8) return;
     const f32x4 lo = *reinterpret_cast<const f32x4 *>(in + i * 8);
     const f32x4 hi = *reinterpret_cast<const f32x4 *>(in + i * 8 + 4);
-    const f16x8h x = {(_Float16)lo[0], (_Float16)lo[1], (_Float16)lo[2], (_Float16)lo[3],
-                      (_Float16)hi[0], (_Float16)hi[1], (_Float16)hi[2], (_Float16)hi[3]};
-    *reinterpret_cast<f16x8h *>(out + i * 8) = x;
+    const f16x8 x = {(_Float16)lo[0], (_Float16)lo[1], (_Float16)lo[2], (_Float16)lo[3],
+                     (_Float16)hi[0], (_Float16)hi[1], (_Float16)hi[2], (_Float16)hi[3]};
+    *reinterpret_cast<f16x8 *>(out + i * 8) = x;
 }
 
 // x += y (the skip `Add` of MobileSeparableConv2D, engine/layers/misc.py:105): fp32 sum, one rounding.  Thread i < n8 takes
@@ -62,11 +61,11 @@ __global__ void add_h_kernel(_Float16 *__restrict__ x, const _Float16 *__restric
     const long long i = (long long)blockIdx.x * TPB + threadIdx.x;
     if (i < n8) {
         float a[8], b[8];
-        h8_to_f(*reinterpret_cast<const f16x8h *>(x + i * 8), a);
-        h8_to_f(*reinterpret_cast<const f16x8h *>(y + i * 8), b);
+        h8_to_f(*reinterpret_cast<const f16x8 *>(x + i * 8), a);
+        h8_to_f(*reinterpret_cast<const f16x8 *>(y + i * 8), b);
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[e] += b[e];
-        *reinterpret_cast<f16x8h *>(x + i * 8) = f_to_h8(a);
+        *reinterpret_cast<f16x8 *>(x + i * 8) = f_to_h8(a);
     } else if (i == n8) {
         for (int e = 0; e < tail; ++e) x[i * 8 + e] = (_Float16)((float)x[i * 8 + e] + (float)y[i * 8 + e]);
     }

@@ -37,8 +37,6 @@
 
 namespace {
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PTH = 4, PTW = 16;                  // pooled tile
 constexpr int NT = 256;                           // threads: 4 waves, one per SIMD
 constexpr int CR = 2 * PTH + 1, CC = 2 * PTW + 1; // conv pixels it needs: 9 x 33
@@ -129,7 +127,6 @@ struct StemX3 {
                 unsigned h0, l0, h1, l1;
                 split_hi_lo_pair(stage[j][0], stage[j][1], neg_scale, h0, l0);
                 split_hi_lo_pair(stage[j][2], stage[j][3], neg_scale, h1, l1);
-                typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
                 *reinterpret_cast<u32x2 *>(tin_h + i * 4) = u32x2{h0, h1};
                 *reinterpret_cast<u32x2 *>(tin_l + i * 4) = u32x2{l0, l1};
             }
