@@ -347,9 +347,10 @@ int ml_groupnorm_chunk_f16(const void *x, void *y, const float *gamma, const flo
 
 /* Several independent GroupNormalizations in one launch pair (the five pyramid levels of a tower depth,
  * detection.py:124,194; the three RoI levels of the mask head, instance.py:192): the few-thousand-float problems of
- * the coarse levels ride along instead of being ~10 us launches of their own.  Same arithmetic per problem.
- * Every problem: 16-byte aligned tensors, HWC/G and C multiples of 4.  workspace_bytes >= the sum over the problems of
- * ml_groupnorm_workspace_bytes(N, G).                                                                          */
+ * the coarse levels ride along instead of being ~10 us launches of their own.  A problem has the bits of
+ * ml_groupnorm_chunk_f32 / _f16, alone and in any company.  A problem with 16-byte aligned tensors
+ * and HWC/G, C, out_cstride and out_coff multiples of 4 (8 for half) runs 16-byte accesses, any other one scalar accesses
+ * in the same launches.  workspace_bytes >= the sum over the problems of ml_groupnorm_workspace_bytes(N, G).         */
 typedef struct ml_gn_desc {
     const float *x;
     float *y;
@@ -358,8 +359,8 @@ typedef struct ml_gn_desc {
     int32_t N, C, G, relu;
     int32_t out_cstride, out_coff; /* y view, as in ml_groupnorm_chunk_f32          */
     float eps;
-    int32_t dtype;                 /* 0: x / y are float; 1: x / y point to IEEE half (fp16-storage heads;
-                                      HWC/G and C multiples of 8); gamma / beta are float either way */
+    int32_t dtype;                 /* 0: x / y are float; 1: x / y point to IEEE half (fp16-storage heads);
+                                      gamma / beta are float either way */
     const int32_t *live;           /* NULL, or a device int: sample n exists iff n % live_period < max(1, *live)
                                       (fixed-capacity RoI batches, as ml_conv2d_desc.live); nothing of the others
                                       is read or written, in place or not                                        */
@@ -398,7 +399,7 @@ int ml_groupnorm_chunk_grad_f32(const float *x, const float *dy, const float *ga
 int ml_groupnorm_chunk_stats_f32(const float *x, double *stats, int32_t N, int64_t HWC, int32_t C, int32_t G,
                                  void *workspace, void *stream);
 /* Several backward problems in one launch set (the five pyramid levels of a tower depth), as ml_groupnorm_multi_f32: up to
- * ML_GN_MAX_PROBLEMS problems, each with 16-byte aligned tensors and HWC/G and C multiples of 4; the same bits as the
+ * ML_GN_MAX_PROBLEMS problems of any shape and alignment (16-byte accesses where a problem has them); the same bits as the
  * single calls.  workspace_bytes >= the sum over the problems of ml_groupnorm_grad_workspace_bytes(N, G, C). */
 typedef struct ml_gn_grad_desc {
     const float *x, *dy;           /* the layer's input, the gradient at its output                */

@@ -198,16 +198,19 @@ void launch_onepass(const T *x, T *y, const float *gamma, const float *beta, int
 // ------------------------------------------------------------------ several problems in one launch pair
 // The un-shared towers normalise five pyramid levels (and the mask head three RoI levels) one after the other:
 // the two coarsest levels are a few thousand floats each, i.e. a ~10 us launch apiece behind the 46 us P3 launch.
-// ml_groupnorm_multi_f32 runs all of them as (1) one statistics launch over the problems with large chunks and
-// (2) one launch that applies those AND normalises the small-chunk problems in their register-resident one-pass
-// form.  Same per-problem arithmetic as the single-problem kernels (bit-identical results).
+// ml_groupnorm_multi_f32 runs all of them as (1) one statistics launch over the two-pass problems and (2) one launch
+// that applies those AND normalises the small-chunk problems in their register-resident one-pass form.  A problem
+// without 16-byte accesses (onepass_vpt = -1) runs the two passes with scalar ones beside the others.  Same plan and arithmetic
+// per problem as the single-problem kernels (bit-identical results).  The single-problem kernels stay: a launch of one
+// through these kernels was measured slower (the GroupNormalization kernel row).
 struct GnProb {
     const void *x;            // T = float or _Float16 (one type per launch)
     void *y;
     const float *gamma, *beta;
     double *ws;               // partials of this problem (two-pass only)
     long long L, slice;
-    int NG, S, C, G, relu, out_cs, out_co, onepass_vpt;   // onepass_vpt: 0 = two-pass, else float4 per thread
+    int NG, S, C, G, relu, out_cs, out_co, onepass_vpt;   // onepass_vpt: 0 = two-pass, > 0: float4 per thread,
+                                                          // -1 = two-pass with scalar accesses (no 16-byte ones)
     int Sp;                   // (sum, sum of squares) pairs per chunk in `ws`: S from gn_stats, or the producing conv's tiles
     float eps;
     const int *live;          // fixed-capacity RoI batches: sample n is live iff n % live_period < max(1, *live)
@@ -230,7 +233,9 @@ gn_multi_stats_kernel(const GnMulti A) {
     const GnProb &P = A.p[pi];
     const int id = blockIdx.x - A.start[pi];
     if (gn_dead(P, id / P.S)) return;
-    gn_stats_body<T>(reinterpret_cast<const T *>(P.x), P.ws, P.L, P.slice, P.S, id / P.S, id % P.S);
+    const T *x = reinterpret_cast<const T *>(P.x);
+    if (P.onepass_vpt == 0) gn_stats_body<T, true>(x, P.ws, P.L, P.slice, P.S, id / P.S, id % P.S);          // (block-uniform)
+    else gn_stats_body<T, false>(x, P.ws, P.L, P.slice, P.S, id / P.S, id % P.S);
 }
 
 template <class T>
@@ -242,7 +247,7 @@ gn_multi_apply_kernel(const GnMulti A) {
     const int id = blockIdx.x - A.start[pi];
     const T *x = reinterpret_cast<const T *>(P.x);
     T *y = reinterpret_cast<T *>(P.y);
-    if (gn_dead(P, P.onepass_vpt == 0 ? id / P.S : id)) return;          // (block-uniform)
+    if (gn_dead(P, P.onepass_vpt <= 0 ? id / P.S : id)) return;          // (block-uniform)
     if (P.onepass_vpt == 0) {
         gn_apply_body<T>(x, y, P.gamma, P.beta, P.ws, P.L, P.slice, P.S, P.C, P.G, P.eps, P.relu, P.out_cs, P.out_co,
                          id / P.S, id % P.S, P.Sp);
@@ -250,6 +255,9 @@ gn_multi_apply_kernel(const GnMulti A) {
         gn_onepass_body<T, GN_TPB, 1>(x, y, P.gamma, P.beta, (int)P.L, P.C, P.G, P.eps, P.relu, P.out_cs, P.out_co, id);
     } else if (P.onepass_vpt == 2) {
         gn_onepass_body<T, GN_TPB, 2>(x, y, P.gamma, P.beta, (int)P.L, P.C, P.G, P.eps, P.relu, P.out_cs, P.out_co, id);
+    } else if (P.onepass_vpt < 0) {
+        gn_apply_body<T, false>(x, y, P.gamma, P.beta, P.ws, P.L, P.slice, P.S, P.C, P.G, P.eps, P.relu, P.out_cs, P.out_co,
+                                id / P.S, id % P.S, P.Sp);
     } else {
         if constexpr (std::is_same<T, float>::value)
             gn_onepass_body<T, GN_TPB, 4>(x, y, P.gamma, P.beta, (int)P.L, P.C, P.G, P.eps, P.relu, P.out_cs, P.out_co, id);
@@ -269,7 +277,7 @@ static int gn_validate(const void *x, void *y, int32_t N, int64_t HWC, int32_t C
     ML_REQUIRE(C >= G, "groupnorm: Number of groups (%d) cannot be more than the number of channels (%d).", G, C);
     ML_REQUIRE(C % G == 0, "groupnorm: Number of groups (%d) must be a multiple of the number of channels (%d).", G, C);
     ML_REQUIRE(HWC % C == 0 && HWC % G == 0, "groupnorm: H*W*C (%lld) must be divisible by C and by G", (long long)HWC);
-    ML_REQUIRE((long long)N * G < 65536, "groupnorm: N*G too large for grid.y");
+    ML_REQUIRE((long long)N * G < (1ll << 31), "groupnorm: N*G too large");
     ML_REQUIRE(out_cstride >= C && out_coff >= 0 && out_coff + C <= out_cstride, "groupnorm: bad output slice");
     ML_REQUIRE(out_cstride == C ? out_coff == 0 : true, "groupnorm: dense output must have out_coff 0");
     return ML_OK;
@@ -286,35 +294,31 @@ static int gn_multi(const ml_gn_desc *descs, int32_t n, void *workspace, int64_t
         const ml_gn_desc &d = descs[i];
         if (int rc = gn_validate(d.x, d.y, d.N, d.HWC, d.C, d.G, d.out_cstride, d.out_coff)) return rc;
         const long long L = d.HWC / d.G;
-        const bool vec = (L % W == 0) && (d.C % W == 0) && (d.out_cstride % W == 0) && (d.out_coff % W == 0) &&
-                         ml_aligned16(d.x) && ml_aligned16(d.y);
-        ML_REQUIRE(vec, "groupnorm_multi: problem %d needs 16-byte aligned tensors and chunk / channel counts that are "
-                   "multiples of %d (use ml_groupnorm_chunk_f32 / _f16 otherwise)", i, W);
         GnProb P;
         P.x = d.x; P.y = d.y; P.gamma = d.gamma; P.beta = d.beta;
         P.L = L; P.NG = d.N * d.G; P.C = d.C; P.G = d.G; P.relu = d.relu; P.out_cs = d.out_cstride; P.out_co = d.out_coff;
         P.eps = d.eps;
+        const bool vec = (L % W == 0) && (d.C % W == 0) && (d.out_cstride % W == 0) && (d.out_coff % W == 0) &&
+                         ml_aligned16(d.x) && ml_aligned16(d.y);
         P.live = d.live; P.live_period = d.live_period;
         if (d.live) ML_REQUIRE(d.live_period >= 1 && d.N % d.live_period == 0, "groupnorm_multi: live_period must divide N");
         P.ws = nullptr; P.S = 1; P.slice = L; P.onepass_vpt = 0; P.Sp = -1;
-        if (L <= GN_ONEPASS_MAX) {
+        if (vec && L <= GN_ONEPASS_MAX) {
             const int vn = (int)((L + W - 1) / W);
             P.onepass_vpt = vn <= 256 ? 1 : (vn <= 512 ? 2 : 4);
-            ap.start[i] = (int)ab;
-            ab += P.NG;
-        } else if (d.partials) {
+        } else {
+            // gn_single's slices: they fix the order of the fp64 partial sums, hence the bits (scalar: cut as floats are)
+            const GnPlan plan = gn_plan(L, P.NG, vec ? W : 4);
+            P.S = plan.S; P.slice = plan.slice;
+            if (!vec) P.onepass_vpt = -1;
+        }
+        if (P.onepass_vpt <= 0 && d.partials) {
             // the producing conv summed its tiles (ml_conv2d_desc.gn_partials): no statistics pass over this tensor
             ML_REQUIRE(d.n_partials >= 1 && d.n_partials <= 4096,
                        "groupnorm_multi: problem %d: 1..4096 fp64 (sum, sum of squares) pairs per chunk", i);
-            const GnPlan plan = gn_plan(L, P.NG, W);
-            P.S = plan.S; P.slice = plan.slice;
             P.ws = const_cast<double *>(d.partials);
             P.Sp = d.n_partials;
-            ap.start[i] = (int)ab;
-            ab += (long long)P.NG * P.S;
-        } else {
-            const GnPlan plan = gn_plan(L, P.NG, W);
-            P.S = plan.S; P.slice = plan.slice;
+        } else if (P.onepass_vpt <= 0) {
             const long long bytes = (long long)P.NG * P.S * 2 * (long long)sizeof(double);
             ML_REQUIRE(ws_off + bytes <= workspace_bytes, "groupnorm_multi: workspace too small (%lld bytes needed so far)",
                        ws_off + bytes);
@@ -323,9 +327,9 @@ static int gn_multi(const ml_gn_desc *descs, int32_t n, void *workspace, int64_t
             st.start[st.n] = (int)sb;
             st.p[st.n++] = P;
             sb += (long long)P.NG * P.S;
-            ap.start[i] = (int)ab;
-            ab += (long long)P.NG * P.S;
         }
+        ap.start[i] = (int)ab;
+        ab += (long long)P.NG * P.S;
         ap.p[i] = P;
         ML_REQUIRE(ab < (1ll << 31) && sb < (1ll << 31), "groupnorm_multi: grid too large");
     }
@@ -355,6 +359,12 @@ static int gn_single(const T *x, T *y, const float *gamma, const float *beta, in
     constexpr int W = VW<T>::value;
     ML_REQUIRE(workspace, "groupnorm: null pointer");
     if (int rc = gn_validate(x, y, N, HWC, C, G, out_cstride, out_coff)) return rc;
+    if ((long long)N * G >= 65536) {         // more chunks than grid.y holds: the one-dimensional launch pair, same bits
+        ml_gn_desc d = {};
+        d.x = reinterpret_cast<const float *>(x); d.y = reinterpret_cast<float *>(y); d.gamma = gamma; d.beta = beta;
+        d.HWC = HWC; d.N = N; d.C = C; d.G = G; d.relu = relu; d.out_cstride = out_cstride; d.out_coff = out_coff; d.eps = eps;
+        return gn_multi<T>(&d, 1, workspace, ml_groupnorm_workspace_bytes(N, G), stream);
+    }
     const long long L = HWC / G;
     const bool vec = (L % W == 0) && (C % W == 0) && (out_cstride % W == 0) && (out_coff % W == 0) &&
                      ml_aligned16(x) && ml_aligned16(y);

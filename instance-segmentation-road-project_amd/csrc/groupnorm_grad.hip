@@ -397,9 +397,8 @@ static bool gg_overlap(const void *a, const void *b, long long bytes) {
     return pa < pb + (uintptr_t)bytes && pb < pa + (uintptr_t)bytes;
 }
 
-static int gg_run(const ml_gn_grad_desc *descs, int32_t n, bool multi, void *workspace, int64_t workspace_bytes,
+static int gg_run(const ml_gn_grad_desc *descs, int32_t n, const char *what, void *workspace, int64_t workspace_bytes,
                   void *stream) {
-    const char *what = multi ? "groupnorm_grad_multi" : "groupnorm_grad";
     GgMulti st, rd, ap, fi;
     st.n = rd.n = fi.n = 0;
     ap.n = n;
@@ -419,9 +418,6 @@ static int gg_run(const ml_gn_grad_desc *descs, int32_t n, bool multi, void *wor
         P.L = L; P.N = d.N; P.NG = d.N * d.G; P.C = d.C; P.G = d.G; P.relu = d.relu != 0; P.input_relu = d.input_relu != 0;
         P.eps = d.eps;
         P.vec = (L % 4 == 0) && (d.C % 4 == 0) && ml_aligned16(d.x) && ml_aligned16(d.dy) && ml_aligned16(d.dx);
-        if (multi)
-            ML_REQUIRE(P.vec, "groupnorm_grad_multi: problem %d needs 16-byte aligned tensors and chunk / channel counts that "
-                       "are multiples of 4 (use ml_groupnorm_chunk_grad_f32 otherwise)", i);
         P.fast = P.vec && (cg & (cg - 1)) == 0 && cg <= GN_TPB;
         const GnPlan plan = gn_plan(L, P.NG, 4);         // the forward's slices (vec or not)
         const bool onepass = P.vec && L <= GN_ONEPASS_MAX;
@@ -496,14 +492,14 @@ extern "C" int ml_groupnorm_chunk_grad_f32(const float *x, const float *dy, cons
     d.x = x; d.dy = dy; d.gamma = gamma; d.beta = beta; d.dx = dx; d.dgamma = dgamma; d.dbeta = dbeta; d.stats = stats;
     d.HWC = HWC; d.N = N; d.C = C; d.G = G; d.eps = eps; d.relu = relu; d.input_relu = input_relu;
     if (int rc = gg_validate_dims(x, N, HWC, C, G, "groupnorm_grad")) return rc;
-    return gg_run(&d, 1, false, workspace, ml_groupnorm_grad_workspace_bytes(N, G, C), stream);
+    return gg_run(&d, 1, "groupnorm_grad", workspace, ml_groupnorm_grad_workspace_bytes(N, G, C), stream);
 }
 
 extern "C" int ml_groupnorm_grad_multi_f32(const ml_gn_grad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
                                            void *stream) {
     ML_REQUIRE(descs && n >= 1 && n <= ML_GN_MAX_PROBLEMS && workspace, "groupnorm_grad_multi: need 1..%d problems and a workspace",
                ML_GN_MAX_PROBLEMS);
-    return gg_run(descs, n, true, workspace, workspace_bytes, stream);
+    return gg_run(descs, n, "groupnorm_grad_multi", workspace, workspace_bytes, stream);
 }
 
 extern "C" int ml_groupnorm_chunk_stats_f32(const float *x, double *stats, int32_t N, int64_t HWC, int32_t C, int32_t G,

@@ -60,33 +60,22 @@ class GroupNormalization(Layer):
         self.beta = torch.from_numpy(self._get(weights, "beta")).to(device) if self.center else None
 
     def call(self, inputs, fuse_relu=False, inplace=False, **kwargs):
-        if not self.built:
-            self.build(tuple(inputs.shape))
-        if (self.scale and self.gamma is None) or (self.center and self.beta is None):
-            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+        self._check_loaded(inputs.shape)
         return ops.groupnorm_chunk(inputs, self.gamma, self.beta, self.groups, self.epsilon, relu=fuse_relu,
                                    out=inputs if inplace else None)
 
     @staticmethod
     def call_multi(layers, inputs, inplace=False, lives=None, partials=None):
         """The same layers applied to their own inputs in ONE launch pair (the un-shared towers normalise five pyramid
-        levels at every depth, reference engine/layers/detection.py:124,194): results identical to calling each.
+        levels at every depth, reference engine/layers/detection.py:124,194): results identical to calling each,
+        whatever the shapes.
         lives: per input None or (device int32 [1], slots per image) -- a fixed-capacity RoI batch whose samples past
         max(1, live) per image do not exist and are skipped."""
         probs = []
         lives = lives if lives is not None else [None] * len(inputs)
         partials = partials if partials is not None else [None] * len(inputs)   # per input None or (float64 pairs, per chunk)
         for layer, x, live, part in zip(layers, inputs, lives, partials):
-            if not layer.built:
-                layer.build(tuple(x.shape))
-            if (layer.scale and layer.gamma is None) or (layer.center and layer.beta is None):
-                raise RuntimeError(f"layer '{layer.name}' has no weights loaded")
-            hwc = x.numel() // x.shape[0]
-            vw = 16 // x.element_size()                             # elements per 16-byte access: 4 floats / 8 halves
-            if (hwc // layer.groups) % vw or x.shape[-1] % vw:      # the multi launch takes vectorisable problems only
-                if any(lv is not None for lv in lives):
-                    raise NotImplementedError("GroupNormalization: fixed-capacity batches need vectorisable chunks")
-                return [l(x_, inplace=inplace) for l, x_ in zip(layers, inputs)]
+            layer._check_loaded(x.shape)
             probs.append(dict(x=x, gamma=layer.gamma, beta=layer.beta, groups=layer.groups, eps=layer.epsilon,
                               out=x if inplace else None, live=live, partials=part))
         return ops.groupnorm_chunk_multi(probs)
@@ -117,8 +106,8 @@ class GroupNormalization(Layer):
     @staticmethod
     def backward_multi(layers, inputs, grad_outputs, fuse_relu=False, input_relu=False, inplace=False):
         """backward() of several layers on their own inputs in ONE launch set (the counterpart of call_multi: the towers run
-        depth-major over five pyramid levels): results identical to calling each.  With a problem that is not vectorisable
-        in the list the single calls run, as in call_multi (ops.groupnorm_chunk_grad_multi).  -> list of (grad_inputs, {...})"""
+        depth-major over five pyramid levels): results identical to calling each, whatever the shapes.
+        -> list of (grad_inputs, {...})"""
         probs = []
         for layer, x, dy in zip(layers, inputs, grad_outputs):
             layer._check_loaded(x.shape)

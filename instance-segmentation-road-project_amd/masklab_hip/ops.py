@@ -635,37 +635,42 @@ def preprocess(images, flip, mean, divisor, shift, out_channels=4):
     return out
 
 
-def groupnorm_chunk(x, gamma, beta, groups, eps=1e-5, relu=False, out=None, out_coff=0):
-    """`out` may be x itself (in place), a same-shape tensor, or a wider concat buffer
-    [N,H,W,Cbuf] written at channels [out_coff, out_coff+C)."""
-    lib = _lib.load()
+def _gn_output(x, out, out_coff, dtype):
+    """The output and dtype checks of one forward problem (`dtype`: the launch's) -> out"""
     _require_dev(x, "x")
-    N = x.shape[0]
-    Cc = x.shape[-1]
-    hwc = x.numel() // N
     if out is None:
         out = torch.empty_like(x)
     _require_dev(out, "out")
-    out_cs = out.shape[-1]
-    if out_cs == Cc:
+    if out.shape[-1] == x.shape[-1]:
         if out.numel() != x.numel() or out_coff != 0:
             raise ValueError("groupnorm: dense output must match the input size")
     elif tuple(out.shape[:-1]) != tuple(x.shape[:-1]):
         raise ValueError("groupnorm: concat buffer spatial shape mismatch")
-    if out.dtype != x.dtype or x.dtype not in (torch.float32, torch.float16):
-        raise ValueError("groupnorm: x and out must share a dtype (float32 or float16)")
+    if out.dtype != x.dtype or x.dtype != dtype or x.dtype not in (torch.float32, torch.float16):
+        raise ValueError("groupnorm: every x / out of one launch must share a dtype (float32 or float16)")
+    return out
+
+
+def groupnorm_chunk(x, gamma, beta, groups, eps=1e-5, relu=False, out=None, out_coff=0):
+    """`out` may be x itself (in place), a same-shape tensor, or a wider concat buffer
+    [N,H,W,Cbuf] written at channels [out_coff, out_coff+C).  The single-problem kernels (a launch of one through
+    groupnorm_chunk_multi has the same bits and is a little slower)."""
+    lib = _lib.load()
+    out = _gn_output(x, out, out_coff, x.dtype)
+    N, Cc, hwc = x.shape[0], x.shape[-1], x.numel() // x.shape[0]
     half = x.dtype == torch.float16
     ws = workspace(lib.ml_groupnorm_workspace_bytes(N, groups), x.device, "gn")
     fn = lib.ml_groupnorm_chunk_f16 if half else lib.ml_groupnorm_chunk_f32
     with _Prof("groupnorm_chunk_h" if half else "groupnorm_chunk", 0, 2 * x.element_size() * x.numel(),
                f"N={N} HWC={hwc} G={groups}"):
         _lib.check(fn(_ptr(x), _ptr(out), _ptr(gamma), _ptr(beta), N, hwc, Cc, groups,
-                      float(eps), int(relu), out_cs, out_coff, _ptr(ws), _stream()), "ml_groupnorm_chunk")
+                      float(eps), int(relu), out.shape[-1], out_coff, _ptr(ws), _stream()), "ml_groupnorm_chunk")
     return out
 
 
 def groupnorm_chunk_multi(problems):
-    """ml_groupnorm_multi_f32: several independent GroupNormalizations in one launch pair.
+    """ml_groupnorm_multi_f32: several independent GroupNormalizations in one launch pair, whatever their shapes (a
+    problem that has no 16-byte accesses runs scalar ones beside the others).
     problems: list of dicts (x, gamma, beta, groups, eps, relu=False, out=None, out_coff=0) -> list of outputs."""
     lib = _lib.load()
     n = len(problems)
@@ -676,26 +681,14 @@ def groupnorm_chunk_multi(problems):
     arr = (_lib.GnDesc * n)()
     outs, nbytes, ws_bytes = [], 0, 0
     for i, pr in enumerate(problems):
-        x = pr["x"]
-        _require_dev(x, "x")
-        out = pr.get("out")
-        if out is None:
-            out = torch.empty_like(x)
-        _require_dev(out, "out")
-        N, Cc = x.shape[0], x.shape[-1]
-        out_cs, out_coff = out.shape[-1], pr.get("out_coff", 0)
-        if out_cs == Cc:
-            if out.numel() != x.numel() or out_coff != 0:
-                raise ValueError("groupnorm: dense output must match the input size")
-        elif tuple(out.shape[:-1]) != tuple(x.shape[:-1]):
-            raise ValueError("groupnorm: concat buffer spatial shape mismatch")
+        x, out_coff = pr["x"], pr.get("out_coff", 0)
+        out = _gn_output(x, pr.get("out"), out_coff, problems[0]["x"].dtype)
+        N, Cc, out_cs = x.shape[0], x.shape[-1], out.shape[-1]
         d = arr[i]
         d.x, d.y = x.data_ptr(), out.data_ptr()
         d.gamma = pr["gamma"].data_ptr() if pr.get("gamma") is not None else None
         d.beta = pr["beta"].data_ptr() if pr.get("beta") is not None else None
         d.HWC, d.N, d.C, d.G = x.numel() // N, N, Cc, pr["groups"]
-        if out.dtype != x.dtype or x.dtype != problems[0]["x"].dtype:
-            raise ValueError("groupnorm_multi: every x / out of one launch must share the dtype")
         d.relu, d.out_cstride, d.out_coff, d.eps = int(pr.get("relu", False)), out_cs, out_coff, float(pr.get("eps", 1e-5))
         d.dtype = int(x.dtype == torch.float16)
         if pr.get("live") is not None:
@@ -787,19 +780,13 @@ def groupnorm_chunk_grad(x, dy, gamma, beta, groups, eps=1e-5, relu=False, input
 def groupnorm_chunk_grad_multi(problems):
     """ml_groupnorm_grad_multi_f32: several backward problems in one launch set.  problems: list of dicts with
     groupnorm_chunk_grad's arguments (x, dy, gamma, beta, groups, ...) -> list of (dx, dgamma, dbeta), the bits of the
-    single calls.  The launch takes vectorisable problems only (chunk and channel counts multiples of 4): with another one
-    in the list the single calls run instead, as GroupNormalization.call_multi does for the forward."""
+    single calls, whatever the shapes."""
     n = len(problems)
     if n == 0:
         return []
     if n > _lib.GN_MAX_PROBLEMS:
         return (groupnorm_chunk_grad_multi(problems[:_lib.GN_MAX_PROBLEMS]) +
                 groupnorm_chunk_grad_multi(problems[_lib.GN_MAX_PROBLEMS:]))
-    for pr in problems:                  # the multi launch takes vectorisable problems only: single calls otherwise
-        x = pr["x"]
-        if isinstance(x, torch.Tensor) and x.dim() >= 2 and x.numel() and pr["groups"] >= 1 and (
-                (x.numel() // x.shape[0] // pr["groups"]) % 4 or x.shape[-1] % 4):
-            return [groupnorm_chunk_grad(**p) for p in problems]
     outs = [_gn_grad_problem(**pr) for pr in problems]
     lib = _lib.load()
     arr = (_lib.GnGradDesc * n)()

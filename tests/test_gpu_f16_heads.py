@@ -153,9 +153,13 @@ def test_groupnorm_half_storage(shape, G, relu):
 
 def test_groupnorm_half_multi_and_concat_slice():
     from masklab_hip import ops
+    from test_gpu_ops import GN_SCALAR_SHAPES, gn_scalar_inputs
     shapes = [(2, 64, 64, 128, 16), (2, 32, 32, 128, 16), (2, 8, 8, 128, 16), (2, 4, 4, 128, 16), (9, 14, 14, 128, 16)]
     xs = [to_half(rnd(*s[:4]) + 0.5) for s in shapes]
     gb = [(RNG.uniform(0.5, 1.5, s[3]).astype(np.float32), rnd(s[3])) for s in shapes]
+    shapes = shapes + GN_SCALAR_SHAPES                  # as halves: scalar accesses (C % 8 != 0) beside the vector problems
+    xs += [to_half(x) for x, _, _ in gn_scalar_inputs()]
+    gb += [(g, b) for _, g, b in gn_scalar_inputs()]
     single = [host(ops.groupnorm_chunk(dev(x), dev(g), dev(b), s[4])) for x, (g, b), s in zip(xs, gb, shapes)]
     multi = ops.groupnorm_chunk_multi([dict(x=dev(x), gamma=dev(g), beta=dev(b), groups=s[4])
                                        for x, (g, b), s in zip(xs, gb, shapes)])

@@ -91,7 +91,7 @@ def _problem(name, combo="plain", **kw):
 
 def test_groupnorm_chunk_grad_multi_equals_single_launches():
     """B (one-pass) and D (sliced; with relu: its statistics pass rides along) in one launch set.  With A in the list, which
-    is not vectorisable, the single calls run: the same triples either way."""
+    has no 16-byte accesses, it is still one launch set (scalar accesses beside the others): the same triples either way."""
     from masklab_hip import ops
     picks = [("B", "input_relu"), ("D", "relu"), ("D", "plain"), ("B", "no_gamma")]
     singles = [DM.snapshot(ops.groupnorm_chunk_grad(**_problem(*p))) for p in picks]
@@ -148,7 +148,7 @@ def test_layer_backward_equals_the_op(name):
 
 
 def test_backward_multi_equals_backward_per_layer():
-    """[B, D, E] in one launch set; [B, A]: A is not vectorisable, so the single calls run -- the same results either way"""
+    """[B, D, E] in one launch set; [B, A]: A has no 16-byte accesses and runs scalar ones in the same launch set -- the same results either way"""
     from masklab_hip.normalization import GroupNormalization
     for names in (["B", "D", "E"], ["B", "A"]):
         layers = _layers(names)

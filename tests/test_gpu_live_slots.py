@@ -340,16 +340,25 @@ def test_conv3x3_levels_in_one_launch(conv_math):
 GN_C, GN_G, GN_PERIOD = 128, 16, 4
 GN_N = LC.PERIODS * GN_PERIOD
 GN_SIZES = (7, 14, 20, 28)           # floats per chunk 392 / 1568 / 3200 / 6272: one-pass at 1, 2, 4 vectors per thread, two-pass
+# (h, w, C, G), chunks of 120 / 60, one slice.  C = 12: scalar accesses as halves (C % 8 != 0), a one-pass vector problem as
+# floats; C = 6: scalar accesses either way
+GN_SCALAR, GN_SCALAR_F32 = (6, 5, 12, 3), (6, 5, 6, 3)
+
+
+def _gn_dims(size):
+    """a case of the sweep -> (h, w, C, G)"""
+    return (size, size, GN_C, GN_G) if isinstance(size, int) else size
 
 
 @functools.lru_cache(maxsize=None)
 def _gn_case(size, half):
-    x = randn(100 + size, GN_N, size, size, GN_C) * 3 + 1.5
+    h, w, C, G = _gn_dims(size)
+    x = randn(100 + h + C % 8, GN_N, h, w, C) * 3 + 1.5
     if half:
         x = x.half()
-    r = np.random.default_rng(200 + size)
-    gamma, beta = r.uniform(0.5, 1.5, GN_C).astype(np.float32), r.normal(size=GN_C).astype(np.float32)
-    ref = T.group_norm(host(x).astype(np.float64), gamma, beta, GN_G)
+    r = np.random.default_rng(200 + h)
+    gamma, beta = r.uniform(0.5, 1.5, C).astype(np.float32), r.normal(size=C).astype(np.float32)
+    ref = T.group_norm(host(x).astype(np.float64), gamma, beta, G)
     return x, dev(gamma), dev(beta), ref
 
 
@@ -364,7 +373,7 @@ def _gn_problem(size, half, relu, inplace, live):
     else:
         xin = poisoned(x, alive)
         out = torch.full_like(x, CANARY)
-    pr = dict(x=xin, gamma=gamma, beta=beta, groups=GN_G, relu=relu, out=out)
+    pr = dict(x=xin, gamma=gamma, beta=beta, groups=_gn_dims(size)[3], relu=relu, out=out)
     if live is not None:
         pr["live"] = (live_int(live), GN_PERIOD)
     return pr, alive, out
@@ -380,12 +389,12 @@ def _gn_check(size, half, relu, out, alive, plain):
 
 
 @pytest.mark.parametrize("half", [False, True])
-@pytest.mark.parametrize("size", GN_SIZES)
+@pytest.mark.parametrize("size", GN_SIZES + (GN_SCALAR, GN_SCALAR_F32), ids=[str(s) for s in GN_SIZES] + ["scalar", "scalar_f32"])
 def test_groupnorm_live(size, half):
     from masklab_hip import ops
     x, gamma, beta, _ = _gn_case(size, half)
     for relu in (False, True):
-        (plain,) = ops.groupnorm_chunk_multi([dict(x=x, gamma=gamma, beta=beta, groups=GN_G, relu=relu)])
+        (plain,) = ops.groupnorm_chunk_multi([dict(x=x, gamma=gamma, beta=beta, groups=_gn_dims(size)[3], relu=relu)])
         for inplace in (False, True):
             for live in LC.live_sweep(GN_PERIOD):
                 pr, alive, out = _gn_problem(size, half, relu, inplace, live)
@@ -397,16 +406,17 @@ def test_groupnorm_live(size, half):
 
 @pytest.mark.parametrize("half", [False, True])
 def test_groupnorm_four_sizes_in_one_launch(half):
-    """One launch pair (statistics of the two-pass problem, then every apply) of the four kernel forms, each with its own
-    `live` int, one without."""
+    """One launch pair (statistics of the two-pass problems, then every apply) of the four vector forms and a scalar problem,
+    each with its own `live` int, one or two without."""
     from masklab_hip import ops
-    for lives in ((1, 2, 3, None), (None, 0, 1, 2), (3, None, 6, 1)):
+    sizes = GN_SIZES + (GN_SCALAR_F32,)
+    for lives in ((1, 2, 3, None, 2), (None, 0, 1, 2, None), (3, None, 6, 1, 0)):
         for inplace in (False, True):
-            prs = [_gn_problem(s, half, True, inplace, lv) for s, lv in zip(GN_SIZES, lives)]
+            prs = [_gn_problem(s, half, True, inplace, lv) for s, lv in zip(sizes, lives)]
             ops.groupnorm_chunk_multi([p[0] for p in prs])
-            for s, (pr, alive, out) in zip(GN_SIZES, prs):
+            for s, (pr, alive, out) in zip(sizes, prs):
                 x, gamma, beta, _ = _gn_case(s, half)
-                (plain,) = ops.groupnorm_chunk_multi([dict(x=x, gamma=gamma, beta=beta, groups=GN_G, relu=True)])
+                (plain,) = ops.groupnorm_chunk_multi([dict(x=x, gamma=gamma, beta=beta, groups=_gn_dims(s)[3], relu=True)])
                 _gn_check(s, half, True, out, alive, plain)
 
 

@@ -531,9 +531,23 @@ def test_global_mean_and_scale():
     np.testing.assert_allclose(host(ops.scale_channels_(dev(x), dev(s))), x * s, atol=1e-6)
 
 
+# Problems without 16-byte accesses.  (2, 6, 5, 12): chunk 120, one slice -- scalar as halves only (C % 8 != 0; as floats it
+# is a one-pass vector problem); (1, 30, 30, 6): chunk 1800, two slices of 1024, C no multiple of 4 -- scalar either way.
+GN_SCALAR_SHAPES = [(2, 6, 5, 12, 3), (1, 30, 30, 6, 3)]
+
+
+def gn_scalar_inputs():
+    """-> [(x, gamma, beta)] for GN_SCALAR_SHAPES, float32, from a generator of their own"""
+    r = np.random.default_rng(1203)
+    return [((r.normal(size=s[:4]) + 0.5).astype(np.float32), r.uniform(0.5, 1.5, s[3]).astype(np.float32),
+             r.normal(size=s[3]).astype(np.float32)) for s in GN_SCALAR_SHAPES]
+
+
 def test_groupnorm_multi_equals_single_launches():
-    """ml_groupnorm_multi_f32: the five pyramid levels of a tower depth (two-pass P3..P5, register-resident P6 / P7) and
-    a non-pixel-aligned RoI map in ONE launch pair -- bit-identical to the single-problem launches, and to the oracle."""
+    """ml_groupnorm_multi_f32: the five pyramid levels of a tower depth (two-pass P3..P5, register-resident P6 / P7), a
+    non-pixel-aligned RoI map and the problems of GN_SCALAR_SHAPES in ONE launch pair each (eight problems, then three).  A
+    problem's bits depend neither on its companions nor on its place in the launch: identical to the single-problem
+    kernels (ops.groupnorm_chunk), to a multi launch of that problem alone, and within the bar of the oracle."""
     from masklab_hip import ops
     shapes = [(2, 64, 64, 128, 16), (2, 32, 32, 128, 16), (2, 16, 16, 128, 16), (2, 8, 8, 128, 16), (2, 4, 4, 128, 16),
               (9, 14, 14, 128, 16), (2, 16, 16, 128, 32),
@@ -541,12 +555,22 @@ def test_groupnorm_multi_equals_single_launches():
               (2, 80, 80, 128, 16)]        # chunk 51 200: slices that do not divide it
     xs = [rnd(*s[:4]) + 0.5 for s in shapes]
     gb = [(RNG.uniform(0.5, 1.5, s[3]).astype(np.float32), rnd(s[3])) for s in shapes]
+    shapes = shapes + GN_SCALAR_SHAPES
+    xs += [x for x, _, _ in gn_scalar_inputs()]
+    gb += [(g, b) for _, g, b in gn_scalar_inputs()]
     single = [host(ops.groupnorm_chunk(dev(x), dev(g), dev(b), s[4])) for x, (g, b), s in zip(xs, gb, shapes)]
     multi = ops.groupnorm_chunk_multi([dict(x=dev(x), gamma=dev(g), beta=dev(b), groups=s[4])
                                        for x, (g, b), s in zip(xs, gb, shapes)])
     for x, (g, b), s, one, m in zip(xs, gb, shapes, single, multi):
         np.testing.assert_array_equal(host(m), one)
+        (alone,) = ops.groupnorm_chunk_multi([dict(x=dev(x), gamma=dev(g), beta=dev(b), groups=s[4])])
+        np.testing.assert_array_equal(host(alone), one)
         np.testing.assert_allclose(one, T.group_norm(x.astype(np.float64), g, b, s[4]), atol=2e-5)
+    # a scalar problem first, vector problems behind it: another place, other companions, the same bits
+    mixed = [10, 0, 9, 3]
+    for k, m in zip(mixed, ops.groupnorm_chunk_multi([dict(x=dev(xs[k]), gamma=dev(gb[k][0]), beta=dev(gb[k][1]),
+                                                           groups=shapes[k][4]) for k in mixed])):
+        np.testing.assert_array_equal(host(m), single[k])
     # data whose mean dwarfs its spread (fp64 running sums; a float4 is folded in fp32 before it joins them, so the
     # variance carries ~mean^2 * 2^-24 of rounding noise per quad: 300 is the regime the 2e-3 bar covers)
     big = (rnd(1, 128, 128, 32) + 300.0).astype(np.float32)
@@ -563,6 +587,57 @@ def test_groupnorm_multi_equals_single_launches():
     hb = host(buf)
     assert np.all(hb[..., :32] == 7.0)
     np.testing.assert_array_equal(hb[..., 32:], np.maximum(single[1], 0.0))
+
+
+def test_groupnorm_more_than_65535_chunks():
+    """N*G = 65 600 chunks of 8 floats, more than the y dimension of a grid holds: the one-dimensional launch pair takes
+    them, from the single-problem entry point too.  As a one-problem call and as the second problem of a multi launch,
+    against the oracle."""
+    from masklab_hip import ops
+    r = np.random.default_rng(65600)
+    x = (r.normal(size=(4100, 1, 1, 128)) * 2 + 0.5).astype(np.float32)
+    g, b = r.uniform(0.5, 1.5, 128).astype(np.float32), r.normal(size=128).astype(np.float32)
+    ref = T.group_norm(x.astype(np.float64), g, b, 16)
+    one = host(ops.groupnorm_chunk(dev(x), dev(g), dev(b), 16))
+    np.testing.assert_allclose(one, ref, atol=2e-5)
+    x0 = rnd(2, 8, 8, 128)
+    outs = ops.groupnorm_chunk_multi([dict(x=dev(x0), gamma=dev(g), beta=dev(b), groups=16),
+                                      dict(x=dev(x), gamma=dev(g), beta=dev(b), groups=16)])
+    np.testing.assert_allclose(host(outs[0]), T.group_norm(x0.astype(np.float64), g, b, 16), atol=2e-5)
+    np.testing.assert_array_equal(host(outs[1]), one)
+
+
+def test_groupnorm_layers_mixed_inputs_one_launch():
+    """GroupNormalization.call_multi / backward_multi on a vectorisable input and one that is scalar as float32 (C = 6, no
+    multiple of 4): ONE launch (one profile record `multi x2`) each, the results of the layers called one by one."""
+    from masklab_hip import ops
+    from masklab_hip.normalization import GroupNormalization
+    layers, xs, dys = [], [], []
+    for k, (shape, G) in enumerate((((2, 8, 8, 128), 16), ((2, 6, 5, 6), 3))):
+        layer = GroupNormalization(G, name=f"mix/gn{k}")
+        layer.build(shape)
+        layer.load_weights({f"mix/gn{k}/gamma": RNG.uniform(0.5, 1.5, shape[-1]).astype(np.float32),
+                            f"mix/gn{k}/beta": rnd(shape[-1])}, torch.device("cuda:0"))
+        layers.append(layer); xs.append(dev(rnd(*shape) + 0.5)); dys.append(dev(rnd(*shape)))
+    want = [host(l(x)) for l, x in zip(layers, xs)]
+    want_grad = [l.backward(x, dy) for l, x, dy in zip(layers, xs, dys)]
+    ops.PROFILE = []
+    try:
+        outs = GroupNormalization.call_multi(layers, xs)
+        fwd, ops.PROFILE = ops.PROFILE, []
+        grads = GroupNormalization.backward_multi(layers, xs, dys)
+        bwd = ops.PROFILE
+    finally:
+        ops.PROFILE = None
+    assert [(r["kernel"], r["shape"]) for r in fwd] == [("groupnorm_chunk", "multi x2")], fwd
+    assert [(r["kernel"], r["shape"]) for r in bwd] == [("groupnorm_chunk_grad", "multi x2")], bwd
+    for o, w, x, l in zip(outs, want, xs, layers):
+        np.testing.assert_array_equal(host(o), w)
+        np.testing.assert_allclose(w, T.group_norm(host(x).astype(np.float64), host(l.gamma), host(l.beta), l.groups), atol=2e-5)
+    for (dx, pg), (wdx, wpg) in zip(grads, want_grad):
+        np.testing.assert_array_equal(host(dx), host(wdx))
+        for name in ("gamma", "beta"):
+            np.testing.assert_array_equal(host(pg[name]), host(wpg[name]))
 
 
 def test_groupnorm_statistics_from_the_conv_epilogue(conv_math):

@@ -96,3 +96,17 @@ def test_new_symbols_are_declared_and_bound_with_matching_arity():
     assert names == [f[0] for f in _lib.GnGradDesc._fields_], names
     assert ctypes.sizeof(_lib.GnGradDesc) == 8 * 8 + 8 + 5 * 4 + 4 and _lib.GnGradDesc.HWC.offset == 64
     assert lib.ml_groupnorm_grad_workspace_bytes(8, 16, 256) >= 8 * 64 * 2 * (16 + 256) * 8
+
+
+def test_forward_refuses_more_chunks_than_a_grid_has_blocks():
+    """N*G >= 2^31 chunks would wrap the int block counts: refused on the host, before any launch, by both forward entries."""
+    from masklab_hip import _lib
+    lib = _lib.load()
+    p = lambda k: ctypes.c_void_p(4096 * k)                                  # aligned, never dereferenced
+    N, G = 1 << 16, 1 << 15
+    assert lib.ml_groupnorm_chunk_f32(p(1), p(2), None, None, N, G, G, G, 1e-5, 0, G, 0, p(3), None) != 0
+    assert b"N*G too large" in lib.ml_last_error(), lib.ml_last_error()
+    d = (_lib.GnDesc * 1)()
+    d[0].x, d[0].y, d[0].HWC, d[0].N, d[0].C, d[0].G, d[0].out_cstride = 4096, 8192, G, N, G, G, G
+    assert lib.ml_groupnorm_multi_f32(d, 1, p(3), 1 << 20, None) != 0
+    assert b"N*G too large" in lib.ml_last_error(), lib.ml_last_error()
