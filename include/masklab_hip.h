@@ -71,7 +71,8 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             ml_optimizer_plan / _scalars / _apply_f32;
                                             (additive, same version) ml_roi_grad_level, ml_roi_crop_resize_grad_f32,
                                             ml_resize_bilinear_ac_grad_f32 / _grad_workspace_bytes,
-                                            ml_global_mean_grad_f32 */
+                                            ml_global_mean_grad_f32;
+                                            (additive, same version) ml_gconv3x3_launch_plan */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -228,6 +229,14 @@ int ml_gconv3x3_f32(const float *in, const float *wgt, const float *bias, float 
 int ml_gconv3x3_f16(const void *in, const float *wgt, const float *bias, void *out,
                     int32_t B, int32_t H, int32_t W, int32_t C, int32_t c, int32_t Ho, int32_t Wo,
                     int32_t stride, int32_t pad_t, int32_t pad_l, int32_t act, void *stream);
+
+/* Host only, launches nothing: the launch ml_gconv3x3_f32 (is_half = 0) / ml_gconv3x3_f16 (is_half = 1) would make for
+ * this problem on the current device (256 compute units where there is none), from the code the launchers themselves use:
+ * plan = {tile_h, tile_w, tiles_x, tiles_y, run, blocks}.  A block covers `run` tile_h x tile_w output tiles down one tile
+ * column of an image and 64-channel slab (c = 32: the whole column, run = tiles_y); blocks = tiles_x * ceil(tiles_y / run)
+ * * (C / 64) * B, saturated at INT32_MAX.  Refuses, with ML_E_BADARG and the same message, every shape the launch refuses. */
+int ml_gconv3x3_launch_plan(int32_t B, int32_t H, int32_t W, int32_t C, int32_t c, int32_t stride, int32_t Ho, int32_t Wo,
+                            int32_t is_half, int32_t plan[6]);
 
 /* ---------------------------------------------------------------- fp16-storage helpers (BASELINE config 5)
  * ZeroPadding2D(1)+MaxPooling2D(3,2) on an fp16 map (ResNext.py:351-352; resnext.py:196-197), C % 8 == 0. */

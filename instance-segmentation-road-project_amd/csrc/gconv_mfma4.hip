@@ -618,19 +618,18 @@ gconv32h_kernel(const _Float16 *__restrict__ in, const float *__restrict__ wgt, 
     }
 }
 
-template <int STRIDE>
-int launch32h(const _Float16 *in, const float *wgt, const float *bias, _Float16 *out, int B, int H, int W, int C, int Ho, int Wo,
-              int pad_t, int pad_l, int act, hipStream_t s) {
-    constexpr int THIN = 7 * STRIDE + 3, TWIN = 7 * STRIDE + 3;
-    constexpr int LDS_BYTES = THIN * TWIN * PS16H * 2;
-    auto kern = gconv32h_kernel<STRIDE>;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), LDS_BYTES, lds_ok, "gconv3x3")) return rc;
-    const int tiles_x = (Wo + 7) / 8, tiles_y = (Ho + 7) / 8;
-    hipLaunchKernelGGL(kern, dim3(tiles_x, C / CS, B), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H, W, C, Ho, Wo,
-                       pad_t, pad_l, act, tiles_y);
-    ML_CHECK_LAUNCH("gconv3x3");
-    return ML_OK;
+// ---- the launch plan: tile shape, tile counts, run and grid of a problem.  The launchers below take their grid and the
+// kernels' tiles_x / tiles_y / seg from it, and ml_gconv3x3_launch_plan reports it ("One definition").
+
+// Tile heights: half tensors take tiles twice as tall as fp32 ones.  A halo pixel of a 64-channel slab is ONE 128-byte
+// line in half (two in fp32), so a half block of the fp32 tile shape moves half the bytes per request and per block
+// prologue; 16 x 8 (stride 2: 8 x 8) tiles cut the halo share from 56 % to 41 % of a patch and measured 9-29 % faster
+// on the 16 x 1280^2 ResNeXt-101 shapes (round 4), while fp32 tensors lose 2-14 % with them
+// (22-46 KB of LDS per block: fewer blocks per CU to hide the load -> LDS -> compute chain of a block).  c = 32 (half
+// only): the 8 x 8 tile of gconv32h_kernel.
+constexpr int GCONV_TW = 8;
+constexpr int gconv_tile_h(bool half, int c, int stride) {
+    return c == 32 ? 8 : stride == 1 ? (half ? GCONV_TH1_HALF : 8) : (half ? 8 : 4);
 }
 
 // Tiles a block walks down its tile column: the longest run that still leaves GCONV_BLOCKS_PER_CU blocks per CU (the blocks
@@ -643,6 +642,38 @@ static int column_run(int tiles_x, int tiles_y, int slabs, int B) {
     int seg = tiles_y;
     while (seg > 1 && (long long)tiles_x * ((tiles_y + seg - 1) / seg) * slabs * B < want) seg = (seg + 1) / 2;
     return seg;
+}
+
+struct GconvPlan {
+    int tile_h, tile_w, tiles_x, tiles_y, run;
+    long long blocks;
+};
+// walks = false: the c = 32 kernel, whose block always takes its whole tile column
+static GconvPlan gconv_plan(int th, int tw, bool walks, int B, int C, int Ho, int Wo) {
+    GconvPlan p;
+    p.tile_h = th, p.tile_w = tw;
+    p.tiles_x = (Wo + tw - 1) / tw, p.tiles_y = (Ho + th - 1) / th;
+    p.run = walks ? column_run(p.tiles_x, p.tiles_y, C / CS, B) : p.tiles_y;
+    p.blocks = (long long)p.tiles_x * ((p.tiles_y + p.run - 1) / p.run) * (C / CS) * B;
+    return p;
+}
+static dim3 gconv_grid(const GconvPlan &p, int B, int C) {
+    return dim3(p.tiles_x * ((p.tiles_y + p.run - 1) / p.run), C / CS, B);
+}
+
+template <int STRIDE>
+int launch32h(const _Float16 *in, const float *wgt, const float *bias, _Float16 *out, int B, int H, int W, int C, int Ho, int Wo,
+              int pad_t, int pad_l, int act, hipStream_t s) {
+    constexpr int THIN = 7 * STRIDE + 3, TWIN = 7 * STRIDE + 3;
+    constexpr int LDS_BYTES = THIN * TWIN * PS16H * 2;
+    auto kern = gconv32h_kernel<STRIDE>;
+    static std::atomic<unsigned long long> lds_ok{0};
+    if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), LDS_BYTES, lds_ok, "gconv3x3")) return rc;
+    const GconvPlan p = gconv_plan(gconv_tile_h(true, 32, STRIDE), GCONV_TW, false, B, C, Ho, Wo);
+    hipLaunchKernelGGL(kern, gconv_grid(p, B, C), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H, W, C, Ho, Wo,
+                       pad_t, pad_l, act, p.tiles_y);
+    ML_CHECK_LAUNCH("gconv3x3");
+    return ML_OK;
 }
 
 // kernel of a tensor type: fp32 tensors -> the fp32 MFMA forms, fp16 tensors -> the fp16 MFMA forms
@@ -666,10 +697,9 @@ int launch16(const TIO *in, const float *wgt, const float *bias, TIO *out, int B
     auto kern = pick16<STRIDE, TH, TW, TIO>();
     static std::atomic<unsigned long long> lds_ok{0};      // per kernel instantiation, one bit per device
     if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), LDS_BYTES, lds_ok, "gconv3x3")) return rc;
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
-    const int seg = column_run(tiles_x, tiles_y, C / CS, B);
-    hipLaunchKernelGGL(kern, dim3(tiles_x * ((tiles_y + seg - 1) / seg), C / CS, B), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H,
-                       W, C, Ho, Wo, pad_t, pad_l, act, tiles_x, tiles_y, seg);
+    const GconvPlan p = gconv_plan(TH, TW, true, B, C, Ho, Wo);
+    hipLaunchKernelGGL(kern, gconv_grid(p, B, C), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H, W, C, Ho, Wo, pad_t, pad_l,
+                       act, p.tiles_x, p.tiles_y, p.run);
     ML_CHECK_LAUNCH("gconv3x3");
     return ML_OK;
 }
@@ -683,52 +713,70 @@ int launch(const TIO *in, const float *wgt, const float *bias, TIO *out, int B, 
     auto kern = pick4<STRIDE, TH, TW, CPG, TIO>();
     static std::atomic<unsigned long long> lds_ok{0};      // per kernel instantiation, one bit per device
     if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), LDS_BYTES, lds_ok, "gconv3x3")) return rc;
-    const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
-    const int seg = column_run(tiles_x, tiles_y, C / CS, B);
-    hipLaunchKernelGGL(kern, dim3(tiles_x * ((tiles_y + seg - 1) / seg), C / CS, B), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H,
-                       W, C, Ho, Wo, pad_t, pad_l, act, tiles_x, tiles_y, seg);
+    const GconvPlan p = gconv_plan(TH, TW, true, B, C, Ho, Wo);
+    hipLaunchKernelGGL(kern, gconv_grid(p, B, C), dim3(256), LDS_BYTES, s, in, wgt, bias, out, H, W, C, Ho, Wo, pad_t, pad_l,
+                       act, p.tiles_x, p.tiles_y, p.run);
     ML_CHECK_LAUNCH("gconv3x3");
     return ML_OK;
 }
 
 }  // namespace
 
-template <class TIO>
-static int gconv3x3_any(const TIO *in, const float *wgt, const float *bias, TIO *out, int32_t B, int32_t H, int32_t W,
-                        int32_t C, int32_t c, int32_t Ho, int32_t Wo, int32_t stride, int32_t pad_t, int32_t pad_l,
-                        int32_t act, void *stream) {
-    ML_REQUIRE(in && wgt && out, "gconv3x3: null pointer");
+// what a problem's shape must satisfy, pointers aside: the launch and ml_gconv3x3_launch_plan refuse the same problems
+static int gconv_check_shape(bool half, int32_t B, int32_t H, int32_t W, int32_t C, int32_t c, int32_t Ho, int32_t Wo,
+                             int32_t stride) {
     ML_REQUIRE(B > 0 && B < 65536 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "gconv3x3: bad dims");
     ML_REQUIRE(C > 0 && C % CS == 0 && C / CS < 65536, "gconv3x3: channels must be a multiple of %d", CS);
-    ML_REQUIRE(c == 4 || c == 8 || c == 16 || (c == 32 && sizeof(TIO) == 2),
+    ML_REQUIRE(c == 4 || c == 8 || c == 16 || (c == 32 && half),
                "gconv3x3: channels per group %d must be 4, 8 or 16 (half tensors: also 32; fp32 groups of 32: ml_conv2d_f32 "
                "with group_cin_step)", c);
     ML_REQUIRE(C % c == 0, "gconv3x3: C must be a multiple of c");
     ML_REQUIRE(stride == 1 || stride == 2, "gconv3x3: stride must be 1 or 2");
+    ML_REQUIRE((long long)B * H * W < (1ll << 31), "gconv3x3: too many pixels");
+    return ML_OK;
+}
+
+template <class TIO>
+static int gconv3x3_any(const TIO *in, const float *wgt, const float *bias, TIO *out, int32_t B, int32_t H, int32_t W,
+                        int32_t C, int32_t c, int32_t Ho, int32_t Wo, int32_t stride, int32_t pad_t, int32_t pad_l,
+                        int32_t act, void *stream) {
+    constexpr bool HALF = sizeof(TIO) == 2;
+    ML_REQUIRE(in && wgt && out, "gconv3x3: null pointer");
+    if (int rc = gconv_check_shape(HALF, B, H, W, C, c, Ho, Wo, stride)) return rc;
     ML_REQUIRE(ml_aligned16(in) && ml_aligned16(wgt) && ml_aligned16(out) && (!bias || ml_aligned16(bias)),
                "gconv3x3: pointers must be 16-byte aligned");
-    ML_REQUIRE((long long)B * H * W < (1ll << 31), "gconv3x3: too many pixels");
     hipStream_t s = (hipStream_t)stream;
 #define GC_ARGS in, wgt, bias, out, B, H, W, C, Ho, Wo, pad_t, pad_l, act, s
-    // Tile heights: half tensors take tiles twice as tall as fp32 ones.  A halo pixel of a 64-channel slab is ONE 128-byte
-    // line in half (two in fp32), so a half block of the fp32 tile shape moves half the bytes per request and per block
-    // prologue; 16 x 8 (stride 2: 8 x 8) tiles cut the halo share from 56 % to 41 % of a patch and measured 9-29 % faster
-    // on the 16 x 1280^2 ResNeXt-101 shapes (gpurun_out/r04g_gconv_*.txt), while fp32 tensors lose 2-14 % with them
-    // (22-46 KB of LDS per block: fewer blocks per CU to hide the load -> LDS -> compute chain of a block).
-    constexpr bool HALF = sizeof(TIO) == 2;
-    constexpr int TH1 = HALF ? GCONV_TH1_HALF : 8, TH2 = HALF ? 8 : 4;
+    constexpr int TH1 = gconv_tile_h(HALF, 4, 1), TH2 = gconv_tile_h(HALF, 4, 2), TW = GCONV_TW;   // (c = 4, 8, 16 share a shape)
+    static_assert(gconv_tile_h(HALF, 8, 1) == TH1 && gconv_tile_h(HALF, 16, 1) == TH1 && gconv_tile_h(HALF, 8, 2) == TH2 &&
+                  gconv_tile_h(HALF, 16, 2) == TH2 && gconv_tile_h(true, 32, 1) == 8 && gconv_tile_h(true, 32, 2) == 8 && TW == 8,
+                  "the kernels instantiated here have the tile shapes of gconv_tile_h");
     if constexpr (HALF) {
         if (c == 32) return stride == 1 ? launch32h<1>(GC_ARGS) : launch32h<2>(GC_ARGS);
     }
     if (stride == 1) {
-        if (c == 4) return launch<1, TH1, 8, 4, TIO>(GC_ARGS);
-        if (c == 8) return launch<1, TH1, 8, 8, TIO>(GC_ARGS);
-        return launch16<1, TH1, 8, TIO>(GC_ARGS);
+        if (c == 4) return launch<1, TH1, TW, 4, TIO>(GC_ARGS);
+        if (c == 8) return launch<1, TH1, TW, 8, TIO>(GC_ARGS);
+        return launch16<1, TH1, TW, TIO>(GC_ARGS);
     }
-    if (c == 4) return launch<2, TH2, 8, 4, TIO>(GC_ARGS);
-    if (c == 8) return launch<2, TH2, 8, 8, TIO>(GC_ARGS);
-    return launch16<2, TH2, 8, TIO>(GC_ARGS);
+    if (c == 4) return launch<2, TH2, TW, 4, TIO>(GC_ARGS);
+    if (c == 8) return launch<2, TH2, TW, 8, TIO>(GC_ARGS);
+    return launch16<2, TH2, TW, TIO>(GC_ARGS);
 #undef GC_ARGS
+}
+
+// Host only: {tile_h, tile_w, tiles_x, tiles_y, run, blocks} of the launch ml_gconv3x3_f32 (is_half = 0) / _f16 would make
+// for this problem on the current device -- the plan the launchers use -- or their refusal.  `run` = tiles a block walks down
+// its tile column (c = 32: the whole column); `blocks` saturates at INT32_MAX.
+extern "C" int ml_gconv3x3_launch_plan(int32_t B, int32_t H, int32_t W, int32_t C, int32_t c, int32_t stride, int32_t Ho,
+                                       int32_t Wo, int32_t is_half, int32_t plan[6]) {
+    ML_REQUIRE(plan, "gconv3x3: null pointer");
+    const bool half = is_half != 0;
+    if (int rc = gconv_check_shape(half, B, H, W, C, c, Ho, Wo, stride)) return rc;
+    const GconvPlan p = gconv_plan(gconv_tile_h(half, c, stride), GCONV_TW, c != 32, B, C, Ho, Wo);
+    plan[0] = p.tile_h, plan[1] = p.tile_w, plan[2] = p.tiles_x, plan[3] = p.tiles_y, plan[4] = p.run;
+    plan[5] = p.blocks > INT32_MAX ? INT32_MAX : (int32_t)p.blocks;
+    return ML_OK;
 }
 
 extern "C" int ml_gconv3x3_f32(const float *in, const float *wgt, const float *bias, float *out, int32_t B, int32_t H,

@@ -138,6 +138,7 @@ SIGNATURES = {
     "ml_deconv2x2_out1x1_f32": (C.c_int, [C.POINTER(DeconvOutProblem), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ml_gconv3x3_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
     "ml_gconv3x3_f16": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
+    "ml_gconv3x3_launch_plan": (C.c_int, [_i32] * 9 + [C.POINTER(C.c_int32)]),
     "ml_maxpool3x3s2_f16": (C.c_int, [_vp, _vp] + [_i32] * 8 + [_vp]),
     "ml_stem7x7s2_pool_f16": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp]),
     "ml_stem7x7s2_pool_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 5 + [_vp]),

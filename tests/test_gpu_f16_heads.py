@@ -14,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import dwconv_cases as DW
 from oracle import masklab as O
 from oracle import tfops as T
 
@@ -204,6 +205,33 @@ def test_dwconv3x3_and_global_mean_half_storage(dil, C, hw):
     m = ops.global_mean(dev(x))
     assert m.dtype == torch.float16 and tuple(m.shape) == (2, 1, 1, C)
     close_half(host(m)[:, 0, 0], x.astype(np.float64).mean((1, 2)))
+
+
+@pytest.mark.parametrize("name", list(DW.CASES))
+def test_dwconv3x3_more_arms_half_storage(name):
+    """tests/dwconv_cases.py on half tensors, twice the channels (8 per lane: the smallest count is 8)"""
+    from masklab_hip import _lib, ops, packing
+    stride, padding, dil, C, hw, act, _ = DW.CASES[name]
+    x, k, b, pre = DW.case(name, 2 * C, half=True)
+    got = ops.dwconv3x3(dev(x), dev(packing.pack_depthwise(k)), None if b is None else dev(b), stride=stride,
+                        padding=padding, dilation=dil, act=_lib.ACT_BY_NAME[act])
+    assert got.dtype == torch.float16 and tuple(got.shape) == pre.shape
+    close_half(host(got), DW.ACT[act](pre))
+
+
+def test_dwconv3x3_into_a_channel_slice_half_storage():
+    """`out=` / `out_coff`: channels [8, 24) of a 40-channel sentinel buffer; the other channels stay untouched"""
+    from masklab_hip import _lib, ops, packing
+    from sentinel_dest import SENT
+    rng = np.random.default_rng(78)
+    x = to_half(rng.normal(size=(2, 9, 7, 16)))
+    k, b = (rng.normal(size=(3, 3, 16, 1)) * 0.3).astype(np.float32), rng.normal(size=16).astype(np.float32)
+    ref = T.relu(T.depthwise_conv2d(x.astype(np.float64), k.astype(np.float64), 2, "same", 1) + b.astype(np.float64))
+    wide = torch.full((2, 5, 4, 40), SENT, device="cuda", dtype=torch.float16)
+    assert ops.dwconv3x3(dev(x), dev(packing.pack_depthwise(k)), dev(b), stride=2, act=_lib.ACT_RELU, out=wide, out_coff=8) is wide
+    got = host(wide)
+    close_half(got[..., 8:24], ref)
+    assert (got[..., :8] == SENT).all() and (got[..., 24:] == SENT).all()
 
 
 def test_roi_crop_half_storage():

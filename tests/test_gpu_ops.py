@@ -7,6 +7,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import dwconv_cases as DW
 from oracle import masklab as O
 from oracle import tfops as T
 
@@ -436,6 +437,36 @@ def test_dwconv3x3(stride, padding, dil, C, hw):
     got = host(ops.dwconv3x3(dev(x), dev(packing.pack_depthwise(k)), dev(b), stride=stride, padding=padding,
                              dilation=dil, act=_lib.ACT_RELU6))
     np.testing.assert_allclose(got, ref, atol=1e-5)
+
+
+# what the table above leaves out: tests/dwconv_cases.py (above, ReLU6 meets a pre-activation of standard deviation 1.35 --
+# about 0.3 elements per case beyond 6 -- and always a bias)
+@pytest.mark.parametrize("name", list(DW.CASES))
+def test_dwconv3x3_more_arms(name):
+    from masklab_hip import _lib, ops, packing
+    stride, padding, dil, C, hw, act, _ = DW.CASES[name]
+    x, k, b, pre = DW.case(name, C)
+    ref = DW.ACT[act](pre)
+    got = host(ops.dwconv3x3(dev(x), dev(packing.pack_depthwise(k)), None if b is None else dev(b), stride=stride,
+                             padding=padding, dilation=dil, act=_lib.ACT_BY_NAME[act]))
+    assert got.shape == ref.shape
+    np.testing.assert_allclose(got, ref, rtol=0, atol=1e-5)
+
+
+def test_dwconv3x3_into_a_channel_slice():
+    """`out=` / `out_coff`: channels [8, 24) of a 40-channel sentinel buffer; the other channels stay untouched"""
+    from masklab_hip import _lib, ops, packing
+    from sentinel_dest import SENT
+    rng = np.random.default_rng(77)
+    x = rng.normal(size=(2, 9, 7, 16)).astype(np.float32)
+    k, b = (rng.normal(size=(3, 3, 16, 1)) * 0.3).astype(np.float32), rng.normal(size=16).astype(np.float32)
+    ref = T.relu(T.depthwise_conv2d(x.astype(np.float64), k, 2, "same", 1) + b)
+    wide = torch.full((2, 5, 4, 40), SENT, device="cuda")
+    ret = ops.dwconv3x3(dev(x), dev(packing.pack_depthwise(k)), dev(b), stride=2, act=_lib.ACT_RELU, out=wide, out_coff=8)
+    assert ret is wide
+    got = host(wide)
+    np.testing.assert_allclose(got[..., 8:24], ref, rtol=0, atol=1e-5)
+    assert (got[..., :8] == SENT).all() and (got[..., 24:] == SENT).all()
 
 
 def test_maxpool3x3s2():
