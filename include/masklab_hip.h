@@ -72,7 +72,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_roi_grad_level, ml_roi_crop_resize_grad_f32,
                                             ml_resize_bilinear_ac_grad_f32 / _grad_workspace_bytes,
                                             ml_global_mean_grad_f32;
-                                            (additive, same version) ml_gconv3x3_launch_plan */
+                                            (additive, same version) ml_gconv3x3_launch_plan;
+                                            (additive, same version) ml_conv2d_wgrad_desc, ml_conv2d_wgrad_multi_f32 /
+                                            _wgrad_plan, ml_conv2d_grad_gather_dy_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -214,6 +216,46 @@ int ml_conv2d_wino_narrow(const ml_conv2d_desc *d);
 /* Smallest launch, in 128 x 128 tiles over all its problems, that ml_conv2d_multi_f32 neither narrows to 128 x 64 / 128 x 32
  * tiles nor cuts along K on the current device: the size from which ml_conv2d_desc.gn_partials may be set. */
 int64_t ml_conv2d_gn_min_launch_tiles(void);
+
+/* ---------------------------------------------------------------- dense convolution, backward (fp32 only)
+ * Weight and bias gradient of a dense ml_conv2d_desc problem (csrc/conv_grad.hip):
+ *   dkernel[kh,kw,ci,co] = sum over (b,oy,ox) of x[b, oy*stride + kh*dil - pad_t, ox*stride + kw*dil - pad_l, ci] * dy[b,oy,ox,co]
+ *   dbias[co]            = sum over (b,oy,ox) of dy[b,oy,ox,co]
+ * (samples outside the image contribute zero), on v_mfma_f32_32x32x2_f32: per tap a GEMM with M = cin, N = cout and
+ * K = B*Ho*Wo pixels.  `conv` is the FORWARD problem: `in` = x with in_cstride / in_coff, span = cin (% 4 == 0; any
+ * multiple), KH x KW up to 5 x 5, stride 1 or 2, any dilation, pad_t / pad_l, cout >= 1; `out` with out_cstride / out_coff /
+ * out_bstride is the dy VIEW and is only read (rows that are not 16-byte aligned -- the towers' [B, A, d] predictions -- are
+ * read with dword loads).  wgt, bias, residual, act, n_pad, span_pad, tile, live and gn_partials are ignored.  Refused by
+ * name: half tensors (math = ML_MATH_F16S or out_f16), grouped / depthwise (group_cin_step), row-span (cpp_shift != 30) and
+ * shuffle2x2 problems, and a workspace that is too small.
+ * dkernel: contiguous [KH,KW,cin,cout], the Keras layout; dbias: [cout] or NULL (skipped).  add_kernel / add_bias: NULL, or
+ * like the output: output = add + gradient with one fp32 addition; an output may be its add itself (in place).
+ * No float atomics: the pixels are cut into slices (ml_conv2d_wgrad_plan: 1 / 128 of the problem's pixels rounded up to a
+ * multiple of 32, at least 512 and at most 1024; longer only where a problem's partials would exceed 96 MiB) -- a function
+ * of the problem's geometry alone.  A block sums a slice in fp32 in pixel order; the finish kernel adds an element's partials in ascending
+ * slice order in fp64 and rounds once.  Every element is written (exact zeros for a tap that only meets padding); the same
+ * bits run to run, alone or inside a multi launch, and whatever outputs and workspace held.
+ * workspace: the conv workspace, 256-byte aligned, >= the sum of the problems' ml_conv2d_wgrad_plan bytes (a set that
+ * needs more than ml_conv2d_workspace_bytes() goes in several launches: the results are the same bits); nothing in it needs
+ * initialising. */
+#define ML_CONV_WGRAD_MAX_PROBLEMS 8
+typedef struct ml_conv2d_wgrad_desc {
+    ml_conv2d_desc conv;            /* the forward problem: in = x, out = the dy view                */
+    float *dkernel;                 /* [KH,KW,cin,cout]                                              */
+    float *dbias;                   /* [cout] or NULL                                                */
+    const float *add_kernel;        /* NULL or like dkernel                                          */
+    const float *add_bias;          /* NULL or like dbias                                            */
+} ml_conv2d_wgrad_desc;
+int ml_conv2d_wgrad_multi_f32(const ml_conv2d_wgrad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
+                              void *stream);
+/* Host only: the slices of one problem (count, pixels per slice; the last slice may be shorter) and the bytes of its
+ * partials.  Checks the descriptor's geometry as the launch does (tensor pointers may be NULL). */
+int ml_conv2d_wgrad_plan(const ml_conv2d_wgrad_desc *desc, int32_t *slices, int32_t *slice_pixels, int64_t *workspace_bytes);
+/* A dy view [B, HW pixels, cout] (channel stride dy_cstride, dy_bstride floats between images, 0 = dense) -> contiguous
+ * [B, HW, roundup4(cout)] with zeros in the pad channels: what the data gradient -- the forward kernels on the transposed
+ * weights (packing.pack_dense_transposed) -- reads.  Every element of `out` is written. */
+int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t B, int32_t HW, int32_t cout, int32_t dy_cstride,
+                                 int64_t dy_bstride, void *stream);
 
 /* ResNeXt grouped 3x3 (reference engine/backbone/ResNext.py:212-219: DepthwiseConv2D(depth_multiplier=c)
  * + SplitGroups/ReduceGroups/MergeGroups), c = channels per group in {4,8,16}, C % 64 == 0, on

@@ -1,0 +1,392 @@
+// Backward of the dense convolutions, fp32: the weight and bias gradient (this file's GEMM kernel) and the small gather
+// that brings a `dy` view into the form the data gradient reads.  The data gradient itself is the FORWARD kernels on
+// transposed weights (masklab_hip/packing.py pack_dense_transposed, ops.conv2d_dgrad): nothing of it lives here.
+//
+//   dW[kh,kw,ci,co] = sum over (b,oy,ox) of x[b, oy*s + kh*d - pad_t, ox*s + kw*d - pad_l, ci] * dy[b,oy,ox,co]
+//   db[co]          = sum over (b,oy,ox) of dy[b,oy,ox,co]
+//
+// Per tap a GEMM with M = cin, N = cout and K = the B*Ho*Wo output pixels, on v_mfma_f32_32x32x2_f32 (exact fp32 products,
+// a k-ordered fp32 fma chain).  Both operands are NHWC, so a [pixel][channel] LDS image feeds A (x: row = ci) and B (dy:
+// column = co) with consecutive-dword reads: lane l takes (channel l % 32, pixel l / 32) of a 2-pixel step, no transpose.
+//
+// Work units.  A UNIT is (32-channel cin tile, tap); a block holds up to WG_UNITS = 9 units as accumulators (the nine taps of
+// one cin tile of a 3x3 conv; the cin tiles of a 1x1 conv; three groups for 5x5) for a 128-wide cout tile -- 4 waves x 32
+// columns -- over ONE slice of the pixels.  Per 16-pixel chunk the dy tile is staged once and shared by the units; x is
+// staged per unit (the shifted pixels of its tap), zeros where a tap leaves the image; two staging buffers, so the next
+// chunk's requests fly under this chunk's 72 MFMAs per wave.  x and an aligned dy arrive by
+// LDS-DMA (gfx_mem.h); a dy view whose rows are not 16-byte aligned (the towers' 75- and 60-wide output convs write into
+// [B, A, d] predictions) is read with dword loads.
+//
+// No float atomics.  K is cut into slices of about 1 / 128 of the problem's pixels, at least WG_SLICE_MIN = 512 and at most
+// WG_SLICE_MAX = 1024 pixels (longer only where the partials of a problem would exceed WG_SHARE bytes of the conv workspace):
+// a function of the problem's geometry alone, never of the launch, the other problems or the device.  A block accumulates
+// its slice in fp32 in pixel order and writes a partial; the finish kernel adds the partials of an element in ascending
+// slice order in fp64, rounds once, adds `add` with one fp32 addition and writes dkernel [kh,kw,cin,cout] (the Keras
+// layout) and dbias.  The column sums of dy ride in the blocks of unit group 0 (fp64 over the
+// slice, from the staged tile: dy is read once).  Every element is written; a tap that only meets padding gets exact zeros.
+#include "gfx_mem.h"
+
+namespace {
+
+constexpr int WG_TPB = 256;
+constexpr int WG_BM = 32;            // cin per unit
+constexpr int WG_BN = 128;           // cout per block: 4 waves x 32
+constexpr int WG_KP = 16;            // pixels per staged chunk
+constexpr int WG_ROUND = 32;         // slice lengths are multiples of this (and of WG_KP)
+constexpr int WG_UNITS = 9;          // (cin tile, tap) units a block accumulates
+constexpr int WG_SLICE_MIN = 512;    // pixels per slice (multiples of WG_KP): P / 128 clamped to [MIN, MAX] -- the 8 x 128 x 128
+constexpr int WG_SLICE_MAX = 1024;   // map of a tower is 128 slices x 4 unit groups = two blocks on each of 256 CUs
+constexpr long long WG_SHARE = 96ll << 20;   // bytes of partials one problem may take: beyond, its slices grow
+constexpr int WG_OOB = (int)0x80000000;      // a buffer offset beyond every extent (< 2 GiB): the lane reads zeros
+
+struct WgProblem {
+    const float *x, *dy;             // dy: the view's first element (channel offset applied)
+    float *part, *bpart;             // [slices][T*cin*cout], [slices][cout]
+    const float *add_k, *add_b;
+    float *dk, *db;
+    long long dy_bs;                 // floats between images of dy
+    int H, W, Wo, HoWo, P;           // P = B*Ho*Wo
+    int in_cs, in_co, cin, cout, dy_cs;
+    int KW, T, stride, dil, pad_t, pad_l;
+    int x_bytes, dy_bytes;
+    int slices, sp;
+    int NT, units, ugroups;          // cout tiles, (cin tile, tap) units, groups of WG_UNITS units
+    int dy_vec;                      // 1: 16-byte rows (LDS-DMA), 0: dword loads
+    int first_block, first_fblock;   // of the partial / finish launch
+    int tcc;                         // T*cin*cout
+};
+struct WgArgs {
+    WgProblem p[ML_CONV_WGRAD_MAX_PROBLEMS];
+    int n;
+};
+
+__global__ void __launch_bounds__(WG_TPB, 2) conv_wgrad_partial_kernel(const WgArgs A) {
+    // two staging buffers: chunk i + 1 is on its way into one while the MFMAs read chunk i from the other
+    __shared__ __align__(16) float sx[2][WG_UNITS][WG_KP * WG_BM];
+    __shared__ __align__(16) float sy[2][WG_KP * WG_BN];
+    int pi = 0;
+    while (pi + 1 < A.n && (int)blockIdx.x >= A.p[pi + 1].first_block) ++pi;
+    const WgProblem &p = A.p[pi];
+    int id = blockIdx.x - p.first_block;
+    const int nt = id % p.NT; id /= p.NT;
+    const int ug = id % p.ugroups;
+    const int slice = id / p.ugroups;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int H = p.H, W = p.W, Wo = p.Wo, HoWo = p.HoWo, cin = p.cin, cout = p.cout, T = p.T;
+    const int in_cs = p.in_cs, in_co = p.in_co, dy_cs = p.dy_cs, stride = p.stride, pad_t = p.pad_t, pad_l = p.pad_l;
+    const long long dy_bs = p.dy_bs;
+    const float *dyp = p.dy;
+    const bool dy_vec = p.dy_vec != 0;
+    const int n0 = nt * WG_BN;
+    const int wn0 = n0 + wave * 32;                          // this wave's first column
+    const int nu = min(WG_UNITS, p.units - ug * WG_UNITS);   // units of this block
+    const int q_begin = slice * p.sp, q_end = min(q_begin + p.sp, p.P);
+    const bool do_bias = ug == 0;
+
+    // per unit: its tap's pixel offset (dy, dx) and its cin tile, wave-uniform (past the problem's last unit: that unit again)
+    int u_dy[WG_UNITS], u_dx[WG_UNITS], u_c[WG_UNITS];
+#pragma unroll
+    for (int u = 0; u < WG_UNITS; ++u) {
+        const int U = min(ug * WG_UNITS + u, p.units - 1);
+        const int mt = U / T, tap = U - mt * T;
+        const int kh = tap / p.KW, kw = tap - kh * p.KW;
+        u_dy[u] = kh * p.dil; u_dx[u] = kw * p.dil; u_c[u] = mt * WG_BM;
+    }
+
+    const __amdgpu_buffer_rsrc_t rsrc_x = rsrc_bytes(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_y = rsrc_bytes(p.dy, p.dy_bytes);
+    // x staging: a unit's tile is 16 pixels x 32 channels = two 1 KB DMAs (8 pixels each).  Waves 0 / 1 bring the two halves
+    // of the even units, waves 2 / 3 those of the odd units; a lane's pixel row and channels are the same for every unit.
+    const int xhalf = wave & 1, xpar = wave >> 1;
+    const int xrow = xhalf * 8 + (lane >> 3), xc4 = (lane & 7) * 4;
+    constexpr int YS = WG_KP * WG_BN / WG_TPB;               // floats of a dy tile per thread on the dword path
+    float yreg[YS];
+
+    // requests chunk `base` into buffer `buf`; on the dword path the dy tile comes into registers (commit() stores it)
+    auto issue = [&](int buf, int base) {
+        {
+            const int q = base + xrow;
+            const bool valid = q < q_end;
+            const int b = q / HoWo, rem = q - b * HoWo;
+            const int oy = rem / Wo, ox = rem - oy * Wo;
+            const int iy0 = oy * stride - pad_t, ix0 = ox * stride - pad_l;
+            const long long pix0 = ((long long)b * H + iy0) * W + ix0;
+#pragma unroll
+            for (int u = 0; u < WG_UNITS; ++u) {
+                if ((u & 1) != xpar) continue;               // wave-uniform
+                const int iy = iy0 + u_dy[u], ix = ix0 + u_dx[u];
+                const int c = u_c[u] + xc4;
+                const bool ok = valid && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W && c < cin;
+                const long long off = (pix0 + (long long)u_dy[u] * W + u_dx[u]) * in_cs + in_co + c;
+                lds_dma16(rsrc_x, (char *)(&sx[buf][u][0] + xhalf * 8 * WG_BM), ok ? (int)(off * 4) : WG_OOB, 0);
+            }
+        }
+        // dy: [16 pixels][128 columns], zeros past the slice and past cout
+        if (dy_vec) {
+#pragma unroll
+            for (int j = 0; j < WG_KP / 8; ++j) {
+                const int row = j * 8 + wave * 2;
+                const int q = base + row + h;
+                const int b = q / HoWo, rem = q - b * HoWo;
+                const int c = n0 + r * 4;
+                const bool ok = q < q_end && c < cout;
+                const long long off = (long long)b * dy_bs + (long long)rem * dy_cs + c;
+                lds_dma16(rsrc_y, (char *)(&sy[buf][0] + row * WG_BN), ok ? (int)(off * 4) : WG_OOB, 0);
+            }
+        } else {
+            const int c = n0 + (tid & 127);
+#pragma unroll
+            for (int j = 0; j < YS; ++j) {
+                const int q = base + j * 2 + (tid >> 7);
+                const int b = q / HoWo, rem = q - b * HoWo;
+                float v = 0.f;
+                if (q < q_end && c < cout) v = dyp[(long long)b * dy_bs + (long long)rem * dy_cs + c];
+                yreg[j] = v;
+            }
+        }
+    };
+    auto commit = [&](int buf) {
+        if (!dy_vec) {
+#pragma unroll
+            for (int j = 0; j < YS; ++j) sy[buf][(j * 2 + (tid >> 7)) * WG_BN + (tid & 127)] = yreg[j];
+        }
+    };
+
+    f32x16 acc[WG_UNITS];
+#pragma unroll
+    for (int u = 0; u < WG_UNITS; ++u)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[u][e] = 0.f;
+    double bacc = 0.0;
+
+    issue(0, q_begin);
+    commit(0);
+    int buf = 0;
+    for (int base = q_begin; base < q_end; base += WG_KP) {
+        // this chunk has landed (every wave waits for its own requests, then for the others), and every wave is past its
+        // reads of the other buffer
+        wait_vmcnt<0>();
+        __syncthreads();
+        const bool more = base + WG_KP < q_end;
+        if (more) issue(buf ^ 1, base + WG_KP);
+        const float *cy = &sy[buf][0];
+        if (do_bias && tid < WG_BN) {
+#pragma unroll
+            for (int k = 0; k < WG_KP; ++k) bacc += (double)cy[k * WG_BN + tid];
+        }
+        if (wn0 < cout) {                                    // wave-uniform: a 32-column quarter past cout runs no MFMA
+            // No test per unit: it would put every LDS read behind the MFMA before it, and each MFMA behind its read's
+            // latency.  The units a last, partial group lacks repeat the problem's last unit; their sums are not stored.
+#pragma unroll
+            for (int ks = 0; ks < WG_KP / 2; ++ks) {
+                const int k = 2 * ks + h;
+                const float bv = cy[k * WG_BN + wave * 32 + r];
+                static_for<0, WG_UNITS>([&](auto uc) {
+                    constexpr int u = decltype(uc)::value;
+                    acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(sx[buf][u][k * WG_BM + r], bv, acc[u], 0, 0, 0);
+                });
+            }
+        }
+        if (more) commit(buf ^ 1);
+        buf ^= 1;
+    }
+
+    // ---- the partial.  C/D layout: col = lane & 31 (cout), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (cin)
+    float *part = p.part + (long long)slice * p.tcc;
+    const int co = wn0 + r;
+    if (co < cout) {
+        static_for<0, WG_UNITS>([&](auto uc) {
+            constexpr int u = decltype(uc)::value;
+            if (u < nu) {
+                const int U = ug * WG_UNITS + u;
+                const int mt = U / T, tap = U - mt * T;
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int ci = mt * WG_BM + (e & 3) + 8 * (e >> 2) + 4 * h;
+                    if (ci < cin) part[((long long)tap * cin + ci) * cout + co] = acc[u][e];
+                }
+            }
+        });
+    }
+    if (do_bias && tid < WG_BN && n0 + tid < cout) p.bpart[(long long)slice * cout + n0 + tid] = (float)bacc;
+}
+
+// element i of a problem: i < tcc -> dkernel[i], else dbias[i - tcc]; partials added in ascending slice order in fp64
+__global__ void __launch_bounds__(WG_TPB) conv_wgrad_finish_kernel(const WgArgs A) {
+    int pi = 0;
+    while (pi + 1 < A.n && (int)blockIdx.x >= A.p[pi + 1].first_fblock) ++pi;
+    const WgProblem &p = A.p[pi];
+    const int i = (blockIdx.x - p.first_fblock) * WG_TPB + threadIdx.x;
+    const int total = p.tcc + (p.db ? p.cout : 0);
+    if (i >= total) return;
+    const bool bias = i >= p.tcc;
+    const int j = bias ? i - p.tcc : i;
+    const float *src = bias ? p.bpart : p.part;
+    const long long pitch = bias ? p.cout : p.tcc;
+    double t = 0.0;
+    for (int s = 0; s < p.slices; ++s) t += (double)src[(long long)s * pitch + j];
+    float v = (float)t;
+    const float *add = bias ? p.add_b : p.add_k;
+    if (add) v = add[j] + v;
+    (bias ? p.db : p.dk)[j] = v;
+}
+
+__global__ void __launch_bounds__(WG_TPB)
+gather_dy_kernel(const float *__restrict__ dy, float *__restrict__ out, int HW, int cout, int cp, int dy_cs, long long dy_bs,
+                 long long total) {
+    const long long i = (long long)blockIdx.x * WG_TPB + threadIdx.x;
+    if (i >= total) return;
+    const int c = (int)(i % cp);
+    const long long pix = i / cp;
+    const int b = (int)(pix / HW), rem = (int)(pix - (long long)b * HW);
+    out[i] = c < cout ? dy[(long long)b * dy_bs + (long long)rem * dy_cs + c] : 0.f;
+}
+
+struct WgPlan {
+    int slices, sp, T, MT, NT, units, ugroups;
+    long long tcc, bytes, dy_bs, P;
+};
+
+inline long long align256(long long v) { return (v + 255) & ~255ll; }
+
+// the checks of one problem and its slices: geometry only
+int wg_plan(const ml_conv2d_desc &d, WgPlan &pl) {
+    const char *what = "conv2d_wgrad";
+    ML_REQUIRE(d.math != ML_MATH_F16S && !d.out_f16, "%s: half tensors are refused (the backward is float32 only)", what);
+    ML_REQUIRE(!d.group_cin_step, "%s: grouped / depthwise problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(d.cpp_shift == 30, "%s: row-span (image input) problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(!d.shuffle2x2, "%s: shuffle2x2 (Conv2DTranspose) problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Ho > 0 && d.Wo > 0, "%s: bad dims", what);
+    ML_REQUIRE(d.KH >= 1 && d.KH <= 5 && d.KW >= 1 && d.KW <= 5, "%s: kernel %d x %d: at most 5 x 5", what, d.KH, d.KW);
+    ML_REQUIRE(d.stride == 1 || d.stride == 2, "%s: stride %d: 1 or 2", what, d.stride);
+    ML_REQUIRE(d.dil >= 1, "%s: bad dilation", what);
+    ML_REQUIRE(d.span > 0 && d.span % 4 == 0 && d.in_cstride % 4 == 0 && d.in_coff % 4 == 0 && d.in_coff >= 0 &&
+               d.in_coff + d.span <= d.in_cstride, "%s: cin, the input's channel stride and offset must be multiples of 4, "
+               "the slice inside the buffer", what);
+    ML_REQUIRE(d.cout >= 1 && d.out_coff >= 0 && d.out_coff + d.cout <= d.out_cstride, "%s: dy: cout channels from its offset "
+               "must fit its channel stride", what);
+    const long long HoWo = (long long)d.Ho * d.Wo;
+    ML_REQUIRE(d.out_bstride == 0 || d.out_bstride >= HoWo * d.out_cstride, "%s: dy: images overlap", what);
+    pl.dy_bs = d.out_bstride ? d.out_bstride : HoWo * d.out_cstride;
+    pl.P = (long long)d.B * HoWo;
+    ML_REQUIRE(pl.P < (1ll << 31) - WG_SLICE_MAX, "%s: too many pixels", what);
+    ML_REQUIRE((long long)d.B * d.H * d.W * d.in_cstride * 4 < (1ll << 31), "%s: x must be smaller than 2 GiB", what);
+    ML_REQUIRE((((long long)d.B - 1) * pl.dy_bs + HoWo * d.out_cstride) * 4 < (1ll << 31), "%s: dy must span less than 2 GiB", what);
+    pl.T = d.KH * d.KW;
+    pl.tcc = (long long)pl.T * d.span * d.cout;
+    ML_REQUIRE(pl.tcc + d.cout < (1ll << 31), "%s: too many weights", what);
+    pl.MT = (d.span + WG_BM - 1) / WG_BM;
+    pl.NT = (d.cout + WG_BN - 1) / WG_BN;
+    pl.units = pl.MT * pl.T;
+    pl.ugroups = (pl.units + WG_UNITS - 1) / WG_UNITS;
+    // a problem's partials may take WG_SHARE bytes of the conv workspace (the five levels of a tower depth take 170 MiB)
+    const long long per_slice = (pl.tcc + d.cout) * 4;
+    const long long max_slices = (WG_SHARE - 512) / per_slice;
+    ML_REQUIRE(max_slices >= 1, "%s: one partial (%lld bytes) exceeds a problem's share of the conv workspace", what, per_slice);
+    long long sp = ((pl.P + 127) / 128 + WG_ROUND - 1) / WG_ROUND * WG_ROUND;
+    sp = sp < WG_SLICE_MIN ? WG_SLICE_MIN : (sp > WG_SLICE_MAX ? WG_SLICE_MAX : sp);
+    if ((pl.P + sp - 1) / sp > max_slices) sp = ((pl.P + max_slices - 1) / max_slices + WG_ROUND - 1) / WG_ROUND * WG_ROUND;
+    pl.sp = (int)sp;
+    pl.slices = (int)((pl.P + sp - 1) / sp);
+    pl.bytes = align256(pl.slices * pl.tcc * 4) + align256((long long)pl.slices * d.cout * 4);
+    return ML_OK;
+}
+
+bool wg_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
+}
+
+}  // namespace
+
+extern "C" int ml_conv2d_wgrad_plan(const ml_conv2d_wgrad_desc *desc, int32_t *slices, int32_t *slice_pixels,
+                                    int64_t *workspace_bytes) {
+    ML_REQUIRE(desc, "conv2d_wgrad_plan: null descriptor");
+    WgPlan pl;
+    const int rc = wg_plan(desc->conv, pl);
+    if (rc != ML_OK) return rc;
+    if (slices) *slices = pl.slices;
+    if (slice_pixels) *slice_pixels = pl.sp;
+    if (workspace_bytes) *workspace_bytes = pl.bytes;
+    return ML_OK;
+}
+
+extern "C" int ml_conv2d_wgrad_multi_f32(const ml_conv2d_wgrad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
+                                         void *stream) {
+    const char *what = "conv2d_wgrad";
+    ML_REQUIRE(descs && n >= 1 && n <= ML_CONV_WGRAD_MAX_PROBLEMS, "%s: need 1..%d problems", what, ML_CONV_WGRAD_MAX_PROBLEMS);
+    ML_REQUIRE(workspace && (((uintptr_t)workspace) & 255) == 0, "%s: needs a 256-byte aligned workspace", what);
+    WgArgs A;
+    long long used = 0, blocks = 0, fblocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const ml_conv2d_wgrad_desc &g = descs[i];
+        const ml_conv2d_desc &d = g.conv;
+        WgPlan pl;
+        const int rc = wg_plan(d, pl);
+        if (rc != ML_OK) return rc;
+        ML_REQUIRE(d.in && d.out && g.dkernel, "%s: problem %d: null pointer", what, i);
+        ML_REQUIRE(ml_aligned16(d.in), "%s: problem %d: x must be 16-byte aligned", what, i);
+        ML_REQUIRE((((uintptr_t)d.out | (uintptr_t)g.dkernel | (uintptr_t)g.dbias | (uintptr_t)g.add_kernel |
+                     (uintptr_t)g.add_bias) & 3) == 0, "%s: problem %d: 4-byte alignment", what, i);
+        const long long x_bytes = (long long)d.B * d.H * d.W * d.in_cstride * 4;
+        const long long dy_bytes = (((long long)d.B - 1) * pl.dy_bs + (long long)d.Ho * d.Wo * d.out_cstride) * 4;
+        const long long dk_bytes = pl.tcc * 4, db_bytes = (long long)d.cout * 4;
+        ML_REQUIRE(!wg_overlap(g.dkernel, dk_bytes, d.in, x_bytes) && !wg_overlap(g.dkernel, dk_bytes, d.out, dy_bytes),
+                   "%s: problem %d: dkernel may not overlap x or dy", what, i);
+        ML_REQUIRE(!g.add_kernel || g.add_kernel == g.dkernel || !wg_overlap(g.dkernel, dk_bytes, g.add_kernel, dk_bytes),
+                   "%s: problem %d: dkernel may be add itself, not a shifted view of it", what, i);
+        if (g.dbias) {
+            ML_REQUIRE(!wg_overlap(g.dbias, db_bytes, d.in, x_bytes) && !wg_overlap(g.dbias, db_bytes, d.out, dy_bytes) &&
+                       !wg_overlap(g.dbias, db_bytes, g.dkernel, dk_bytes), "%s: problem %d: dbias may not overlap x, dy or dkernel",
+                       what, i);
+            ML_REQUIRE(!g.add_bias || g.add_bias == g.dbias || !wg_overlap(g.dbias, db_bytes, g.add_bias, db_bytes),
+                       "%s: problem %d: dbias may be add itself, not a shifted view of it", what, i);
+        }
+        ML_REQUIRE(used + pl.bytes <= workspace_bytes, "%s: the workspace is too small: problem %d needs %lld bytes at offset %lld "
+                   "of %lld", what, i, pl.bytes, used, (long long)workspace_bytes);
+        WgProblem &p = A.p[i];
+        p.x = d.in; p.dy = d.out + d.out_coff;
+        p.part = reinterpret_cast<float *>((char *)workspace + used);
+        p.bpart = reinterpret_cast<float *>((char *)workspace + used + align256(pl.slices * pl.tcc * 4));
+        used += pl.bytes;
+        p.add_k = g.add_kernel; p.add_b = g.dbias ? g.add_bias : nullptr; p.dk = g.dkernel; p.db = g.dbias;
+        p.dy_bs = pl.dy_bs;
+        p.H = d.H; p.W = d.W; p.Wo = d.Wo; p.HoWo = d.Ho * d.Wo; p.P = (int)pl.P;
+        p.in_cs = d.in_cstride; p.in_co = d.in_coff; p.cin = d.span; p.cout = d.cout; p.dy_cs = d.out_cstride;
+        p.KW = d.KW; p.T = pl.T; p.stride = d.stride; p.dil = d.dil; p.pad_t = d.pad_t; p.pad_l = d.pad_l;
+        p.x_bytes = (int)x_bytes; p.dy_bytes = (int)(dy_bytes - (long long)d.out_coff * 4);
+        p.slices = pl.slices; p.sp = pl.sp; p.NT = pl.NT; p.units = pl.units; p.ugroups = pl.ugroups;
+        p.dy_vec = d.cout % 4 == 0 && d.out_cstride % 4 == 0 && d.out_coff % 4 == 0 && pl.dy_bs % 4 == 0 && ml_aligned16(d.out);
+        p.tcc = (int)pl.tcc;
+        p.first_block = (int)blocks; p.first_fblock = (int)fblocks;
+        blocks += (long long)pl.slices * pl.ugroups * pl.NT;
+        fblocks += (pl.tcc + d.cout + WG_TPB - 1) / WG_TPB;
+        ML_REQUIRE(blocks < (1ll << 31) && fblocks < (1ll << 31), "%s: grid too large", what);
+    }
+    A.n = n;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(conv_wgrad_partial_kernel, dim3((unsigned)blocks), dim3(WG_TPB), 0, s, A);
+    hipLaunchKernelGGL(conv_wgrad_finish_kernel, dim3((unsigned)fblocks), dim3(WG_TPB), 0, s, A);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+extern "C" int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t B, int32_t HW, int32_t cout, int32_t dy_cstride,
+                                            int64_t dy_bstride, void *stream) {
+    const char *what = "conv2d_grad_gather_dy";
+    ML_REQUIRE(dy && out && B > 0 && HW > 0 && cout > 0, "%s: bad arguments", what);
+    ML_REQUIRE(dy_cstride >= cout && (dy_bstride == 0 || dy_bstride >= (long long)HW * dy_cstride), "%s: bad view", what);
+    const int cp = (cout + 3) / 4 * 4;
+    const long long bs = dy_bstride ? dy_bstride : (long long)HW * dy_cstride;
+    const long long total = (long long)B * HW * cp;
+    ML_REQUIRE((long long)B * HW < (1ll << 31) && total < (1ll << 31) * WG_TPB, "%s: too many pixels", what);
+    ML_REQUIRE(!wg_overlap(out, total * 4, dy, (((long long)B - 1) * bs + (long long)HW * dy_cstride) * 4),
+               "%s: out may not overlap dy", what);
+    hipLaunchKernelGGL(gather_dy_kernel, dim3((unsigned)((total + WG_TPB - 1) / WG_TPB)), dim3(WG_TPB), 0, (hipStream_t)stream, dy,
+                       out, HW, cout, cp, dy_cstride, bs, total);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}

@@ -40,6 +40,12 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvWgradDesc(C.Structure):
+    """Mirror of `ml_conv2d_wgrad_desc` (include/masklab_hip.h)."""
+    _fields_ = [("conv", ConvDesc), ("dkernel", C.c_void_p), ("dbias", C.c_void_p), ("add_kernel", C.c_void_p),
+                ("add_bias", C.c_void_p)]
+
+
 class GnDesc(C.Structure):
     """Mirror of `ml_gn_desc` (include/masklab_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -114,6 +120,7 @@ class OptScalars(C.Structure):
 
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
+CONV_WGRAD_MAX_PROBLEMS = 8                                          # ML_CONV_WGRAD_MAX_PROBLEMS
 SE_MAX_PROBLEMS = 8
 RESAMPLE_MAX_LEVELS = 8                                             # ML_RESAMPLE_MAX_LEVELS
 DECONV_OUT_MAX_PROBLEMS = 4
@@ -135,6 +142,9 @@ SIGNATURES = {
     "ml_conv2d_gn_min_launch_tiles": (_i64, []),
     "ml_conv2d_workspace_bytes": (_i64, []),
     "ml_conv2d_multi_f32": (C.c_int, [C.POINTER(ConvDesc), _i32, _vp, _i64, _vp]),
+    "ml_conv2d_wgrad_multi_f32": (C.c_int, [C.POINTER(ConvWgradDesc), _i32, _vp, _i64, _vp]),
+    "ml_conv2d_wgrad_plan": (C.c_int, [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ml_conv2d_grad_gather_dy_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
     "ml_deconv2x2_out1x1_f32": (C.c_int, [C.POINTER(DeconvOutProblem), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ml_gconv3x3_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
     "ml_gconv3x3_f16": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),

@@ -245,6 +245,38 @@ class Conv2D(Layer):
                           dilation=self.dilation_rate[0], act=_lib.ACT_BY_NAME[self.activation],
                           residual=residual, out=out, out_coff=out_coff, out_dtype=out_dtype, gn_partials=gn_partials)
 
+    def _check_backward(self):
+        if type(self) is not Conv2D:
+            raise NotImplementedError(f"{type(self).__name__}.backward ('{self.name}') is not built: dense Conv2D layers only")
+        if self.fold_bn:
+            raise NotImplementedError(f"Conv2D.backward ('{self.name}'): a layer with fold_bn (an inference BatchNormalization "
+                                      f"folded into its weights) has no backward")
+        if self.image_input:
+            raise NotImplementedError(f"Conv2D.backward ('{self.name}'): a layer with image_input (the row-span stem) has no "
+                                      f"backward")
+        if self.dev is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+
+    def _grad_args(self):
+        return dict(dc=self.dev, stride=self.strides[0], padding=self.padding, dilation=self.dilation_rate[0])
+
+    def backward(self, x, dy, need_dx=True, dy_view=None, add=None):
+        """The layer's backward (ops.conv2d_wgrad / ops.conv2d_dgrad), float32 only.
+        x: what the layer was called on.  dy: the gradient at the layer's PRE-activation output (or dy_view, the forward's
+        out_view, with dy=None): the activation's own derivative is the caller's -- a ReLU's mask comes from
+        GroupNormalization.backward(input_relu=True) on the layer above, a sigmoid's from
+        loss_and_gradients(wrt="pre_activation").  add: dx = add + gradient.
+        -> (dx [B,H,W,cin] or None unless need_dx, {"kernel": ..., "bias": ...} with the weights the layer has).  Stride 2
+        has no dx (NotImplementedError); its weight gradient exists."""
+        self._check_backward()
+        args = self._grad_args()
+        dk, db = ops.conv2d_wgrad(x, dy, dy_view=dy_view, want_bias=self.use_bias, **args)
+        grads = {"kernel": dk}
+        if self.use_bias:
+            grads["bias"] = db
+        dx = ops.conv2d_dgrad(dy, in_hw=(x.shape[1], x.shape[2]), dy_view=dy_view, add=add, **args) if need_dx else None
+        return dx, grads
+
     def get_config(self):
         c = super().get_config()
         c.update(filters=self.filters, kernel_size=self.kernel_size, strides=self.strides, padding=self.padding,
@@ -408,6 +440,9 @@ class DepthwiseConv2D(Layer):
         return ops.dwconv3x3(x, self.wgt, self.bias, stride=self.strides[0], padding=self.padding,
                              dilation=self.dilation_rate[0], act=_lib.ACT_BY_NAME[self.activation])
 
+    def backward(self, *args, **kwargs):
+        raise NotImplementedError(f"DepthwiseConv2D.backward ('{self.name}') is not built: dense Conv2D layers only")
+
 
 class Conv2DTranspose(Layer):
     """Conv2DTranspose(filters,(2,2),(2,2),'same') = 1x1 MFMA GEMM (N=4*filters) + pixel shuffle."""
@@ -440,6 +475,9 @@ class Conv2DTranspose(Layer):
 
     def call(self, x, **kwargs):
         return ops.conv2d(x, self.dev, act=_lib.ACT_BY_NAME[self.activation])
+
+    def backward(self, *args, **kwargs):
+        raise NotImplementedError(f"Conv2DTranspose.backward ('{self.name}') is not built: dense Conv2D layers only")
 
 
 class Dense(Layer):

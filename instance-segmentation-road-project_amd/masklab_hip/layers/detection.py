@@ -151,13 +151,19 @@ class _TowerMixin:
         return units
 
     @staticmethod
-    def _run_towers_multi(blocks, xs, lives=None):
+    def _run_towers_multi(blocks, xs, lives=None, tape=None):
         """Depth-major execution of several un-shared towers (one per pyramid level / RoI level):
         the SqueezeExcites of depth i run for ALL towers in one launch pair and their convs in one multi-problem launch,
         so the few-tile problems of the coarse levels ride along with the fine level instead of each being a
         latency-bound launch of its own.  Separable units (MobileSeparableConv2D) run level by level within their depth.
-        Falls back to tower-major order when the towers are not made of the same depth units."""
+        Falls back to tower-major order when the towers are not made of the same depth units.
+        tape: None, or a dict that receives what the backward needs -- per depth, every level's conv input ("conv_in") and
+        post-ReLU conv output ("conv_out"); GroupNormalization then writes a tensor of its own instead of normalising the
+        conv output in place (the same bits).  Towers of [Conv2D, GroupNormalization] units only."""
         units = [_TowerMixin._units(b) for b in blocks]
+        if tape is not None:
+            _TowerMixin._check_tape_units(units, lives)
+            tape["conv_in"], tape["conv_out"] = [], []
         same = (all(u is not None for u in units) and len({len(u) for u in units}) == 1 and
                 all(len({(se is None, type(c)) for se, c, _ in (u[d] for u in units)}) == 1 for d in range(len(units[0]))))
         if not same:
@@ -189,13 +195,32 @@ class _TowerMixin:
                     tpc = ops.gn_fusable(oshape, c.filters, g.groups, c.dev, launch_tiles, x.dtype)
                     if tpc:
                         parts[k] = (torch.empty((t, 4, 2), dtype=torch.float64, device=x.device), tpc)
+            if tape is not None:
+                tape["conv_in"].append(list(xs))
             xs = ops.conv2d_multi([dict(x=x, dc=c.dev, stride=c.strides[0], padding=c.padding,
                                         dilation=c.dilation_rate[0], act=ops._lib.ACT_BY_NAME[c.activation], live=lv,
                                         gn_partials=None if pt is None else pt[0])
                                    for c, x, lv, pt in zip(convs, xs, lives, parts)])
-            xs = GroupNormalization.call_multi(norms, xs, inplace=True, lives=None if no_lives else lives,
+            if tape is not None:
+                tape["conv_out"].append(list(xs))
+            xs = GroupNormalization.call_multi(norms, xs, inplace=tape is None, lives=None if no_lives else lives,
                                                partials=None if all(pt is None for pt in parts) else parts)
         return xs
+
+    @staticmethod
+    def _check_tape_units(units, lives=None):
+        """What the towers' backward is built for: [Conv2D(3x3, relu), GroupNormalization] units, the same depth everywhere"""
+        if any(u is None for u in units) or len({len(u) for u in units}) != 1 or lives is not None:
+            raise NotImplementedError("tower backward: towers of [Conv2D, GroupNormalization] depth units only")
+        for u in units:
+            for se, conv, _ in u:
+                if se is not None:
+                    raise NotImplementedError(f"tower backward: SqueezeExcite ('{se.name}') has no backward")
+                if isinstance(conv, MobileSeparableConv2D):
+                    raise NotImplementedError(f"tower backward: MobileSeparableConv2D ('{conv.name}') has no backward")
+                if conv.activation != 'relu':
+                    raise NotImplementedError(f"tower backward: '{conv.name}' must end in a ReLU (the mask comes from the "
+                                              f"GroupNormalization behind it)")
 
     @staticmethod
     def _build_chain(block, shape):
@@ -260,6 +285,91 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
             off += per_level[idx]
         ops.conv2d_multi(problems)
         return pred
+
+    def _pred_views(self, shapes):
+        """Every level's row range of the [B, A, d] prediction as (element offset, channel stride, batch stride)"""
+        d = self.out_dim
+        per_level = [int(s[1]) * int(s[2]) * self.num_priors for s in shapes]
+        total = sum(per_level)
+        views, off = [], 0
+        for n in per_level:
+            views.append((off * d, self.num_priors * d, total * d))
+            off += n
+        return views, total
+
+    def call_with_tape(self, inputs, **kwargs):
+        """`call` that keeps what `backward` needs.  -> (pred, tape): pred is `call`'s bit for bit; the tape holds every depth's
+        conv input and post-ReLU conv output per level, and the output convs' inputs.  GroupNormalization writes a tensor
+        of its own here (inplace=False) where `call` normalises in place; the epilogue-statistics path is kept where `call`
+        uses it.  Towers with SqueezeExcite or separable units raise NotImplementedError."""
+        d = self.out_dim
+        B = inputs[0].shape[0]
+        blocks = self.blocks[:len(inputs)]
+        tape = {"inputs": list(inputs)}
+        xs = self._run_towers_multi([b[:-1] for b in blocks], inputs, tape=tape)
+        tape["out_in"] = list(xs)
+        views, total = self._pred_views([x.shape for x in xs])
+        pred = torch.empty((B, total, d), dtype=torch.float32, device=inputs[0].device)
+        problems = []
+        for idx, (x, view) in enumerate(zip(xs, views)):
+            out_conv = blocks[idx][-1]
+            problems.append(dict(x=x, dc=out_conv.dev, stride=1, padding='same',
+                                 act=ops._lib.ACT_BY_NAME[out_conv.activation], out_view=(pred,) + view))
+        ops.conv2d_multi(problems)
+        return pred, tape
+
+    def backward(self, tape, d_pred):
+        """Backward of `call_with_tape`: d_pred [B, A, d] float32 is the gradient at the PRE-activation of the prediction (the
+        box head is linear; the class head's sigmoid is the loss's: loss_and_gradients(wrt="pre_activation")).
+        The output convs read it as views (one weight-gradient launch, one data-gradient launch); then, deepest depth
+        first: GroupNormalization.backward_multi(input_relu=True, in place) -> conv2d_wgrad_multi -> conv2d_dgrad_multi.
+        -> (the gradients at `inputs`, one per level; {full weight name: gradient} with the names of init_weights():
+        .../conv{i}/kernel, /bias, .../gn{i}/gamma, /beta, .../output/kernel, /bias -- what apply_gradients takes)."""
+        n = len(tape["inputs"])
+        blocks = self.blocks[:n]
+        units = [self._units(b[:-1]) for b in blocks]
+        self._check_tape_units(units)
+        if not isinstance(d_pred, torch.Tensor) or d_pred.dtype != torch.float32:
+            raise TypeError(f"{type(self).__name__}.backward: d_pred must be a float32 tensor; the backward is float32 only")
+        views, total = self._pred_views([x.shape for x in tape["out_in"]])
+        B = int(tape["inputs"][0].shape[0])
+        if tuple(d_pred.shape) != (B, total, self.out_dim) or not d_pred.is_contiguous():
+            raise ValueError(f"{type(self).__name__}.backward: d_pred is {tuple(d_pred.shape)}, expected a contiguous "
+                             f"{(B, total, self.out_dim)}")
+        grads = {}
+
+        def conv_args(c):
+            return dict(dc=c.dev, stride=c.strides[0], padding=c.padding, dilation=c.dilation_rate[0])
+
+        def take(convs, pairs):
+            for c, (dk, db) in zip(convs, pairs):
+                grads[f"{c.name}/kernel"] = dk
+                if c.use_bias:
+                    grads[f"{c.name}/bias"] = db
+
+        outs = [b[-1] for b in blocks]
+        for c in outs:
+            c._check_backward()
+        take(outs, ops.conv2d_wgrad_multi([dict(x=x, dy=None, dy_view=(d_pred,) + v, want_bias=c.use_bias, **conv_args(c))
+                                           for c, x, v in zip(outs, tape["out_in"], views)]))
+        dxs = ops.conv2d_dgrad_multi([dict(dy=None, dy_view=(d_pred,) + v, in_hw=(x.shape[1], x.shape[2]), **conv_args(c))
+                                      for c, x, v in zip(outs, tape["out_in"], views)])
+        for depth in range(len(units[0]) - 1, -1, -1):
+            convs = [u[depth][1] for u in units]
+            norms = [u[depth][2] for u in units]
+            for c in convs:
+                c._check_backward()
+            back = GroupNormalization.backward_multi(norms, tape["conv_out"][depth], dxs, input_relu=True, inplace=True)
+            for g, (_, gg) in zip(norms, back):
+                for k, v in gg.items():
+                    grads[f"{g.name}/{k}"] = v
+            dys = [dx for dx, _ in back]                     # at the convs' pre-activation
+            xs = tape["conv_in"][depth]
+            take(convs, ops.conv2d_wgrad_multi([dict(x=x, dy=dy, want_bias=c.use_bias, **conv_args(c))
+                                                for c, x, dy in zip(convs, xs, dys)]))
+            dxs = ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **conv_args(c))
+                                          for c, x, dy in zip(convs, xs, dys)])
+        return dxs, grads
 
     def get_config(self):
         config = super().get_config()

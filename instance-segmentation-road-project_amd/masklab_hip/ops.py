@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .packing import PackedConv, pack_winograd, resolve_padding
+from .packing import PackedConv, dgrad_padding, pack_dense_transposed, pack_winograd, resolve_padding, unpack_dense
 
 import weakref
 
@@ -135,6 +135,17 @@ class DeviceConv:
         self._wgt_x3 = None
         self._wgt_wino = None
         self._wgt_stem_h = None
+        self._dgrad = None
+
+    @property
+    def dgrad(self):
+        """The DeviceConv whose FORWARD is this dense conv's data gradient at stride 1 (packing.pack_dense_transposed: the
+        kernel rotated by 180 degrees, cin / cout swapped, the new cin padded to a multiple of 4 with zero weights; no
+        bias); made on first use.  It follows the weights this packing was made from: a layer whose weights step is
+        re-packed (load_weights), which drops it."""
+        if self._dgrad is None:
+            self._dgrad = DeviceConv(pack_dense_transposed(unpack_dense(self.p)), self.wgt.device)
+        return self._dgrad
 
     @property
     def wgt_wino(self):
@@ -909,6 +920,210 @@ def global_mean_grad(dpool, H, W, add=None, out=None):
         _lib.check(lib.ml_global_mean_grad_f32(_ptr(dpool), _ptr(add), _ptr(dx), B, H * W, Cc, _stream()),
                    "ml_global_mean_grad_f32")
     return dx
+
+
+# ------------------------------------------------------------------ dense convolutions, backward (csrc/conv_grad.hip)
+def _dense_only(what, p):
+    """The packings the convolutions' backward takes: pack_dense.  The others are refused by name."""
+    if p.group_cin_step:
+        raise ValueError(f"{what}: grouped / depthwise convolutions are refused (dense convolutions only)")
+    if p.cpp_shift != 30:
+        raise ValueError(f"{what}: row-span (image input) convolutions are refused (dense convolutions only)")
+    if p.shuffle2x2:
+        raise ValueError(f"{what}: shuffle2x2 (Conv2DTranspose) convolutions are refused (dense convolutions only)")
+
+
+def _dy_view(what, dy, dy_view, B, Ho, Wo, cout):
+    """dy as a tensor [B,Ho,Wo,cout] or as the forward's out_view (tensor, element offset, channel stride, batch stride)
+    -> (tensor, element offset, channel stride, batch stride or 0)"""
+    if dy_view is None:
+        _grad_tensor(what, "dy", dy, (B, Ho, Wo, cout))
+        return dy, 0, cout, 0
+    if dy is not None:
+        raise ValueError(f"{what}: give `dy` or `dy_view`, not both")
+    vt, elem_off, vcs, vbs = dy_view
+    _grad_tensor(what, "dy_view", vt)
+    elem_off, vcs, vbs = int(elem_off), int(vcs), int(vbs)
+    if elem_off < 0 or vcs < cout or vbs < Ho * Wo * vcs or elem_off + (B - 1) * vbs + (Ho * Wo - 1) * vcs + cout > vt.numel():
+        raise ValueError(f"{what}: dy_view (offset {elem_off}, channel stride {vcs}, batch stride {vbs}) is no view of "
+                         f"[{B}, {Ho}, {Wo}, {cout}] inside a tensor of {vt.numel()} elements")
+    return vt, elem_off, vcs, vbs
+
+
+def conv2d_wgrad_geometry(x_shape, p, stride=1, padding="same", dilation=1, in_coff=0, dy_cstride=None, dy_bstride=0):
+    """The ml_conv2d_wgrad_desc of a problem without its tensors: geometry only (what ml_conv2d_wgrad_plan reads).
+    x_shape [B,H,W,Cbuf]; p: the forward's PackedConv."""
+    what = "conv2d_wgrad"
+    _dense_only(what, p)
+    B, H, W, Cbuf = (int(v) for v in x_shape)
+    if in_coff < 0 or in_coff + p.span > Cbuf:
+        raise ValueError(f"{what}: x has {Cbuf} channels, the kernel needs [{in_coff}, {in_coff + p.span})")
+    Ho, Wo, pt, pl = resolve_padding(H, W, p.kh_real, p.kw_real, stride, dilation, padding)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"{what}: the kernel does not fit the {H} x {W} input")
+    g = _lib.ConvWgradDesc()
+    d = g.conv
+    d.B, d.H, d.W, d.in_cstride, d.in_coff = B, H, W, Cbuf, in_coff
+    d.span, d.span_pad, d.cpp_shift = p.span, p.span_pad, p.cpp_shift
+    d.Ho, d.Wo = Ho, Wo
+    d.KH, d.KW, d.stride, d.dil, d.pad_t, d.pad_l = p.KH, p.KW, stride, dilation, pt, pl
+    d.cout, d.n_pad = p.cout, p.n_pad
+    d.out_cstride, d.out_coff, d.out_bstride = (p.cout if dy_cstride is None else int(dy_cstride)), 0, int(dy_bstride)
+    d.group_cin_step, d.shuffle2x2, d.math = p.group_cin_step, p.shuffle2x2, 0
+    return g
+
+
+def conv2d_wgrad_plan(x_shape, p, **geometry):
+    """-> (slices, pixels per slice, bytes of the partials) of one weight-gradient problem: ml_conv2d_wgrad_plan, host only.
+    A function of the problem's geometry alone."""
+    g = conv2d_wgrad_geometry(x_shape, p, **geometry)
+    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    _lib.check(_lib.load().ml_conv2d_wgrad_plan(C.byref(g), C.byref(slices), C.byref(sp), C.byref(nbytes)), "ml_conv2d_wgrad_plan")
+    return slices.value, sp.value, nbytes.value
+
+
+def _wgrad_pair(what, v, name):
+    if v is None:
+        return None, None
+    if isinstance(v, torch.Tensor):
+        return v, None
+    if len(v) != 2:
+        raise ValueError(f"{what}: `{name}` is a kernel tensor or a (kernel, bias) pair")
+    return v[0], v[1]
+
+
+def _wgrad_problem(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, dy_view=None, want_bias=True, add=None,
+                   out=None):
+    """The checks of one weight-gradient problem (dtypes and shapes first: they need no device) -> (descriptor, dkernel,
+    dbias or None, the tensors it keeps alive)"""
+    what = "conv2d_wgrad"
+    _grad_tensor(what, "x", x)
+    if x.dim() != 4:
+        raise ValueError(f"{what}: `x` must be [B, H, W, C], got {tuple(x.shape)}")
+    p = dc.p
+    vcs, vbs = (None, 0) if dy_view is None else (int(dy_view[2]), int(dy_view[3]))
+    g = conv2d_wgrad_geometry(x.shape, p, stride, padding, dilation, in_coff, vcs, vbs)
+    d = g.conv
+    vt, elem_off, vcs, vbs = _dy_view(what, dy, dy_view, d.B, d.Ho, d.Wo, p.cout)
+    kshape, bshape = (p.KH, p.KW, p.span, p.cout), (p.cout,)
+    add_k, add_b = _wgrad_pair(what, add, "add")
+    out_k, out_b = _wgrad_pair(what, out, "out")
+    for name, t, shape in (("add kernel", add_k, kshape), ("out kernel", out_k, kshape), ("add bias", add_b, bshape),
+                           ("out bias", out_b, bshape)):
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+    if not want_bias and (add_b is not None or out_b is not None):
+        raise ValueError(f"{what}: a bias `add` / `out` with want_bias=False")
+    for name, t in (("x", x), ("dy", vt), ("add kernel", add_k), ("out kernel", out_k), ("add bias", add_b), ("out bias", out_b)):
+        if t is not None:
+            _require_dev(t, name)
+    dk = torch.empty(kshape, dtype=torch.float32, device=x.device) if out_k is None else out_k
+    db = None if not want_bias else (torch.empty(bshape, dtype=torch.float32, device=x.device) if out_b is None else out_b)
+    d.in_, d.out = x.data_ptr(), vt.data_ptr() + 4 * elem_off
+    g.dkernel, g.dbias = dk.data_ptr(), None if db is None else db.data_ptr()
+    g.add_kernel = None if add_k is None else add_k.data_ptr()
+    g.add_bias = None if add_b is None or db is None else add_b.data_ptr()
+    M = d.B * d.Ho * d.Wo
+    flops = 2.0 * M * p.KH * p.KW * p.span * p.cout
+    nbytes = 4 * (d.B * d.H * d.W * p.span + M * p.cout + dk.numel() * (2 if add_k is not None else 1))
+    shape = f"M={p.span} N={p.cout} K={M} k{p.KH}x{p.KW} s{stride} d{dilation} HxW={d.H}x{d.W}"
+    return g, dk, db, (flops, nbytes, shape)
+
+
+def conv2d_wgrad(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, dy_view=None, want_bias=True, add=None, out=None):
+    """Weight and bias gradient of the dense conv `dc` (csrc/conv_grad.hip), float32: x [B,H,W,Cbuf] is the conv's input (read at
+    channels in_coff : in_coff + cin), dy [B,Ho,Wo,cout] the gradient at its PRE-activation output -- or dy_view=(tensor,
+    element offset, channel stride, batch stride), the forward's out_view (dy=None).  add / out: a kernel tensor or a (kernel,
+    bias) pair; out = add + gradient with one float32 addition, in place if they are the same tensor.
+    -> (dkernel [kh,kw,cin,cout], the Keras layout; dbias [cout], or None unless want_bias).  Exact fp32 products whatever
+    set_conv_math says; a fixed summation order: two launches give the same bits, alone or in conv2d_wgrad_multi."""
+    return conv2d_wgrad_multi([dict(x=x, dy=dy, dc=dc, stride=stride, padding=padding, dilation=dilation, in_coff=in_coff,
+                                    dy_view=dy_view, want_bias=want_bias, add=add, out=out)])[0]
+
+
+def conv2d_wgrad_multi(problems):
+    """ml_conv2d_wgrad_multi_f32: several weight-gradient problems in one launch pair (the five un-shared pyramid levels of a
+    tower depth).  problems: list of dicts with conv2d_wgrad's arguments -> list of (dkernel, dbias or None), the bits of the
+    single calls."""
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.CONV_WGRAD_MAX_PROBLEMS:
+        return (conv2d_wgrad_multi(problems[:_lib.CONV_WGRAD_MAX_PROBLEMS]) +
+                conv2d_wgrad_multi(problems[_lib.CONV_WGRAD_MAX_PROBLEMS:]))
+    made = [_wgrad_problem(**pr) for pr in problems]
+    lib = _lib.load()
+    ws_bytes = int(lib.ml_conv2d_workspace_bytes())
+    need = []
+    for g, _, _, _ in made:
+        nb = C.c_int64()
+        _lib.check(lib.ml_conv2d_wgrad_plan(C.byref(g), None, None, C.byref(nb)), "ml_conv2d_wgrad_plan")
+        need.append(nb.value)
+    if n > 1 and sum(need) > ws_bytes:
+        # more partials than the conv workspace holds (maps far larger than the towers'): two launches, the same bits
+        cut = max(1, next(i for i in range(1, n + 1) if sum(need[:i]) > ws_bytes) - 1)
+        return conv2d_wgrad_multi(problems[:cut]) + conv2d_wgrad_multi(problems[cut:])
+    arr = (_lib.ConvWgradDesc * n)()
+    flops, nbytes = 0.0, 0.0
+    for i, (g, _, _, (f, nb, _)) in enumerate(made):
+        arr[i] = g
+        flops += f
+        nbytes += nb
+    ws = workspace(ws_bytes, problems[0]["x"].device, "conv")
+    with _Prof("conv_wgrad", flops, nbytes, made[0][3][2] if n == 1 else "multi x%d" % n):
+        _lib.check(lib.ml_conv2d_wgrad_multi_f32(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_wgrad_multi_f32")
+    return [(dk, db) for _, dk, db, _ in made]
+
+
+def _dgrad_problem(dy, dc, in_hw, stride=1, padding="same", dilation=1, dy_view=None, add=None, out=None):
+    """One data-gradient problem -> the conv2d problem (a dict of conv2d's arguments) that computes it"""
+    what = "conv2d_dgrad"
+    p = dc.p
+    _dense_only(what, p)
+    hw = tuple(int(v) for v in in_hw)
+    if len(hw) not in (2, 3, 4):
+        raise ValueError(f"{what}: in_hw is (H, W) or the input's shape (B, H, W[, C]), got {hw}")
+    H, W = hw[-2:] if len(hw) == 2 else hw[1:3]
+    pads = dgrad_padding(H, W, p.kh_real, p.kw_real, stride, dilation, padding)        # refuses stride 2 by name
+    Ho, Wo, _, _ = resolve_padding(H, W, p.kh_real, p.kw_real, stride, dilation, padding)
+    vt0 = dy if dy_view is None else dy_view[0]
+    if not isinstance(vt0, torch.Tensor):
+        raise ValueError(f"{what}: `dy` must be a tensor")
+    B = hw[0] if len(hw) > 2 else int(vt0.shape[0])          # (H, W) alone: dy, or the viewed tensor, is batch-major
+    vt, elem_off, vcs, vbs = _dy_view(what, dy, dy_view, B, Ho, Wo, p.cout)
+    shape = (B, H, W, p.span)
+    for name, t in (("add", add), ("out", out)):
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+    if out is not None and add is not None and (out is add or out.data_ptr() == add.data_ptr()):
+        raise ValueError(f"{what}: `out` may not be `add` (a launch cut along K adds the residual after other blocks have "
+                         f"written: aliasing is not safe to assume)")
+    _require_dev(vt, "dy")
+    if dy_view is not None or p.cout % 4:
+        # the forward kernels read 16-byte rows: a contiguous copy with zero pad channels (the transposed weights have zero rows
+        # there); from the caching allocator, every element written
+        cp = -(-p.cout // 4) * 4
+        dense = torch.empty((B, Ho, Wo, cp), dtype=torch.float32, device=vt.device)
+        _lib.check(_lib.load().ml_conv2d_grad_gather_dy_f32(C.c_void_p(vt.data_ptr() + 4 * elem_off), _ptr(dense), B, Ho * Wo,
+                                                            p.cout, vcs, vbs, _stream()), "ml_conv2d_grad_gather_dy_f32")
+        vt = dense
+    return dict(x=vt, dc=dc.dgrad, stride=1, padding=pads, dilation=dilation, act=_lib.ACT_NONE, residual=add, out=out)
+
+
+def conv2d_dgrad(dy, dc, in_hw, stride=1, padding="same", dilation=1, dy_view=None, add=None, out=None):
+    """Data gradient of the dense conv `dc` at stride 1, float32: the FORWARD kernels (generic, persistent 1x1, Winograd -- under
+    whatever set_conv_math is set) on the transposed weights dc.dgrad: dx = conv(dy, kernel rotated by 180 degrees with cin /
+    cout swapped) under the padding (K-1) d - pad.  dy [B,Ho,Wo,cout] at the conv's PRE-activation output, or dy_view as in
+    conv2d_wgrad; in_hw = (H, W) of the conv's input, or its shape (B, H, W[, C]) -- needed where a viewed tensor's first
+    axis is not the batch.  add: dx = add + gradient (the forward's residual); `out` may not be
+    `add`.  -> dx [B,H,W,cin].  Stride 2 raises NotImplementedError."""
+    pr = _dgrad_problem(dy, dc, in_hw, stride, padding, dilation, dy_view, add, out)
+    return conv2d(pr.pop("x"), pr.pop("dc"), **pr)
+
+
+def conv2d_dgrad_multi(problems):
+    """Several data-gradient problems as ONE conv2d_multi launch.  problems: list of dicts with conv2d_dgrad's arguments."""
+    return conv2d_multi([_dgrad_problem(**pr) for pr in problems])
 
 
 def scale_channels_(x, s):

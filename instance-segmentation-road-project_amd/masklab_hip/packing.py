@@ -242,3 +242,42 @@ def pack_winograd(packed: PackedConv):
     if u.shape[0] < 4:
         u = np.concatenate([u, np.zeros((4 - u.shape[0],) + u.shape[1:], np.float32)])
     return np.ascontiguousarray(u)
+
+
+# ---- the dense convolutions' data gradient: the forward kernels on transposed weights
+def unpack_dense(packed: PackedConv):
+    """The Keras kernel [kh,kw,cin,cout] (float32) of a pack_dense packing: its exact inverse."""
+    p = packed
+    if p.cpp_shift != NO_PIX_SPAN or p.group_cin_step or p.shuffle2x2:
+        raise ValueError("unpack_dense: a dense packing only (no row-span, grouped or shuffle2x2 packing)")
+    w = np.asarray(p.wgt, np.float32)[:p.cout].reshape(p.cout, p.KH, p.KW, p.span_pad)[..., :p.span]
+    return np.ascontiguousarray(np.transpose(w, (1, 2, 3, 0)))
+
+
+def transposed_kernel(kernel):
+    """kernel [kh,kw,cin,cout] -> [kh,kw,cp,cin], cp = cout rounded up to a multiple of 4: rotated by 180 degrees, the channel
+    axes swapped, zero weights for the pad channels.  For stride 1, dx = conv(dy, this) with dgrad_padding()."""
+    kh, kw, cin, cout = kernel.shape
+    cp = -(-cout // 4) * 4
+    t = np.zeros((kh, kw, cp, cin), np.float32)
+    t[:, :, :cout, :] = np.transpose(np.asarray(kernel, np.float32)[::-1, ::-1], (0, 1, 3, 2))
+    return t
+
+
+def pack_dense_transposed(kernel, tile=0):
+    """pack_dense of transposed_kernel(kernel): the weights the forward kernels read to compute the data gradient."""
+    return pack_dense(transposed_kernel(kernel), None, tile)
+
+
+def dgrad_padding(H, W, kh, kw, stride, dilation, padding):
+    """The padding ((top, bottom), (left, right)) under which conv(dy, transposed kernel) is H x W: (K-1) d - pad on the leading
+    sides, the trailing sides chosen so the output has the input's size.  Stride 1 only."""
+    if stride != 1:
+        raise NotImplementedError(f"conv2d_dgrad: stride {stride} is not built (the data gradient runs the stride-1 forward "
+                                  f"kernels on transposed weights)")
+    Ho, Wo, pt, pl = resolve_padding(H, W, kh, kw, stride, dilation, padding)
+    ey, ex = (kh - 1) * dilation, (kw - 1) * dilation
+    pads = ((ey - pt, H - Ho - (ey - pt) + ey), (ex - pl, W - Wo - (ex - pl) + ex))
+    if min(pads[0] + pads[1]) < 0:
+        raise ValueError(f"conv2d_dgrad: forward padding larger than the kernel's reach ({padding})")
+    return pads
