@@ -74,7 +74,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             ml_global_mean_grad_f32;
                                             (additive, same version) ml_gconv3x3_launch_plan;
                                             (additive, same version) ml_conv2d_wgrad_desc, ml_conv2d_wgrad_multi_f32 /
-                                            _wgrad_plan, ml_conv2d_grad_gather_dy_f32 */
+                                            _wgrad_plan, ml_conv2d_grad_gather_dy_f32;
+                                            (additive, same version) ml_dwconv3x3_grad_desc, ml_dwconv3x3_wgrad_multi_f32 /
+                                            _wgrad_plan, ml_dwconv3x3_dgrad_multi_f32, ml_relu_grad_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -256,6 +258,48 @@ int ml_conv2d_wgrad_plan(const ml_conv2d_wgrad_desc *desc, int32_t *slices, int3
  * weights (packing.pack_dense_transposed) -- reads.  Every element of `out` is written. */
 int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t B, int32_t HW, int32_t cout, int32_t dy_cstride,
                                  int64_t dy_bstride, void *stream);
+
+/* ---------------------------------------------------------------- depthwise 3x3, backward (csrc/dwconv_grad.hip), fp32
+ * For y = ml_dwconv3x3_f32(x, w) (+ b) with stride 1 or 2, any dilation and leading pads (pad_t, pad_l); dy is the gradient
+ * at the PRE-activation output, read at channels dy_coff : dy_coff + C of a [B,Ho,Wo,dy_cstride] buffer:
+ *   dkernel[kh,kw,c] = sum over (b,oy,ox) of x[b, oy*stride + kh*dil - pad_t, ox*stride + kw*dil - pad_l, c] * dy[b,oy,ox,c]
+ *   dbias[c]         = sum over (b,oy,ox) of dy[b,oy,ox,c]
+ *   dx[b,iy,ix,c]    = sum over the taps whose ty = iy + pad_t - kh*dil and tx = ix + pad_l - kw*dil are multiples of stride
+ *                      with (ty/stride, tx/stride) inside the output, of wgt[kh*3+kw][c] * dy[b, ty/stride, tx/stride, c]
+ * (samples outside the image contribute zero and are never loaded).  C, the channel strides and offsets are multiples of 4.
+ * Weight gradient: x is read at in_cstride / in_coff; dkernel is contiguous [3,3,C,1] (the Keras layout), dbias [C] or NULL
+ * (skipped); add_kernel / add_bias: NULL, or like the output: output = add + gradient with one fp32 addition, an output may
+ * be its add itself.  No float atomics: the pixels (b, oy, ox ascending) are cut into slices of ceil(P / 64) pixels rounded
+ * up to a multiple of 16, at least 64 and at most 1024 -- a function of the problem's pixel count alone; a block sums a slice
+ * in fp32 in a fixed order, the finish kernel adds an element's partials in ascending slice order in fp64 and rounds once.
+ * Every element is written (an exact 0 for a tap that only meets padding); the same bits run to run, alone or in a multi
+ * launch, whatever outputs and workspace held.  workspace: 256-byte aligned, >= the sum of the problems'
+ * ml_dwconv3x3_wgrad_plan bytes; nothing in it needs initialising.
+ * Data gradient: wgt is the forward's [9][C] (packing.pack_depthwise); dx is a dense [B,H,W,C]; add_x: NULL or like dx
+ * (dx = add_x + gradient, dx may be add_x itself).  The problems of one launch write different dx tensors.
+ * Fields a direction does not use are ignored. */
+#define ML_DWCONV_GRAD_MAX_PROBLEMS 8
+typedef struct ml_dwconv3x3_grad_desc {
+    const float *x;                 /* wgrad: [B,H,W,in_cstride]                                     */
+    const float *dy;                /* [B,Ho,Wo,dy_cstride]                                          */
+    const float *wgt;               /* dgrad: [9][C]                                                 */
+    float *dkernel;                 /* wgrad: [3,3,C,1]                                              */
+    float *dbias;                   /* wgrad: [C] or NULL                                            */
+    const float *add_kernel;        /* NULL or like dkernel                                          */
+    const float *add_bias;          /* NULL or like dbias                                            */
+    float *dx;                      /* dgrad: [B,H,W,C]                                              */
+    const float *add_x;             /* NULL or like dx                                               */
+    int32_t B, H, W, C, in_cstride, in_coff, Ho, Wo, dy_cstride, dy_coff, stride, dil, pad_t, pad_l;
+} ml_dwconv3x3_grad_desc;
+int ml_dwconv3x3_wgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
+                                 void *stream);
+/* Host only: the slices of one weight-gradient problem (count, pixels per slice; the last slice may be shorter) and the
+ * bytes of its partials.  Checks the geometry as the launch does (tensor pointers may be NULL). */
+int ml_dwconv3x3_wgrad_plan(const ml_dwconv3x3_grad_desc *desc, int32_t *slices, int32_t *slice_pixels,
+                            int64_t *workspace_bytes);
+int ml_dwconv3x3_dgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs, int32_t n, void *stream);
+/* The gradient in front of a ReLU whose OUTPUT is y: out[i] = y[i] > 0 ? dy[i] : 0, n floats; out may be dy itself. */
+int ml_relu_grad_f32(const float *y, const float *dy, float *out, int64_t n, void *stream);
 
 /* ResNeXt grouped 3x3 (reference engine/backbone/ResNext.py:212-219: DepthwiseConv2D(depth_multiplier=c)
  * + SplitGroups/ReduceGroups/MergeGroups), c = channels per group in {4,8,16}, C % 64 == 0, on

@@ -46,6 +46,15 @@ class ConvWgradDesc(C.Structure):
                 ("add_bias", C.c_void_p)]
 
 
+class DwGradDesc(C.Structure):
+    """Mirror of `ml_dwconv3x3_grad_desc` (include/masklab_hip.h)."""
+    _fields_ = [("x", C.c_void_p), ("dy", C.c_void_p), ("wgt", C.c_void_p), ("dkernel", C.c_void_p), ("dbias", C.c_void_p),
+                ("add_kernel", C.c_void_p), ("add_bias", C.c_void_p), ("dx", C.c_void_p), ("add_x", C.c_void_p),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("in_cstride", C.c_int32),
+                ("in_coff", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("dy_cstride", C.c_int32),
+                ("dy_coff", C.c_int32), ("stride", C.c_int32), ("dil", C.c_int32), ("pad_t", C.c_int32), ("pad_l", C.c_int32)]
+
+
 class GnDesc(C.Structure):
     """Mirror of `ml_gn_desc` (include/masklab_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p),
@@ -121,6 +130,7 @@ class OptScalars(C.Structure):
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 CONV_WGRAD_MAX_PROBLEMS = 8                                          # ML_CONV_WGRAD_MAX_PROBLEMS
+DWCONV_GRAD_MAX_PROBLEMS = 8                                         # ML_DWCONV_GRAD_MAX_PROBLEMS
 SE_MAX_PROBLEMS = 8
 RESAMPLE_MAX_LEVELS = 8                                             # ML_RESAMPLE_MAX_LEVELS
 DECONV_OUT_MAX_PROBLEMS = 4
@@ -145,6 +155,10 @@ SIGNATURES = {
     "ml_conv2d_wgrad_multi_f32": (C.c_int, [C.POINTER(ConvWgradDesc), _i32, _vp, _i64, _vp]),
     "ml_conv2d_wgrad_plan": (C.c_int, [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ml_conv2d_grad_gather_dy_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "ml_dwconv3x3_wgrad_multi_f32": (C.c_int, [C.POINTER(DwGradDesc), _i32, _vp, _i64, _vp]),
+    "ml_dwconv3x3_wgrad_plan": (C.c_int, [C.POINTER(DwGradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ml_dwconv3x3_dgrad_multi_f32": (C.c_int, [C.POINTER(DwGradDesc), _i32, _vp]),
+    "ml_relu_grad_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "ml_deconv2x2_out1x1_f32": (C.c_int, [C.POINTER(DeconvOutProblem), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "ml_gconv3x3_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
     "ml_gconv3x3_f16": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),

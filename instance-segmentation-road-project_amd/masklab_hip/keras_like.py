@@ -440,8 +440,35 @@ class DepthwiseConv2D(Layer):
         return ops.dwconv3x3(x, self.wgt, self.bias, stride=self.strides[0], padding=self.padding,
                              dilation=self.dilation_rate[0], act=_lib.ACT_BY_NAME[self.activation])
 
-    def backward(self, *args, **kwargs):
-        raise NotImplementedError(f"DepthwiseConv2D.backward ('{self.name}') is not built: dense Conv2D layers only")
+    def _check_backward(self):
+        if self.fold_bn:
+            raise NotImplementedError(f"DepthwiseConv2D.backward ('{self.name}'): a layer with fold_bn (an inference "
+                                      f"BatchNormalization folded into its weights) has no backward")
+        if not self.built:
+            # before build() the layer has no channel count and no kernel: there is nothing a gradient could be of
+            raise NotImplementedError(f"DepthwiseConv2D.backward ('{self.name}'): the layer was never built; the backward "
+                                      f"exists for a built layer with its weights loaded")
+        if self.wgt is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+
+    def _grad_args(self):
+        return dict(stride=self.strides[0], padding=self.padding, dilation=self.dilation_rate[0])
+
+    def backward(self, x, dy, need_dx=True, add=None, in_coff=0, dy_coff=0):
+        """The layer's backward (ops.dwconv3x3_wgrad / ops.dwconv3x3_dgrad), float32 only.
+        x: what the layer was called on (read at channels in_coff : in_coff + C).  dy: the gradient at the layer's
+        PRE-activation output (read at channels dy_coff : dy_coff + C): the activation's own derivative is the caller's.
+        add: dx = add + gradient.  -> (dx [B,H,W,C] or None unless need_dx, {"depthwise_kernel": ..., "bias": ...} with the
+        weights the layer has)."""
+        self._check_backward()
+        args = self._grad_args()
+        dk, db = ops.dwconv3x3_wgrad(x, dy, in_coff=in_coff, dy_coff=dy_coff, want_bias=self.use_bias, C=self.C, **args)
+        grads = {"depthwise_kernel": dk}
+        if self.use_bias:
+            grads["bias"] = db
+        dx = ops.dwconv3x3_dgrad(dy, self.wgt, (x.shape[1], x.shape[2]), dy_coff=dy_coff, C=self.C, add=add,
+                                 **args) if need_dx else None
+        return dx, grads
 
 
 class Conv2DTranspose(Layer):

@@ -110,12 +110,20 @@ class _TowerMixin:
         return -(-int(x.shape[0]) * Ho * Wo // 128) * (c.dev.p.n_pad // 128 if c.dev.p.n_pad >= 128 else 1), (int(x.shape[0]), Ho, Wo)
 
     @staticmethod
-    def _run_tower(block, x):
+    def _run_tower(block, x, tape=None):
+        """tape: None, or a dict that receives what the backward needs, in _run_towers_multi's form for ONE tower -- per depth
+        [conv input] ("conv_in") and [post-ReLU conv output] ("conv_out"); GroupNormalization then writes a tensor of its
+        own instead of normalising the conv output in place (the same bits).  [Conv2D, GroupNormalization] units only."""
+        if tape is not None:
+            _TowerMixin._check_tape_units([_TowerMixin._units(block)])
+            tape["conv_in"], tape["conv_out"] = [], []
         block_input = x                          # never modified in place (it is a caller's tensor)
         i = 0
         while i < len(block):
             layer = block[i]
             nxt = block[i + 1] if i + 1 < len(block) else None
+            if tape is not None and isinstance(layer, Conv2D):
+                tape["conv_in"].append([x])
             if isinstance(layer, Conv2D) and isinstance(nxt, GroupNormalization) and layer.dev is not None:
                 # conv -> (ReLU) -> GroupNormalization: the conv's epilogue sums its tiles, no statistics pass (fp32, big maps)
                 tiles, oshape = _TowerMixin._conv_tiles(layer, x)
@@ -123,16 +131,20 @@ class _TowerMixin:
                 if tpc:
                     part = torch.empty((tiles, 4, 2), dtype=torch.float64, device=x.device)
                     x = layer(x, gn_partials=part)
-                    x = GroupNormalization.call_multi([nxt], [x], inplace=True, partials=[(part, tpc)])[0]
+                    if tape is not None:
+                        tape["conv_out"].append([x])
+                    x = GroupNormalization.call_multi([nxt], [x], inplace=tape is None, partials=[(part, tpc)])[0]
                     i += 2
                     continue
             i += 1
             if isinstance(layer, GroupNormalization):
-                x = layer(x, inplace=True)      # conv output is a fresh tensor: normalise in place
+                x = layer(x, inplace=tape is None)      # conv output is a fresh tensor: normalise in place
             elif isinstance(layer, SqueezeExcite):
                 x = layer(x, keep_input=(x is block_input))
             else:
                 x = layer(x)
+                if tape is not None:
+                    tape["conv_out"].append([x])
         return x
 
     @staticmethod
@@ -221,6 +233,42 @@ class _TowerMixin:
                 if conv.activation != 'relu':
                     raise NotImplementedError(f"tower backward: '{conv.name}' must end in a ReLU (the mask comes from the "
                                               f"GroupNormalization behind it)")
+
+    @staticmethod
+    def _conv_args(c):
+        return dict(dc=c.dev, stride=c.strides[0], padding=c.padding, dilation=c.dilation_rate[0])
+
+    @staticmethod
+    def _take_conv_grads(grads, convs, pairs):
+        for c, (dk, db) in zip(convs, pairs):
+            grads[f"{c.name}/kernel"] = dk
+            if c.use_bias:
+                grads[f"{c.name}/bias"] = db
+
+    @staticmethod
+    def _towers_backward(units, tape, dxs, grads, need_dx=True):
+        """The depth units of several towers, deepest depth first: GroupNormalization.backward_multi(input_relu=True, in place
+        on `dxs`, the gradients at the towers' outputs) -> conv2d_wgrad_multi -> conv2d_dgrad_multi.  tape: "conv_in" /
+        "conv_out" per depth and level, as _run_towers_multi / _run_tower record them.  Fills `grads` with the units' weights.
+        -> the gradients at the towers' inputs (None with need_dx=False: the first depth's data gradient is not run)."""
+        for depth in range(len(units[0]) - 1, -1, -1):
+            convs = [u[depth][1] for u in units]
+            norms = [u[depth][2] for u in units]
+            for c in convs:
+                c._check_backward()
+            back = GroupNormalization.backward_multi(norms, tape["conv_out"][depth], dxs, input_relu=True, inplace=True)
+            for g, (_, gg) in zip(norms, back):
+                for k, v in gg.items():
+                    grads[f"{g.name}/{k}"] = v
+            dys = [dx for dx, _ in back]                     # at the convs' pre-activation
+            xs = tape["conv_in"][depth]
+            _TowerMixin._take_conv_grads(grads, convs, ops.conv2d_wgrad_multi(
+                [dict(x=x, dy=dy, want_bias=c.use_bias, **_TowerMixin._conv_args(c)) for c, x, dy in zip(convs, xs, dys)]))
+            if depth == 0 and not need_dx:
+                return None
+            dxs = ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **_TowerMixin._conv_args(c))
+                                          for c, x, dy in zip(convs, xs, dys)])
+        return dxs
 
     @staticmethod
     def _build_chain(block, shape):
@@ -337,15 +385,10 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
             raise ValueError(f"{type(self).__name__}.backward: d_pred is {tuple(d_pred.shape)}, expected a contiguous "
                              f"{(B, total, self.out_dim)}")
         grads = {}
-
-        def conv_args(c):
-            return dict(dc=c.dev, stride=c.strides[0], padding=c.padding, dilation=c.dilation_rate[0])
+        conv_args = self._conv_args
 
         def take(convs, pairs):
-            for c, (dk, db) in zip(convs, pairs):
-                grads[f"{c.name}/kernel"] = dk
-                if c.use_bias:
-                    grads[f"{c.name}/bias"] = db
+            self._take_conv_grads(grads, convs, pairs)
 
         outs = [b[-1] for b in blocks]
         for c in outs:
@@ -354,22 +397,7 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
                                            for c, x, v in zip(outs, tape["out_in"], views)]))
         dxs = ops.conv2d_dgrad_multi([dict(dy=None, dy_view=(d_pred,) + v, in_hw=(x.shape[1], x.shape[2]), **conv_args(c))
                                       for c, x, v in zip(outs, tape["out_in"], views)])
-        for depth in range(len(units[0]) - 1, -1, -1):
-            convs = [u[depth][1] for u in units]
-            norms = [u[depth][2] for u in units]
-            for c in convs:
-                c._check_backward()
-            back = GroupNormalization.backward_multi(norms, tape["conv_out"][depth], dxs, input_relu=True, inplace=True)
-            for g, (_, gg) in zip(norms, back):
-                for k, v in gg.items():
-                    grads[f"{g.name}/{k}"] = v
-            dys = [dx for dx, _ in back]                     # at the convs' pre-activation
-            xs = tape["conv_in"][depth]
-            take(convs, ops.conv2d_wgrad_multi([dict(x=x, dy=dy, want_bias=c.use_bias, **conv_args(c))
-                                                for c, x, dy in zip(convs, xs, dys)]))
-            dxs = ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **conv_args(c))
-                                          for c, x, dy in zip(convs, xs, dys)])
-        return dxs, grads
+        return self._towers_backward(units, tape, dxs, grads), grads
 
     def get_config(self):
         config = super().get_config()

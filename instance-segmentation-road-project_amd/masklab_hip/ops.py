@@ -1126,6 +1126,240 @@ def conv2d_dgrad_multi(problems):
     return conv2d_multi([_dgrad_problem(**pr) for pr in problems])
 
 
+# ------------------------------------------------------------------ depthwise 3x3, backward (csrc/dwconv_grad.hip)
+def _dw_stride(what, stride, kernel_size=(3, 3)):
+    if tuple(int(v) for v in kernel_size) != (3, 3):
+        raise ValueError(f"{what}: kernel {tuple(kernel_size)}: 3 x 3 depthwise kernels only")
+    if stride not in (1, 2):
+        raise ValueError(f"{what}: stride {stride}: 1 or 2")
+
+
+def _dw_slice(what, name, Cbuf, coff, C):
+    if C < 1 or C % 4:
+        raise ValueError(f"{what}: the channel count ({C}) must be a multiple of 4 (16-byte accesses)")
+    if Cbuf % 4 or coff % 4:
+        raise ValueError(f"{what}: {name}'s channel count ({Cbuf}) and the offset ({coff}) must each be a multiple of 4 "
+                         f"(16-byte accesses)")
+    if coff < 0 or coff + C > Cbuf:
+        raise ValueError(f"{what}: {name} has {Cbuf} channels, the kernel needs [{coff}, {coff + C})")
+
+
+def dwconv3x3_wgrad_geometry(x_shape, C=None, stride=1, padding="same", dilation=1, in_coff=0, dy_cstride=None, dy_coff=0,
+                             kernel_size=(3, 3)):
+    """The ml_dwconv3x3_grad_desc of a weight-gradient problem without its tensors: geometry only (what
+    ml_dwconv3x3_wgrad_plan reads).  x_shape [B,H,W,Cbuf]; C=None: the channels of x from in_coff on."""
+    what = "dwconv3x3_wgrad"
+    _dw_stride(what, stride, kernel_size)
+    B, H, W, Cbuf = (int(v) for v in x_shape)
+    C = Cbuf - in_coff if C is None else int(C)
+    dy_cs = C if dy_cstride is None else int(dy_cstride)
+    _dw_slice(what, "x", Cbuf, in_coff, C)
+    _dw_slice(what, "dy", dy_cs, dy_coff, C)
+    Ho, Wo, pt, pl = resolve_padding(H, W, 3, 3, stride, dilation, padding)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"{what}: the kernel does not fit the {H} x {W} input")
+    d = _lib.DwGradDesc()
+    d.B, d.H, d.W, d.C, d.in_cstride, d.in_coff = B, H, W, C, Cbuf, in_coff
+    d.Ho, d.Wo, d.dy_cstride, d.dy_coff = Ho, Wo, dy_cs, dy_coff
+    d.stride, d.dil, d.pad_t, d.pad_l = stride, dilation, pt, pl
+    return d
+
+
+def dwconv3x3_wgrad_plan(x_shape, **geometry):
+    """-> (slices, pixels per slice, bytes of the partials) of one depthwise weight-gradient problem:
+    ml_dwconv3x3_wgrad_plan, host only.  A function of the problem's geometry alone."""
+    d = dwconv3x3_wgrad_geometry(x_shape, **geometry)
+    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    _lib.check(_lib.load().ml_dwconv3x3_wgrad_plan(C.byref(d), C.byref(slices), C.byref(sp), C.byref(nbytes)),
+               "ml_dwconv3x3_wgrad_plan")
+    return slices.value, sp.value, nbytes.value
+
+
+def _dw_wgrad_problem(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy_coff=0, want_bias=True, add=None, out=None,
+                      C=None, kernel_size=(3, 3)):
+    """The checks of one depthwise weight-gradient problem (dtypes and shapes first: they need no device)
+    -> (descriptor, dkernel, dbias or None, algorithmic bytes)"""
+    what = "dwconv3x3_wgrad"
+    _grad_tensor(what, "x", x)
+    _grad_tensor(what, "dy", dy)
+    if x.dim() != 4 or dy.dim() != 4:
+        raise ValueError(f"{what}: `x` and `dy` must be [B, H, W, C], got {tuple(x.shape)} and {tuple(dy.shape)}")
+    Cc = min(int(x.shape[3]) - in_coff, int(dy.shape[3]) - dy_coff) if C is None else int(C)
+    d = dwconv3x3_wgrad_geometry(x.shape, Cc, stride, padding, dilation, in_coff, int(dy.shape[3]), dy_coff, kernel_size)
+    if tuple(dy.shape[:3]) != (d.B, d.Ho, d.Wo):
+        raise ValueError(f"{what}: `dy` is {tuple(dy.shape)}, expected {(d.B, d.Ho, d.Wo)} pixels")
+    kshape, bshape = (3, 3, Cc, 1), (Cc,)
+    add_k, add_b = _wgrad_pair(what, add, "add")
+    out_k, out_b = _wgrad_pair(what, out, "out")
+    for name, t, shape in (("add kernel", add_k, kshape), ("out kernel", out_k, kshape), ("add bias", add_b, bshape),
+                           ("out bias", out_b, bshape)):
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+    if not want_bias and (add_b is not None or out_b is not None):
+        raise ValueError(f"{what}: a bias `add` / `out` with want_bias=False")
+    for name, t in (("x", x), ("dy", dy), ("add kernel", add_k), ("out kernel", out_k), ("add bias", add_b), ("out bias", out_b)):
+        if t is not None:
+            _require_dev(t, name)
+    dk = torch.empty(kshape, dtype=torch.float32, device=x.device) if out_k is None else out_k
+    db = None if not want_bias else (torch.empty(bshape, dtype=torch.float32, device=x.device) if out_b is None else out_b)
+    d.x, d.dy = x.data_ptr(), dy.data_ptr()
+    d.dkernel, d.dbias = dk.data_ptr(), None if db is None else db.data_ptr()
+    d.add_kernel = None if add_k is None else add_k.data_ptr()
+    d.add_bias = None if add_b is None or db is None else add_b.data_ptr()
+    M = d.B * d.Ho * d.Wo
+    nbytes = 4 * (d.B * d.H * d.W * Cc + M * Cc + 9 * Cc * (2 if add_k is not None else 1) +
+                  (0 if db is None else Cc * (2 if add_b is not None else 1)))
+    return d, dk, db, (18.0 * M * Cc, nbytes, f"C={Cc} K={M} s{stride} d{dilation} HxW={d.H}x{d.W}")
+
+
+def dwconv3x3_wgrad(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy_coff=0, want_bias=True, add=None, out=None,
+                    C=None, workspace_bytes=None):
+    """Weight and bias gradient of the depthwise 3x3 conv (csrc/dwconv_grad.hip), float32: x [B,H,W,Cbuf] is the conv's input,
+    read at channels in_coff : in_coff + C; dy [B,Ho,Wo,Cdy] the gradient at its PRE-activation output, read at channels
+    dy_coff : dy_coff + C (C=None: as many as both buffers hold from their offsets).  add / out: a kernel tensor or a
+    (kernel, bias) pair; out = add + gradient with one float32 addition, in place if they are the same tensor.
+    -> (dkernel [3,3,C,1], the Keras layout; dbias [C], or None unless want_bias).  A fixed summation order: two launches give
+    the same bits, alone or in dwconv3x3_wgrad_multi.  workspace_bytes: None, or the size to give the launch (tests)."""
+    return dwconv3x3_wgrad_multi([dict(x=x, dy=dy, stride=stride, padding=padding, dilation=dilation, in_coff=in_coff,
+                                       dy_coff=dy_coff, want_bias=want_bias, add=add, out=out, C=C)],
+                                 workspace_bytes=workspace_bytes)[0]
+
+
+def dwconv3x3_wgrad_multi(problems, workspace_bytes=None):
+    """ml_dwconv3x3_wgrad_multi_f32: up to 8 depthwise weight-gradient problems in one launch pair (the three dilations of
+    the ASPP ride together; more go in several launches).  problems: list of dicts with dwconv3x3_wgrad's arguments
+    -> list of (dkernel, dbias or None), the bits of the single calls."""
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.DWCONV_GRAD_MAX_PROBLEMS:
+        return (dwconv3x3_wgrad_multi(problems[:_lib.DWCONV_GRAD_MAX_PROBLEMS], workspace_bytes) +
+                dwconv3x3_wgrad_multi(problems[_lib.DWCONV_GRAD_MAX_PROBLEMS:], workspace_bytes))
+    made = [_dw_wgrad_problem(**pr) for pr in problems]
+    lib = _lib.load()
+    ws_bytes = int(lib.ml_conv2d_workspace_bytes())
+    arr = (_lib.DwGradDesc * n)()
+    need, flops, nbytes = [], 0.0, 0.0
+    for i, (d, _, _, (f, nb, _)) in enumerate(made):
+        arr[i] = d
+        ws_i = C.c_int64()
+        _lib.check(lib.ml_dwconv3x3_wgrad_plan(C.byref(d), None, None, C.byref(ws_i)), "ml_dwconv3x3_wgrad_plan")
+        need.append(ws_i.value)
+        flops += f
+        nbytes += nb
+    if n > 1 and sum(need) > ws_bytes:
+        # more partials than the conv workspace holds: two launches, the same bits
+        cut = max(1, next(i for i in range(1, n + 1) if sum(need[:i]) > ws_bytes) - 1)
+        return dwconv3x3_wgrad_multi(problems[:cut], workspace_bytes) + dwconv3x3_wgrad_multi(problems[cut:], workspace_bytes)
+    ws = workspace(ws_bytes, problems[0]["x"].device, "conv")
+    given = ws.numel() if workspace_bytes is None else int(workspace_bytes)
+    with _Prof("dwconv3x3_wgrad", flops, nbytes, made[0][3][2] if n == 1 else "multi x%d" % n):
+        _lib.check(lib.ml_dwconv3x3_wgrad_multi_f32(arr, n, _ptr(ws), given, _stream()), "ml_dwconv3x3_wgrad_multi_f32")
+    return [(dk, db) for _, dk, db, _ in made]
+
+
+def _dw_dgrad_problem(dy, wgt, in_hw, stride=1, padding="same", dilation=1, dy_coff=0, C=None, add=None, out=None,
+                      kernel_size=(3, 3)):
+    what = "dwconv3x3_dgrad"
+    _grad_tensor(what, "dy", dy)
+    _grad_tensor(what, "wgt", wgt)
+    _dw_stride(what, stride, kernel_size)
+    if dy.dim() != 4:
+        raise ValueError(f"{what}: `dy` must be [B, Ho, Wo, C], got {tuple(dy.shape)}")
+    hw = tuple(int(v) for v in in_hw)
+    if len(hw) not in (2, 3, 4):
+        raise ValueError(f"{what}: in_hw is (H, W) or the input's shape (B, H, W[, C]), got {hw}")
+    H, W = hw[-2:] if len(hw) == 2 else hw[1:3]
+    B, Cdy = int(dy.shape[0]), int(dy.shape[3])
+    Cc = Cdy - dy_coff if C is None else int(C)
+    _dw_slice(what, "dy", Cdy, dy_coff, Cc)
+    if wgt.dim() != 2 or tuple(wgt.shape) != (9, Cc):
+        raise ValueError(f"{what}: `wgt` is {tuple(wgt.shape)}, expected {(9, Cc)} (packing.pack_depthwise of a 3 x 3 kernel)")
+    Ho, Wo, pt, pl = resolve_padding(H, W, 3, 3, stride, dilation, padding)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"{what}: the kernel does not fit the {H} x {W} input")
+    if tuple(dy.shape[:3]) != (B, Ho, Wo) or (len(hw) > 2 and hw[0] != B):
+        raise ValueError(f"{what}: `dy` is {tuple(dy.shape)}, expected {(B, Ho, Wo)} pixels for a {H} x {W} input")
+    dx = _grad_out(what, (B, H, W, Cc), dy.device, add, out)
+    _require_dev(dy, "dy")
+    _require_dev(wgt, "wgt")
+    d = _lib.DwGradDesc()
+    d.B, d.H, d.W, d.C, d.in_cstride, d.in_coff = B, H, W, Cc, Cc, 0
+    d.Ho, d.Wo, d.dy_cstride, d.dy_coff = Ho, Wo, Cdy, dy_coff
+    d.stride, d.dil, d.pad_t, d.pad_l = stride, dilation, pt, pl
+    d.dy, d.wgt, d.dx = dy.data_ptr(), wgt.data_ptr(), dx.data_ptr()
+    d.add_x = None if add is None else add.data_ptr()
+    nbytes = 4 * (B * Ho * Wo * Cc + 9 * Cc + dx.numel() * (2 if add is not None else 1))
+    return d, dx, (18.0 * B * Ho * Wo * Cc, nbytes, f"C={Cc} s{stride} d{dilation} HxW={H}x{W}")
+
+
+def dwconv3x3_dgrad(dy, wgt, in_hw, stride=1, padding="same", dilation=1, dy_coff=0, C=None, add=None, out=None):
+    """Data gradient of the depthwise 3x3 conv (csrc/dwconv_grad.hip), float32, stride 1 or 2: dy [B,Ho,Wo,Cdy] at the conv's
+    PRE-activation output, read at channels dy_coff : dy_coff + C (C=None: all from dy_coff); wgt: the forward's [9][C]
+    (packing.pack_depthwise); in_hw = (H, W) of the conv's input, or its shape.  add / out: out = add + gradient with one
+    float32 addition, in place if they are the same tensor.  -> dx [B,H,W,C]."""
+    return dwconv3x3_dgrad_multi([dict(dy=dy, wgt=wgt, in_hw=in_hw, stride=stride, padding=padding, dilation=dilation,
+                                       dy_coff=dy_coff, C=C, add=add, out=out)])[0]
+
+
+def dwconv3x3_dgrad_multi(problems):
+    """ml_dwconv3x3_dgrad_multi_f32: up to 8 data-gradient problems in one launch, each into a dx of its own (gradients that
+    add into ONE tensor are chained through add= in separate launches).  -> list of dx, the bits of the single calls."""
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.DWCONV_GRAD_MAX_PROBLEMS:
+        return (dwconv3x3_dgrad_multi(problems[:_lib.DWCONV_GRAD_MAX_PROBLEMS]) +
+                dwconv3x3_dgrad_multi(problems[_lib.DWCONV_GRAD_MAX_PROBLEMS:]))
+    made = [_dw_dgrad_problem(**pr) for pr in problems]
+    arr = (_lib.DwGradDesc * n)()
+    flops, nbytes = 0.0, 0.0
+    for i, (d, _, (f, nb, _)) in enumerate(made):
+        arr[i] = d
+        flops += f
+        nbytes += nb
+    with _Prof("dwconv3x3_dgrad", flops, nbytes, made[0][2][2] if n == 1 else "multi x%d" % n):
+        _lib.check(_lib.load().ml_dwconv3x3_dgrad_multi_f32(arr, n, _stream()), "ml_dwconv3x3_dgrad_multi_f32")
+    return [dx for _, dx, _ in made]
+
+
+def gather_channels(src, coff, out):
+    """ml_conv2d_grad_gather_dy_f32 on a channel slice: channels coff : coff + C of src [B,H,W,Cs] -> out [B,H,W,C], dense
+    (C % 4 == 0), float32: a slice of a concat buffer's gradient in the form GroupNormalization's backward reads."""
+    what = "gather_channels"
+    _grad_tensor(what, "src", src)
+    _grad_tensor(what, "out", out)
+    if src.dim() != 4 or out.dim() != 4 or tuple(out.shape[:3]) != tuple(src.shape[:3]):
+        raise ValueError(f"{what}: `src` {tuple(src.shape)} and `out` {tuple(out.shape)} must be [B, H, W, C] of the same pixels")
+    B, H, W, Cs = src.shape
+    Cc = int(out.shape[3])
+    if Cc % 4 or coff < 0 or coff + Cc > Cs:
+        raise ValueError(f"{what}: channels {coff} : {coff + Cc} of {Cs}: a slice of a multiple of 4 channels")
+    _require_dev(src, "src")
+    _require_dev(out, "out")
+    with _Prof("gather_channels", 0, 8.0 * out.numel()):
+        _lib.check(_lib.load().ml_conv2d_grad_gather_dy_f32(C.c_void_p(src.data_ptr() + 4 * coff), _ptr(out), B, H * W, Cc, Cs, 0,
+                                                            _stream()), "ml_conv2d_grad_gather_dy_f32")
+    return out
+
+
+def relu_grad(y, dy, out=None):
+    """ml_relu_grad_f32: the gradient in front of a ReLU whose OUTPUT is y, float32: dy where y > 0, else 0 (a conv + ReLU
+    with no GroupNormalization behind it to carry the mask: the ASPP's pooled branch).  out: None, or dy (in place)."""
+    what = "relu_grad"
+    _grad_tensor(what, "y", y)
+    _grad_tensor(what, "dy", dy, y.shape)
+    if out is not None:
+        _grad_tensor(what, "out", out, y.shape)
+    for name, t in (("y", y), ("dy", dy), ("out", out)):
+        if t is not None:
+            _require_dev(t, name)
+    out = torch.empty_like(dy) if out is None else out
+    with _Prof("relu_grad", 0, 12.0 * y.numel()):
+        _lib.check(_lib.load().ml_relu_grad_f32(_ptr(y), _ptr(dy), _ptr(out), y.numel(), _stream()), "ml_relu_grad_f32")
+    return out
+
+
 def scale_channels_(x, s):
     lib = _lib.load()
     if x.dtype != torch.float32 or s.dtype != torch.float32:
