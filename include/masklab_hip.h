@@ -76,7 +76,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_conv2d_wgrad_desc, ml_conv2d_wgrad_multi_f32 /
                                             _wgrad_plan, ml_conv2d_grad_gather_dy_f32;
                                             (additive, same version) ml_dwconv3x3_grad_desc, ml_dwconv3x3_wgrad_multi_f32 /
-                                            _wgrad_plan, ml_dwconv3x3_dgrad_multi_f32, ml_relu_grad_f32 */
+                                            _wgrad_plan, ml_dwconv3x3_dgrad_multi_f32, ml_relu_grad_f32;
+                                            (additive, same version) ml_deconv2x2_out1x1_tape_f32, ml_deconv_out_grad_problem,
+                                            ml_deconv2x2_out1x1_grad_f32 / _grad_plan, ml_deconv2x2_grad_relayout_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -400,6 +402,48 @@ int ml_deconv2x2_out1x1_f32(const ml_deconv_out_problem *probs, int32_t nprob, i
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation; bias, the 1x1 conv (fp32 table), sigmoid and `out` stay fp32. */
 int ml_deconv2x2_out1x1_f16(const ml_deconv_out_problem *probs, int32_t nprob, int32_t K, int32_t c_mid, int32_t ncls,
                             int32_t cp, int32_t act_mid, int32_t act_out, void *stream);
+/* The fp32 launch that also keeps T, the transposed conv's post-activation output, for the backward: tapes[i] is problem
+ * i's float32 [M, 4, C_mid] (q = 2 dy + dx the output position; column q * C_mid + c: the column order of the transposed
+ * conv's GEMM packing), 16-byte aligned, disjoint from x and from each other.  `out` is bit-equal to ml_deconv2x2_out1x1_f32's
+ * (the same arithmetic in the same order); rows past a problem's end are not stored.  `live` problems are refused; the
+ * fp16-storage launch keeps no tape. */
+int ml_deconv2x2_out1x1_tape_f32(const ml_deconv_out_problem *probs, float *const *tapes, int32_t nprob, int32_t K,
+                                 int32_t c_mid, int32_t ncls, int32_t cp, int32_t act_mid, int32_t act_out, void *stream);
+
+/* ---------------------------------------------------------------- fused mask-head tail, backward (csrc/deconv_out_grad.hip), fp32
+ * For the tail above with act_mid = ReLU; dy is the gradient at the 1x1 conv's PRE-activation, read in place in the
+ * [B, total, 2h, 2w, ncls] tensor with the forward's addressing (dy_base / dy_image_stride / rois_per_image):
+ *   out[m,q,c]   = t[m,q,c] > 0 ? sum_k dy[pixel(m,q), k] * wo[c,k] : 0     ([M, 4, C_mid]; out may be t itself)
+ *   dkernel[c,k] = sum over (m,q) of t[m,q,c] * dy[pixel(m,q), k]           ([1,1,C_mid,ncls], the Keras layout)
+ *   dbias[k]     = sum over (m,q) of dy[pixel(m,q), k]
+ * in ONE pass over t (read once; out written once; dy read once).  wo is the 1x1 kernel itself, [C_mid, ncls].  Up to 4
+ * problems per launch.  C_mid % 4 == 0, C_mid <= 256, ncls <= 32, M < 2^24.  A row whose dy is all zero loads no t and
+ * stores zeros (the same bits for every finite t).
+ * No float atomics: the pixels are cut into slices of ceil(M / 512) pixels rounded up to a multiple of 32, at least 128 -- a
+ * function of the problem's pixel count alone (ml_deconv2x2_out1x1_grad_plan); a block sums a slice in a fixed order (dkernel
+ * in fp32, the dy sums of dbias in fp64), the finish kernel adds an element's partials in ascending slice order in fp64 and
+ * rounds once.  The same bits run
+ * to run, alone or in a multi launch, whatever out, dkernel, dbias and the workspace held.  workspace: 256-byte aligned,
+ * >= the sum of the problems' plan bytes; nothing in it needs initialising.  The problems of one launch write different
+ * tensors. */
+typedef struct ml_deconv_out_grad_problem {
+    const float *dy, *t, *wo;
+    float *out, *dkernel, *dbias;
+    int64_t M;                      /* input pixels = rois * hw                                       */
+    int32_t hw, w, rois_per_image, c_mid;
+    int64_t dy_image_stride, dy_base;
+} ml_deconv_out_grad_problem;
+int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *probs, int32_t nprob, int32_t ncls, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+/* Host only: the slices of one problem (count, pixels per slice; the last may be shorter) and the bytes of its partials.
+ * Checks the geometry as the launch does (tensor pointers may be NULL). */
+int ml_deconv2x2_out1x1_grad_plan(const ml_deconv_out_grad_problem *prob, int32_t ncls, int32_t *slices, int32_t *slice_pixels,
+                                  int64_t *workspace_bytes);
+/* The transposed conv's weight gradient from its 1x1 view (ml_conv2d_wgrad_multi_f32 on dy = `out` above viewed
+ * [R,h,w,4 C_mid]): dk1x1 [1,1,cin,4 C_mid] -> dkernel [2,2,C_mid,cin] (a transposition), db4 [4 C_mid] -> dbias [C_mid] =
+ * ((db4[c] + db4[C_mid + c]) + db4[2 C_mid + c]) + db4[3 C_mid + c] in fp32 (both NULL: skipped). */
+int ml_deconv2x2_grad_relayout_f32(const float *dk1x1, const float *db4, float *dkernel, float *dbias, int32_t cin,
+                                   int32_t c_mid, void *stream);
 
 /* ---------------------------------------------------------------- depthwise / pooling
  * 3x3 DepthwiseConv2D (depth_multiplier 1), stride 1/2, dilation, explicit pads, +bias

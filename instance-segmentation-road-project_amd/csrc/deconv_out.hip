@@ -36,6 +36,7 @@ struct DoArgs {
     DoProb p[DO_MAX_PROB];
     int nprob, K, ncls, cp, tiles, out_sigmoid;
     float mid_lo, mid_hi, out_lo, out_hi;      // activations as clamps (the output one unless out_sigmoid)
+    float *tape[DO_MAX_PROB];                  // TAPE launches: per problem T [M][4][C_mid], the transposed conv's output
 };
 
 // n / d for 0 <= n < 2^24 (exact in float), d >= 1: one multiply and a two-sided correction
@@ -120,7 +121,13 @@ __device__ __forceinline__ void do_chunk(f32x16 (&acc)[NT], const char *rd, char
 // A block is persistent: it walks work units (tile of 128 pixels, position) u = block, block + grid, ... and its chunk
 // stream crosses unit boundaries -- the first chunk of the next unit is fetched behind the last chunk's MFMAs and lands
 // while the 1x1 conv and the stores of the finished unit run.
-template <int NT, bool HALF>                        // C_mid = 32 NT; HALF: x and wd are IEEE half (fp16-storage mask head)
+// TAPE: the launch also keeps T, the transposed conv's post-activation output, for the backward (deconv_out_grad.hip), in
+// the GEMM layout [M][4][C_mid] (column q * C_mid + c: pack_transpose2x2's order).  A register quad of the accumulators is
+// 4 consecutive channels of the lane's pixel, so it leaves as one float4 into the pixel's row of C_mid * 4 bytes; the
+// wave's 32 x 2 lanes write 32 bytes each of 32 rows per store, and the rows fill up over the 4 NT stores of the unit
+// (the stores hide behind the matrix work: measured).  Rows past the problem's end are not
+// stored.  Nothing else changes: the 1x1 conv reads the same values in the same order.
+template <int NT, bool HALF, bool TAPE>             // C_mid = 32 NT; HALF: x and wd are IEEE half (fp16-storage mask head)
 __global__ void __launch_bounds__(256, NT <= 4 ? 2 : 1)
 deconv_out_kernel(const DoArgs A) {
     constexpr int CM = 32 * NT;
@@ -244,6 +251,16 @@ deconv_out_kernel(const DoArgs A) {
         }
 
         // ---- bias + activation, then the 1x1 conv straight from the accumulators: two independent chains
+        float *tape_row = nullptr;                    // TAPE: channel 4 h of this lane's row of T, or null past the end
+        if constexpr (TAPE) {
+            float *tp = A.tape[0];
+            long long M = A.p[0].M;
+            if (cur.pi == 1) { tp = A.tape[1]; M = A.p[1].M; }
+            if (cur.pi == 2) { tp = A.tape[2]; M = A.p[2].M; }
+            if (cur.pi == 3) { tp = A.tape[3]; M = A.p[3].M; }
+            const int mi = cur.m0 + 32 * wave + r;
+            if (mi < (int)M) tape_row = tp + ((long long)cur.m0 * 4 + pos) * CM + ((32 * wave + r) * 4 * CM + 4 * h);
+        }
         const float bo = lds_bo[r];
         f32x16 y0, y1;
 #pragma unroll
@@ -253,6 +270,7 @@ deconv_out_kernel(const DoArgs A) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const f32x4 bv = *reinterpret_cast<const f32x4 *>(lds_bd + 32 * t + 8 * g + 4 * h);
+                f32x4 tv;
 #pragma unroll
                 for (int c = 0; c < 4; c += 2) {
                     const int e = 4 * g + c;
@@ -260,6 +278,10 @@ deconv_out_kernel(const DoArgs A) {
                     const float a1 = __builtin_amdgcn_fmed3f(acc[t][e + 1] + bv[c + 1], A.mid_lo, A.mid_hi);
                     y0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, tab[(t * 16 + e) * cp2], y0, 0, 0, 0);
                     y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, tab[(t * 16 + e + 1) * cp2], y1, 0, 0, 0);
+                    tv[c] = a0; tv[c + 1] = a1;
+                }
+                if constexpr (TAPE) {
+                    if (tape_row) *reinterpret_cast<f32x4 *>(tape_row + 32 * t + 8 * g) = tv;
                 }
             }
 
@@ -297,9 +319,9 @@ deconv_out_kernel(const DoArgs A) {
     wait_vmcnt<0>();     // (the last chunk's look-ahead loads were empty, but are counted)
 }
 
-template <int NT, bool HALF>
+template <int NT, bool HALF, bool TAPE = false>
 int launch_do(const DoArgs &A, hipStream_t s) {
-    auto kern = deconv_out_kernel<NT, HALF>;
+    auto kern = deconv_out_kernel<NT, HALF, TAPE>;
     const int bytes = 2 * (TM + 32 * NT) * ROWB + (NT * 16 * 2 * A.cp + 32 * NT + 32 + 4 * 32 * A.cp) * 4;
     static std::atomic<unsigned long long> ok{0};
     if (int rc = ml_ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 2 * (TM + 32 * NT) * ROWB + (NT * 16 * 2 * 32 + 32 * NT + 32 + 4 * 32 * 32) * 4,
@@ -316,7 +338,7 @@ int launch_do(const DoArgs &A, hipStream_t s) {
 }  // namespace
 
 static int deconv_out_entry(const ml_deconv_out_problem *probs, int32_t nprob, int32_t K, int32_t c_mid, int32_t ncls,
-                            int32_t cp, int32_t act_mid, int32_t act_out, void *stream, bool half) {
+                            int32_t cp, int32_t act_mid, int32_t act_out, void *stream, bool half, float *const *tapes = nullptr) {
     const int es = half ? 2 : 4, kc = half ? 64 : 32;
     ML_REQUIRE(probs && nprob >= 1 && nprob <= DO_MAX_PROB, "deconv2x2_out1x1: 1..%d problems per launch", DO_MAX_PROB);
     ML_REQUIRE(K >= kc && K % kc == 0, "deconv2x2_out1x1: input channels (%d) must be a multiple of %d", K, kc);
@@ -350,9 +372,26 @@ static int deconv_out_entry(const ml_deconv_out_problem *probs, int32_t nprob, i
         P.r_hw = 1.f / (float)q.hw; P.r_w = 1.f / (float)q.w; P.r_nl = 1.f / (float)q.rois_per_image;
         P.img_stride = q.out_image_stride; P.base = q.out_base;
         tiles += (int)((q.M + TM - 1) / TM);
+        A.tape[i] = nullptr;
+        if (tapes) {
+            const long long t_bytes = q.M * 4 * c_mid * 4;
+            ML_REQUIRE(tapes[i] && ml_aligned16(tapes[i]), "deconv2x2_out1x1_tape: problem %d: the tape must be a 16-byte aligned "
+                       "[M, 4, C_mid] tensor", i);
+            ML_REQUIRE(!q.live, "deconv2x2_out1x1_tape: the fixed-capacity form (`live`) keeps no tape");
+            for (int j = 0; j < i; ++j) {
+                const uintptr_t a = (uintptr_t)tapes[i], b = (uintptr_t)tapes[j];
+                ML_REQUIRE(a + (uintptr_t)t_bytes <= b || b + (uintptr_t)(probs[j].M * 4 * c_mid * 4) <= a,
+                           "deconv2x2_out1x1_tape: problems %d and %d write the same tape", j, i);
+            }
+            const uintptr_t a = (uintptr_t)tapes[i], x = (uintptr_t)q.x;
+            ML_REQUIRE(a + (uintptr_t)t_bytes <= x || x + (uintptr_t)(q.M * K * 4) <= a, "deconv2x2_out1x1_tape: problem %d: the tape "
+                       "overlaps x", i);
+            A.tape[i] = tapes[i];
+        }
     }
-    for (int i = nprob; i < DO_MAX_PROB; ++i) A.p[i] = A.p[0];
+    for (int i = nprob; i < DO_MAX_PROB; ++i) { A.p[i] = A.p[0]; A.tape[i] = A.tape[0]; }
     A.tiles = tiles;
+    if (tapes) return c_mid == 128 ? launch_do<4, false, true>(A, (hipStream_t)stream) : launch_do<8, false, true>(A, (hipStream_t)stream);
     if (half) return c_mid == 128 ? launch_do<4, true>(A, (hipStream_t)stream) : launch_do<8, true>(A, (hipStream_t)stream);
     return c_mid == 128 ? launch_do<4, false>(A, (hipStream_t)stream) : launch_do<8, false>(A, (hipStream_t)stream);
 }
@@ -365,4 +404,11 @@ extern "C" int ml_deconv2x2_out1x1_f32(const ml_deconv_out_problem *probs, int32
 extern "C" int ml_deconv2x2_out1x1_f16(const ml_deconv_out_problem *probs, int32_t nprob, int32_t K, int32_t c_mid,
                                        int32_t ncls, int32_t cp, int32_t act_mid, int32_t act_out, void *stream) {
     return deconv_out_entry(probs, nprob, K, c_mid, ncls, cp, act_mid, act_out, stream, true);
+}
+
+extern "C" int ml_deconv2x2_out1x1_tape_f32(const ml_deconv_out_problem *probs, float *const *tapes, int32_t nprob, int32_t K,
+                                            int32_t c_mid, int32_t ncls, int32_t cp, int32_t act_mid, int32_t act_out,
+                                            void *stream) {
+    ML_REQUIRE(tapes, "deconv2x2_out1x1_tape: null tape list");
+    return deconv_out_entry(probs, nprob, K, c_mid, ncls, cp, act_mid, act_out, stream, false, tapes);
 }

@@ -86,6 +86,13 @@ class DeconvOutProblem(C.Structure):
                 ("out_base", C.c_int64), ("live", C.c_void_p)]
 
 
+class DeconvOutGradProblem(C.Structure):
+    """Mirror of `ml_deconv_out_grad_problem` (include/masklab_hip.h)."""
+    _fields_ = [("dy", C.c_void_p), ("t", C.c_void_p), ("wo", C.c_void_p), ("out", C.c_void_p), ("dkernel", C.c_void_p),
+                ("dbias", C.c_void_p), ("M", C.c_int64), ("hw", C.c_int32), ("w", C.c_int32), ("rois_per_image", C.c_int32),
+                ("c_mid", C.c_int32), ("dy_image_stride", C.c_int64), ("dy_base", C.c_int64)]
+
+
 class SeDesc(C.Structure):
     """Mirror of `ml_se_desc` (include/masklab_hip.h)."""
     _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("w1", C.c_void_p), ("w2", C.c_void_p),
@@ -160,6 +167,11 @@ SIGNATURES = {
     "ml_dwconv3x3_dgrad_multi_f32": (C.c_int, [C.POINTER(DwGradDesc), _i32, _vp]),
     "ml_relu_grad_f32": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "ml_deconv2x2_out1x1_f32": (C.c_int, [C.POINTER(DeconvOutProblem), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "ml_deconv2x2_out1x1_tape_f32": (C.c_int, [C.POINTER(DeconvOutProblem), C.POINTER(C.c_void_p)] + [_i32] * 7 + [_vp]),
+    "ml_deconv2x2_out1x1_grad_f32": (C.c_int, [C.POINTER(DeconvOutGradProblem), _i32, _i32, _vp, _i64, _vp]),
+    "ml_deconv2x2_out1x1_grad_plan": (C.c_int, [C.POINTER(DeconvOutGradProblem), _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int64)]),
+    "ml_deconv2x2_grad_relayout_f32": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp]),
     "ml_gconv3x3_f32": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
     "ml_gconv3x3_f16": (C.c_int, [_vp, _vp, _vp, _vp] + [_i32] * 11 + [_vp]),
     "ml_gconv3x3_launch_plan": (C.c_int, [_i32] * 9 + [C.POINTER(C.c_int32)]),

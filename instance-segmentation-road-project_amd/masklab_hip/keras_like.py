@@ -499,6 +499,10 @@ class Conv2DTranspose(Layer):
 
     def _load_own(self, weights, device):
         self.dev = ops.DeviceConv(self.pack(weights), device)
+        # the same weights as the dense 1x1 conv [1,1,cin,4*filters] on the GEMM layout: what MaskSubNet.backward runs the
+        # transposed conv's weight and data gradients on (dev1x1.dgrad: its pack_dense_transposed, made on first use)
+        self.dev1x1 = ops.DeviceConv(packing.pack_dense(packing.transpose2x2_as_1x1(self._get(weights, "kernel")),
+                                                        np.tile(self._get(weights, "bias"), 4)), device)
 
     def call(self, x, **kwargs):
         return ops.conv2d(x, self.dev, act=_lib.ACT_BY_NAME[self.activation])

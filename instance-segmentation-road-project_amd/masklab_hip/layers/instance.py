@@ -145,7 +145,7 @@ class MaskSubNet(Layer, _TowerMixin):
         super().load_weights(weights, device)
         # the 1x1 output kernels once more, in the lane order of the fused tail kernel (csrc/deconv_out.hip)
         from .. import packing
-        self._tail_tables = []
+        self._tail_tables, self._tail_wo = [], []
         for block in self.blocks:
             deconv, out = block[-2], block[-1]
             p = deconv.dev.p
@@ -157,8 +157,9 @@ class MaskSubNet(Layer, _TowerMixin):
             k, b = out.folded(weights)
             table, bo, _ = packing.pack_out1x1_table(k, b)
             self._tail_tables.append((torch.from_numpy(table).to(device), torch.from_numpy(bo).to(device)))
+            self._tail_wo.append(torch.from_numpy(k.copy()).to(device))       # [1,1,C_mid,ncls] as it is: the backward's operand
 
-    def _fused_tail(self, blocks, xs, shapes, roi_masks, per_roi, lives=None):
+    def _fused_tail(self, blocks, xs, shapes, roi_masks, per_roi, lives=None, tape=None):
         """Conv2DTranspose + ReLU -> Conv2D 1x1 + sigmoid of every level in one launch, written straight into
         `roi_masks` (csrc/deconv_out.hip); False when the configuration is outside that kernel's shapes."""
         from .. import _lib
@@ -176,7 +177,7 @@ class MaskSubNet(Layer, _TowerMixin):
                                  live=None if lives is None else lives[i][0]))
             off += n
         ops.deconv2x2_out1x1_multi(problems, self.num_classes, _lib.ACT_BY_NAME[blocks[0][-2].activation],
-                                   _lib.ACT_BY_NAME[blocks[0][-1].activation])
+                                   _lib.ACT_BY_NAME[blocks[0][-1].activation], tape=tape)
         return True
 
     def capacity_supported(self, crop_size):
@@ -229,6 +230,109 @@ class MaskSubNet(Layer, _TowerMixin):
             off += n
         ops.conv2d_multi(problems)
         return roi_masks
+
+    def _check_train(self, what, xs):
+        """What call_with_tape / backward are built for: float32 tensors under exact or f32x3 products on the fused tail"""
+        if ops.CONV_MATH == "f16" or any(x.dtype != torch.float32 for x in xs):
+            raise NotImplementedError(f"MaskSubNet.{what}: float32 tensors only (no half tensors, no set_conv_math('f16'))")
+        if getattr(self, "_tail_tables", None) is None:
+            raise NotImplementedError(f"MaskSubNet.{what}: this configuration is outside the fused tail kernel (transposed-conv "
+                                      f"filters 128 or 256 on an input width that is a multiple of 32, at most 32 classes)")
+        for b in self.blocks:
+            if b[-2].activation != 'relu' or b[-1].activation != 'sigmoid':
+                raise NotImplementedError(f"MaskSubNet.{what}: the tail must be Conv2DTranspose + ReLU -> Conv2D 1x1 + sigmoid")
+
+    def call_with_tape(self, inputs, lives=None, **kwargs):
+        """`call` that keeps what `backward` needs.  -> (roi_masks, tape): roi_masks is `call`'s bit for bit; the tape holds
+        the towers' tape of _run_towers_multi(tape=) (every depth's conv input and post-ReLU conv output per level), the
+        towers' outputs ("tail_in") and, per level, T = the transposed conv's post-ReLU output [R h w, 4, C_mid] float32
+        in GEMM layout, which the fused tail's tape launch stores.  Refused by name: the
+        fixed-capacity form, half tensors / set_conv_math('f16'), configurations outside the fused tail, towers with
+        SqueezeExcite or separable units."""
+        if lives is not None:
+            raise NotImplementedError("MaskSubNet.call_with_tape: the fixed-capacity form (`lives`) keeps no tape")
+        if not isinstance(inputs, list):
+            inputs = [inputs]
+        self._check_train("call_with_tape", inputs)
+        blocks = self.blocks[:len(inputs)]
+        shapes = [(int(h.shape[0]), int(h.shape[1])) for h in inputs]
+        if any(n < 1 for _, n in shapes):
+            raise ValueError("MaskSubNet.call_with_tape: every level needs at least one RoI per image")
+        xs = [h.reshape((h.shape[0] * h.shape[1],) + tuple(h.shape[2:])) for h in inputs]
+        if any(x.shape[0] * x.shape[1] * x.shape[2] >= 1 << 24 for x in xs):
+            raise NotImplementedError("MaskSubNet.call_with_tape: 2^24 or more input pixels in a level are outside the fused tail")
+        tape = {"inputs": list(inputs), "shapes": shapes}
+        xs = self._run_towers_multi([b[:-2] for b in blocks], xs, tape=tape)
+        tape["tail_in"] = list(xs)
+        B = shapes[0][0]
+        oh, ow, ncls = 2 * int(xs[0].shape[1]), 2 * int(xs[0].shape[2]), self.num_classes
+        total = sum(n for _, n in shapes)
+        roi_masks = torch.empty((B, total, oh, ow, ncls), dtype=torch.float32, device=xs[0].device)
+        tape["T"] = []
+        if not self._fused_tail(blocks, xs, shapes, roi_masks, oh * ow * ncls, tape=tape["T"]):
+            raise NotImplementedError("MaskSubNet.call_with_tape: this configuration is outside the fused tail kernel")
+        return roi_masks, tape
+
+    def backward(self, tape, d_masks, need_dx=True, consume_tape=False):
+        """Backward of `call_with_tape`: d_masks [B, total, 2h, 2w, classes] float32 is the gradient at the PRE-activation of
+        roi_masks (the sigmoid is the loss's: MaskLoss.call_with_grad(through_sigmoid=True)).  Order of work: the tail of
+        every level in one launch (ops.deconv2x2_out1x1_grad_multi: dT, and the 1x1 output conv's gradients, in one pass over
+        T); the transposed conv as the 1x1 conv [1,1,cin,4 C_mid] it is on dT in GEMM layout -- one conv2d_wgrad_multi, one
+        conv2d_dgrad_multi, the weight gradient brought back to [2,2,C_mid,cin] / [C_mid]; then _towers_backward.
+        consume_tape: dT overwrites T (no T-sized allocation; the tape cannot be used again).
+        -> (the gradients at `inputs`, one [B,n_l,h,w,C] per level, or None with need_dx=False: the first depth's data
+        gradient is not run and the weight gradients are the same bits; {full weight name: gradient} with the names of
+        init_weights(): .../conv{i}/kernel, /bias, .../gn{i}/gamma, /beta, .../deconv/kernel, /bias, .../output/kernel, /bias
+        -- what apply_gradients takes)."""
+        n = len(tape["inputs"])
+        blocks = self.blocks[:n]
+        units = [self._units(b[:-2]) for b in blocks]
+        self._check_tape_units(units)
+        if not isinstance(d_masks, torch.Tensor) or d_masks.dtype != torch.float32:
+            raise TypeError("MaskSubNet.backward: d_masks must be a float32 tensor; the backward is float32 only")
+        if tape.get("T") is None or len(tape["T"]) != n:
+            raise ValueError("MaskSubNet.backward: the tape holds no T (consumed by an earlier backward?)")
+        self._check_train("backward", tape["T"])
+        xs, shapes = tape["tail_in"], tape["shapes"]
+        B, total = shapes[0][0], sum(s[1] for s in shapes)
+        h, w = int(xs[0].shape[1]), int(xs[0].shape[2])
+        ncls = self.num_classes
+        if tuple(d_masks.shape) != (B, total, 2 * h, 2 * w, ncls) or not d_masks.is_contiguous():
+            raise ValueError(f"MaskSubNet.backward: d_masks is {tuple(d_masks.shape)}, expected a contiguous "
+                             f"{(B, total, 2 * h, 2 * w, ncls)}")
+        deconvs, outs = [b[-2] for b in blocks], [b[-1] for b in blocks]
+        for c in outs:
+            c._check_backward()
+        for c in deconvs:
+            if getattr(c, "dev1x1", None) is None:
+                raise RuntimeError(f"layer '{c.name}' has no weights loaded")
+        grads = {}
+        per_roi = 4 * h * w * ncls
+        problems, off = [], 0
+        for i, (_, n_l) in enumerate(shapes):
+            problems.append(dict(dy=d_masks, T=tape["T"][i], wo=self._tail_wo[i], hw=(h, w), rois_per_image=n_l,
+                                 dy_base=off * per_roi, out=tape["T"][i] if consume_tape else None))
+            off += n_l
+        tails = ops.deconv2x2_out1x1_grad_multi(problems)
+        if consume_tape:
+            tape["T"] = None
+        for c, (_, dk, db) in zip(outs, tails):
+            grads[f"{c.name}/kernel"] = dk
+            if c.use_bias:
+                grads[f"{c.name}/bias"] = db
+        # the transposed conv = a 1x1 conv with 4 C_mid outputs on the GEMM layout
+        dys = [dT.view(x.shape[0], h, w, dT.shape[1] * dT.shape[2]) for x, (dT, _, _) in zip(xs, tails)]
+        args = dict(stride=1, padding="same", dilation=1)
+        pairs = ops.conv2d_wgrad_multi([dict(x=x, dy=dy, dc=c.dev1x1, want_bias=True, **args) for c, x, dy in zip(deconvs, xs, dys)])
+        for c, (dk1, db4) in zip(deconvs, pairs):
+            grads[f"{c.name}/kernel"], grads[f"{c.name}/bias"] = ops.deconv2x2_grad_relayout(dk1, db4)
+        if not need_dx and not units[0]:
+            return None, grads
+        dxs = ops.conv2d_dgrad_multi([dict(dy=dy, dc=c.dev1x1, in_hw=(h, w), **args) for c, dy in zip(deconvs, dys)])
+        dxs = self._towers_backward(units, tape, dxs, grads, need_dx=need_dx)
+        if dxs is None:
+            return None, grads
+        return [dx.reshape(tuple(t.shape)) for dx, t in zip(dxs, tape["inputs"])], grads
 
     def get_config(self):
         config = super().get_config()

@@ -448,19 +448,30 @@ def conv2d_multi(problems):
     return rets
 
 
-def deconv2x2_out1x1_multi(problems, ncls, act_mid, act_out):
+def deconv2x2_out1x1_multi(problems, ncls, act_mid, act_out, tape=None):
     """ml_deconv2x2_out1x1_f32: Conv2DTranspose(2x2, s2) + act_mid -> Conv2D 1x1 + act_out, up to 4 RoI levels per launch.
     problems: dicts x [R,h,w,K] fp32 (R = images * rois_per_image), dc (DeviceConv of the transposed conv), wo_table,
     bo (device tensors from packing.pack_out1x1_table), out (the [B,total,2h,2w,ncls] tensor), out_base (elements),
-    rois_per_image."""
+    rois_per_image.
+    tape: None, or a list that receives, per problem, T = the transposed conv's post-activation output as float32
+    [R*h*w, 4, C_mid] (the GEMM layout; ml_deconv2x2_out1x1_tape_f32) for deconv2x2_out1x1_grad; `out` is bit-equal to
+    the plain launch's.  float32 problems without `live` only.  A problem may name the tensor to store into ("tape_out")."""
     lib = _lib.load()
     n = len(problems)
     if n == 0:
         return
     if n > _lib.DECONV_OUT_MAX_PROBLEMS:
-        deconv2x2_out1x1_multi(problems[:_lib.DECONV_OUT_MAX_PROBLEMS], ncls, act_mid, act_out)
-        deconv2x2_out1x1_multi(problems[_lib.DECONV_OUT_MAX_PROBLEMS:], ncls, act_mid, act_out)
+        deconv2x2_out1x1_multi(problems[:_lib.DECONV_OUT_MAX_PROBLEMS], ncls, act_mid, act_out, tape)
+        deconv2x2_out1x1_multi(problems[_lib.DECONV_OUT_MAX_PROBLEMS:], ncls, act_mid, act_out, tape)
         return
+    if tape is not None:
+        if not isinstance(tape, list):
+            raise TypeError("deconv2x2_out1x1: `tape` must be a list (it receives one tensor per problem)")
+        for pr in problems:
+            if isinstance(pr["x"], torch.Tensor) and pr["x"].dtype != torch.float32:
+                raise TypeError(f"deconv2x2_out1x1: x is {pr['x'].dtype}; the tape launch is float32 only")
+            if pr.get("live") is not None:
+                raise ValueError("deconv2x2_out1x1: the fixed-capacity form (`live`) keeps no tape")
     arr = (_lib.DeconvOutProblem * n)()
     flops = nbytes = 0.0
     K = cmid = cp = None
@@ -498,9 +509,155 @@ def deconv2x2_out1x1_multi(problems, ncls, act_mid, act_out):
         flops += 2.0 * R * h * w * (4 * cmid * Kx + 4 * cmid * ncls)
         nbytes += x.element_size() * (x.numel() + 4 * cmid * Kx) + 4.0 * 4 * R * h * w * ncls
     half = problems[0]["x"].dtype == torch.float16
+    if tape is not None:
+        ts = []
+        for i, pr in enumerate(problems):
+            t = pr.get("tape_out")                # (tests: a tape inside a guarded buffer)
+            if t is None:
+                t = torch.empty((int(arr[i].M), 4, cmid), dtype=torch.float32, device=pr["x"].device)
+            else:
+                _grad_tensor("deconv2x2_out1x1", "tape_out", t, (int(arr[i].M), 4, cmid))
+                _require_dev(t, "tape_out")
+            ts.append(t)
+        ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+        with _Prof("deconv2x2_out1x1_tape", flops, nbytes + sum(4.0 * t.numel() for t in ts), f"multi x{n}"):
+            _lib.check(lib.ml_deconv2x2_out1x1_tape_f32(arr, ptrs, n, K, cmid, ncls, cp, act_mid, act_out, _stream()),
+                       "ml_deconv2x2_out1x1_tape_f32")
+        tape.extend(ts)
+        return
     fn = lib.ml_deconv2x2_out1x1_f16 if half else lib.ml_deconv2x2_out1x1_f32
     with _Prof("deconv2x2_out1x1_h" if half else "deconv2x2_out1x1", flops, nbytes, f"multi x{n}"):
         _lib.check(fn(arr, n, K, cmid, ncls, cp, act_mid, act_out, _stream()), "ml_deconv2x2_out1x1")
+
+
+# ------------------------------------------------------------------ fused mask-head tail, backward (csrc/deconv_out_grad.hip)
+def deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid, dy_image_stride=0, dy_base=0):
+    """The ml_deconv_out_grad_problem of a problem without its tensors: geometry only (what the plan reads)."""
+    d = _lib.DeconvOutGradProblem()
+    d.M, d.hw, d.w, d.rois_per_image, d.c_mid = int(M), int(hw), int(w), int(rois_per_image), int(c_mid)
+    d.dy_image_stride, d.dy_base = int(dy_image_stride), int(dy_base)
+    return d
+
+
+def deconv2x2_out1x1_grad_plan(M, hw, w, rois_per_image, c_mid, ncls):
+    """-> (slices, pixels per slice, bytes of the partials) of one tail-backward problem: ml_deconv2x2_out1x1_grad_plan, host
+    only.  A function of the problem's geometry alone."""
+    d = deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid)
+    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    _lib.check(_lib.load().ml_deconv2x2_out1x1_grad_plan(C.byref(d), int(ncls), C.byref(slices), C.byref(sp), C.byref(nbytes)),
+               "ml_deconv2x2_out1x1_grad_plan")
+    return slices.value, sp.value, nbytes.value
+
+
+def _tail_grad_problem(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, out_kernel=None, out_bias=None):
+    """The checks of one tail-backward problem (dtypes and shapes first: they need no device) -> (descriptor, dT, dkernel,
+    dbias, (flops, bytes))"""
+    what = "deconv2x2_out1x1_grad"
+    for name, t in (("dy", dy), ("T", T), ("wo", wo)):
+        _grad_tensor(what, name, t)
+    if dy.dim() != 5:
+        raise ValueError(f"{what}: `dy` must be the [B, total, 2h, 2w, ncls] tensor, got {tuple(dy.shape)}")
+    B, total, oh, ow, ncls = (int(v) for v in dy.shape)
+    h, w = (int(v) for v in hw)
+    if (oh, ow) != (2 * h, 2 * w):
+        raise ValueError(f"{what}: dy maps are {oh} x {ow}, the crops {h} x {w}")
+    if T.dim() != 3 or T.shape[1] != 4:
+        raise ValueError(f"{what}: `T` must be [M, 4, C_mid], got {tuple(T.shape)}")
+    M, _, cmid = (int(v) for v in T.shape)
+    n_l, dy_base = int(rois_per_image), int(dy_base)
+    if n_l < 1 or M != B * n_l * h * w:
+        raise ValueError(f"{what}: T has {M} pixels, {B} images x {n_l} RoIs x {h} x {w} are {B * n_l * h * w}")
+    if cmid % 4 or cmid > 256:
+        raise ValueError(f"{what}: C_mid = {cmid} must be a multiple of 4, at most 256")
+    if ncls > 32:
+        raise ValueError(f"{what}: {ncls} classes: at most 32")
+    if M >= 1 << 24:
+        raise ValueError(f"{what}: {M} input pixels: fewer than 2^24 per problem")
+    if tuple(wo.shape[-2:]) != (cmid, ncls) or wo.numel() != cmid * ncls:
+        raise ValueError(f"{what}: `wo` is {tuple(wo.shape)}, expected the 1x1 kernel [1, 1, {cmid}, {ncls}]")
+    per_roi = 4 * h * w * ncls
+    if dy_base < 0 or dy_base % per_roi or dy_base // per_roi + n_l > total:
+        raise ValueError(f"{what}: dy_base {dy_base} with {n_l} RoIs per image is no RoI block of {total} RoIs")
+    for name, t, shape in (("out", out, (M, 4, cmid)), ("out_kernel", out_kernel, (1, 1, cmid, ncls)), ("out_bias", out_bias, (ncls,))):
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+    for name, t in (("dy", dy), ("T", T), ("wo", wo), ("out", out), ("out_kernel", out_kernel), ("out_bias", out_bias)):
+        if t is not None:
+            _require_dev(t, name)
+    dT = torch.empty((M, 4, cmid), dtype=torch.float32, device=T.device) if out is None else out
+    dk = torch.empty((1, 1, cmid, ncls), dtype=torch.float32, device=T.device) if out_kernel is None else out_kernel
+    db = torch.empty((ncls,), dtype=torch.float32, device=T.device) if out_bias is None else out_bias
+    d = deconv2x2_out1x1_grad_geometry(M, h * w, w, n_l, cmid, dy.stride(0), dy_base)
+    d.dy, d.t, d.wo, d.out, d.dkernel, d.dbias = (t.data_ptr() for t in (dy, T, wo, dT, dk, db))
+    flops = 2.0 * M * 4 * cmid * ncls * 2
+    nbytes = 4.0 * (2 * T.numel() + M * 4 * ncls)
+    return d, dT, dk, db, (flops, nbytes)
+
+
+def deconv2x2_out1x1_grad(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, out_kernel=None, out_bias=None,
+                          workspace_bytes=None):
+    """Backward of the fused mask-head tail (csrc/deconv_out_grad.hip), float32, in one pass over T: dy [B,total,2h,2w,ncls]
+    is the gradient at the 1x1 conv's PRE-activation, read in place (this problem's RoIs are rows dy_base / (4 h w ncls) ..
+    + rois_per_image of every image); T [M,4,C_mid] the tape of deconv2x2_out1x1_multi(tape=); wo the 1x1 kernel
+    [1,1,C_mid,ncls]; hw = (h, w) of the crops.  -> (dT [M,4,C_mid], the gradient at the transposed conv's pre-activation in
+    T's layout -- out=T writes it over the tape --, dkernel [1,1,C_mid,ncls], dbias [ncls]).  A fixed summation order: two
+    launches give the same bits, alone or in deconv2x2_out1x1_grad_multi.  workspace_bytes: None, or the size to give the
+    launch (tests)."""
+    return deconv2x2_out1x1_grad_multi([dict(dy=dy, T=T, wo=wo, hw=hw, rois_per_image=rois_per_image, dy_base=dy_base, out=out,
+                                             out_kernel=out_kernel, out_bias=out_bias)], workspace_bytes)[0]
+
+
+def deconv2x2_out1x1_grad_multi(problems, workspace_bytes=None):
+    """ml_deconv2x2_out1x1_grad_f32: up to 4 RoI levels in one launch pair (more go in several launches).  problems: list
+    of dicts with deconv2x2_out1x1_grad's arguments -> list of (dT, dkernel, dbias), the bits of the single calls."""
+    n = len(problems)
+    if n == 0:
+        return []
+    if n > _lib.DECONV_OUT_MAX_PROBLEMS:
+        return (deconv2x2_out1x1_grad_multi(problems[:_lib.DECONV_OUT_MAX_PROBLEMS], workspace_bytes) +
+                deconv2x2_out1x1_grad_multi(problems[_lib.DECONV_OUT_MAX_PROBLEMS:], workspace_bytes))
+    what = "deconv2x2_out1x1_grad"
+    for pr in problems:
+        _grad_tensor(what, "dy", pr["dy"])
+    ncls = int(problems[0]["dy"].shape[-1])
+    if any(int(pr["dy"].shape[-1]) != ncls for pr in problems):
+        raise ValueError(f"{what}: the problems of one launch must share the class count")
+    made = [_tail_grad_problem(**pr) for pr in problems]
+    lib = _lib.load()
+    arr = (_lib.DeconvOutGradProblem * n)()
+    need, flops, nbytes = 0, 0.0, 0.0
+    for i, (d, _, _, _, (f, nb)) in enumerate(made):
+        arr[i] = d
+        ws_i = C.c_int64()
+        _lib.check(lib.ml_deconv2x2_out1x1_grad_plan(C.byref(d), ncls, None, None, C.byref(ws_i)), "ml_deconv2x2_out1x1_grad_plan")
+        need += ws_i.value
+        flops += f
+        nbytes += nb
+    # the partials live in the conv workspace, as the other weight gradients' do
+    ws = workspace(max(int(lib.ml_conv2d_workspace_bytes()), need), problems[0]["T"].device, "conv")
+    given = ws.numel() if workspace_bytes is None else int(workspace_bytes)
+    with _Prof("deconv2x2_out1x1_grad", flops, nbytes, f"multi x{n}"):
+        _lib.check(lib.ml_deconv2x2_out1x1_grad_f32(arr, n, ncls, _ptr(ws), given, _stream()), "ml_deconv2x2_out1x1_grad_f32")
+    return [(dT, dk, db) for _, dT, dk, db, _ in made]
+
+
+def deconv2x2_grad_relayout(dk1x1, db4):
+    """The transposed conv's weight gradient in the layer's own shapes (ml_deconv2x2_grad_relayout_f32): dk1x1
+    [1,1,cin,4*C_mid] -> [2,2,C_mid,cin]; db4 [4*C_mid] (or None) -> [C_mid], the four positions added in the order 0..3."""
+    what = "deconv2x2_grad_relayout"
+    _grad_tensor(what, "dk1x1", dk1x1)
+    if dk1x1.dim() != 4 or tuple(dk1x1.shape[:2]) != (1, 1) or dk1x1.shape[3] % 4:
+        raise ValueError(f"{what}: `dk1x1` must be [1, 1, cin, 4*C_mid], got {tuple(dk1x1.shape)}")
+    cin, cmid = int(dk1x1.shape[2]), int(dk1x1.shape[3]) // 4
+    if db4 is not None:
+        _grad_tensor(what, "db4", db4, (4 * cmid,))
+        _require_dev(db4, "db4")
+    _require_dev(dk1x1, "dk1x1")
+    dk = torch.empty((2, 2, cmid, cin), dtype=torch.float32, device=dk1x1.device)
+    db = None if db4 is None else torch.empty((cmid,), dtype=torch.float32, device=dk1x1.device)
+    _lib.check(_lib.load().ml_deconv2x2_grad_relayout_f32(_ptr(dk1x1), _ptr(db4), _ptr(dk), _ptr(db), cin, cmid, _stream()),
+               "ml_deconv2x2_grad_relayout_f32")
+    return dk, db
 
 
 def gconv3x3(x, wgt, bias, c, stride=1, padding=((1, 1), (1, 1)), act=_lib.ACT_NONE):

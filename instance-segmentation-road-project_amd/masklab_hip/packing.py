@@ -188,6 +188,22 @@ def pack_transpose2x2(kernel, bias=None, tile=0):
                       tile=tile, cin_buffer=cin, k_real=cin)
 
 
+def transpose2x2_as_1x1(kernel):
+    """Conv2DTranspose kernel [2,2,cout,cin] -> the dense 1x1 kernel [1,1,cin,4*cout] of the same GEMM: column (a*2+b)*cout + o
+    (pack_transpose2x2's column order) of input channel c is kernel[a,b,o,c].  What the transposed conv's backward runs on: its
+    weight and data gradients are those of this 1x1 conv on the output in GEMM layout [R,h,w,4*cout]."""
+    assert kernel.shape[:2] == (2, 2)
+    _, _, cout, cin = kernel.shape
+    return np.ascontiguousarray(np.asarray(kernel, np.float32).reshape(4 * cout, cin).T).reshape(1, 1, cin, 4 * cout)
+
+
+def transpose2x2_from_1x1(kernel1x1):
+    """The inverse of transpose2x2_as_1x1, for the kernel and for its gradient: [1,1,cin,4*cout] -> [2,2,cout,cin]."""
+    _, _, cin, n = kernel1x1.shape
+    assert kernel1x1.shape[:2] == (1, 1) and n % 4 == 0
+    return np.ascontiguousarray(np.asarray(kernel1x1).reshape(cin, n).T).reshape(2, 2, n // 4, cin)
+
+
 def pack_out1x1_table(kernel, bias=None):
     """1x1 conv kernel [1,1,C_mid,ncls] -> the lane table of ml_deconv2x2_out1x1_f32 (include/masklab_hip.h):
     [C_mid/32][16][2][cp], entry (t, e, half, c) = kernel[32 t + (e & 3) + 8 (e >> 2) + 4 half, c]; cp = the power of two
