@@ -25,6 +25,7 @@
 // layout) and dbias.  The column sums of dy ride in the blocks of unit group 0 (fp64 over the
 // slice, from the staged tile: dy is read once).  Every element is written; a tap that only meets padding gets exact zeros.
 #include "gfx_mem.h"
+#include "slice_sum.h"
 
 namespace {
 
@@ -226,9 +227,7 @@ __global__ void __launch_bounds__(WG_TPB) conv_wgrad_finish_kernel(const WgArgs 
     const int j = bias ? i - p.tcc : i;
     const float *src = bias ? p.bpart : p.part;
     const long long pitch = bias ? p.cout : p.tcc;
-    double t = 0.0;
-    for (int s = 0; s < p.slices; ++s) t += (double)src[(long long)s * pitch + j];
-    float v = (float)t;
+    float v = (float)ml_sum_slices_f64(src + j, pitch, p.slices);
     const float *add = bias ? p.add_b : p.add_k;
     if (add) v = add[j] + v;
     (bias ? p.db : p.dk)[j] = v;
@@ -249,8 +248,6 @@ struct WgPlan {
     int slices, sp, T, MT, NT, units, ugroups;
     long long tcc, bytes, dy_bs, P;
 };
-
-inline long long align256(long long v) { return (v + 255) & ~255ll; }
 
 // the checks of one problem and its slices: geometry only
 int wg_plan(const ml_conv2d_desc &d, WgPlan &pl) {
@@ -286,18 +283,12 @@ int wg_plan(const ml_conv2d_desc &d, WgPlan &pl) {
     const long long per_slice = (pl.tcc + d.cout) * 4;
     const long long max_slices = (WG_SHARE - 512) / per_slice;
     ML_REQUIRE(max_slices >= 1, "%s: one partial (%lld bytes) exceeds a problem's share of the conv workspace", what, per_slice);
-    long long sp = ((pl.P + 127) / 128 + WG_ROUND - 1) / WG_ROUND * WG_ROUND;
-    sp = sp < WG_SLICE_MIN ? WG_SLICE_MIN : (sp > WG_SLICE_MAX ? WG_SLICE_MAX : sp);
+    long long sp = ml_slice_pixels(pl.P, 128, WG_ROUND, WG_SLICE_MIN, WG_SLICE_MAX);
     if ((pl.P + sp - 1) / sp > max_slices) sp = ((pl.P + max_slices - 1) / max_slices + WG_ROUND - 1) / WG_ROUND * WG_ROUND;
     pl.sp = (int)sp;
     pl.slices = (int)((pl.P + sp - 1) / sp);
-    pl.bytes = align256(pl.slices * pl.tcc * 4) + align256((long long)pl.slices * d.cout * 4);
+    pl.bytes = ml_align256(pl.slices * pl.tcc * 4) + ml_align256((long long)pl.slices * d.cout * 4);
     return ML_OK;
-}
-
-bool wg_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
 }
 
 }  // namespace
@@ -308,9 +299,7 @@ extern "C" int ml_conv2d_wgrad_plan(const ml_conv2d_wgrad_desc *desc, int32_t *s
     WgPlan pl;
     const int rc = wg_plan(desc->conv, pl);
     if (rc != ML_OK) return rc;
-    if (slices) *slices = pl.slices;
-    if (slice_pixels) *slice_pixels = pl.sp;
-    if (workspace_bytes) *workspace_bytes = pl.bytes;
+    ml_plan_out(pl.slices, pl.sp, pl.bytes, slices, slice_pixels, workspace_bytes);
     return ML_OK;
 }
 
@@ -334,24 +323,20 @@ extern "C" int ml_conv2d_wgrad_multi_f32(const ml_conv2d_wgrad_desc *descs, int3
         const long long x_bytes = (long long)d.B * d.H * d.W * d.in_cstride * 4;
         const long long dy_bytes = (((long long)d.B - 1) * pl.dy_bs + (long long)d.Ho * d.Wo * d.out_cstride) * 4;
         const long long dk_bytes = pl.tcc * 4, db_bytes = (long long)d.cout * 4;
-        ML_REQUIRE(!wg_overlap(g.dkernel, dk_bytes, d.in, x_bytes) && !wg_overlap(g.dkernel, dk_bytes, d.out, dy_bytes),
-                   "%s: problem %d: dkernel may not overlap x or dy", what, i);
-        ML_REQUIRE(!g.add_kernel || g.add_kernel == g.dkernel || !wg_overlap(g.dkernel, dk_bytes, g.add_kernel, dk_bytes),
-                   "%s: problem %d: dkernel may be add itself, not a shifted view of it", what, i);
-        if (g.dbias) {
-            ML_REQUIRE(!wg_overlap(g.dbias, db_bytes, d.in, x_bytes) && !wg_overlap(g.dbias, db_bytes, d.out, dy_bytes) &&
-                       !wg_overlap(g.dbias, db_bytes, g.dkernel, dk_bytes), "%s: problem %d: dbias may not overlap x, dy or dkernel",
-                       what, i);
-            ML_REQUIRE(!g.add_bias || g.add_bias == g.dbias || !wg_overlap(g.dbias, db_bytes, g.add_bias, db_bytes),
-                       "%s: problem %d: dbias may be add itself, not a shifted view of it", what, i);
-        }
-        ML_REQUIRE(used + pl.bytes <= workspace_bytes, "%s: the workspace is too small: problem %d needs %lld bytes at offset %lld "
-                   "of %lld", what, i, pl.bytes, used, (long long)workspace_bytes);
+        ML_REQUIRE(!ml_ranges_overlap(g.dkernel, dk_bytes, d.in, x_bytes) &&
+                   !ml_ranges_overlap(g.dkernel, dk_bytes, d.out, dy_bytes), "%s: problem %d: dkernel may not overlap x or dy", what, i);
+        ML_REQUIRE(ml_add_or_disjoint(g.dkernel, g.add_kernel, dk_bytes), "%s: problem %d: dkernel may be add itself, not a shifted "
+                   "view of it", what, i);
+        ML_REQUIRE(!ml_ranges_overlap(g.dbias, db_bytes, d.in, x_bytes) && !ml_ranges_overlap(g.dbias, db_bytes, d.out, dy_bytes) &&
+                   !ml_ranges_overlap(g.dbias, db_bytes, g.dkernel, dk_bytes), "%s: problem %d: dbias may not overlap x, dy or "
+                   "dkernel", what, i);
+        ML_REQUIRE(ml_add_or_disjoint(g.dbias, g.add_bias, db_bytes), "%s: problem %d: dbias may be add itself, not a shifted view "
+                   "of it", what, i);
         WgProblem &p = A.p[i];
         p.x = d.in; p.dy = d.out + d.out_coff;
-        p.part = reinterpret_cast<float *>((char *)workspace + used);
-        p.bpart = reinterpret_cast<float *>((char *)workspace + used + align256(pl.slices * pl.tcc * 4));
-        used += pl.bytes;
+        p.part = ml_carve_partials(what, i, workspace, workspace_bytes, used, pl.bytes);
+        if (!p.part) return ML_E_BADARG;
+        p.bpart = p.part + ml_align256(pl.slices * pl.tcc * 4) / 4;
         p.add_k = g.add_kernel; p.add_b = g.dbias ? g.add_bias : nullptr; p.dk = g.dkernel; p.db = g.dbias;
         p.dy_bs = pl.dy_bs;
         p.H = d.H; p.W = d.W; p.Wo = d.Wo; p.HoWo = d.Ho * d.Wo; p.P = (int)pl.P;
@@ -383,7 +368,7 @@ extern "C" int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t
     const long long bs = dy_bstride ? dy_bstride : (long long)HW * dy_cstride;
     const long long total = (long long)B * HW * cp;
     ML_REQUIRE((long long)B * HW < (1ll << 31) && total < (1ll << 31) * WG_TPB, "%s: too many pixels", what);
-    ML_REQUIRE(!wg_overlap(out, total * 4, dy, (((long long)B - 1) * bs + (long long)HW * dy_cstride) * 4),
+    ML_REQUIRE(!ml_ranges_overlap(out, total * 4, dy, (((long long)B - 1) * bs + (long long)HW * dy_cstride) * 4),
                "%s: out may not overlap dy", what);
     hipLaunchKernelGGL(gather_dy_kernel, dim3((unsigned)((total + WG_TPB - 1) / WG_TPB)), dim3(WG_TPB), 0, (hipStream_t)stream, dy,
                        out, HW, cout, cp, dy_cstride, bs, total);

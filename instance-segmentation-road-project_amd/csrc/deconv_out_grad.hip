@@ -31,7 +31,7 @@
 // ml_deconv2x2_grad_relayout_f32: the transposed conv's weight gradient comes back from conv_grad.hip as the 1x1 view's
 // [1,1,cin,4C] and [4C]; the layer's own shapes are kernel [2,2,C,cin] (a transposition, no arithmetic) and bias [C] =
 // ((b[0C + c] + b[1C + c]) + b[2C + c]) + b[3C + c]: three fp32 additions in the order q = 0..3.
-#include "common.h"
+#include "slice_sum.h"
 
 namespace {
 
@@ -192,18 +192,7 @@ __global__ void __launch_bounds__(TG_TPB) tail_grad_finish_kernel(const TgArgs A
         p.db[i - nk] = (float)t;
         return;
     }
-    const float *src = p.part + (long long)(i % ncls) * p.C + i / ncls;
-    double t = 0.0;
-    int s = 0;
-    for (; s + 16 <= p.slices; s += 16) {                 // ascending slice order, sixteen loads in flight
-        float v[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] = src[(long long)(s + j) * pitch];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) t += (double)v[j];
-    }
-    for (; s < p.slices; ++s) t += (double)src[(long long)s * pitch];
-    p.dk[i] = (float)t;
+    p.dk[i] = (float)ml_sum_slices_f64(p.part + (long long)(i % ncls) * p.C + i / ncls, pitch, p.slices);
 }
 
 // dk1 [cin][4][C] -> dkernel [4][C][cin]; db4 [4][C] -> dbias [C]
@@ -227,13 +216,6 @@ struct TgPlan {
     long long bytes;
 };
 
-inline long long tg_align256(long long v) { return (v + 255) & ~255ll; }
-
-bool tg_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
-}
-
 int tg_plan(const ml_deconv_out_grad_problem &d, int ncls, TgPlan &pl) {
     const char *what = "deconv2x2_out1x1_grad";
     ML_REQUIRE(ncls >= 1 && ncls <= 32, "%s: 1..32 classes (got %d)", what, ncls);
@@ -244,8 +226,7 @@ int tg_plan(const ml_deconv_out_grad_problem &d, int ncls, TgPlan &pl) {
                    (d.M / d.hw) % d.rois_per_image == 0,
                "%s: pixels (%lld) must be whole maps of %d (width %d) for whole images of %d RoIs", what, (long long)d.M, d.hw, d.w,
                d.rois_per_image);
-    long long sp = ((d.M + TG_SLICE_DIV - 1) / TG_SLICE_DIV + TG_ROUND - 1) / TG_ROUND * TG_ROUND;
-    sp = sp < TG_SLICE_MIN ? TG_SLICE_MIN : sp;
+    const long long sp = ml_slice_pixels(d.M, TG_SLICE_DIV, TG_ROUND, TG_SLICE_MIN, 0);
     pl.sp = (int)sp;
     pl.slices = (int)((d.M + sp - 1) / sp);
     // a slice's rows of T: 32-bit byte offsets inside it
@@ -254,7 +235,7 @@ int tg_plan(const ml_deconv_out_grad_problem &d, int ncls, TgPlan &pl) {
     ML_REQUIRE((long long)d.hw * 4 * ncls < (1ll << 31), "%s: a RoI's output map exceeds 32-bit offsets", what);
     pl.cl_shift = 0;
     while ((1 << pl.cl_shift) < d.c_mid / 4) ++pl.cl_shift;
-    pl.bytes = tg_align256((long long)pl.slices * ((long long)ncls * d.c_mid + ((2 * ncls + 3) & ~3)) * 4);
+    pl.bytes = ml_align256((long long)pl.slices * ((long long)ncls * d.c_mid + ((2 * ncls + 3) & ~3)) * 4);
     return ML_OK;
 }
 
@@ -271,9 +252,7 @@ extern "C" int ml_deconv2x2_out1x1_grad_plan(const ml_deconv_out_grad_problem *p
     TgPlan pl;
     const int rc = tg_plan(*prob, ncls, pl);
     if (rc != ML_OK) return rc;
-    if (slices) *slices = pl.slices;
-    if (slice_pixels) *slice_pixels = pl.sp;
-    if (workspace_bytes) *workspace_bytes = pl.bytes;
+    ml_plan_out(pl.slices, pl.sp, pl.bytes, slices, slice_pixels, workspace_bytes);
     return ML_OK;
 }
 
@@ -300,36 +279,35 @@ extern "C" int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *pr
         const long long images = d.M / d.hw / d.rois_per_image;
         const float *dy_lo = d.dy + d.dy_base;
         const long long dy_bytes = ((images - 1) * d.dy_image_stride + (long long)d.rois_per_image * 4 * d.hw * ncls) * 4;
-        ML_REQUIRE(d.out == d.t || !tg_overlap(d.out, t_bytes, d.t, t_bytes), "%s: problem %d: out may be T itself, not a shifted "
+        ML_REQUIRE(ml_add_or_disjoint(d.out, d.t, t_bytes), "%s: problem %d: out may be T itself, not a shifted "
                    "view of it", what, i);
-        ML_REQUIRE(!tg_overlap(d.out, t_bytes, dy_lo, dy_bytes) && !tg_overlap(d.out, t_bytes, d.wo, dk_bytes),
+        ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, dy_lo, dy_bytes) && !ml_ranges_overlap(d.out, t_bytes, d.wo, dk_bytes),
                    "%s: problem %d: out may not overlap dy or the 1x1 kernel", what, i);
         writes[i][0] = {d.out, t_bytes}; writes[i][1] = {d.dkernel, dk_bytes}; writes[i][2] = {d.dbias, db_bytes};
         for (int a = 1; a < 3; ++a)
-            ML_REQUIRE(!tg_overlap(writes[i][a].p, writes[i][a].bytes, d.t, t_bytes) &&
-                       !tg_overlap(writes[i][a].p, writes[i][a].bytes, dy_lo, dy_bytes) &&
-                       !tg_overlap(writes[i][a].p, writes[i][a].bytes, d.wo, dk_bytes) &&
-                       !tg_overlap(writes[i][a].p, writes[i][a].bytes, d.out, t_bytes) &&
-                       !tg_overlap(writes[i][a].p, writes[i][a].bytes, workspace, workspace_bytes),
+            ML_REQUIRE(!ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.t, t_bytes) &&
+                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, dy_lo, dy_bytes) &&
+                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.wo, dk_bytes) &&
+                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.out, t_bytes) &&
+                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, workspace, workspace_bytes),
                        "%s: problem %d: dkernel / dbias may not overlap T, dy, the 1x1 kernel, out or the workspace", what, i);
-        ML_REQUIRE(!tg_overlap(d.dkernel, dk_bytes, d.dbias, db_bytes), "%s: problem %d: dkernel overlaps dbias", what, i);
-        ML_REQUIRE(!tg_overlap(d.out, t_bytes, workspace, workspace_bytes) && !tg_overlap(d.t, t_bytes, workspace, workspace_bytes),
+        ML_REQUIRE(!ml_ranges_overlap(d.dkernel, dk_bytes, d.dbias, db_bytes), "%s: problem %d: dkernel overlaps dbias", what, i);
+        ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, workspace, workspace_bytes) &&
+                   !ml_ranges_overlap(d.t, t_bytes, workspace, workspace_bytes),
                    "%s: problem %d: T / out overlap the workspace", what, i);
         for (int j = 0; j < i; ++j)
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b)
-                    ML_REQUIRE(!tg_overlap(writes[i][a].p, writes[i][a].bytes, writes[j][b].p, writes[j][b].bytes),
+                    ML_REQUIRE(!ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, writes[j][b].p, writes[j][b].bytes),
                                "%s: problems %d and %d write the same tensor", what, j, i);
         for (int j = 0; j < nprob; ++j)
             if (j != i)
-                ML_REQUIRE(!tg_overlap(d.out, t_bytes, probs[j].t, probs[j].M * 4 * probs[j].c_mid * 4),
+                ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, probs[j].t, probs[j].M * 4 * probs[j].c_mid * 4),
                            "%s: problem %d writes the T of problem %d", what, i, j);
-        ML_REQUIRE(used + pl.bytes <= workspace_bytes, "%s: the workspace is too small: problem %d needs %lld bytes at offset %lld "
-                   "of %lld", what, i, pl.bytes, used, (long long)workspace_bytes);
         TgProb &p = A.p[i];
         p.T = d.t; p.dy = d.dy; p.wo = d.wo; p.out = d.out; p.dk = d.dkernel; p.db = d.dbias;
-        p.part = reinterpret_cast<float *>((char *)workspace + used);
-        used += pl.bytes;
+        p.part = ml_carve_partials(what, i, workspace, workspace_bytes, used, pl.bytes);
+        if (!p.part) return ML_E_BADARG;
         p.M = (int)d.M; p.hw = d.hw; p.w = d.w; p.n_l = d.rois_per_image; p.C = d.c_mid;
         p.r_hw = 1.f / (float)d.hw; p.r_w = 1.f / (float)d.w; p.r_nl = 1.f / (float)d.rois_per_image;
         p.img_stride = d.dy_image_stride; p.base = d.dy_base;
@@ -363,9 +341,9 @@ extern "C" int ml_deconv2x2_grad_relayout_f32(const float *dk1x1, const float *d
     ML_REQUIRE((db4 == nullptr) == (dbias == nullptr), "%s: give both bias tensors or neither", what);
     const long long nk = (long long)cin * 4 * c_mid, n = nk + c_mid;
     ML_REQUIRE(n < (1ll << 31), "%s: too large", what);
-    ML_REQUIRE(!tg_overlap(dkernel, nk * 4, dk1x1, nk * 4) && !tg_overlap(dbias, c_mid * 4ll, db4, c_mid * 16ll) &&
-               !tg_overlap(dkernel, nk * 4, db4, c_mid * 16ll) && !tg_overlap(dbias, c_mid * 4ll, dk1x1, nk * 4) &&
-               !tg_overlap(dkernel, nk * 4, dbias, c_mid * 4ll), "%s: the tensors may not overlap", what);
+    ML_REQUIRE(!ml_ranges_overlap(dkernel, nk * 4, dk1x1, nk * 4) && !ml_ranges_overlap(dbias, c_mid * 4ll, db4, c_mid * 16ll) &&
+               !ml_ranges_overlap(dkernel, nk * 4, db4, c_mid * 16ll) && !ml_ranges_overlap(dbias, c_mid * 4ll, dk1x1, nk * 4) &&
+               !ml_ranges_overlap(dkernel, nk * 4, dbias, c_mid * 4ll), "%s: the tensors may not overlap", what);
     hipLaunchKernelGGL(deconv_grad_relayout_kernel, dim3((unsigned)((n + TG_TPB - 1) / TG_TPB)), dim3(TG_TPB), 0, (hipStream_t)stream,
                        dk1x1, db4, dkernel, dbias, cin, 4 * c_mid);
     ML_CHECK_LAUNCH(what);

@@ -26,7 +26,7 @@
 // Data gradient.  A gather: one thread per (input pixel, channel quad) walks the nine taps in (kh, kw) order; stride 2 is
 // a divisibility test.  out = add + gradient with one fp32 addition; out may be add itself (a thread reads its own element
 // before it writes it).
-#include "common.h"
+#include "slice_sum.h"
 
 namespace {
 
@@ -124,19 +124,7 @@ __global__ void __launch_bounds__(DW_TPB) dw_wgrad_finish_kernel(const DwArgs A)
     const int nk = 9 * p.C;
     if (i >= nk + (p.db ? p.C : 0)) return;
     const long long pitch = (long long)DW_ROWS * p.C;
-    // ascending slice order; sixteen loads are in flight at a time (one load per addition would leave the sum waiting on each)
-    const float *src = p.part + i;
-    double t = 0.0;
-    int s = 0;
-    for (; s + 16 <= p.slices; s += 16) {
-        float part[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) part[j] = src[(long long)(s + j) * pitch];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) t += (double)part[j];
-    }
-    for (; s < p.slices; ++s) t += (double)src[(long long)s * pitch];
-    float v = (float)t;
+    float v = (float)ml_sum_slices_f64(p.part + i, pitch, p.slices);
     if (i < nk) {
         if (p.add_k) v = p.add_k[i] + v;
         p.dk[i] = v;
@@ -195,13 +183,6 @@ struct DwPlan {
     long long P, bytes;
 };
 
-inline long long dw_align256(long long v) { return (v + 255) & ~255ll; }
-
-bool dw_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
-}
-
 // the geometry both directions share
 int dw_geometry(const char *what, const ml_dwconv3x3_grad_desc &d) {
     ML_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0 && d.Ho > 0 && d.Wo > 0, "%s: bad dims", what);
@@ -227,15 +208,14 @@ int dw_wgrad_plan(const ml_dwconv3x3_grad_desc &d, DwPlan &pl) {
     ML_REQUIRE(d.in_cstride % 4 == 0 && d.in_coff % 4 == 0 && d.in_coff >= 0 && d.in_coff + d.C <= d.in_cstride,
                "%s: x: channels [%d, %d) must be a 4-aligned slice of its %d", what, d.in_coff, d.in_coff + d.C, d.in_cstride);
     pl.P = (long long)d.B * d.Ho * d.Wo;
-    long long sp = ((pl.P + 63) / 64 + DW_ROUND - 1) / DW_ROUND * DW_ROUND;
-    sp = sp < DW_SLICE_MIN ? DW_SLICE_MIN : (sp > DW_SLICE_MAX ? DW_SLICE_MAX : sp);
+    const long long sp = ml_slice_pixels(pl.P, 64, DW_ROUND, DW_SLICE_MIN, DW_SLICE_MAX);
     pl.sp = (int)sp;
     pl.slices = (int)((pl.P + sp - 1) / sp);
     const int CQ = d.C / 4;
     pl.cl_shift = 0;
     while ((1 << pl.cl_shift) < CQ && pl.cl_shift < 6) ++pl.cl_shift;
     pl.ctiles = (CQ + (1 << pl.cl_shift) - 1) >> pl.cl_shift;
-    pl.bytes = dw_align256((long long)pl.slices * DW_ROWS * d.C * 4);
+    pl.bytes = ml_align256((long long)pl.slices * DW_ROWS * d.C * 4);
     return ML_OK;
 }
 
@@ -260,9 +240,7 @@ extern "C" int ml_dwconv3x3_wgrad_plan(const ml_dwconv3x3_grad_desc *desc, int32
     DwPlan pl;
     const int rc = dw_wgrad_plan(*desc, pl);
     if (rc != ML_OK) return rc;
-    if (slices) *slices = pl.slices;
-    if (slice_pixels) *slice_pixels = pl.sp;
-    if (workspace_bytes) *workspace_bytes = pl.bytes;
+    ml_plan_out(pl.slices, pl.sp, pl.bytes, slices, slice_pixels, workspace_bytes);
     return ML_OK;
 }
 
@@ -284,20 +262,18 @@ extern "C" int ml_dwconv3x3_wgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs,
                    "%s: problem %d: 4-byte alignment", what, i);
         const long long x_bytes = (long long)d.B * d.H * d.W * d.in_cstride * 4, dy_bytes = pl.P * d.dy_cstride * 4;
         const long long dk_bytes = 9ll * d.C * 4, db_bytes = (long long)d.C * 4;
-        ML_REQUIRE(!dw_overlap(d.dkernel, dk_bytes, d.x, x_bytes) && !dw_overlap(d.dkernel, dk_bytes, d.dy, dy_bytes) &&
-                   !dw_overlap(d.dbias, db_bytes, d.x, x_bytes) && !dw_overlap(d.dbias, db_bytes, d.dy, dy_bytes) &&
-                   !dw_overlap(d.dbias, db_bytes, d.dkernel, dk_bytes), "%s: problem %d: the outputs may not overlap x, dy or "
+        ML_REQUIRE(!ml_ranges_overlap(d.dkernel, dk_bytes, d.x, x_bytes) && !ml_ranges_overlap(d.dkernel, dk_bytes, d.dy, dy_bytes) &&
+                   !ml_ranges_overlap(d.dbias, db_bytes, d.x, x_bytes) && !ml_ranges_overlap(d.dbias, db_bytes, d.dy, dy_bytes) &&
+                   !ml_ranges_overlap(d.dbias, db_bytes, d.dkernel, dk_bytes), "%s: problem %d: the outputs may not overlap x, dy or "
                    "each other", what, i);
-        ML_REQUIRE(d.add_kernel == d.dkernel || !dw_overlap(d.dkernel, dk_bytes, d.add_kernel, dk_bytes),
+        ML_REQUIRE(ml_add_or_disjoint(d.dkernel, d.add_kernel, dk_bytes),
                    "%s: problem %d: dkernel may be add itself, not a shifted view of it", what, i);
-        ML_REQUIRE(d.add_bias == d.dbias || !dw_overlap(d.dbias, db_bytes, d.add_bias, db_bytes),
+        ML_REQUIRE(ml_add_or_disjoint(d.dbias, d.add_bias, db_bytes),
                    "%s: problem %d: dbias may be add itself, not a shifted view of it", what, i);
-        ML_REQUIRE(used + pl.bytes <= workspace_bytes, "%s: the workspace is too small: problem %d needs %lld bytes at offset %lld "
-                   "of %lld", what, i, pl.bytes, used, (long long)workspace_bytes);
         DwProblem &p = A.p[i];
         dw_fill(p, d);
-        p.part = reinterpret_cast<float *>((char *)workspace + used);
-        used += pl.bytes;
+        p.part = ml_carve_partials(what, i, workspace, workspace_bytes, used, pl.bytes);
+        if (!p.part) return ML_E_BADARG;
         p.slices = pl.slices; p.sp = pl.sp; p.cl_shift = pl.cl_shift; p.ctiles = pl.ctiles;
         p.first_block = (int)blocks; p.first_fblock = (int)fblocks;
         blocks += (long long)pl.slices * pl.ctiles;
@@ -325,12 +301,12 @@ extern "C" int ml_dwconv3x3_dgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs,
         ML_REQUIRE(ml_aligned16(d.dy) && ml_aligned16(d.wgt) && ml_aligned16(d.dx) && ml_aligned16(d.add_x),
                    "%s: problem %d: pointers must be 16-byte aligned", what, i);
         const long long dx_bytes = (long long)d.B * d.H * d.W * d.C * 4;
-        ML_REQUIRE(!dw_overlap(d.dx, dx_bytes, d.dy, (long long)d.B * d.Ho * d.Wo * d.dy_cstride * 4) &&
-                   !dw_overlap(d.dx, dx_bytes, d.wgt, 9ll * d.C * 4), "%s: problem %d: dx may not overlap dy or the kernel", what, i);
-        ML_REQUIRE(d.add_x == d.dx || !dw_overlap(d.dx, dx_bytes, d.add_x, dx_bytes),
+        ML_REQUIRE(!ml_ranges_overlap(d.dx, dx_bytes, d.dy, (long long)d.B * d.Ho * d.Wo * d.dy_cstride * 4) &&
+                   !ml_ranges_overlap(d.dx, dx_bytes, d.wgt, 9ll * d.C * 4), "%s: problem %d: dx may not overlap dy or the kernel", what, i);
+        ML_REQUIRE(ml_add_or_disjoint(d.dx, d.add_x, dx_bytes),
                    "%s: problem %d: dx may be add itself, not a shifted view of it", what, i);
         for (int j = 0; j < i; ++j)
-            ML_REQUIRE(!dw_overlap(d.dx, dx_bytes, descs[j].dx, (long long)descs[j].B * descs[j].H * descs[j].W * descs[j].C * 4),
+            ML_REQUIRE(!ml_ranges_overlap(d.dx, dx_bytes, descs[j].dx, (long long)descs[j].B * descs[j].H * descs[j].W * descs[j].C * 4),
                        "%s: problems %d and %d write the same dx (chain them through add= in separate launches)", what, j, i);
         DwProblem &p = A.p[i];
         dw_fill(p, d);
@@ -347,8 +323,8 @@ extern "C" int ml_dwconv3x3_dgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs,
 
 extern "C" int ml_relu_grad_f32(const float *y, const float *dy, float *out, int64_t n, void *stream) {
     ML_REQUIRE(y && dy && out && n > 0 && n < (1ll << 31) * DW_TPB, "relu_grad: bad arguments");
-    ML_REQUIRE(out == dy || !dw_overlap(out, n * 4, dy, n * 4), "relu_grad: out may be dy itself, not a shifted view of it");
-    ML_REQUIRE(!dw_overlap(out, n * 4, y, n * 4), "relu_grad: out may not overlap y");
+    ML_REQUIRE(ml_add_or_disjoint(out, dy, n * 4), "relu_grad: out may be dy itself, not a shifted view of it");
+    ML_REQUIRE(!ml_ranges_overlap(out, n * 4, y, n * 4), "relu_grad: out may not overlap y");
     hipLaunchKernelGGL(relu_grad_kernel, dim3((unsigned)((n + DW_TPB - 1) / DW_TPB)), dim3(DW_TPB), 0, (hipStream_t)stream, y, dy,
                        out, (long long)n);
     ML_CHECK_LAUNCH("relu_grad");

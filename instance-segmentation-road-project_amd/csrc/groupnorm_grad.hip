@@ -18,6 +18,7 @@
 // forward's own code (gn_common.h) over the forward's slices, so they have the bits of ml_groupnorm_chunk_stats_f32 and of the
 // sliced forward, and the mask is decided by the forward's gn_y().
 #include "gn_common.h"
+#include "slice_sum.h"
 
 namespace {
 
@@ -392,11 +393,6 @@ static int gg_validate_dims(const void *x, int32_t N, int64_t HWC, int32_t C, in
     return ML_OK;
 }
 
-static bool gg_overlap(const void *a, const void *b, long long bytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + (uintptr_t)bytes && pb < pa + (uintptr_t)bytes;
-}
-
 static int gg_run(const ml_gn_grad_desc *descs, int32_t n, const char *what, void *workspace, int64_t workspace_bytes,
                   void *stream) {
     GgMulti st, rd, ap, fi;
@@ -408,8 +404,8 @@ static int gg_run(const ml_gn_grad_desc *descs, int32_t n, const char *what, voi
         if (int rc = gg_validate_dims(d.x, d.N, d.HWC, d.C, d.G, what)) return rc;
         ML_REQUIRE(d.dy && d.dx, "%s: null pointer", what);
         const long long bytes = (long long)d.N * d.HWC * (long long)sizeof(float);
-        ML_REQUIRE(!gg_overlap(d.x, d.dx, bytes), "%s: dx may not alias x (the layer's input is needed as it was)", what);
-        ML_REQUIRE(d.dx == d.dy || !gg_overlap(d.dy, d.dx, bytes), "%s: dx may be dy itself, not a shifted view of it", what);
+        ML_REQUIRE(!ml_ranges_overlap(d.x, bytes, d.dx, bytes), "%s: dx may not alias x (the layer's input is needed as it was)", what);
+        ML_REQUIRE(d.dx == d.dy || !ml_ranges_overlap(d.dy, bytes, d.dx, bytes), "%s: dx may be dy itself, not a shifted view of it", what);
         const long long L = d.HWC / d.G;
         const int cg = d.C / d.G;
         GgProb P;

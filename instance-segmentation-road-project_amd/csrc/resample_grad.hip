@@ -12,7 +12,7 @@
 // no bit-equal coordinates between forward and backward; the test decides.  This file is compiled without FP contraction and
 // with correctly rounded division (Makefile): a coordinate is the float32 value of its expression, one rounding per
 // operation in the order written, whatever the compiler would have fused.
-#include "common.h"
+#include "slice_sum.h"
 
 namespace {
 
@@ -304,11 +304,6 @@ global_mean_grad_kernel(const float *__restrict__ dpool, const float *add, float
     st4(dx + idx * 4, v);
 }
 
-bool rg_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
-}
-
 }  // namespace
 
 extern "C" int ml_roi_crop_resize_grad_f32(const ml_roi_grad_level *levels, int32_t n_levels, const float *rows,
@@ -332,8 +327,8 @@ extern "C" int ml_roi_crop_resize_grad_f32(const ml_roi_grad_level *levels, int3
         const long long px = (long long)d.Hf * d.Wf;
         ML_REQUIRE((long long)B * px < (1ll << 31), "%s: level %d: too many pixels", what, i);
         const long long dx_bytes = (long long)B * px * C * 4, dy_bytes = (long long)B * d.n_l * ch * cw * C * 4;
-        ML_REQUIRE(!rg_overlap(d.dx, dx_bytes, d.dy, dy_bytes), "%s: level %d: dx may not overlap dy", what, i);
-        ML_REQUIRE(!d.add || d.add == d.dx || !rg_overlap(d.dx, dx_bytes, d.add, dx_bytes),
+        ML_REQUIRE(!ml_ranges_overlap(d.dx, dx_bytes, d.dy, dy_bytes), "%s: level %d: dx may not overlap dy", what, i);
+        ML_REQUIRE(ml_add_or_disjoint(d.dx, d.add, dx_bytes),
                    "%s: level %d: dx may be add itself, not a shifted view of it", what, i);
         RgLevel &P = A.lv[i];
         P.dy = d.dy; P.add = d.add; P.dx = d.dx; P.Hf = d.Hf; P.Wf = d.Wf; P.n_l = d.n_l;
@@ -370,9 +365,8 @@ extern "C" int ml_resize_bilinear_ac_grad_f32(const float *dy, const float *add,
     ML_REQUIRE(ml_aligned16(dy) && ml_aligned16(dx) && ml_aligned16(add), "%s: pointers must be 16-byte aligned", what);
     ML_REQUIRE((long long)B * H * W < (1ll << 31) && (long long)B * Ho * Wo < (1ll << 31), "%s: too many pixels", what);
     const long long dx_bytes = (long long)B * H * W * C * 4, dy_bytes = (long long)B * Ho * Wo * dy_cstride * 4;
-    ML_REQUIRE(!rg_overlap(dx, dx_bytes, dy, dy_bytes), "%s: dx may not overlap dy", what);
-    ML_REQUIRE(!add || add == dx || !rg_overlap(dx, dx_bytes, add, dx_bytes), "%s: dx may be add itself, not a shifted view of it",
-               what);
+    ML_REQUIRE(!ml_ranges_overlap(dx, dx_bytes, dy, dy_bytes), "%s: dx may not overlap dy", what);
+    ML_REQUIRE(ml_add_or_disjoint(dx, add, dx_bytes), "%s: dx may be add itself, not a shifted view of it", what);
     hipStream_t s = (hipStream_t)stream;
     const int CV = C / 4;
     if (H == 1 && W == 1) {
@@ -408,9 +402,8 @@ extern "C" int ml_global_mean_grad_f32(const float *dpool, const float *add, flo
     ML_REQUIRE(C % 4 == 0, "%s: C (%d) must be a multiple of 4 (16-byte accesses)", what, C);
     ML_REQUIRE(ml_aligned16(dpool) && ml_aligned16(dx) && ml_aligned16(add), "%s: pointers must be 16-byte aligned", what);
     const long long dx_bytes = (long long)B * HW * C * 4;
-    ML_REQUIRE(!rg_overlap(dx, dx_bytes, dpool, (long long)B * C * 4), "%s: dx may not overlap dpool", what);
-    ML_REQUIRE(!add || add == dx || !rg_overlap(dx, dx_bytes, add, dx_bytes), "%s: dx may be add itself, not a shifted view of it",
-               what);
+    ML_REQUIRE(!ml_ranges_overlap(dx, dx_bytes, dpool, (long long)B * C * 4), "%s: dx may not overlap dpool", what);
+    ML_REQUIRE(ml_add_or_disjoint(dx, add, dx_bytes), "%s: dx may be add itself, not a shifted view of it", what);
     const long long total = (long long)B * HW * (C / 4);
     ML_REQUIRE(total < (1ll << 31) * TPB, "%s: grid too large", what);
     hipLaunchKernelGGL(global_mean_grad_kernel, dim3(grid_for(total)), dim3(TPB), 0, (hipStream_t)stream, dpool, add, dx, HW, C / 4,

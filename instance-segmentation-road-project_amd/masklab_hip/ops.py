@@ -530,6 +530,79 @@ def deconv2x2_out1x1_multi(problems, ncls, act_mid, act_out, tape=None):
         _lib.check(fn(arr, n, K, cmid, ncls, cp, act_mid, act_out, _stream()), "ml_deconv2x2_out1x1")
 
 
+# ------------------------------------------------------------------ slice-sum weight gradients (csrc/slice_sum.h)
+def _slice_plan(entry_name, desc, *extra):
+    """-> (slices, pixels per slice, bytes of the partials) of one problem, from the library's plan entry: host only"""
+    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
+    _lib.check(getattr(_lib.load(), entry_name)(C.byref(desc), *extra, C.byref(slices), C.byref(sp), C.byref(nbytes)), entry_name)
+    return slices.value, sp.value, nbytes.value
+
+
+def _wgrad_pair(what, v, name):
+    if v is None:
+        return None, None
+    if isinstance(v, torch.Tensor):
+        return v, None
+    if len(v) != 2:
+        raise ValueError(f"{what}: `{name}` is a kernel tensor or a (kernel, bias) pair")
+    return v[0], v[1]
+
+
+def _wgrad_outputs(what, device, kshape, bshape, want_bias, add, out):
+    """add / out of a weight gradient, each a kernel tensor or a (kernel, bias) pair (out = add + gradient; out may be add
+    itself): shapes and dtypes first, they need no device -> (dkernel, dbias or None, add kernel, add bias)"""
+    add_k, add_b = _wgrad_pair(what, add, "add")
+    out_k, out_b = _wgrad_pair(what, out, "out")
+    named = (("add kernel", add_k, kshape), ("out kernel", out_k, kshape), ("add bias", add_b, bshape), ("out bias", out_b, bshape))
+    for name, t, shape in named:
+        if t is not None:
+            _grad_tensor(what, name, t, shape)
+    if not want_bias and (add_b is not None or out_b is not None):
+        raise ValueError(f"{what}: a bias `add` / `out` with want_bias=False")
+    for name, t, _ in named:
+        if t is not None:
+            _require_dev(t, name)
+    dk = torch.empty(kshape, dtype=torch.float32, device=device) if out_k is None else out_k
+    db = None if not want_bias else (torch.empty(bshape, dtype=torch.float32, device=device) if out_b is None else out_b)
+    return dk, db, add_k, add_b
+
+
+def _slice_sum_multi(prof, made, device, limit, desc_type, plan_entry, launch_entry, extra=(), workspace_bytes=None):
+    """The launch pairs of the weight-gradient problems `made`, a list of (descriptor, outputs, (flops, bytes, shape or None)):
+    at most `limit` problems ride in one pair, and a pair is cut where its partials would exceed the conv workspace (more
+    launches, the same bits).  extra: what the plan and launch entries take between the problems and the workspace;
+    workspace_bytes: None, or the size to give the launch (tests).  -> the problems' outputs"""
+    def split(cut):
+        return (_slice_sum_multi(prof, made[:cut], device, limit, desc_type, plan_entry, launch_entry, extra, workspace_bytes) +
+                _slice_sum_multi(prof, made[cut:], device, limit, desc_type, plan_entry, launch_entry, extra, workspace_bytes))
+
+    n = len(made)
+    if n == 0:
+        return []
+    if n > limit:
+        return split(limit)
+    lib = _lib.load()
+    plan = getattr(lib, plan_entry)
+    ws_bytes = int(lib.ml_conv2d_workspace_bytes())
+    arr = (desc_type * n)()
+    need, flops, nbytes = [], 0.0, 0.0
+    for i, (d, _, (f, nb, _)) in enumerate(made):
+        arr[i] = d
+        ws_i = C.c_int64()
+        _lib.check(plan(C.byref(d), *extra, None, None, C.byref(ws_i)), plan_entry)
+        need.append(ws_i.value)
+        flops += f
+        nbytes += nb
+    if n > 1 and sum(need) > ws_bytes:
+        # more partials than the conv workspace holds (maps far larger than the towers'): two launches, the same bits
+        return split(max(1, next(i for i in range(1, n + 1) if sum(need[:i]) > ws_bytes) - 1))
+    ws = workspace(ws_bytes, device, "conv")
+    given = ws.numel() if workspace_bytes is None else int(workspace_bytes)
+    with _Prof(prof, flops, nbytes, made[0][2][2] if n == 1 and made[0][2][2] else "multi x%d" % n):
+        _lib.check(getattr(lib, launch_entry)(arr, n, *extra, _ptr(ws), given, _stream()), launch_entry)
+    return [outs for _, outs, _ in made]
+
+
 # ------------------------------------------------------------------ fused mask-head tail, backward (csrc/deconv_out_grad.hip)
 def deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid, dy_image_stride=0, dy_base=0):
     """The ml_deconv_out_grad_problem of a problem without its tensors: geometry only (what the plan reads)."""
@@ -542,16 +615,12 @@ def deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid, dy_image_str
 def deconv2x2_out1x1_grad_plan(M, hw, w, rois_per_image, c_mid, ncls):
     """-> (slices, pixels per slice, bytes of the partials) of one tail-backward problem: ml_deconv2x2_out1x1_grad_plan, host
     only.  A function of the problem's geometry alone."""
-    d = deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid)
-    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    _lib.check(_lib.load().ml_deconv2x2_out1x1_grad_plan(C.byref(d), int(ncls), C.byref(slices), C.byref(sp), C.byref(nbytes)),
-               "ml_deconv2x2_out1x1_grad_plan")
-    return slices.value, sp.value, nbytes.value
+    return _slice_plan("ml_deconv2x2_out1x1_grad_plan", deconv2x2_out1x1_grad_geometry(M, hw, w, rois_per_image, c_mid), int(ncls))
 
 
 def _tail_grad_problem(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, out_kernel=None, out_bias=None):
-    """The checks of one tail-backward problem (dtypes and shapes first: they need no device) -> (descriptor, dT, dkernel,
-    dbias, (flops, bytes))"""
+    """The checks of one tail-backward problem (dtypes and shapes first: they need no device) -> (descriptor, (dT, dkernel,
+    dbias), (flops, bytes, None))"""
     what = "deconv2x2_out1x1_grad"
     for name, t in (("dy", dy), ("T", T), ("wo", wo)):
         _grad_tensor(what, name, t)
@@ -591,7 +660,7 @@ def _tail_grad_problem(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, out_k
     d.dy, d.t, d.wo, d.out, d.dkernel, d.dbias = (t.data_ptr() for t in (dy, T, wo, dT, dk, db))
     flops = 2.0 * M * 4 * cmid * ncls * 2
     nbytes = 4.0 * (2 * T.numel() + M * 4 * ncls)
-    return d, dT, dk, db, (flops, nbytes)
+    return d, (dT, dk, db), (flops, nbytes, None)
 
 
 def deconv2x2_out1x1_grad(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, out_kernel=None, out_bias=None,
@@ -610,35 +679,17 @@ def deconv2x2_out1x1_grad(dy, T, wo, hw, rois_per_image, dy_base=0, out=None, ou
 def deconv2x2_out1x1_grad_multi(problems, workspace_bytes=None):
     """ml_deconv2x2_out1x1_grad_f32: up to 4 RoI levels in one launch pair (more go in several launches).  problems: list
     of dicts with deconv2x2_out1x1_grad's arguments -> list of (dT, dkernel, dbias), the bits of the single calls."""
-    n = len(problems)
-    if n == 0:
+    if not problems:
         return []
-    if n > _lib.DECONV_OUT_MAX_PROBLEMS:
-        return (deconv2x2_out1x1_grad_multi(problems[:_lib.DECONV_OUT_MAX_PROBLEMS], workspace_bytes) +
-                deconv2x2_out1x1_grad_multi(problems[_lib.DECONV_OUT_MAX_PROBLEMS:], workspace_bytes))
     what = "deconv2x2_out1x1_grad"
     for pr in problems:
         _grad_tensor(what, "dy", pr["dy"])
     ncls = int(problems[0]["dy"].shape[-1])
     if any(int(pr["dy"].shape[-1]) != ncls for pr in problems):
         raise ValueError(f"{what}: the problems of one launch must share the class count")
-    made = [_tail_grad_problem(**pr) for pr in problems]
-    lib = _lib.load()
-    arr = (_lib.DeconvOutGradProblem * n)()
-    need, flops, nbytes = 0, 0.0, 0.0
-    for i, (d, _, _, _, (f, nb)) in enumerate(made):
-        arr[i] = d
-        ws_i = C.c_int64()
-        _lib.check(lib.ml_deconv2x2_out1x1_grad_plan(C.byref(d), ncls, None, None, C.byref(ws_i)), "ml_deconv2x2_out1x1_grad_plan")
-        need += ws_i.value
-        flops += f
-        nbytes += nb
-    # the partials live in the conv workspace, as the other weight gradients' do
-    ws = workspace(max(int(lib.ml_conv2d_workspace_bytes()), need), problems[0]["T"].device, "conv")
-    given = ws.numel() if workspace_bytes is None else int(workspace_bytes)
-    with _Prof("deconv2x2_out1x1_grad", flops, nbytes, f"multi x{n}"):
-        _lib.check(lib.ml_deconv2x2_out1x1_grad_f32(arr, n, ncls, _ptr(ws), given, _stream()), "ml_deconv2x2_out1x1_grad_f32")
-    return [(dT, dk, db) for _, dT, dk, db, _ in made]
+    return _slice_sum_multi(what, [_tail_grad_problem(**pr) for pr in problems], problems[0]["T"].device,
+                            _lib.DECONV_OUT_MAX_PROBLEMS, _lib.DeconvOutGradProblem, "ml_deconv2x2_out1x1_grad_plan",
+                            "ml_deconv2x2_out1x1_grad_f32", (ncls,), workspace_bytes)
 
 
 def deconv2x2_grad_relayout(dk1x1, db4):
@@ -1133,26 +1184,13 @@ def conv2d_wgrad_geometry(x_shape, p, stride=1, padding="same", dilation=1, in_c
 def conv2d_wgrad_plan(x_shape, p, **geometry):
     """-> (slices, pixels per slice, bytes of the partials) of one weight-gradient problem: ml_conv2d_wgrad_plan, host only.
     A function of the problem's geometry alone."""
-    g = conv2d_wgrad_geometry(x_shape, p, **geometry)
-    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    _lib.check(_lib.load().ml_conv2d_wgrad_plan(C.byref(g), C.byref(slices), C.byref(sp), C.byref(nbytes)), "ml_conv2d_wgrad_plan")
-    return slices.value, sp.value, nbytes.value
-
-
-def _wgrad_pair(what, v, name):
-    if v is None:
-        return None, None
-    if isinstance(v, torch.Tensor):
-        return v, None
-    if len(v) != 2:
-        raise ValueError(f"{what}: `{name}` is a kernel tensor or a (kernel, bias) pair")
-    return v[0], v[1]
+    return _slice_plan("ml_conv2d_wgrad_plan", conv2d_wgrad_geometry(x_shape, p, **geometry))
 
 
 def _wgrad_problem(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, dy_view=None, want_bias=True, add=None,
                    out=None):
-    """The checks of one weight-gradient problem (dtypes and shapes first: they need no device) -> (descriptor, dkernel,
-    dbias or None, the tensors it keeps alive)"""
+    """The checks of one weight-gradient problem (dtypes and shapes first: they need no device) -> (descriptor, (dkernel,
+    dbias or None), (flops, bytes, shape))"""
     what = "conv2d_wgrad"
     _grad_tensor(what, "x", x)
     if x.dim() != 4:
@@ -1162,20 +1200,9 @@ def _wgrad_problem(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, d
     g = conv2d_wgrad_geometry(x.shape, p, stride, padding, dilation, in_coff, vcs, vbs)
     d = g.conv
     vt, elem_off, vcs, vbs = _dy_view(what, dy, dy_view, d.B, d.Ho, d.Wo, p.cout)
-    kshape, bshape = (p.KH, p.KW, p.span, p.cout), (p.cout,)
-    add_k, add_b = _wgrad_pair(what, add, "add")
-    out_k, out_b = _wgrad_pair(what, out, "out")
-    for name, t, shape in (("add kernel", add_k, kshape), ("out kernel", out_k, kshape), ("add bias", add_b, bshape),
-                           ("out bias", out_b, bshape)):
-        if t is not None:
-            _grad_tensor(what, name, t, shape)
-    if not want_bias and (add_b is not None or out_b is not None):
-        raise ValueError(f"{what}: a bias `add` / `out` with want_bias=False")
-    for name, t in (("x", x), ("dy", vt), ("add kernel", add_k), ("out kernel", out_k), ("add bias", add_b), ("out bias", out_b)):
-        if t is not None:
-            _require_dev(t, name)
-    dk = torch.empty(kshape, dtype=torch.float32, device=x.device) if out_k is None else out_k
-    db = None if not want_bias else (torch.empty(bshape, dtype=torch.float32, device=x.device) if out_b is None else out_b)
+    dk, db, add_k, add_b = _wgrad_outputs(what, x.device, (p.KH, p.KW, p.span, p.cout), (p.cout,), want_bias, add, out)
+    _require_dev(x, "x")
+    _require_dev(vt, "dy")
     d.in_, d.out = x.data_ptr(), vt.data_ptr() + 4 * elem_off
     g.dkernel, g.dbias = dk.data_ptr(), None if db is None else db.data_ptr()
     g.add_kernel = None if add_k is None else add_k.data_ptr()
@@ -1184,7 +1211,7 @@ def _wgrad_problem(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, d
     flops = 2.0 * M * p.KH * p.KW * p.span * p.cout
     nbytes = 4 * (d.B * d.H * d.W * p.span + M * p.cout + dk.numel() * (2 if add_k is not None else 1))
     shape = f"M={p.span} N={p.cout} K={M} k{p.KH}x{p.KW} s{stride} d{dilation} HxW={d.H}x{d.W}"
-    return g, dk, db, (flops, nbytes, shape)
+    return g, (dk, db), (flops, nbytes, shape)
 
 
 def conv2d_wgrad(x, dy, dc, stride=1, padding="same", dilation=1, in_coff=0, dy_view=None, want_bias=True, add=None, out=None):
@@ -1202,34 +1229,18 @@ def conv2d_wgrad_multi(problems):
     """ml_conv2d_wgrad_multi_f32: several weight-gradient problems in one launch pair (the five un-shared pyramid levels of a
     tower depth).  problems: list of dicts with conv2d_wgrad's arguments -> list of (dkernel, dbias or None), the bits of the
     single calls."""
-    n = len(problems)
-    if n == 0:
+    if not problems:
         return []
-    if n > _lib.CONV_WGRAD_MAX_PROBLEMS:
-        return (conv2d_wgrad_multi(problems[:_lib.CONV_WGRAD_MAX_PROBLEMS]) +
-                conv2d_wgrad_multi(problems[_lib.CONV_WGRAD_MAX_PROBLEMS:]))
-    made = [_wgrad_problem(**pr) for pr in problems]
-    lib = _lib.load()
-    ws_bytes = int(lib.ml_conv2d_workspace_bytes())
-    need = []
-    for g, _, _, _ in made:
-        nb = C.c_int64()
-        _lib.check(lib.ml_conv2d_wgrad_plan(C.byref(g), None, None, C.byref(nb)), "ml_conv2d_wgrad_plan")
-        need.append(nb.value)
-    if n > 1 and sum(need) > ws_bytes:
-        # more partials than the conv workspace holds (maps far larger than the towers'): two launches, the same bits
-        cut = max(1, next(i for i in range(1, n + 1) if sum(need[:i]) > ws_bytes) - 1)
-        return conv2d_wgrad_multi(problems[:cut]) + conv2d_wgrad_multi(problems[cut:])
-    arr = (_lib.ConvWgradDesc * n)()
-    flops, nbytes = 0.0, 0.0
-    for i, (g, _, _, (f, nb, _)) in enumerate(made):
-        arr[i] = g
-        flops += f
-        nbytes += nb
-    ws = workspace(ws_bytes, problems[0]["x"].device, "conv")
-    with _Prof("conv_wgrad", flops, nbytes, made[0][3][2] if n == 1 else "multi x%d" % n):
-        _lib.check(lib.ml_conv2d_wgrad_multi_f32(arr, n, _ptr(ws), ws.numel(), _stream()), "ml_conv2d_wgrad_multi_f32")
-    return [(dk, db) for _, dk, db, _ in made]
+    return _slice_sum_multi("conv_wgrad", [_wgrad_problem(**pr) for pr in problems], problems[0]["x"].device,
+                            _lib.CONV_WGRAD_MAX_PROBLEMS, _lib.ConvWgradDesc, "ml_conv2d_wgrad_plan", "ml_conv2d_wgrad_multi_f32")
+
+
+def _in_hw(what, in_hw, B_default):
+    """in_hw = (H, W) of a conv's input, or its shape (B, H, W[, C]) -> (B, or B_default where in_hw has none, H, W)"""
+    hw = tuple(int(v) for v in in_hw)
+    if len(hw) not in (2, 3, 4):
+        raise ValueError(f"{what}: in_hw is (H, W) or the input's shape (B, H, W[, C]), got {hw}")
+    return (B_default, *hw) if len(hw) == 2 else hw[:3]
 
 
 def _dgrad_problem(dy, dc, in_hw, stride=1, padding="same", dilation=1, dy_view=None, add=None, out=None):
@@ -1237,16 +1248,14 @@ def _dgrad_problem(dy, dc, in_hw, stride=1, padding="same", dilation=1, dy_view=
     what = "conv2d_dgrad"
     p = dc.p
     _dense_only(what, p)
-    hw = tuple(int(v) for v in in_hw)
-    if len(hw) not in (2, 3, 4):
-        raise ValueError(f"{what}: in_hw is (H, W) or the input's shape (B, H, W[, C]), got {hw}")
-    H, W = hw[-2:] if len(hw) == 2 else hw[1:3]
+    B, H, W = _in_hw(what, in_hw, None)
     pads = dgrad_padding(H, W, p.kh_real, p.kw_real, stride, dilation, padding)        # refuses stride 2 by name
     Ho, Wo, _, _ = resolve_padding(H, W, p.kh_real, p.kw_real, stride, dilation, padding)
     vt0 = dy if dy_view is None else dy_view[0]
     if not isinstance(vt0, torch.Tensor):
         raise ValueError(f"{what}: `dy` must be a tensor")
-    B = hw[0] if len(hw) > 2 else int(vt0.shape[0])          # (H, W) alone: dy, or the viewed tensor, is batch-major
+    if B is None:
+        B = int(vt0.shape[0])                                # (H, W) alone: dy, or the viewed tensor, is batch-major
     vt, elem_off, vcs, vbs = _dy_view(what, dy, dy_view, B, Ho, Wo, p.cout)
     shape = (B, H, W, p.span)
     for name, t in (("add", add), ("out", out)):
@@ -1325,17 +1334,13 @@ def dwconv3x3_wgrad_geometry(x_shape, C=None, stride=1, padding="same", dilation
 def dwconv3x3_wgrad_plan(x_shape, **geometry):
     """-> (slices, pixels per slice, bytes of the partials) of one depthwise weight-gradient problem:
     ml_dwconv3x3_wgrad_plan, host only.  A function of the problem's geometry alone."""
-    d = dwconv3x3_wgrad_geometry(x_shape, **geometry)
-    slices, sp, nbytes = C.c_int32(), C.c_int32(), C.c_int64()
-    _lib.check(_lib.load().ml_dwconv3x3_wgrad_plan(C.byref(d), C.byref(slices), C.byref(sp), C.byref(nbytes)),
-               "ml_dwconv3x3_wgrad_plan")
-    return slices.value, sp.value, nbytes.value
+    return _slice_plan("ml_dwconv3x3_wgrad_plan", dwconv3x3_wgrad_geometry(x_shape, **geometry))
 
 
 def _dw_wgrad_problem(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy_coff=0, want_bias=True, add=None, out=None,
                       C=None, kernel_size=(3, 3)):
     """The checks of one depthwise weight-gradient problem (dtypes and shapes first: they need no device)
-    -> (descriptor, dkernel, dbias or None, algorithmic bytes)"""
+    -> (descriptor, (dkernel, dbias or None), (flops, bytes, shape))"""
     what = "dwconv3x3_wgrad"
     _grad_tensor(what, "x", x)
     _grad_tensor(what, "dy", dy)
@@ -1345,20 +1350,9 @@ def _dw_wgrad_problem(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy
     d = dwconv3x3_wgrad_geometry(x.shape, Cc, stride, padding, dilation, in_coff, int(dy.shape[3]), dy_coff, kernel_size)
     if tuple(dy.shape[:3]) != (d.B, d.Ho, d.Wo):
         raise ValueError(f"{what}: `dy` is {tuple(dy.shape)}, expected {(d.B, d.Ho, d.Wo)} pixels")
-    kshape, bshape = (3, 3, Cc, 1), (Cc,)
-    add_k, add_b = _wgrad_pair(what, add, "add")
-    out_k, out_b = _wgrad_pair(what, out, "out")
-    for name, t, shape in (("add kernel", add_k, kshape), ("out kernel", out_k, kshape), ("add bias", add_b, bshape),
-                           ("out bias", out_b, bshape)):
-        if t is not None:
-            _grad_tensor(what, name, t, shape)
-    if not want_bias and (add_b is not None or out_b is not None):
-        raise ValueError(f"{what}: a bias `add` / `out` with want_bias=False")
-    for name, t in (("x", x), ("dy", dy), ("add kernel", add_k), ("out kernel", out_k), ("add bias", add_b), ("out bias", out_b)):
-        if t is not None:
-            _require_dev(t, name)
-    dk = torch.empty(kshape, dtype=torch.float32, device=x.device) if out_k is None else out_k
-    db = None if not want_bias else (torch.empty(bshape, dtype=torch.float32, device=x.device) if out_b is None else out_b)
+    dk, db, add_k, add_b = _wgrad_outputs(what, x.device, (3, 3, Cc, 1), (Cc,), want_bias, add, out)
+    _require_dev(x, "x")
+    _require_dev(dy, "dy")
     d.x, d.dy = x.data_ptr(), dy.data_ptr()
     d.dkernel, d.dbias = dk.data_ptr(), None if db is None else db.data_ptr()
     d.add_kernel = None if add_k is None else add_k.data_ptr()
@@ -1366,7 +1360,7 @@ def _dw_wgrad_problem(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy
     M = d.B * d.Ho * d.Wo
     nbytes = 4 * (d.B * d.H * d.W * Cc + M * Cc + 9 * Cc * (2 if add_k is not None else 1) +
                   (0 if db is None else Cc * (2 if add_b is not None else 1)))
-    return d, dk, db, (18.0 * M * Cc, nbytes, f"C={Cc} K={M} s{stride} d{dilation} HxW={d.H}x{d.W}")
+    return d, (dk, db), (18.0 * M * Cc, nbytes, f"C={Cc} K={M} s{stride} d{dilation} HxW={d.H}x{d.W}")
 
 
 def dwconv3x3_wgrad(x, dy, stride=1, padding="same", dilation=1, in_coff=0, dy_coff=0, want_bias=True, add=None, out=None,
@@ -1386,33 +1380,11 @@ def dwconv3x3_wgrad_multi(problems, workspace_bytes=None):
     """ml_dwconv3x3_wgrad_multi_f32: up to 8 depthwise weight-gradient problems in one launch pair (the three dilations of
     the ASPP ride together; more go in several launches).  problems: list of dicts with dwconv3x3_wgrad's arguments
     -> list of (dkernel, dbias or None), the bits of the single calls."""
-    n = len(problems)
-    if n == 0:
+    if not problems:
         return []
-    if n > _lib.DWCONV_GRAD_MAX_PROBLEMS:
-        return (dwconv3x3_wgrad_multi(problems[:_lib.DWCONV_GRAD_MAX_PROBLEMS], workspace_bytes) +
-                dwconv3x3_wgrad_multi(problems[_lib.DWCONV_GRAD_MAX_PROBLEMS:], workspace_bytes))
-    made = [_dw_wgrad_problem(**pr) for pr in problems]
-    lib = _lib.load()
-    ws_bytes = int(lib.ml_conv2d_workspace_bytes())
-    arr = (_lib.DwGradDesc * n)()
-    need, flops, nbytes = [], 0.0, 0.0
-    for i, (d, _, _, (f, nb, _)) in enumerate(made):
-        arr[i] = d
-        ws_i = C.c_int64()
-        _lib.check(lib.ml_dwconv3x3_wgrad_plan(C.byref(d), None, None, C.byref(ws_i)), "ml_dwconv3x3_wgrad_plan")
-        need.append(ws_i.value)
-        flops += f
-        nbytes += nb
-    if n > 1 and sum(need) > ws_bytes:
-        # more partials than the conv workspace holds: two launches, the same bits
-        cut = max(1, next(i for i in range(1, n + 1) if sum(need[:i]) > ws_bytes) - 1)
-        return dwconv3x3_wgrad_multi(problems[:cut], workspace_bytes) + dwconv3x3_wgrad_multi(problems[cut:], workspace_bytes)
-    ws = workspace(ws_bytes, problems[0]["x"].device, "conv")
-    given = ws.numel() if workspace_bytes is None else int(workspace_bytes)
-    with _Prof("dwconv3x3_wgrad", flops, nbytes, made[0][3][2] if n == 1 else "multi x%d" % n):
-        _lib.check(lib.ml_dwconv3x3_wgrad_multi_f32(arr, n, _ptr(ws), given, _stream()), "ml_dwconv3x3_wgrad_multi_f32")
-    return [(dk, db) for _, dk, db, _ in made]
+    return _slice_sum_multi("dwconv3x3_wgrad", [_dw_wgrad_problem(**pr) for pr in problems], problems[0]["x"].device,
+                            _lib.DWCONV_GRAD_MAX_PROBLEMS, _lib.DwGradDesc, "ml_dwconv3x3_wgrad_plan",
+                            "ml_dwconv3x3_wgrad_multi_f32", (), workspace_bytes)
 
 
 def _dw_dgrad_problem(dy, wgt, in_hw, stride=1, padding="same", dilation=1, dy_coff=0, C=None, add=None, out=None,
@@ -1423,11 +1395,8 @@ def _dw_dgrad_problem(dy, wgt, in_hw, stride=1, padding="same", dilation=1, dy_c
     _dw_stride(what, stride, kernel_size)
     if dy.dim() != 4:
         raise ValueError(f"{what}: `dy` must be [B, Ho, Wo, C], got {tuple(dy.shape)}")
-    hw = tuple(int(v) for v in in_hw)
-    if len(hw) not in (2, 3, 4):
-        raise ValueError(f"{what}: in_hw is (H, W) or the input's shape (B, H, W[, C]), got {hw}")
-    H, W = hw[-2:] if len(hw) == 2 else hw[1:3]
     B, Cdy = int(dy.shape[0]), int(dy.shape[3])
+    B_in, H, W = _in_hw(what, in_hw, B)
     Cc = Cdy - dy_coff if C is None else int(C)
     _dw_slice(what, "dy", Cdy, dy_coff, Cc)
     if wgt.dim() != 2 or tuple(wgt.shape) != (9, Cc):
@@ -1435,7 +1404,7 @@ def _dw_dgrad_problem(dy, wgt, in_hw, stride=1, padding="same", dilation=1, dy_c
     Ho, Wo, pt, pl = resolve_padding(H, W, 3, 3, stride, dilation, padding)
     if Ho < 1 or Wo < 1:
         raise ValueError(f"{what}: the kernel does not fit the {H} x {W} input")
-    if tuple(dy.shape[:3]) != (B, Ho, Wo) or (len(hw) > 2 and hw[0] != B):
+    if tuple(dy.shape[:3]) != (B, Ho, Wo) or B_in != B:
         raise ValueError(f"{what}: `dy` is {tuple(dy.shape)}, expected {(B, Ho, Wo)} pixels for a {H} x {W} input")
     dx = _grad_out(what, (B, H, W, Cc), dy.device, add, out)
     _require_dev(dy, "dy")

@@ -98,6 +98,9 @@ LEVELS = [(2, 16, 16, 32), (2, 8, 8, 32), (2, 4, 4, 32), (2, 2, 2, 32), (2, 1, 1
 for _i, _s in enumerate(LEVELS):
     WGRAD_CASES[f"levels{_i}"] = dict(x=_s, cout=32, k=3)
 LEVEL_NAMES = [f"levels{i}" for i in range(len(LEVELS))]
+# 9 216 pixels = 18 slices of 512: one pass of the finish kernel's sixteen-wide loop, then two remainders (the table's last
+# row: the cases before it keep their seeds)
+WGRAD_CASES["slices18"] = dict(x=(1, 96, 96, 4), cout=8, k=3)
 VIEW_GAP, VIEW_OFF = 152, 30          # floats between the images of a dy view beyond their own, and before the first
 
 

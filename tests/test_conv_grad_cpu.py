@@ -117,6 +117,8 @@ def test_the_plan_of_every_case_reaches_the_arm_its_row_names(name):
         assert (pixels % sp) % 32 != 0                                      # and a ragged last 32-pixel chunk inside it
     elif name == "long_slices":
         assert sp == R.SLICE_MAX and slices == 128 and pixels % sp != 0     # the longest fp32 chains the plan makes
+    elif name == "slices18":
+        assert sp == 512 and slices == 18                                   # the finish kernel's sixteen-wide loop and its remainder
     else:
         assert slices == 1
     if name == "cout75_view":

@@ -10,7 +10,7 @@ Largest |got - want| / S measured on the MI355X, per case (the bar is 1e-5):
     dW / db   tower 1.8e-07 / 8.0e-09   cout75_view 2.8e-07 / 6.3e-09   cin_tail 1.4e-07 / 5.8e-09   two_tiles 2.5e-07 / 1.5e-08
               stride2 2.4e-07 / 1.1e-08   k1s2 1.4e-07 / 1.1e-08   dil3 2.1e-07 / 1.6e-08   dead_taps 1.1e-07 / 2.6e-08
               one_pixel 8.6e-08 / 5.4e-08   k5 2.3e-07 / 1.3e-08   in_slice 2.3e-07 / 7.9e-09   no_bias 2.1e-07 / -
-              slices 5.9e-08 / 1.7e-09   long_slices (1 024-pixel slices) 7.6e-09 / 1.6e-10
+              slices 5.9e-08 / 1.7e-09   long_slices (1 024-pixel slices) 7.6e-09 / 1.6e-10   slices18 2.9e-08 / 7.4e-10
               levels0..4 1.9e-07, 2.3e-07, 1.5e-07, 1.6e-07, 9.2e-08 / 7.0e-09 .. 4.7e-08
     dx        tower 1.8e-07   cout75_view 1.0e-07   dil3 1.7e-07   k1 2.0e-07   valid 2.0e-07   wino128 (Winograd) 1.3e-07
               tower under "f32x3" 8.3e-08; with add= the same figures to within 2e-08
@@ -107,6 +107,32 @@ def test_conv2d_wgrad_levels_in_one_launch_are_their_single_launches():
     both = DM.snapshot(ops.conv2d_wgrad_multi([args for args, _ in others]))
     for name, b, (args, _) in zip(mixed, both, others):
         _bits(ops.conv2d_wgrad(**args), b, f"{name}: alone against a mixed launch")
+
+
+def test_conv2d_wgrad_is_the_ascending_fp64_fold_of_its_partials():
+    """The finish kernel's sum (csrc/slice_sum.h), restated on the host from the partials the launch left in the conv
+    workspace: 18 slices, so the sixteen-wide loop runs once and the remainder loop twice.  part [18][T cin cout] fp32 at
+    offset 0, bpart [18][cout] at the next multiple of 256 bytes; added in ascending slice order in float64 and rounded once,
+    these are the very additions the kernel makes: bit equality, no tolerance."""
+    from masklab_hip import ops
+    g, x, w = wgrad_reference("slices18")[:3]
+    args, _ = _wgrad_problem("slices18")
+    slices, _, nbytes = ops.conv2d_wgrad_plan(g["x_shape"], args["dc"].p)
+    assert slices == 18
+    dk, db = ops.conv2d_wgrad(**args)
+    torch.cuda.synchronize()
+    tcc, cout = w.size, g["cout"]
+    boff = (slices * tcc * 4 + 255) // 256 * 256
+    assert nbytes == boff + (slices * cout * 4 + 255) // 256 * 256
+    ws = host(ops.workspace(0, args["x"].device, "conv")[:nbytes])
+    part = ws[:slices * tcc * 4].view(np.float32).reshape(slices, tcc)
+    bpart = ws[boff:boff + slices * cout * 4].view(np.float32).reshape(slices, cout)
+    for got, p, what in ((dk, part, "dkernel"), (db, bpart, "dbias")):
+        t = np.zeros(p.shape[1], np.float64)
+        for s in range(slices):
+            t = t + p[s].astype(np.float64)
+        np.testing.assert_array_equal(host(got).reshape(-1).view(np.uint32), t.astype(np.float32).view(np.uint32),
+                                      err_msg=f"slices18: {what} against the host fold of its partials")
 
 
 # ------------------------------------------------------------------ the data gradient
