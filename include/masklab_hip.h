@@ -78,7 +78,8 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_dwconv3x3_grad_desc, ml_dwconv3x3_wgrad_multi_f32 /
                                             _wgrad_plan, ml_dwconv3x3_dgrad_multi_f32, ml_relu_grad_f32;
                                             (additive, same version) ml_deconv2x2_out1x1_tape_f32, ml_deconv_out_grad_problem,
-                                            ml_deconv2x2_out1x1_grad_f32 / _grad_plan, ml_deconv2x2_grad_relayout_f32 */
+                                            ml_deconv2x2_out1x1_grad_f32 / _grad_plan, ml_deconv2x2_grad_relayout_f32;
+                                            (additive, same version) ml_repack_job, ml_repack_plan, ml_repack_f32 */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -1323,6 +1324,69 @@ int ml_optimizer_scalars(int32_t kind, ml_opt_state *state, ml_opt_scalars *scal
 /* table [n] and scalars: device memory; total_chunks as ml_optimizer_plan returned it for this table.                   */
 int ml_optimizer_apply_f32(int32_t kind, const ml_opt_tensor *table, int32_t n, int64_t total_chunks, const ml_opt_scalars *scalars,
                            void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Re-pack: master weights on the device in the Keras layout -> every packed form the kernels read, written in place into
+ * the tensors that already hold them (csrc/repack.hip).  What a training step runs after the optimizer: the addresses stay,
+ * so a captured graph replays with the new weights.  One launch on `stream` for every job of the device table, no
+ * workspace, no atomics, no host read.  Every element of every destination is written exactly once, pads and zero blocks
+ * included: the result does not depend on what the memory held.
+ * A job is one master seen as element (tap, c, n) = src[tap s_tap + c s_c + n s_n] (strides in floats), N outputs, C input
+ * channels, KH x KW taps:
+ *   Conv2D kernel[kh,kw,cin,cout]            N = cout, C = cin, s_n = 1, s_c = cout, s_tap = cin cout; a cin slice of a
+ *                                            1x1 kernel moves src by c0 cout and takes C = the slice's width
+ *   Conv2DTranspose kernel[2,2,cout,cin]     N = 4 cout (column (a 2 + b) cout + o), C = cin, s_n = cin, s_c = 1, one tap;
+ *                                            bias_n = cout; bias_reps = 4 for the bias of the same GEMM run as a 1x1 conv
+ * and up to nine destinations, each optional, each the bits of the host function that defines it (masklab_hip/packing.py,
+ * ops.DeviceConv):
+ *   fwd_wgt     pack_dense: [fwd_n_pad][taps][fwd_span_pad], zero padded
+ *   fwd_x3      the same, every 32-float chunk as 32 halves hi(w) then 32 halves 2^11 (w - hi(w)), round to nearest even
+ *   fwd_h       [fwd_n_pad][taps][fwd_span_pad_h] halves
+ *   fwd_wino    pack_winograd: U = G g G^T in fp64 rounded once, [max(4, fwd_n_pad / 32)][fwd_span_pad / 8][8][32][16]
+ *               (3x3 only; each sum starts at +0.0 as the host's does, so the bits are the host's wherever the fp64 sums
+ *               are exact, and differ at most by the order of the additions elsewhere; terms with a zero coefficient of
+ *               G are left out, so an Inf / NaN weight spoils only the positions it has a coefficient in, where the
+ *               host's 0 * Inf spoils all sixteen)
+ *   bias        [bias_reps][bias_n] copies of src_bias [bias_n]
+ *   tr_*        the four forms of pack_dense_transposed (the data gradient's weights): element (tap, c, n) at row c, tap
+ *               taps - 1 - tap, channel n; tr_n_pad >= C rows, tr_span_pad >= N rounded up to 4
+ * or, kind = ML_REPACK_TABLE, pack_out1x1_table of a 1x1 kernel [1,1,C,N]: `table` [C / 32][16][2][cp] and `table_bias` [cp]
+ * (zeros where src_bias is NULL), cp = the power of two >= N.
+ * Work units: a conv job is cut into [32 n][32 c][taps] tiles over the largest padded extent any of its forms has, nb x cb
+ * of them, plus one unit for a bias; a table job is one unit.  A tile is read once and feeds every form of the job.
+ * ------------------------------------------------------------------------------------------- */
+enum { ML_REPACK_CONV = 0, ML_REPACK_TABLE = 1 };
+typedef struct ml_repack_job {
+    const float *src;              /* the master's element (0, 0, 0)                                 */
+    const float *src_bias;         /* [bias_n] or NULL                                                   */
+    int64_t s_n, s_c, s_tap;       /* strides in floats                                              */
+    int32_t kind;                  /* ML_REPACK_*                                                    */
+    int32_t N, C, KH, KW;
+    int32_t cpp_shift;             /* of the packing: 30, a row-span (image) packing is refused      */
+    int32_t group_cin_step;        /* of the packing: 0, a grouped packing is refused                */
+    int32_t bias_reps;
+    float *fwd_wgt, *fwd_x3;
+    void *fwd_h;
+    float *fwd_wino;
+    float *bias;
+    float *tr_wgt, *tr_x3;
+    void *tr_h;
+    float *tr_wino;
+    float *table, *table_bias;
+    int32_t fwd_n_pad, fwd_span_pad, fwd_span_pad_h;
+    int32_t tr_n_pad, tr_span_pad, tr_span_pad_h;
+    int32_t cp;
+    int32_t nb, cb;                /* tiles along n and c (ml_repack_plan fills them)                */
+    int32_t bias_n;                /* floats of src_bias (conv jobs; a table job's bias has N)       */
+    int64_t first_unit;            /* units of the jobs in front (ml_repack_plan fills it)           */
+} ml_repack_job;
+/* Host.  Validates the n jobs of a table in HOST memory and fills nb, cb, first_unit -> the number of work units, or
+ * ML_E_BADARG, each refusal by name: a destination that overlaps a master or another destination (masters may share
+ * memory), a row-span or grouped packing, more than 5 x 5 taps, a Winograd form of a kernel that is not 3x3, extents that
+ * do not hold the kernel.                                                                                               */
+int64_t ml_repack_plan(ml_repack_job *host_table, int32_t n);
+/* table [n]: device memory; total_units as ml_repack_plan returned it for this table.                                    */
+int ml_repack_f32(const ml_repack_job *table, int32_t n, int64_t total_units, void *stream);
 
 #ifdef __cplusplus
 }

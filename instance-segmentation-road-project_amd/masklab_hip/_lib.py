@@ -134,6 +134,19 @@ class OptScalars(C.Structure):
                 ("eta_wd", C.c_float), ("rectified", C.c_int32), ("decays", C.c_int32)]
 
 
+class RepackJob(C.Structure):
+    """Mirror of `ml_repack_job` (include/masklab_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("src_bias", C.c_void_p), ("s_n", C.c_int64), ("s_c", C.c_int64), ("s_tap", C.c_int64),
+                ("kind", C.c_int32), ("N", C.c_int32), ("C", C.c_int32), ("KH", C.c_int32), ("KW", C.c_int32),
+                ("cpp_shift", C.c_int32), ("group_cin_step", C.c_int32), ("bias_reps", C.c_int32),
+                ("fwd_wgt", C.c_void_p), ("fwd_x3", C.c_void_p), ("fwd_h", C.c_void_p), ("fwd_wino", C.c_void_p),
+                ("bias", C.c_void_p), ("tr_wgt", C.c_void_p), ("tr_x3", C.c_void_p), ("tr_h", C.c_void_p),
+                ("tr_wino", C.c_void_p), ("table", C.c_void_p), ("table_bias", C.c_void_p),
+                ("fwd_n_pad", C.c_int32), ("fwd_span_pad", C.c_int32), ("fwd_span_pad_h", C.c_int32),
+                ("tr_n_pad", C.c_int32), ("tr_span_pad", C.c_int32), ("tr_span_pad_h", C.c_int32),
+                ("cp", C.c_int32), ("nb", C.c_int32), ("cb", C.c_int32), ("bias_n", C.c_int32), ("first_unit", C.c_int64)]
+
+
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 GN_MAX_PROBLEMS = 8
 CONV_WGRAD_MAX_PROBLEMS = 8                                          # ML_CONV_WGRAD_MAX_PROBLEMS
@@ -286,7 +299,10 @@ SIGNATURES = {
     "ml_optimizer_plan": (_i64, [_vp, _i32]),
     "ml_optimizer_scalars": (C.c_int, [_i32, _vp, _vp] + [_f64] * 6 + [_vp]),
     "ml_optimizer_apply_f32": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _vp]),
+    "ml_repack_plan": (_i64, [_vp, _i32]),
+    "ml_repack_f32": (C.c_int, [_vp, _i32, _i64, _vp]),
 }
+REPACK_CONV, REPACK_TABLE = 0, 1                                    # ML_REPACK_*
 OPT_RADAM, OPT_ADAMW = 0, 1                                         # ML_OPT_*
 OPT_CHUNK = 4096                                                    # ML_OPT_CHUNK
 POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1                           # ML_POLYGON_*

@@ -128,6 +128,43 @@ class Layer:
     def _load_own(self, weights, device):
         pass
 
+    # -- training: the weights as device tensors, and the packings that follow them ("Re-pack")
+    def device_params(self):
+        """{full weight name: float32 device tensor} of this layer and everything below it, the names of init_weights().
+        Where the kernels read the Keras layout the tensor is the one they read; elsewhere the layer uploads a master once
+        and binds its packings to it (ops.DeviceConv.bind_master), so that repack() brings them up to a stepped master.
+        load_weights() unbinds: the next call uploads again.  A layer that cannot be trained yet raises NotImplementedError."""
+        out = collections.OrderedDict(self._own_device_params())
+        for ch in self.children():
+            out.update(ch.device_params())
+        return out
+
+    def _own_device_params(self):
+        if self._specs:
+            raise NotImplementedError(f"{type(self).__name__}.device_params ('{self.name}'): this layer's weights "
+                                      f"({', '.join(self._specs)}) cannot be trained yet: it has no device parameters")
+        return {}
+
+    def repack_jobs(self):
+        """The re-pack jobs of every packing under this layer that follows a master (after device_params())."""
+        jobs = list(self._own_repack_jobs())
+        for ch in self.children():
+            jobs += ch.repack_jobs()
+        return jobs
+
+    def _own_repack_jobs(self):
+        return []
+
+    def repack(self):
+        """Brings every packing under this layer up to its stepped master, in one launch (ops.repack_weights).  The job list
+        is kept while no packing was made, bound or given a new form anywhere (ops.forms_epoch), so a step that re-packs the
+        same forms as the last hands the table the same job dicts and skips the host checks."""
+        if getattr(self, "_repack_table", None) is None:
+            self._repack_table, self._repack_kept = ops.RepackTable(), (None, None)
+        if self._repack_kept[0] != ops.forms_epoch():
+            self._repack_kept = (ops.forms_epoch(), self.repack_jobs())
+        ops.repack_weights(self._repack_kept[1], self._repack_table)
+
     def _get(self, weights, key):
         full = f"{self.name}/{key}"
         if full not in weights:
@@ -151,6 +188,12 @@ def init_weights(specs, seed=0):
 # =========================================================================== primitives
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _check_f32_training(what):
+    if ops.CONV_MATH in ("f16", "f16s"):
+        raise NotImplementedError(f"{what}: training runs in float32 only; set_conv_math({ops.CONV_MATH!r}) / half tensors are "
+                                  f"not trained")
 
 
 class Conv2D(Layer):
@@ -237,6 +280,44 @@ class Conv2D(Layer):
 
     def _load_own(self, weights, device):
         self.dev = ops.DeviceConv(self.pack(weights), device)
+
+    def _check_trainable(self):
+        what = f"{type(self).__name__}.device_params ('{self.name}')"
+        if type(self) is not Conv2D:
+            raise NotImplementedError(f"{what}: not trainable yet: dense Conv2D layers only")
+        if self.fold_bn:
+            raise NotImplementedError(f"{what}: a layer with fold_bn (an inference BatchNormalization folded into its weights) "
+                                      f"cannot be re-packed from a stepped kernel")
+        if self.image_input:
+            raise NotImplementedError(f"{what}: a layer with image_input (the row-span stem) is not re-packed on the device")
+        _check_f32_training(what)
+        if self.dev is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+
+    def bind_params(self, kernel=None):
+        """Uploads this layer's masters (kernel: a device tensor to use as the kernel's master instead) and binds self.dev,
+        unless that was done for the weights now loaded.  -> {"kernel": ..., "bias": ...}"""
+        self._check_trainable()
+        if kernel is not None and getattr(self, "_params_of", None) is self.dev and self._params["kernel"] is not kernel:
+            raise RuntimeError(f"Conv2D.bind_params ('{self.name}'): the layer already follows another master kernel for the "
+                               f"weights now loaded (device_params() was called on it directly): load_weights first")
+        if getattr(self, "_params_of", None) is not self.dev:
+            import torch
+            device = self.dev.wgt.device
+            if kernel is None:
+                kernel = torch.from_numpy(packing.unpack_dense(self.dev.p)).to(device)
+            params = {"kernel": kernel}
+            if self.use_bias:
+                params["bias"] = torch.from_numpy(np.array(self.dev.p.bias, np.float32)).to(device)
+            self.dev.bind_master(kernel, params.get("bias"))
+            self._params, self._params_of = params, self.dev
+        return self._params
+
+    def _own_device_params(self):
+        return {f"{self.name}/{k}": v for k, v in self.bind_params().items()}
+
+    def _own_repack_jobs(self):
+        return self.dev.repack_jobs() if self.dev is not None and self.dev.follows_master else []
 
     def call(self, x, residual=None, out=None, out_coff=0, out_dtype=None, gn_partials=None, **kwargs):
         if self.dev is None:
@@ -434,6 +515,19 @@ class DepthwiseConv2D(Layer):
         self.wgt = torch.from_numpy(packing.pack_depthwise(k)).to(device)
         self.bias = None if b is None else torch.from_numpy(np.ascontiguousarray(b)).to(device)
 
+    def _own_device_params(self):
+        what = f"DepthwiseConv2D.device_params ('{self.name}')"
+        if self.fold_bn:
+            raise NotImplementedError(f"{what}: a layer with fold_bn (an inference BatchNormalization folded into its weights) "
+                                      f"cannot be trained from its folded weights")
+        _check_f32_training(what)
+        if self.wgt is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+        out = {f"{self.name}/depthwise_kernel": self.wgt.view(3, 3, self.C, 1)}     # [9][C] IS the Keras layout: no copy
+        if self.use_bias:
+            out[f"{self.name}/bias"] = self.bias
+        return out
+
     def call(self, x, **kwargs):
         if self.wgt is None:
             raise RuntimeError(f"layer '{self.name}' has no weights loaded")
@@ -503,6 +597,26 @@ class Conv2DTranspose(Layer):
         # transposed conv's weight and data gradients on (dev1x1.dgrad: its pack_dense_transposed, made on first use)
         self.dev1x1 = ops.DeviceConv(packing.pack_dense(packing.transpose2x2_as_1x1(self._get(weights, "kernel")),
                                                         np.tile(self._get(weights, "bias"), 4)), device)
+
+    def _own_device_params(self):
+        what = f"Conv2DTranspose.device_params ('{self.name}')"
+        _check_f32_training(what)
+        if self.dev is None:
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+        if getattr(self, "_params_of", None) is not self.dev:
+            import torch
+            p, device = self.dev.p, self.dev.wgt.device
+            k = np.array(p.wgt[:p.cout, :p.span], np.float32).reshape(2, 2, self.filters, self.cin)   # pack_transpose2x2's inverse, a copy
+            params = {"kernel": torch.from_numpy(k).to(device), "bias": torch.from_numpy(np.array(p.bias, np.float32)).to(device)}
+            self.dev.bind_master(params["kernel"], params["bias"], layout="deconv")
+            self.dev1x1.bind_master(params["kernel"], params["bias"], layout="deconv", bias_reps=4)
+            self._params, self._params_of = params, self.dev
+        return {f"{self.name}/{k}": v for k, v in self._params.items()}
+
+    def _own_repack_jobs(self):
+        if self.dev is None or not self.dev.follows_master:
+            return []
+        return self.dev.repack_jobs() + self.dev1x1.repack_jobs()
 
     def call(self, x, **kwargs):
         return ops.conv2d(x, self.dev, act=_lib.ACT_BY_NAME[self.activation])

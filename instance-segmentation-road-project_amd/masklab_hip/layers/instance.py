@@ -159,6 +159,24 @@ class MaskSubNet(Layer, _TowerMixin):
             self._tail_tables.append((torch.from_numpy(table).to(device), torch.from_numpy(bo).to(device)))
             self._tail_wo.append(torch.from_numpy(k.copy()).to(device))       # [1,1,C_mid,ncls] as it is: the backward's operand
 
+    def device_params(self):
+        """The output convs' kernels are the very tensors the tail's backward reads (`_tail_wo`): they become those convs'
+        masters, so one step moves the conv packing, the lane table and the backward's operand together."""
+        if getattr(self, "_tail_tables", None) is not None:
+            for block, wo in zip(self.blocks, self._tail_wo):
+                block[-1].bind_params(kernel=wo)
+        return super().device_params()
+
+    def _own_repack_jobs(self):
+        if getattr(self, "_tail_tables", None) is None:
+            return []
+        jobs = []
+        for block, wo, (table, bo) in zip(self.blocks, self._tail_wo, self._tail_tables):
+            out = block[-1]
+            if out.dev is not None and out.dev.follows_master and getattr(out, "_params_of", None) is out.dev:
+                jobs.append(ops.repack_table_job(out._params["kernel"], out._params.get("bias"), table, bo))
+        return jobs
+
     def _fused_tail(self, blocks, xs, shapes, roi_masks, per_roi, lives=None, tape=None):
         """Conv2DTranspose + ReLU -> Conv2D 1x1 + sigmoid of every level in one launch, written straight into
         `roi_masks` (csrc/deconv_out.hip); False when the configuration is outside that kernel's shapes."""

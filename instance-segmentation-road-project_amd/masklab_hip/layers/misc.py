@@ -91,6 +91,10 @@ class SqueezeExcite(Layer):
         self.w1 = torch.from_numpy(np.ascontiguousarray(self.dense1._get(weights, "kernel"))).to(device)   # [C, Hd]
         self.w2 = torch.from_numpy(np.ascontiguousarray(self.dense2._get(weights, "kernel"))).to(device)   # [Hd, C]
 
+    def device_params(self):
+        raise NotImplementedError(f"SqueezeExcite.device_params ('{self.name}'): SqueezeExcite has no backward yet, so it is "
+                                  f"not trained")
+
     def _problem(self, x, keep_input, live=None):
         if self.w1 is None:
             raise RuntimeError(f"layer '{self.name}' has no weights loaded")
@@ -159,6 +163,10 @@ class MobileSeparableConv2D(Layer):
         s = self.squeeze_conv2d.build(s)
         self.built = True
         return self.squeeze_norm.build(s)
+
+    def device_params(self):
+        raise NotImplementedError(f"MobileSeparableConv2D.device_params ('{self.name}'): the separable unit has no backward "
+                                  f"yet, so it is not trained")
 
     def call(self, inputs, live=None, **kwargs):
         """live: None, or (device int32 [1], slots per image) -- a fixed-capacity RoI batch (the mask head at capacity):

@@ -223,6 +223,24 @@ class ASPPNetwork(Layer):
             self._slices_of = dev
         return self._slices
 
+    def device_params(self):
+        """The concat slices are cut from the concat conv's host weights BEFORE that conv binds (afterwards it holds none),
+        then follow the conv's master, each as its cin slice."""
+        conv = self.concat_conv
+        fresh = conv.dev is not None and getattr(conv, "_params_of", None) is not conv.dev
+        slices = self._concat_slices() if fresh else None
+        out = super().device_params()
+        if fresh:
+            nf = self.num_features
+            for i, dc in enumerate(slices):
+                dc.bind_master(conv._params["kernel"], cin_slice=(i * nf, (i + 1) * nf))
+        return out
+
+    def _own_repack_jobs(self):
+        if getattr(self, "_slices_of", None) is not self.concat_conv.dev or not self.concat_conv.dev.follows_master:
+            return []
+        return [j for dc in self._slices if dc.follows_master for j in dc.repack_jobs()]
+
     def backward(self, tape, dy, need_dx=True):
         """Backward of `call_with_tape`: dy [B,H,W,num_features] float32 is the gradient at the output (left unchanged).
         concat_gn (relu) -> concat_conv's weight gradient and, as one multi launch of five problems on cin-sliced transposed

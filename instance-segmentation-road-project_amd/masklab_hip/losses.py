@@ -4,8 +4,8 @@ csrc/train_losses.hip (through masklab_hip.ops): float32 terms as the reference 
 order, so two calls give the same bits.  `call` is the forward.  `call_with_grad(inputs, upstream=None,
 through_sigmoid=False)` returns (loss [B], grad): the same loss bit for bit and, from the same pass of the same kernel,
 the gradient of sum_b upstream[b] * loss[b] with respect to the layer's prediction -- upstream None is 1 / B, the K.mean the
-reference compiles; through_sigmoid gives the gradient at the output conv's pre-activation.  The gradients stop there: the
-heads and the backbone have no backward pass yet.  No CPU fallback."""
+reference compiles; through_sigmoid gives the gradient at the output conv's pre-activation.  These layers stop there: the head
+groups' own `backward`s take the gradients on (the FPN and the backbone have none yet).  No CPU fallback."""
 import numpy as np
 import torch
 

@@ -59,6 +59,16 @@ class GroupNormalization(Layer):
         self.gamma = torch.from_numpy(self._get(weights, "gamma")).to(device) if self.scale else None
         self.beta = torch.from_numpy(self._get(weights, "beta")).to(device) if self.center else None
 
+    def _own_device_params(self):
+        if (self.scale and self.gamma is None) or (self.center and self.beta is None):
+            raise RuntimeError(f"layer '{self.name}' has no weights loaded")
+        out = {}                                             # the vectors the kernels read: no copy, no re-pack
+        if self.scale:
+            out[f"{self.name}/gamma"] = self.gamma
+        if self.center:
+            out[f"{self.name}/beta"] = self.beta
+        return out
+
     def call(self, inputs, fuse_relu=False, inplace=False, **kwargs):
         self._check_loaded(inputs.shape)
         return ops.groupnorm_chunk(inputs, self.gamma, self.beta, self.groups, self.epsilon, relu=fuse_relu,

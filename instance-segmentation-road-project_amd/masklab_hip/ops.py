@@ -6,13 +6,15 @@ slice of a wider buffer so concat / add are fused into the producing kernel.
 There is no torch compute and no CPU fallback here.
 """
 import ctypes as C
+import dataclasses
 import threading
 
 import numpy as np
 import torch
 
 from . import _lib
-from .packing import PackedConv, dgrad_padding, pack_dense_transposed, pack_winograd, resolve_padding, unpack_dense
+from .packing import (NO_PIX_SPAN, PackedConv, dgrad_padding, pack_dense_transposed, pack_winograd, resolve_padding,
+                      transposed_geometry, unpack_dense)
 
 import weakref
 
@@ -124,6 +126,15 @@ def workspace(nbytes, device, tag="ws"):
     return buf
 
 
+# Counts every event after which a layer's list of re-pack jobs may differ: a packing made, bound, or a lazy form materialised.
+# Layer.repack() keeps its job list while this stands still, so that RepackTable's identity fast path applies to it.
+_forms_epoch = [0]
+
+
+def forms_epoch():
+    return _forms_epoch[0]
+
+
 class DeviceConv:
     """A PackedConv uploaded to the GPU."""
 
@@ -131,20 +142,30 @@ class DeviceConv:
         self.p = packed
         self.wgt = torch.from_numpy(np.ascontiguousarray(packed.wgt)).to(device)
         self.bias = None if packed.bias is None else torch.from_numpy(packed.bias).to(device)
+        self._init_forms()
+
+    def _init_forms(self):
+        _forms_epoch[0] += 1
         self._wgt_h = None
         self._wgt_x3 = None
         self._wgt_wino = None
         self._wgt_stem_h = None
         self._dgrad = None
+        self._master = None         # bind_master: the device tensors this packing follows
+        self._tr_of = None          # a data-gradient packing: the DeviceConv it is the `dgrad` of
 
     @property
     def dgrad(self):
         """The DeviceConv whose FORWARD is this dense conv's data gradient at stride 1 (packing.pack_dense_transposed: the
         kernel rotated by 180 degrees, cin / cout swapped, the new cin padded to a multiple of 4 with zero weights; no
-        bias); made on first use.  It follows the weights this packing was made from: a layer whose weights step is
-        re-packed (load_weights), which drops it."""
+        bias); made on first use -- on the device from the master once the packing follows one (bind_master; repack_jobs() then
+        lists it), from the host weights otherwise."""
         if self._dgrad is None:
-            self._dgrad = DeviceConv(pack_dense_transposed(unpack_dense(self.p)), self.wgt.device)
+            if self._master is not None:
+                self._dgrad = self._dgrad_from_master()
+            else:
+                self._dgrad = DeviceConv(pack_dense_transposed(unpack_dense(self.p)), self.wgt.device)
+                self._dgrad._tr_of = self
         return self._dgrad
 
     @property
@@ -153,13 +174,19 @@ class DeviceConv:
         32-output blocks (a packing narrower than 128 rows is padded with zero blocks) -- what ml_conv2d_desc.tile = 6 reads
         with n_pad = 128; made on first use."""
         if self._wgt_wino is None:
-            self._wgt_wino = torch.from_numpy(pack_winograd(self.p)).to(self.wgt.device)
+            _forms_epoch[0] += 1
+            self._wgt_wino = self._form_from_master("wino") if self.follows_master else \
+                torch.from_numpy(pack_winograd(self.p)).to(self.wgt.device)
         return self._wgt_wino
 
     @property
     def wgt_x3(self):
         """The packed weights split for ML_MATH_F32X3 (include/masklab_hip.h): every 32-float chunk of a row becomes 32
         halves hi(w) followed by 32 halves 2^11 (w - hi(w)) -- same bytes, same strides; made on first use."""
+        if self._wgt_x3 is None:
+            _forms_epoch[0] += 1
+        if self._wgt_x3 is None and self.follows_master:
+            self._wgt_x3 = self._form_from_master("x3")
         if self._wgt_x3 is None:
             w = np.ascontiguousarray(self.p.wgt, dtype=np.float32)
             rows, ktot = w.shape
@@ -190,6 +217,10 @@ class DeviceConv:
         """The packed weights rounded to IEEE half (fp16-storage convs), every tap padded to span_pad_h; made on first
         use."""
         if self._wgt_h is None:
+            _forms_epoch[0] += 1
+        if self._wgt_h is None and self.follows_master:
+            self._wgt_h = self._form_from_master("h")
+        if self._wgt_h is None:
             p = self.p
             if p.cpp_shift != 30 or p.group_cin_step:
                 raise RuntimeError("fp16 storage: image (row-span) and grouped-window convs have no half packing")
@@ -199,6 +230,117 @@ class DeviceConv:
             wh[:, :, :p.span] = w
             self._wgt_h = torch.from_numpy(np.ascontiguousarray(wh.reshape(p.n_pad, taps * self.span_pad_h))).to(self.wgt.device)
         return self._wgt_h
+
+
+    # ---- a packing that follows master weights on the device (csrc/repack.hip; DESIGN 7a-train, "Re-pack")
+    @property
+    def follows_master(self):
+        """True once bind_master() was called on this packing, or on the packing this one is the `dgrad` of."""
+        return self._master is not None or (self._tr_of is not None and self._tr_of._master is not None)
+
+    def bind_master(self, kernel, bias=None, layout="conv", cin_slice=None, bias_reps=1):
+        """From now on this packing follows `kernel` (and `bias`), float32 tensors on the packing's device in the Keras
+        layout: [kh,kw,cin,cout] for layout="conv" (cin_slice=(c0, c1): this packing is that cin slice of the kernel, packed
+        as a conv of its own), [2,2,cout,cin] for layout="deconv" (pack_transpose2x2's GEMM; bias_reps=4 where the packing
+        holds the bias tiled four times).  repack_jobs() then describes every form this packing has materialised, `dgrad` and
+        its forms included, for ops.repack_weights; a form first asked for later is made on the device from the master.  The
+        host copy of the weights (self.p.wgt / .bias) is dropped: after a step it would be stale, so nothing may read it
+        (packing.unpack_dense raises).  Nothing is launched here: the forms hold what they held."""
+        what, p = "DeviceConv.bind_master", self.p
+        if self._tr_of is not None:
+            raise ValueError(f"{what}: a data-gradient packing follows the master of the packing it belongs to; bind that one")
+        if p.cpp_shift != NO_PIX_SPAN:
+            raise NotImplementedError(f"{what}: a row-span (image_input) packing is not re-packed on the device")
+        if p.group_cin_step:
+            raise NotImplementedError(f"{what}: a grouped packing is not re-packed on the device")
+        if layout not in ("conv", "deconv"):
+            raise ValueError(f"{what}: layout must be 'conv' or 'deconv', got {layout!r}")
+        for name, t in (("kernel", kernel), ("bias", bias)):
+            if t is None and name == "bias":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError(f"{what}: `{name}` must be a contiguous float32 torch tensor")
+            if t.device != self.wgt.device:
+                raise RuntimeError(f"{what}: `{name}` is on {t.device}, the packing on {self.wgt.device}")
+        if kernel.dim() != 4:
+            raise ValueError(f"{what}: `kernel` must have four axes, got {tuple(kernel.shape)}")
+        if layout == "conv":
+            kh, kw, cin, cout = (int(v) for v in kernel.shape)
+            c0, c1 = (0, cin) if cin_slice is None else (int(cin_slice[0]), int(cin_slice[1]))
+            if not 0 <= c0 < c1 <= cin:
+                raise ValueError(f"{what}: cin_slice {cin_slice} is not inside the kernel's {cin} input channels")
+            geom = dict(N=cout, C=c1 - c0, KH=kh, KW=kw, s_n=1, s_c=cout, s_tap=cin * cout, offset=c0 * cout)
+        else:
+            if tuple(kernel.shape[:2]) != (2, 2) or cin_slice is not None:
+                raise ValueError(f"{what}: layout 'deconv' takes a whole [2,2,cout,cin] kernel, got {tuple(kernel.shape)}")
+            cout, cin = int(kernel.shape[2]), int(kernel.shape[3])
+            geom = dict(N=4 * cout, C=cin, KH=1, KW=1, s_n=cin, s_c=1, s_tap=0, offset=0)
+        if (geom["N"], geom["C"], geom["KH"], geom["KW"]) != (p.cout, p.span, p.KH, p.KW):
+            raise ValueError(f"{what}: the master is a {geom['KH']}x{geom['KW']} kernel of {geom['C']} -> {geom['N']} channels, the "
+                             f"packing one of {p.KH}x{p.KW}, {p.span} -> {p.cout}")
+        if (bias is None) != (self.bias is None):
+            raise ValueError(f"{what}: the packing has {'no' if self.bias is None else 'a'} bias, the master "
+                             f"{'none' if bias is None else 'one'}")
+        if bias is not None and (bias_reps < 1 or bias.numel() * bias_reps != self.bias.numel()):
+            raise ValueError(f"{what}: a bias of {bias.numel()} elements x {bias_reps} is not the packing's {self.bias.numel()}")
+        self._master = dict(kernel=kernel, bias=bias, bias_reps=int(bias_reps), **geom)
+        _forms_epoch[0] += 1
+        self.p = dataclasses.replace(p, wgt=None, bias=None)
+        if self._dgrad is not None:
+            self._dgrad.p = dataclasses.replace(self._dgrad.p, wgt=None)
+
+    def _side(self, forms=None):
+        """This packing's destinations as one orientation of a re-pack job: every materialised form, or those of `forms`."""
+        have = {"wgt": self.wgt, "x3": self._wgt_x3, "h": self._wgt_h, "wino": self._wgt_wino}
+        side = {k: v for k, v in (have if forms is None else forms).items() if v is not None}
+        side.update(n_pad=self.p.n_pad, span_pad=self.p.span_pad, span_pad_h=self.span_pad_h)
+        return side
+
+    def _job(self, fwd=None, tr=None, bias=None):
+        m = self._master
+        return dict(kind="conv", src=m["kernel"], src_bias=m["bias"], bias=bias, cpp_shift=self.p.cpp_shift,
+                    group_cin_step=self.p.group_cin_step, fwd=fwd, tr=tr,
+                    **{k: m[k] for k in ("N", "C", "KH", "KW", "s_n", "s_c", "s_tap", "offset", "bias_reps")})
+
+    def repack_jobs(self):
+        """The jobs (one) that bring every materialised form of this packing, and of its `dgrad` if that exists, up to the
+        master it is bound to: what ops.repack_weights takes."""
+        if self._master is None:
+            raise RuntimeError("DeviceConv.repack_jobs: the packing follows no master (bind_master)")
+        return [self._job(fwd=self._side(), tr=None if self._dgrad is None else self._dgrad._side(), bias=self.bias)]
+
+    def _empty_form(self, form, dev=None):
+        p, dev = self.p, (self.wgt.device if dev is None else dev)
+        taps = p.KH * p.KW
+        if form == "wino":
+            if (p.KH, p.KW) != (3, 3) or p.shuffle2x2 or p.n_pad % 32 or p.span_pad % 8:
+                raise ValueError("winograd packing needs a dense 3x3 conv (n_pad % 32 == 0)")
+            return torch.empty((max(4, p.n_pad // 32), p.span_pad // 8, 8, 32, 16), dtype=torch.float32, device=dev)
+        if form == "h":
+            return torch.empty((p.n_pad, taps * self.span_pad_h), dtype=torch.float16, device=dev)
+        return torch.empty((p.n_pad, taps * p.span_pad), dtype=torch.float32, device=dev)
+
+    def _form_from_master(self, form):
+        """A form first asked for after binding: made on the device from the master, never from the stale host weights."""
+        t = self._empty_form(form)
+        if self._master is not None:
+            repack_weights([self._job(fwd=self._side({form: t}))])
+        else:
+            repack_weights([self._tr_of._job(tr=self._side({form: t}))])
+        return t
+
+    def _dgrad_from_master(self):
+        m, p = self._master, self.p
+        if p.shuffle2x2:
+            raise ValueError("unpack_dense: a dense packing only (no row-span, grouped or shuffle2x2 packing)")
+        tp = transposed_geometry(p.KH, p.KW, m["C"], m["N"])
+        d = DeviceConv.__new__(DeviceConv)
+        d.p, d.bias = tp, None
+        d._init_forms()
+        d._tr_of = self
+        d.wgt = d._empty_form("wgt", self.wgt.device)
+        repack_weights([self._job(tr=d._side())])
+        return d
 
 
 def _conv_desc(x, dc, stride=1, padding="same", dilation=1, act=_lib.ACT_NONE, residual=None, out=None,
@@ -3223,3 +3365,191 @@ def optimizer_step(kind, tensors, table, state, scalars, beta_1, beta_2, epsilon
                                                 float(decay), float(weight_decay), float(init_lr), _stream()), "ml_optimizer_scalars")
             _lib.check(lib.ml_optimizer_apply_f32(code, _ptr(table.table), table.n, table.chunks, _ptr(scalars), _stream()),
                        "ml_optimizer_apply_f32")
+
+
+# ----------------------------------------------------------------------------- re-packing stepped weights (csrc/repack.hip)
+_REPACK_FORMS = (("wgt", torch.float32), ("x3", torch.float32), ("h", torch.float16), ("wino", torch.float32))
+
+
+def _repack_tensor(on_gpu, what, name, t, dtype, numel, device):
+    """-> (address, device) of destination or master `t`, checked against what the job's geometry says it holds; on_gpu: a
+    launch follows, so the tensor must be on a device (a plan alone takes tensors from anywhere)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{what}: `{name}` must be a contiguous {dtype} torch tensor")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{what}: `{name}` has {t.numel()} elements, the job's geometry asks for {numel}")
+    if on_gpu and not t.is_cuda:
+        raise RuntimeError(f"{what}: `{name}` is on {t.device}: the re-pack runs only on the MI355X kernels (no CPU fallback)")
+    if device is not None and t.device != device:
+        raise RuntimeError(f"{what}: `{name}` is on {t.device}, the tensors before it on {device}")
+    return t.data_ptr(), t.device
+
+
+def _repack_fill(e, i, job, device, on_gpu=True):
+    """Job dict `job` (DeviceConv.repack_jobs, repack_table_job) -> entry `e` of the host table.  -> (device, bytes moved)"""
+    what = f"repack_weights: job {i}"
+    kind = job.get("kind", "conv")
+    if kind not in ("conv", "table"):
+        raise ValueError(f"{what}: kind must be 'conv' or 'table', got {kind!r}")
+    N, Cc, KH, KW = (int(job[k]) for k in ("N", "C", "KH", "KW"))
+    taps = KH * KW
+    s_n, s_c, s_tap, offset = (int(job[k]) for k in ("s_n", "s_c", "s_tap", "offset"))
+    src = job["src"]
+    extent = offset + (taps - 1) * s_tap + (Cc - 1) * s_c + (N - 1) * s_n + 1
+    ptr, device = _repack_tensor(on_gpu, what, "kernel", src, torch.float32, None, device)
+    if min(N, Cc, KH, KW, s_n, s_c) < 1 or s_tap < 0 or offset < 0 or extent > src.numel():
+        raise ValueError(f"{what}: the view (N {N}, C {Cc}, {KH}x{KW}, strides {s_n}, {s_c}, {s_tap}, offset {offset}) does not lie "
+                         f"inside the master's {src.numel()} elements")
+    e.src, e.s_n, e.s_c, e.s_tap = ptr + 4 * offset, s_n, s_c, s_tap
+    e.kind, e.N, e.C, e.KH, e.KW = (_lib.REPACK_TABLE if kind == "table" else _lib.REPACK_CONV), N, Cc, KH, KW
+    e.cpp_shift, e.group_cin_step = int(job.get("cpp_shift", NO_PIX_SPAN)), int(job.get("group_cin_step", 0))
+    e.bias_reps = int(job.get("bias_reps", 1))
+    nbytes = 4 * N * Cc * taps
+    if job.get("src_bias") is not None:
+        e.src_bias = _repack_tensor(on_gpu, what, "bias", job["src_bias"], torch.float32, N if kind == "table" else None, device)[0]
+        e.bias_n = job["src_bias"].numel()
+    if kind == "table":
+        cp = int(job["cp"])
+        e.cp = cp
+        e.table = _repack_tensor(on_gpu, what, "table", job["table"], torch.float32, Cc * cp, device)[0]
+        if job.get("table_bias") is not None:
+            e.table_bias = _repack_tensor(on_gpu, what, "table_bias", job["table_bias"], torch.float32, cp, device)[0]
+        return device, nbytes + 4 * (Cc + 1) * cp
+    if job.get("bias") is not None:
+        if job.get("src_bias") is None:
+            raise ValueError(f"{what}: a bias form needs a master bias")
+        e.bias = _repack_tensor(on_gpu, what, "bias form", job["bias"], torch.float32, e.bias_n * e.bias_reps, device)[0]
+        nbytes += 4 * e.bias_n * e.bias_reps
+    for side, prefix in (("fwd", "fwd_"), ("tr", "tr_")):
+        d = job.get(side)
+        if not d:
+            continue
+        n_pad, span_pad, span_pad_h = int(d["n_pad"]), int(d["span_pad"]), int(d.get("span_pad_h", 0))
+        setattr(e, prefix + "n_pad", n_pad), setattr(e, prefix + "span_pad", span_pad), setattr(e, prefix + "span_pad_h", span_pad_h)
+        sizes = {"wgt": n_pad * taps * span_pad, "x3": n_pad * taps * span_pad, "h": n_pad * taps * span_pad_h,
+                 "wino": max(n_pad, 128) * span_pad * 16}
+        for form, dtype in _REPACK_FORMS:
+            if d.get(form) is not None:
+                addr = _repack_tensor(on_gpu, what, f"{side} {form}", d[form], dtype, sizes[form], device)[0]
+                setattr(e, prefix + form, addr)
+                nbytes += sizes[form] * (2 if form == "h" else 4)
+    return device, nbytes
+
+
+def repack_table_job(kernel, bias, table, table_bias):
+    """The job of the fused mask tail's lane table (packing.pack_out1x1_table): kernel [1,1,C_mid,ncls] and bias [ncls] or None
+    on the device -> `table` [C_mid / 32, 16, 2, cp] and `table_bias` [cp]."""
+    if not isinstance(kernel, torch.Tensor) or kernel.dim() != 4 or tuple(kernel.shape[:2]) != (1, 1):
+        raise ValueError("repack_table_job: `kernel` must be a [1,1,C_mid,ncls] tensor")
+    cmid, ncls = int(kernel.shape[2]), int(kernel.shape[3])
+    cp = 1
+    while cp < ncls:
+        cp *= 2
+    return dict(kind="table", src=kernel, src_bias=bias, N=ncls, C=cmid, KH=1, KW=1, s_n=1, s_c=ncls, s_tap=0, offset=0,
+                table=table, table_bias=table_bias, cp=cp)
+
+
+class RepackTable:
+    """The device table of a re-pack (`ml_repack_job` per job) and its pinned staging memory, kept by whoever re-packs the
+    same layers every step: update() plans and uploads only when a job differs from the last upload's (a stream-ordered copy
+    from pinned memory, never a device synchronise).  A captured re-pack holds the table's address: take one eager call with
+    the same jobs first."""
+
+    def __init__(self):
+        self.raw = None
+        self.table = None
+        self.n = 0
+        self.units = 0
+        self.nbytes = 0
+        self.uploads = 0
+        self._staging = _Staging()
+        self._retired = []          # outgrown tables, kept for good: a graph captured earlier may replay with their address
+        self._seen = None           # (job dicts, their tensors, the tensors' addresses, device) of the last update
+
+    @staticmethod
+    def _job_tensors(jobs):
+        out = []
+        for j in jobs:
+            out += [j.get(k) for k in ("src", "src_bias", "bias", "table", "table_bias")]
+            for side in ("fwd", "tr"):
+                out += [v for v in (j.get(side) or {}).values() if isinstance(v, torch.Tensor)]
+        return [t for t in out if isinstance(t, torch.Tensor)]
+
+    def update(self, jobs):
+        """-> the jobs' device (None for no jobs).  The SAME job dicts as the last call (by identity) whose tensors sit where
+        they sat are not checked again: a caller that keeps its job list pays for the checks once.  Job dicts are immutable
+        once handed over: a caller that wants another tensor in a job builds a new dict (a dict changed in place would go
+        unseen here)."""
+        n = len(jobs)
+        if self._seen is not None and len(self._seen[0]) == n and all(a is b for a, b in zip(self._seen[0], jobs)) and \
+                [t.data_ptr() for t in self._seen[1]] == self._seen[2]:
+            return self._seen[3]
+        self._seen = None
+        device = self._update(jobs)
+        tensors = self._job_tensors(jobs)
+        self._seen = (list(jobs), tensors, [t.data_ptr() for t in tensors], device)
+        return device
+
+    def _update(self, jobs):
+        n = len(jobs)
+        arr = (_lib.RepackJob * max(n, 1))()
+        device, moved = None, 0
+        for i, job in enumerate(jobs):
+            device, b = _repack_fill(arr[i], i, job, device)
+            moved += b
+        raw = bytes(arr) if n else b""
+        if raw == self.raw and (self.table is None or self.table.device == device):
+            return device
+        if n and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("repack_weights: the jobs differ from the last eager call's, and the device table cannot be "
+                               "uploaded while a graph is captured: take one eager call with these jobs first")
+        units = 0
+        if n:
+            units = int(_lib.load().ml_repack_plan(C.cast(arr, C.c_void_p), n))
+            if units < 0:
+                _lib.check(units, "ml_repack_plan")
+            nbytes = n * C.sizeof(_lib.RepackJob)
+            slot = self._staging.take(nbytes)
+            host = slot[0]
+            C.memmove(host.data_ptr(), arr, nbytes)
+            if self.table is None or self.table.numel() < nbytes or self.table.device != device:
+                if self.table is not None:
+                    self._retired.append(self.table)
+                self.table = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            with torch.cuda.device(device):
+                self.table[:nbytes].copy_(host[:nbytes], non_blocking=True)
+                slot[1] = torch.cuda.Event()
+                slot[1].record()
+            self.uploads += 1
+        self.raw, self.n, self.units, self.nbytes = raw, n, units, moved
+        return device
+
+
+def repack_plan(jobs):
+    """Host only: validates `jobs` as ml_repack_plan does and -> (work units, [(nb, cb, first_unit) per job]).  Nothing is
+    launched, so the tensors may live anywhere (a packing on the CPU plans like one on the device)."""
+    n = len(jobs)
+    arr = (_lib.RepackJob * max(n, 1))()
+    device = None
+    for i, job in enumerate(jobs):
+        device, _ = _repack_fill(arr[i], i, job, device, on_gpu=False)
+    units = int(_lib.load().ml_repack_plan(C.cast(arr, C.c_void_p), n)) if n else 0
+    if units < 0:
+        _lib.check(units, "ml_repack_plan")
+    return units, [(arr[i].nb, arr[i].cb, arr[i].first_unit) for i in range(n)]
+
+
+def repack_weights(jobs, table=None):
+    """Brings packed forms up to their master weights on the device, in place, every job in ONE launch on the current stream
+    (ml_repack_f32): what a training step runs after the optimizer's step.  jobs: DeviceConv.repack_jobs() lists and
+    repack_table_job() dicts, concatenated.  Every element of every destination is written (pads and zero blocks included),
+    no address changes, nothing is read on the host.  table: the caller's RepackTable (a step that re-packs the same layers
+    every time uploads its table once); None makes one for this call."""
+    jobs = list(jobs)
+    if not jobs:
+        return
+    table = RepackTable() if table is None else table
+    device = table.update(jobs)
+    with torch.cuda.device(device):
+        with _Prof("repack_weights", 0, table.nbytes, f"x{table.n} ({table.units} units)"):
+            _lib.check(_lib.load().ml_repack_f32(_ptr(table.table), table.n, table.units, _stream()), "ml_repack_f32")

@@ -7,8 +7,9 @@ replay.
     opt = RectifiedAdam(1e-4)
     opt.apply_gradients(params, grads)            # {name: device tensor}, the names of model.init_weights()
 
-Not here: `constraint`, fp16 parameter copies, gradient reduction across devices.  Packed / folded inference weights are
-re-packed by load_weights, not by a step."""
+Not here: `constraint`, fp16 parameter copies, gradient reduction across devices.  A step updates Keras-layout tensors only: the packed forms the
+kernels read follow them through ops.repack_weights (packings bound with DeviceConv.bind_master), or through load_weights;
+folded (fold_bn) weights through load_weights alone."""
 import numpy as np
 import torch
 

@@ -10,6 +10,7 @@ Keras layouts in -> the layouts the gfx950 kernels read:
   * BatchNormalization (inference) folded into the preceding conv's weights / bias.
 Pure numpy; no GPU needed (unit-tested on CPU against the oracle through tests/emulate.py).
 """
+import dataclasses
 import math
 from dataclasses import dataclass, field
 
@@ -96,18 +97,29 @@ def fold_bn(kernel, bias, gamma, beta, mean, var, eps, depthwise=False):
     return k.astype(np.float32), b.astype(np.float32)
 
 
+def dense_geometry(kh, kw, cin, cout, tile=0):
+    """pack_dense's PackedConv without its arrays (wgt and bias None): every size the kernels and the re-pack read."""
+    if cin % 4:
+        raise ValueError(f"dense conv needs cin % 4 == 0 (got {cin}); use pack_rowspan for image inputs")
+    bn = ntile_for(cout, tile)
+    return PackedConv(wgt=None, bias=None, KH=kh, KW=kw, span=cin, span_pad=-(-cin // 32) * 32, cout=cout,
+                      n_pad=-(-cout // bn) * bn, tile=tile, cin_buffer=cin, kh_real=kh, kw_real=kw, k_real=kh * kw * cin)
+
+
+def transposed_geometry(kh, kw, cin, cout, tile=0):
+    """pack_dense_transposed's PackedConv without its arrays: cin' = cout rounded up to 4, cout' = cin."""
+    return dense_geometry(kh, kw, -(-cout // 4) * 4, cin, tile)
+
+
 def pack_dense(kernel, bias=None, tile=0):
     """Conv2D kernel [kh,kw,cin,cout] with cin % 4 == 0."""
     kh, kw, cin, cout = kernel.shape
-    if cin % 4:
-        raise ValueError(f"dense conv needs cin % 4 == 0 (got {cin}); use pack_rowspan for image inputs")
-    span_pad = -(-cin // 32) * 32
-    w = np.zeros((cout, kh, kw, span_pad), np.float32)
+    g = dense_geometry(kh, kw, cin, cout, tile)
+    w = np.zeros((cout, kh, kw, g.span_pad), np.float32)
     w[..., :cin] = np.transpose(kernel, (3, 0, 1, 2))
-    w2d, n_pad = _pad_rows(w.reshape(cout, kh * kw * span_pad), cout, tile)
-    return PackedConv(wgt=w2d, bias=None if bias is None else np.ascontiguousarray(bias, np.float32),
-                      KH=kh, KW=kw, span=cin, span_pad=span_pad, cout=cout, n_pad=n_pad, tile=tile,
-                      cin_buffer=cin, kh_real=kh, kw_real=kw, k_real=kh * kw * cin)
+    w2d, n_pad = _pad_rows(w.reshape(cout, kh * kw * g.span_pad), cout, tile)
+    assert n_pad == g.n_pad
+    return dataclasses.replace(g, wgt=w2d, bias=None if bias is None else np.ascontiguousarray(bias, np.float32))
 
 
 def pack_rowspan(kernel, bias=None, cpad=4, tile=0):
@@ -266,6 +278,9 @@ def unpack_dense(packed: PackedConv):
     p = packed
     if p.cpp_shift != NO_PIX_SPAN or p.group_cin_step or p.shuffle2x2:
         raise ValueError("unpack_dense: a dense packing only (no row-span, grouped or shuffle2x2 packing)")
+    if p.wgt is None:
+        raise RuntimeError("unpack_dense: this packing follows master weights on the device (DeviceConv.bind_master) and holds "
+                           "no host copy: read the master")
     w = np.asarray(p.wgt, np.float32)[:p.cout].reshape(p.cout, p.KH, p.KW, p.span_pad)[..., :p.span]
     return np.ascontiguousarray(np.transpose(w, (1, 2, 3, 0)))
 

@@ -570,7 +570,7 @@ class TrainerModel(K.Layer):
     """The Keras functional `Model([images, gt_boxes, gt_boxes_exist, gt_masks, gt_seg, gt_seg_exist] -> losses and metrics)`
     of reference :223-395, executed eagerly (no hipGraph, no fixed-capacity stage 2): what
     `fit_generator(validation_data=...)` evaluates to report a checkpoint's validation losses.  `loss_and_gradients` adds the
-    gradients of the compiled scalar at the four head outputs; they stop there (the heads have no backward pass yet).  The backbone and head layers
+    gradients of the compiled scalar at the four head outputs; `train_on_batch` carries them through the head groups' `backward`s into an optimizer's step and one re-pack (the FPN and the backbone are frozen).  The backbone and head layers
     are the OBJECTS the inference model holds, as in the reference; the assignment, loss and metric layers are the model's
     own.  Every output is float32 [B]; the lists shrink like the reference's when a head group is None.
     `last_forward` keeps the intermediate tensors of the last call."""
@@ -670,6 +670,38 @@ class TrainerModel(K.Layer):
             l.load_weights(weights, self.device)
         return self
 
+    # ---- the head groups' weights as device tensors ("Re-pack")
+    def head_groups(self):
+        """The head groups whose backward exists, those present: class, box, mask, ASPP, segmentation sub-networks."""
+        out = []
+        if self.detection_networks is not None:
+            out += list(self.detection_networks[2:4])
+            if self.instance_networks is not None:
+                out.append(self.instance_networks[3])
+        if self.semantic_networks is not None:
+            out += list(self.semantic_networks)
+        return out
+
+    def device_params(self):
+        """{full weight name: float32 device tensor} of every head group present (Layer.device_params): what an optimizer's
+        apply_gradients steps.  The FPN and the backbone are not in it: their layers cannot be trained yet (stride-2 data
+        gradient, folded BatchNormalization) and say so when asked."""
+        if self.device is None:
+            raise RuntimeError("TrainerModel: call load_weights(weights, device) first")
+        out = {}
+        for g in self.head_groups():
+            out.update(g.device_params())
+        return out
+
+    def repack(self):
+        """After the head parameters stepped: every packing under the head groups up to its master, in ONE launch."""
+        from . import ops
+        if getattr(self, "_repack_table", None) is None:
+            self._repack_table, self._repack_kept = ops.RepackTable(), (None, None)
+        if self._repack_kept[0] != ops.forms_epoch():              # kept while no packing or form was made anywhere
+            self._repack_kept = (ops.forms_epoch(), [j for g in self.head_groups() for j in g.repack_jobs()])
+        ops.repack_weights(self._repack_kept[1], self._repack_table)
+
     # ---- forward (reference :233-391)
     def _named_inputs(self, inputs):
         if isinstance(inputs, dict):
@@ -702,7 +734,7 @@ class TrainerModel(K.Layer):
         sum_b upstream[loss][b] * loss[b].  upstream None is 1 / B everywhere -- the scalar engine/train.py compiles,
         add_loss(K.mean(loss)) per loss; a dict {loss name: float32 [B]} overrides single losses.  wrt="pre_activation"
         gives the class, mask and seg gradients at the pre-activation of their output convs' fused sigmoid (loc_pred is
-        linear).  The gradients stop here: the heads have no backward pass yet.  Also kept in last_forward["grads"]."""
+        linear).  train_on_batch carries them on: through the heads' `backward`s into an optimizer's step and `repack()`.  Also kept in last_forward["grads"]."""
         if wrt not in ("predictions", "pre_activation"):
             raise ValueError(f"TrainerModel.loss_and_gradients: wrt must be 'predictions' or 'pre_activation', got {wrt!r}")
         unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
@@ -724,6 +756,79 @@ class TrainerModel(K.Layer):
         loss, want["grads"][self.GRAD_OF[layer.name]] = layer.call_with_grad(inputs, upstream=up, through_sigmoid=sig)
         return loss
 
+    @staticmethod
+    def _head(layer, inputs, want):
+        """A head group's forward: `call`, or with want["tapes"] its `call_with_tape` (the same bits), the tape kept by name."""
+        if want is None or want.get("tapes") is None:
+            return layer(inputs)
+        out, want["tapes"][layer.name] = layer.call_with_tape(inputs)
+        return out
+
+    # ---- one training step (DESIGN 7a-train, "The step")
+    def _trainable_names(self, trainable, params):
+        """The names of `params` a step updates.  "heads": all of them; a set of names or a predicate narrows it.  A name under
+        the FPN or the backbone raises NotImplementedError, any other unknown name ValueError."""
+        if isinstance(trainable, str):
+            if trainable != "heads":
+                raise ValueError(f"TrainerModel.train_on_batch: trainable must be 'heads', a set of weight names or a predicate, "
+                                 f"got {trainable!r}")
+            return set(params)
+        frozen_specs = dict(self.backbone_network.weight_specs())
+        if self.detection_networks is not None:
+            frozen_specs.update(self.detection_networks[1].weight_specs())
+        if callable(trainable):
+            frozen = [n for n in frozen_specs if trainable(n)]
+            names = {n for n in params if trainable(n)}
+        else:
+            names = set(trainable)
+            unknown = sorted(names - set(params) - set(frozen_specs))
+            if unknown:
+                raise ValueError(f"TrainerModel.train_on_batch: {unknown[:5]} are not trainable weights of this model")
+            frozen = sorted(names & set(frozen_specs))
+        if frozen:
+            raise NotImplementedError(f"TrainerModel.train_on_batch: {list(frozen)[:5]} lie under the FPN or the backbone, which "
+                                      f"cannot be trained yet: the FPN's backward and the stride-2 data gradient of its P6 / P7 "
+                                      f"convs are missing, and the backbone's BatchNormalization is folded into its weights")
+        return names
+
+    def train_on_batch(self, inputs, optimizer, trainable="heads", upstream=None):
+        """One eager training step with Keras's semantics -> the outputs of `call` for this batch as they were BEFORE the
+        update, bit for bit (the head groups run as call_with_tape, documented bit-equal to call).
+        The gradients are those of loss_and_gradients(wrt="pre_activation", upstream=upstream), routed through
+        cls_subnet.backward, loc_subnet.backward, mask_subnet.backward(need_dx=False) and seg_subnet.backward ->
+        aspp.backward(need_dx=False); the gradients at the head inputs are dropped: the FPN and the backbone are frozen.
+        The merged {name: gradient} dict (kept as last_forward["weight_grads"]) goes to
+        optimizer.apply_gradients(device_params(), grads, trainable=names), then ONE repack_weights brings every packing of
+        the head groups up to its master.  trainable: "heads" (every weight of the head groups present), a set of names or a
+        predicate; a name under the FPN or the backbone raises NotImplementedError, a name the model does not have
+        ValueError.  Head groups with SqueezeExcite or separable towers, half tensors and set_conv_math("f16") raise
+        NotImplementedError before anything runs; a refused step changes no weight."""
+        params = self.device_params()                         # raises by name for what cannot be trained
+        names = self._trainable_names(trainable, params)
+        unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
+        if unknown:
+            raise ValueError(f"TrainerModel.train_on_batch: upstream names {unknown} are not losses ({sorted(self.GRAD_OF)})")
+        grads, tapes = {}, {}
+        outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=True, grads=grads, tapes=tapes))
+        wg = {}
+        if self.detection_networks is not None:
+            _, _, cls_subnet, loc_subnet = self.detection_networks
+            wg.update(cls_subnet.backward(tapes[cls_subnet.name], grads["cls_pred"])[1])
+            wg.update(loc_subnet.backward(tapes[loc_subnet.name], grads["loc_pred"])[1])
+            if self.instance_networks is not None:
+                mask_subnet = self.instance_networks[3]
+                wg.update(mask_subnet.backward(tapes[mask_subnet.name], grads["roi_masks"], need_dx=False)[1])
+        if self.semantic_networks is not None:
+            aspp_subnet, seg_subnet = self.semantic_networks
+            (d_aspp, _), g = seg_subnet.backward(tapes[seg_subnet.name], grads["seg_pred"], need_dx=(True, False))
+            wg.update(g)
+            wg.update(aspp_subnet.backward(tapes[aspp_subnet.name], d_aspp, need_dx=False)[1])
+        self.last_forward["grads"] = grads
+        self.last_forward["weight_grads"] = wg
+        optimizer.apply_gradients(params, wg, trainable=names)
+        self.repack()
+        return outputs
+
     def _forward(self, inputs, want):
         if self.device is None:
             raise RuntimeError("TrainerModel: call load_weights(weights, device) first")
@@ -740,8 +845,8 @@ class TrainerModel(K.Layer):
             fpn_inputs = [by_name[n] for n in bb.output_names if n in det_config.feature_pyramid_inputs]
             without_fpn = [by_name[n] for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
             feature_outputs = fpn_subnet(fpn_inputs) + without_fpn
-            cls_pred = cls_subnet(feature_outputs)
-            loc_pred = loc_subnet(feature_outputs)
+            cls_pred = self._head(cls_subnet, feature_outputs, want)
+            loc_pred = self._head(loc_subnet, feature_outputs, want)
             gt_boxes = self._dev(x['gt_boxes'], torch.float32)
             gt_boxes_exist = self._dev(x['gt_boxes_exist'], torch.float32)
             cls_true, loc_true, assign_mask = self.assign_boxes([gt_boxes, pr_boxes])
@@ -763,7 +868,7 @@ class TrainerModel(K.Layer):
                 chosen_boxes = torch.cat([gt_boxes, proposed_loss], dim=1)              # Concatenate(axis=1)
                 dist_boxes = distribute_layer(chosen_boxes)
                 roi_fmaps, roi_boxes = pyramid_roi_align([feature_outputs[:cfg.instance.max_k + 1], dist_boxes, images])
-                roi_masks = mask_subnet(roi_fmaps)
+                roi_masks = self._head(mask_subnet, roi_fmaps, want)
                 gt_masks = self._dev(x['gt_masks'])
                 match_gt_masks = self.assign_masks([roi_boxes, roi_masks, gt_boxes, gt_masks])
                 outputs.append(self._loss(self.mask_loss, [match_gt_masks, roi_masks], want))
@@ -771,7 +876,8 @@ class TrainerModel(K.Layer):
         if self.semantic_networks is not None:
             sem_config = cfg.semantic
             aspp_subnet, seg_subnet = self.semantic_networks
-            seg_pred = seg_subnet([aspp_subnet(by_name[sem_config.aspp_input_name]), by_name[sem_config.skip_input_name]])
+            aspp_out = self._head(aspp_subnet, by_name[sem_config.aspp_input_name], want)
+            seg_pred = self._head(seg_subnet, [aspp_out, by_name[sem_config.skip_input_name]], want)
             gt_seg = self._dev(x['gt_seg'])
             gt_seg_exist = self._dev(x['gt_seg_exist'], torch.float32)
             seg_assigned = self.assign_seg([gt_seg, seg_pred])
@@ -790,7 +896,7 @@ class TrainerModel(K.Layer):
 
 def construct_trainer_network(configuration: ModelConfiguration, backbone_network, detection_networks=None,
                               semantic_networks=None, instance_networks=None):
-    """Same signature as reference :223-227; the returned model's gradients stop at the head outputs."""
+    """Same signature as reference :223-227; the returned model trains its head groups (train_on_batch); the FPN and the backbone are frozen."""
     return TrainerModel(configuration, backbone_network, detection_networks=detection_networks,
                         semantic_networks=semantic_networks, instance_networks=instance_networks)
 
