@@ -155,6 +155,10 @@ class Layer:
     def _own_repack_jobs(self):
         return []
 
+    def _repack_job_source(self):
+        """The jobs repack() runs: everything under this layer.  A model that steps only part of itself overrides it."""
+        return self.repack_jobs()
+
     def repack(self):
         """Brings every packing under this layer up to its stepped master, in one launch (ops.repack_weights).  The job list
         is kept while no packing was made, bound or given a new form anywhere (ops.forms_epoch), so a step that re-packs the
@@ -162,8 +166,14 @@ class Layer:
         if getattr(self, "_repack_table", None) is None:
             self._repack_table, self._repack_kept = ops.RepackTable(), (None, None)
         if self._repack_kept[0] != ops.forms_epoch():
-            self._repack_kept = (ops.forms_epoch(), self.repack_jobs())
+            self._repack_kept = (ops.forms_epoch(), self._repack_job_source())
         ops.repack_weights(self._repack_kept[1], self._repack_table)
+
+    def name_grads(self, grads, into):
+        """Files this layer's gradients, keyed like its weights ("kernel", "gamma", ...: what its backward returns), into
+        `into` under their full names: the names of init_weights(), what apply_gradients takes."""
+        for k, v in grads.items():
+            into[f"{self.name}/{k}"] = v
 
     def _get(self, weights, key):
         full = f"{self.name}/{key}"
@@ -194,6 +204,24 @@ def _check_f32_training(what):
     if ops.CONV_MATH in ("f16", "f16s"):
         raise NotImplementedError(f"{what}: training runs in float32 only; set_conv_math({ops.CONV_MATH!r}) / half tensors are "
                                   f"not trained")
+
+
+def pair_grads(layer, pair):
+    """The (dk, db) of a weight-gradient launch as the conv layer's gradient dict: what Layer.name_grads files."""
+    grads = {"depthwise_kernel" if isinstance(layer, DepthwiseConv2D) else "kernel": pair[0]}
+    if layer.use_bias:
+        grads["bias"] = pair[1]
+    return grads
+
+
+def check_incoming_grad(what, grad, shape=None):
+    """The gradient a head's backward is handed: a float32 tensor and, with `shape`, contiguous of that shape.
+    what: "Class.backward: argument"."""
+    import torch
+    if not isinstance(grad, torch.Tensor) or grad.dtype != torch.float32:
+        raise TypeError(f"{what} must be a float32 tensor; the backward is float32 only")
+    if shape is not None and (tuple(grad.shape) != tuple(shape) or not grad.is_contiguous()):
+        raise ValueError(f"{what} is {tuple(grad.shape)}, expected a contiguous {tuple(shape)}")
 
 
 class Conv2D(Layer):
@@ -351,10 +379,7 @@ class Conv2D(Layer):
         has no dx (NotImplementedError); its weight gradient exists."""
         self._check_backward()
         args = self._grad_args()
-        dk, db = ops.conv2d_wgrad(x, dy, dy_view=dy_view, want_bias=self.use_bias, **args)
-        grads = {"kernel": dk}
-        if self.use_bias:
-            grads["bias"] = db
+        grads = pair_grads(self, ops.conv2d_wgrad(x, dy, dy_view=dy_view, want_bias=self.use_bias, **args))
         dx = ops.conv2d_dgrad(dy, in_hw=(x.shape[1], x.shape[2]), dy_view=dy_view, add=add, **args) if need_dx else None
         return dx, grads
 
@@ -556,10 +581,8 @@ class DepthwiseConv2D(Layer):
         weights the layer has)."""
         self._check_backward()
         args = self._grad_args()
-        dk, db = ops.dwconv3x3_wgrad(x, dy, in_coff=in_coff, dy_coff=dy_coff, want_bias=self.use_bias, C=self.C, **args)
-        grads = {"depthwise_kernel": dk}
-        if self.use_bias:
-            grads["bias"] = db
+        grads = pair_grads(self, ops.dwconv3x3_wgrad(x, dy, in_coff=in_coff, dy_coff=dy_coff, want_bias=self.use_bias,
+                                                     C=self.C, **args))
         dx = ops.dwconv3x3_dgrad(dy, self.wgt, (x.shape[1], x.shape[2]), dy_coff=dy_coff, C=self.C, add=add,
                                  **args) if need_dx else None
         return dx, grads

@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..keras_like import Conv2D, Layer
+from ..keras_like import Conv2D, Layer, check_incoming_grad, pair_grads
 from ..normalization import GroupNormalization
 from ..prior import PriorBoxes
 from .misc import MobileSeparableConv2D, SqueezeExcite
@@ -235,17 +235,6 @@ class _TowerMixin:
                                               f"GroupNormalization behind it)")
 
     @staticmethod
-    def _conv_args(c):
-        return dict(dc=c.dev, stride=c.strides[0], padding=c.padding, dilation=c.dilation_rate[0])
-
-    @staticmethod
-    def _take_conv_grads(grads, convs, pairs):
-        for c, (dk, db) in zip(convs, pairs):
-            grads[f"{c.name}/kernel"] = dk
-            if c.use_bias:
-                grads[f"{c.name}/bias"] = db
-
-    @staticmethod
     def _towers_backward(units, tape, dxs, grads, need_dx=True):
         """The depth units of several towers, deepest depth first: GroupNormalization.backward_multi(input_relu=True, in place
         on `dxs`, the gradients at the towers' outputs) -> conv2d_wgrad_multi -> conv2d_dgrad_multi.  tape: "conv_in" /
@@ -258,15 +247,16 @@ class _TowerMixin:
                 c._check_backward()
             back = GroupNormalization.backward_multi(norms, tape["conv_out"][depth], dxs, input_relu=True, inplace=True)
             for g, (_, gg) in zip(norms, back):
-                for k, v in gg.items():
-                    grads[f"{g.name}/{k}"] = v
+                g.name_grads(gg, grads)
             dys = [dx for dx, _ in back]                     # at the convs' pre-activation
             xs = tape["conv_in"][depth]
-            _TowerMixin._take_conv_grads(grads, convs, ops.conv2d_wgrad_multi(
-                [dict(x=x, dy=dy, want_bias=c.use_bias, **_TowerMixin._conv_args(c)) for c, x, dy in zip(convs, xs, dys)]))
+            pairs = ops.conv2d_wgrad_multi([dict(x=x, dy=dy, want_bias=c.use_bias, **c._grad_args())
+                                            for c, x, dy in zip(convs, xs, dys)])
+            for c, pair in zip(convs, pairs):
+                c.name_grads(pair_grads(c, pair), grads)
             if depth == 0 and not need_dx:
                 return None
-            dxs = ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **_TowerMixin._conv_args(c))
+            dxs = ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **c._grad_args())
                                           for c, x, dy in zip(convs, xs, dys)])
         return dxs
 
@@ -315,24 +305,7 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
         return [l for b in self.blocks for l in b]
 
     def call(self, inputs, **kwargs):
-        # Reshape((-1, d)) + Concatenate(axis=1) (reference :138-140) are fused: every level's
-        # output conv writes straight into its row range of the [B, A, d] prediction.
-        d = self.out_dim
-        B = inputs[0].shape[0]
-        per_level = [int(x.shape[1]) * int(x.shape[2]) * self.num_priors for x in inputs]
-        total = sum(per_level)
-        pred = torch.empty((B, total, d), dtype=torch.float32, device=inputs[0].device)
-        blocks = self.blocks[:len(inputs)]
-        xs = self._run_towers_multi([b[:-1] for b in blocks], inputs)
-        problems, off = [], 0
-        for idx, x in enumerate(xs):
-            out_conv = blocks[idx][-1]
-            problems.append(dict(x=x, dc=out_conv.dev, stride=1, padding='same',
-                                 act=ops._lib.ACT_BY_NAME[out_conv.activation],
-                                 out_view=(pred, off * d, self.num_priors * d, total * d)))
-            off += per_level[idx]
-        ops.conv2d_multi(problems)
-        return pred
+        return self._forward(inputs)
 
     def _pred_views(self, shapes):
         """Every level's row range of the [B, A, d] prediction as (element offset, channel stride, batch stride)"""
@@ -345,26 +318,30 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
             off += n
         return views, total
 
+    def _forward(self, inputs, tape=None):
+        """The one forward of `call` (tape None) and `call_with_tape` (tape: a dict that receives what `backward` needs;
+        GroupNormalization then writes a tensor of its own instead of normalising in place: _run_towers_multi)."""
+        # Reshape((-1, d)) + Concatenate(axis=1) (reference :138-140) are fused: every level's
+        # output conv writes straight into its row range of the [B, A, d] prediction.
+        views, total = self._pred_views([x.shape for x in inputs])      # the towers keep every level's height and width
+        pred = torch.empty((inputs[0].shape[0], total, self.out_dim), dtype=torch.float32, device=inputs[0].device)
+        blocks = self.blocks[:len(inputs)]
+        if tape is not None:
+            tape["inputs"] = list(inputs)
+        xs = self._run_towers_multi([b[:-1] for b in blocks], inputs, tape=tape)
+        if tape is not None:
+            tape["out_in"] = list(xs)
+        ops.conv2d_multi([dict(x=x, dc=b[-1].dev, stride=1, padding='same', act=ops._lib.ACT_BY_NAME[b[-1].activation],
+                               out_view=(pred,) + view) for b, x, view in zip(blocks, xs, views)])
+        return pred
+
     def call_with_tape(self, inputs, **kwargs):
         """`call` that keeps what `backward` needs.  -> (pred, tape): pred is `call`'s bit for bit; the tape holds every depth's
         conv input and post-ReLU conv output per level, and the output convs' inputs.  GroupNormalization writes a tensor
         of its own here (inplace=False) where `call` normalises in place; the epilogue-statistics path is kept where `call`
         uses it.  Towers with SqueezeExcite or separable units raise NotImplementedError."""
-        d = self.out_dim
-        B = inputs[0].shape[0]
-        blocks = self.blocks[:len(inputs)]
-        tape = {"inputs": list(inputs)}
-        xs = self._run_towers_multi([b[:-1] for b in blocks], inputs, tape=tape)
-        tape["out_in"] = list(xs)
-        views, total = self._pred_views([x.shape for x in xs])
-        pred = torch.empty((B, total, d), dtype=torch.float32, device=inputs[0].device)
-        problems = []
-        for idx, (x, view) in enumerate(zip(xs, views)):
-            out_conv = blocks[idx][-1]
-            problems.append(dict(x=x, dc=out_conv.dev, stride=1, padding='same',
-                                 act=ops._lib.ACT_BY_NAME[out_conv.activation], out_view=(pred,) + view))
-        ops.conv2d_multi(problems)
-        return pred, tape
+        tape = {}
+        return self._forward(inputs, tape), tape
 
     def backward(self, tape, d_pred):
         """Backward of `call_with_tape`: d_pred [B, A, d] float32 is the gradient at the PRE-activation of the prediction (the
@@ -377,25 +354,18 @@ class BoxRegressionSubNet(Layer, _TowerMixin):
         blocks = self.blocks[:n]
         units = [self._units(b[:-1]) for b in blocks]
         self._check_tape_units(units)
-        if not isinstance(d_pred, torch.Tensor) or d_pred.dtype != torch.float32:
-            raise TypeError(f"{type(self).__name__}.backward: d_pred must be a float32 tensor; the backward is float32 only")
         views, total = self._pred_views([x.shape for x in tape["out_in"]])
-        B = int(tape["inputs"][0].shape[0])
-        if tuple(d_pred.shape) != (B, total, self.out_dim) or not d_pred.is_contiguous():
-            raise ValueError(f"{type(self).__name__}.backward: d_pred is {tuple(d_pred.shape)}, expected a contiguous "
-                             f"{(B, total, self.out_dim)}")
+        check_incoming_grad(f"{type(self).__name__}.backward: d_pred", d_pred,
+                            (int(tape["inputs"][0].shape[0]), total, self.out_dim))
         grads = {}
-        conv_args = self._conv_args
-
-        def take(convs, pairs):
-            self._take_conv_grads(grads, convs, pairs)
-
         outs = [b[-1] for b in blocks]
         for c in outs:
             c._check_backward()
-        take(outs, ops.conv2d_wgrad_multi([dict(x=x, dy=None, dy_view=(d_pred,) + v, want_bias=c.use_bias, **conv_args(c))
-                                           for c, x, v in zip(outs, tape["out_in"], views)]))
-        dxs = ops.conv2d_dgrad_multi([dict(dy=None, dy_view=(d_pred,) + v, in_hw=(x.shape[1], x.shape[2]), **conv_args(c))
+        pairs = ops.conv2d_wgrad_multi([dict(x=x, dy=None, dy_view=(d_pred,) + v, want_bias=c.use_bias, **c._grad_args())
+                                        for c, x, v in zip(outs, tape["out_in"], views)])
+        for c, pair in zip(outs, pairs):
+            c.name_grads(pair_grads(c, pair), grads)
+        dxs = ops.conv2d_dgrad_multi([dict(dy=None, dy_view=(d_pred,) + v, in_hw=(x.shape[1], x.shape[2]), **c._grad_args())
                                       for c, x, v in zip(outs, tape["out_in"], views)])
         return self._towers_backward(units, tape, dxs, grads), grads
 

@@ -3,7 +3,7 @@ MaskDistribute :32-74, PyramidRoiAlign :77-147, MaskSubNet :158-240."""
 import torch
 
 from .. import ops
-from ..keras_like import Conv2D, Conv2DTranspose, Layer
+from ..keras_like import Conv2D, Conv2DTranspose, Layer, check_incoming_grad, pair_grads
 from .detection import _TowerMixin
 
 
@@ -208,21 +208,42 @@ class MaskSubNet(Layer, _TowerMixin):
         """lives (fixed-capacity form, PyramidRoiAlign.crop_capacity): per level (device int32 [1], cap) -- RoI slots past
         max(1, live) of an image do not exist; the result is then [B, L*cap, 2h, 2w, classes] with level l's RoIs at
         rows l*cap .. (molded by ops.mold_levels once the host knows the maxima)."""
+        return self._forward(inputs, lives)
+
+    def _forward(self, inputs, lives=None, tape=None):
+        """The one forward of `call` (tape None) and `call_with_tape` (tape: a dict that receives what `backward` needs; the
+        towers' GroupNormalization then writes tensors of its own instead of normalising in place, the fused tail stores
+        T, and what keeps no tape is refused before anything runs)."""
         if not isinstance(inputs, list):
             inputs = [inputs]
+        if tape is not None:
+            if lives is not None:
+                raise NotImplementedError("MaskSubNet.call_with_tape: the fixed-capacity form (`lives`) keeps no tape")
+            self._check_train("call_with_tape", inputs)
+            if any(h.shape[1] < 1 for h in inputs):
+                raise ValueError("MaskSubNet.call_with_tape: every level needs at least one RoI per image")
+            if any(h.shape[0] * h.shape[1] * h.shape[2] * h.shape[3] >= 1 << 24 for h in inputs):
+                raise NotImplementedError("MaskSubNet.call_with_tape: 2^24 or more input pixels in a level are outside the fused tail")
         from .. import _lib
         blocks = self.blocks[:len(inputs)]
-        shapes = [(h.shape[0], h.shape[1]) for h in inputs]
+        shapes = [(int(h.shape[0]), int(h.shape[1])) for h in inputs]
         # fold rois into the batch (:211-213); all levels advance together (multi-problem launches)
         xs = [h.reshape((h.shape[0] * h.shape[1],) + tuple(h.shape[2:])) for h in inputs]
-        xs = self._run_towers_multi([b[:-2] for b in blocks], xs, lives=lives)
+        if tape is not None:
+            tape.update(inputs=list(inputs), shapes=shapes)
+        xs = self._run_towers_multi([b[:-2] for b in blocks], xs, lives=lives, tape=tape)
+        if tape is not None:
+            tape.update(tail_in=list(xs), T=[])
         if all(n > 0 for _, n in shapes):
             B = shapes[0][0]
             oh, ow, ncls = 2 * int(xs[0].shape[1]), 2 * int(xs[0].shape[2]), self.num_classes
             total = sum(n for _, n in shapes)
             roi_masks = torch.empty((B, total, oh, ow, ncls), dtype=torch.float32, device=xs[0].device)
-            if self._fused_tail(blocks, xs, shapes, roi_masks, oh * ow * ncls, lives=lives):
+            if self._fused_tail(blocks, xs, shapes, roi_masks, oh * ow * ncls, lives=lives,
+                                tape=None if tape is None else tape["T"]):
                 return roi_masks
+        if tape is not None:
+            raise NotImplementedError("MaskSubNet.call_with_tape: this configuration is outside the fused tail kernel")
         if lives is not None:
             raise NotImplementedError("MaskSubNet: the fixed-capacity form needs the fused tail kernel")
         if xs[0].dtype == torch.float16:          # (the pixel-shuffle epilogue of the unfused pair is fp32 only)
@@ -267,29 +288,8 @@ class MaskSubNet(Layer, _TowerMixin):
         in GEMM layout, which the fused tail's tape launch stores.  Refused by name: the
         fixed-capacity form, half tensors / set_conv_math('f16'), configurations outside the fused tail, towers with
         SqueezeExcite or separable units."""
-        if lives is not None:
-            raise NotImplementedError("MaskSubNet.call_with_tape: the fixed-capacity form (`lives`) keeps no tape")
-        if not isinstance(inputs, list):
-            inputs = [inputs]
-        self._check_train("call_with_tape", inputs)
-        blocks = self.blocks[:len(inputs)]
-        shapes = [(int(h.shape[0]), int(h.shape[1])) for h in inputs]
-        if any(n < 1 for _, n in shapes):
-            raise ValueError("MaskSubNet.call_with_tape: every level needs at least one RoI per image")
-        xs = [h.reshape((h.shape[0] * h.shape[1],) + tuple(h.shape[2:])) for h in inputs]
-        if any(x.shape[0] * x.shape[1] * x.shape[2] >= 1 << 24 for x in xs):
-            raise NotImplementedError("MaskSubNet.call_with_tape: 2^24 or more input pixels in a level are outside the fused tail")
-        tape = {"inputs": list(inputs), "shapes": shapes}
-        xs = self._run_towers_multi([b[:-2] for b in blocks], xs, tape=tape)
-        tape["tail_in"] = list(xs)
-        B = shapes[0][0]
-        oh, ow, ncls = 2 * int(xs[0].shape[1]), 2 * int(xs[0].shape[2]), self.num_classes
-        total = sum(n for _, n in shapes)
-        roi_masks = torch.empty((B, total, oh, ow, ncls), dtype=torch.float32, device=xs[0].device)
-        tape["T"] = []
-        if not self._fused_tail(blocks, xs, shapes, roi_masks, oh * ow * ncls, tape=tape["T"]):
-            raise NotImplementedError("MaskSubNet.call_with_tape: this configuration is outside the fused tail kernel")
-        return roi_masks, tape
+        tape = {}
+        return self._forward(inputs, lives, tape), tape
 
     def backward(self, tape, d_masks, need_dx=True, consume_tape=False):
         """Backward of `call_with_tape`: d_masks [B, total, 2h, 2w, classes] float32 is the gradient at the PRE-activation of
@@ -306,8 +306,7 @@ class MaskSubNet(Layer, _TowerMixin):
         blocks = self.blocks[:n]
         units = [self._units(b[:-2]) for b in blocks]
         self._check_tape_units(units)
-        if not isinstance(d_masks, torch.Tensor) or d_masks.dtype != torch.float32:
-            raise TypeError("MaskSubNet.backward: d_masks must be a float32 tensor; the backward is float32 only")
+        check_incoming_grad("MaskSubNet.backward: d_masks", d_masks)      # its shape once the tape itself is known good
         if tape.get("T") is None or len(tape["T"]) != n:
             raise ValueError("MaskSubNet.backward: the tape holds no T (consumed by an earlier backward?)")
         self._check_train("backward", tape["T"])
@@ -315,9 +314,7 @@ class MaskSubNet(Layer, _TowerMixin):
         B, total = shapes[0][0], sum(s[1] for s in shapes)
         h, w = int(xs[0].shape[1]), int(xs[0].shape[2])
         ncls = self.num_classes
-        if tuple(d_masks.shape) != (B, total, 2 * h, 2 * w, ncls) or not d_masks.is_contiguous():
-            raise ValueError(f"MaskSubNet.backward: d_masks is {tuple(d_masks.shape)}, expected a contiguous "
-                             f"{(B, total, 2 * h, 2 * w, ncls)}")
+        check_incoming_grad("MaskSubNet.backward: d_masks", d_masks, (B, total, 2 * h, 2 * w, ncls))
         deconvs, outs = [b[-2] for b in blocks], [b[-1] for b in blocks]
         for c in outs:
             c._check_backward()
@@ -334,10 +331,8 @@ class MaskSubNet(Layer, _TowerMixin):
         tails = ops.deconv2x2_out1x1_grad_multi(problems)
         if consume_tape:
             tape["T"] = None
-        for c, (_, dk, db) in zip(outs, tails):
-            grads[f"{c.name}/kernel"] = dk
-            if c.use_bias:
-                grads[f"{c.name}/bias"] = db
+        for c, tail in zip(outs, tails):
+            c.name_grads(pair_grads(c, tail[1:]), grads)
         # the transposed conv = a 1x1 conv with 4 C_mid outputs on the GEMM layout
         dys = [dT.view(x.shape[0], h, w, dT.shape[1] * dT.shape[2]) for x, (dT, _, _) in zip(xs, tails)]
         args = dict(stride=1, padding="same", dilation=1)

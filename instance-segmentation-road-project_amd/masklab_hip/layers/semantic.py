@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..keras_like import Conv2D, DepthwiseConv2D, Layer
+from ..keras_like import Conv2D, DepthwiseConv2D, Layer, check_incoming_grad, pair_grads
 from ..normalization import GroupNormalization
 from .detection import _TowerMixin
 
@@ -44,27 +44,28 @@ class AtrousSeparableConv2D(Layer):
             out.update(ch.weight_specs())
         return out
 
-    def call(self, inputs, out=None, out_coff=0, **kwargs):
-        x = self.depth_conv2d(inputs)
-        x = self.depth_norm(x, fuse_relu=True, inplace=True)
-        x = self.point_conv2d(x)
+    def _forward(self, inputs, out=None, out_coff=0, tape=None):
+        """The one forward of `call` (tape None: the norms normalise in place) and `call_with_tape` (tape: a dict that
+        receives each conv's input and each norm's input; the norms then write tensors of their own)."""
+        d = self.depth_conv2d(inputs)
+        dn = self.depth_norm(d, fuse_relu=True, inplace=tape is None)
+        p = self.point_conv2d(dn)
+        if tape is not None:
+            tape.update(inputs=inputs, depth_out=d, point_in=dn, point_out=p)
         if out is None:
-            return self.point_norm(x, fuse_relu=True, inplace=True)
-        return ops.groupnorm_chunk(x, self.point_norm.gamma, self.point_norm.beta, self.groups,
+            return self.point_norm(p, fuse_relu=True, inplace=tape is None)
+        return ops.groupnorm_chunk(p, self.point_norm.gamma, self.point_norm.beta, self.groups,
                                    self.point_norm.epsilon, relu=True, out=out, out_coff=out_coff)
+
+    def call(self, inputs, out=None, out_coff=0, **kwargs):
+        return self._forward(inputs, out, out_coff)
 
     def call_with_tape(self, inputs, out=None, out_coff=0, **kwargs):
         """`call` that keeps what `backward` needs.  -> (output, tape): the output is `call`'s bit for bit; the tape holds each
         conv's input and each norm's input.  The depthwise GroupNormalization writes a tensor of its own here where `call`
         normalises in place."""
-        d = self.depth_conv2d(inputs)
-        dn = self.depth_norm(d, fuse_relu=True, inplace=False)
-        p = self.point_conv2d(dn)
-        tape = {"inputs": inputs, "depth_out": d, "point_in": dn, "point_out": p}
-        if out is None:
-            return self.point_norm(p, fuse_relu=True, inplace=False), tape
-        return ops.groupnorm_chunk(p, self.point_norm.gamma, self.point_norm.beta, self.groups,
-                                   self.point_norm.epsilon, relu=True, out=out, out_coff=out_coff), tape
+        tape = {}
+        return self._forward(inputs, out, out_coff, tape), tape
 
     def backward(self, tape, dy, need_dx=True, add=None):
         """Backward of `call_with_tape`: dy [B,H,W,filters] float32 (dense) is the gradient at the branch's output; it is
@@ -76,11 +77,6 @@ class AtrousSeparableConv2D(Layer):
         config = super().get_config()
         config.update({'filters': self.filters, 'dilation_rate': self.dilation_rate, 'groups': self.groups})
         return config
-
-
-def _name_grads(grads, layer, named):
-    for k, v in named.items():
-        grads[f"{layer.name}/{k}"] = v
 
 
 def _branches_backward(branches, tapes, dys, need_dx=True, add=None, lead=None):
@@ -104,29 +100,28 @@ def _branches_backward(branches, tapes, dys, need_dx=True, add=None, lead=None):
         br.depth_conv2d._check_backward()
     back = GroupNormalization.backward_multi(norms, norm_in, dys, fuse_relu=True, inplace=True)
     for g, (_, gg) in zip(norms, back):
-        _name_grads(grads, g, gg)
+        g.name_grads(gg, grads)
     dzs = [dz for dz, _ in back]                             # at the 1x1 convs' output
-    args = _TowerMixin._conv_args
-    _TowerMixin._take_conv_grads(grads, convs, ops.conv2d_wgrad_multi(
-        [dict(x=x, dy=dz, want_bias=c.use_bias, **args(c)) for c, x, dz in zip(convs, conv_in, dzs)]))
+    pairs = ops.conv2d_wgrad_multi([dict(x=x, dy=dz, want_bias=c.use_bias, **c._grad_args())
+                                    for c, x, dz in zip(convs, conv_in, dzs)])
+    for c, pair in zip(convs, pairs):
+        c.name_grads(pair_grads(c, pair), grads)
     k = 0 if lead is None else 1
     dx = add
     if lead is not None and need_dx:
-        dx = ops.conv2d_dgrad(dzs[0], in_hw=(conv_in[0].shape[1], conv_in[0].shape[2]), add=add, **args(convs[0]))
-    ddn = ops.conv2d_dgrad_multi([dict(dy=dz, in_hw=(x.shape[1], x.shape[2]), **args(c))
+        dx = ops.conv2d_dgrad(dzs[0], in_hw=(conv_in[0].shape[1], conv_in[0].shape[2]), add=add, **convs[0]._grad_args())
+    ddn = ops.conv2d_dgrad_multi([dict(dy=dz, in_hw=(x.shape[1], x.shape[2]), **c._grad_args())
                                   for c, x, dz in zip(convs[k:], conv_in[k:], dzs[k:])])
     dnorms = [br.depth_norm for br in branches]
     back = GroupNormalization.backward_multi(dnorms, [t["depth_out"] for t in tapes], ddn, fuse_relu=True, inplace=True)
     for g, (_, gg) in zip(dnorms, back):
-        _name_grads(grads, g, gg)
+        g.name_grads(gg, grads)
     dds = [dd for dd, _ in back]                             # at the depthwise convs' output
     dws = [br.depth_conv2d for br in branches]
     pairs = ops.dwconv3x3_wgrad_multi([dict(x=t["inputs"], dy=dd, want_bias=c.use_bias, C=c.C, **c._grad_args())
                                        for c, t, dd in zip(dws, tapes, dds)])
-    for c, (dk, db) in zip(dws, pairs):
-        grads[f"{c.name}/depthwise_kernel"] = dk
-        if c.use_bias:
-            grads[f"{c.name}/bias"] = db
+    for c, pair in zip(dws, pairs):
+        c.name_grads(pair_grads(c, pair), grads)
     if not need_dx:
         return None, grads
     for c, t, dd in zip(dws, tapes, dds):
@@ -173,25 +168,10 @@ class ASPPNetwork(Layer):
             out.update(ch.weight_specs())
         return out
 
-    def call(self, inputs, **kwargs):
-        B, H, W, _ = inputs.shape
-        nf = self.num_features
-        cat = torch.empty((B, H, W, nf * (2 + len(self.aspp_branches))), dtype=inputs.dtype, device=inputs.device)
-        x = self.aspp_1x1(inputs)
-        ops.groupnorm_chunk(x, self.aspp_1x1_gn.gamma, self.aspp_1x1_gn.beta, self.groups,
-                            self.aspp_1x1_gn.epsilon, relu=True, out=cat, out_coff=0)
-        for i, br in enumerate(self.aspp_branches):
-            br(inputs, out=cat, out_coff=nf * (1 + i))
-        pool = ops.global_mean(inputs)                       # tf.reduce_mean(axis=(1,2)) (:149)
-        pool = self.aspp_pool_conv(pool)                     # 1x1 + ReLU, no GN (:126-129)
-        ops.resize_bilinear_ac(pool, H, W, out=cat, out_coff=nf * (1 + len(self.aspp_branches)))  # :152
-        x = self.concat_conv(cat)
-        return self.concat_gn(x, fuse_relu=True, inplace=True)
-
-    def call_with_tape(self, inputs, **kwargs):
-        """`call` that keeps what `backward` needs.  -> (output, tape): the output is `call`'s bit for bit; it differs from
-        `call` only in that GroupNormalization writes a tensor of its own where `call` normalises in place.  The tape holds
-        each conv's input, each norm's input and the pool conv's post-ReLU output."""
+    def _forward(self, inputs, tape=None):
+        """The one forward of `call` (tape None: the norms normalise in place) and `call_with_tape` (tape: a dict that
+        receives each conv's input, each norm's input and the pool conv's post-ReLU output, the branches' tapes under
+        "branches"; the norms then write tensors of their own)."""
         B, H, W, _ = inputs.shape
         nf = self.num_features
         n_br = len(self.aspp_branches)
@@ -199,15 +179,27 @@ class ASPPNetwork(Layer):
         x1 = self.aspp_1x1(inputs)
         ops.groupnorm_chunk(x1, self.aspp_1x1_gn.gamma, self.aspp_1x1_gn.beta, self.groups,
                             self.aspp_1x1_gn.epsilon, relu=True, out=cat, out_coff=0)
-        tape = {"inputs": inputs, "aspp_1x1_out": x1, "branches": []}
-        for i, br in enumerate(self.aspp_branches):
-            tape["branches"].append(br.call_with_tape(inputs, out=cat, out_coff=nf * (1 + i))[1])
-        tape["pool_in"] = ops.global_mean(inputs)
-        tape["pool_out"] = self.aspp_pool_conv(tape["pool_in"])
-        ops.resize_bilinear_ac(tape["pool_out"], H, W, out=cat, out_coff=nf * (1 + n_br))
-        tape["cat"] = cat
-        tape["concat_out"] = self.concat_conv(cat)
-        return self.concat_gn(tape["concat_out"], fuse_relu=True, inplace=False), tape
+        branch_tapes = [None if tape is None else {} for _ in self.aspp_branches]
+        for i, (br, br_tape) in enumerate(zip(self.aspp_branches, branch_tapes)):
+            br._forward(inputs, out=cat, out_coff=nf * (1 + i), tape=br_tape)
+        pool_in = ops.global_mean(inputs)                    # tf.reduce_mean(axis=(1,2)) (:149)
+        pool_out = self.aspp_pool_conv(pool_in)              # 1x1 + ReLU, no GN (:126-129)
+        ops.resize_bilinear_ac(pool_out, H, W, out=cat, out_coff=nf * (1 + n_br))  # :152
+        concat_out = self.concat_conv(cat)
+        if tape is not None:
+            tape.update(inputs=inputs, aspp_1x1_out=x1, branches=branch_tapes, pool_in=pool_in, pool_out=pool_out, cat=cat,
+                        concat_out=concat_out)
+        return self.concat_gn(concat_out, fuse_relu=True, inplace=tape is None)
+
+    def call(self, inputs, **kwargs):
+        return self._forward(inputs)
+
+    def call_with_tape(self, inputs, **kwargs):
+        """`call` that keeps what `backward` needs.  -> (output, tape): the output is `call`'s bit for bit; it differs from
+        `call` only in that GroupNormalization writes a tensor of its own where `call` normalises in place.  The tape holds
+        each conv's input, each norm's input and the pool conv's post-ReLU output."""
+        tape = {}
+        return self._forward(inputs, tape), tape
 
     def _concat_slices(self):
         """concat_projection cut along its input channels into the concat's 2 + len(rates) slices, each a dense 1x1 conv of
@@ -249,25 +241,23 @@ class ASPPNetwork(Layer):
         weight / data gradient -> global_mean_grad.  The input's gradient is chained through add= in the fixed order
         aspp_1x1, the atrous branches in the order of `atrous_rate`, the pool branch.
         -> (dx [B,H,W,C] or None unless need_dx, {full weight name: gradient} with the names of init_weights())."""
-        if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32:
-            raise TypeError("ASPPNetwork.backward: dy must be a float32 tensor; the backward is float32 only")
+        check_incoming_grad("ASPPNetwork.backward: dy", dy)
         x = tape["inputs"]
         B, H, W, _ = x.shape
         for c in (self.aspp_1x1, self.aspp_pool_conv, self.concat_conv):
             c._check_backward()
         grads = {}
         dz, gg = self.concat_gn.backward(tape["concat_out"], dy, fuse_relu=True)
-        _name_grads(grads, self.concat_gn, gg)
-        args = _TowerMixin._conv_args
-        _TowerMixin._take_conv_grads(grads, [self.concat_conv], [ops.conv2d_wgrad(
-            tape["cat"], dz, want_bias=self.concat_conv.use_bias, **args(self.concat_conv))])
+        self.concat_gn.name_grads(gg, grads)
+        cc = self.concat_conv
+        cc.name_grads(pair_grads(cc, ops.conv2d_wgrad(tape["cat"], dz, want_bias=cc.use_bias, **cc._grad_args())), grads)
         dcat = ops.conv2d_dgrad_multi([dict(dy=dz, dc=dc, in_hw=(H, W), stride=1, padding="same", dilation=1)
                                        for dc in self._concat_slices()])
         # the pool branch first (it is small); its part of dx comes last in the chain
         d_pool = ops.resize_bilinear_ac_grad(dcat[-1], 1, 1)
         d_pool = ops.relu_grad(tape["pool_out"], d_pool, out=d_pool)
         d_mean, gp = self.aspp_pool_conv.backward(tape["pool_in"], d_pool, need_dx=need_dx)
-        _name_grads(grads, self.aspp_pool_conv, gp)
+        self.aspp_pool_conv.name_grads(gp, grads)
         dx, gb = _branches_backward(self.aspp_branches, tape["branches"], dcat[1:-1], need_dx,
                                     lead=(self.aspp_1x1, self.aspp_1x1_gn, x, tape["aspp_1x1_out"], dcat[0]))
         grads.update(gb)
@@ -322,7 +312,10 @@ class SegmentationSubNet(Layer, _TowerMixin):
             out.update(ch.weight_specs())
         return out
 
-    def call(self, inputs, **kwargs):
+    def _forward(self, inputs, tape=None):
+        """The one forward of `call` (tape None) and `call_with_tape` (tape: a dict that receives the skip conv's input and
+        output, the tower's tape and the output conv's input; the tower's GroupNormalization then writes tensors of its
+        own instead of normalising in place: _run_tower)."""
         dec_input, skip_dec_input = inputs[0], inputs[1]
         B, H, W, _ = skip_dec_input.shape
         c_dec = dec_input.shape[-1]
@@ -332,28 +325,24 @@ class SegmentationSubNet(Layer, _TowerMixin):
         ops.groupnorm_chunk(s, self.skip_gn.gamma, self.skip_gn.beta, self.groups, self.skip_gn.epsilon,
                             relu=True, out=cat, out_coff=c_dec)
         ops.resize_bilinear_ac(dec_input, H, W, out=cat, out_coff=0)      # ResizeLike (:226) into the concat (:227)
-        x = self._run_tower(self.block, cat)
+        if tape is not None:
+            tape.update(inputs=[dec_input, skip_dec_input], skip_out=s)
+        x = self._run_tower(self.block, cat, tape=tape)
+        if tape is not None:
+            tape["out_in"] = x
         return self.output_layer(x)
+
+    def call(self, inputs, **kwargs):
+        return self._forward(inputs)
 
     def call_with_tape(self, inputs, **kwargs):
         """`call` that keeps what `backward` needs.  -> (seg_pred, tape): seg_pred is `call`'s bit for bit; the tape holds the
         skip conv's input and output, the concat, every tower unit's conv input and post-ReLU output, and the output conv's
         input.  GroupNormalization writes a tensor of its own here where `call` normalises in place.  Towers with
         SqueezeExcite or separable units raise NotImplementedError."""
-        self._check_tape_units([self._units(self.block)])
-        dec_input, skip_dec_input = inputs[0], inputs[1]
-        B, H, W, _ = skip_dec_input.shape
-        c_dec = dec_input.shape[-1]
-        cat = torch.empty((B, H, W, c_dec + self.num_skip_features), dtype=dec_input.dtype,
-                          device=dec_input.device)
-        s = self.skip_conv(skip_dec_input)
-        ops.groupnorm_chunk(s, self.skip_gn.gamma, self.skip_gn.beta, self.groups, self.skip_gn.epsilon,
-                            relu=True, out=cat, out_coff=c_dec)
-        ops.resize_bilinear_ac(dec_input, H, W, out=cat, out_coff=0)
-        tape = {"inputs": [dec_input, skip_dec_input], "skip_out": s}
-        x = self._run_tower(self.block, cat, tape=tape)
-        tape["out_in"] = x
-        return self.output_layer(x), tape
+        self._check_tape_units([self._units(self.block)])      # before any launch
+        tape = {}
+        return self._forward(inputs, tape), tape
 
     def backward(self, tape, d_seg, need_dx=(True, True)):
         """Backward of `call_with_tape`: d_seg [B,H,W,num_classes] float32 is the gradient at the PRE-activation of the output
@@ -368,16 +357,12 @@ class SegmentationSubNet(Layer, _TowerMixin):
         self._check_tape_units(units)
         dec_input, skip_in = tape["inputs"]
         B, H, W, _ = skip_in.shape
-        if not isinstance(d_seg, torch.Tensor) or d_seg.dtype != torch.float32:
-            raise TypeError("SegmentationSubNet.backward: d_seg must be a float32 tensor; the backward is float32 only")
-        if tuple(d_seg.shape) != (B, H, W, self.num_classes) or not d_seg.is_contiguous():
-            raise ValueError(f"SegmentationSubNet.backward: d_seg is {tuple(d_seg.shape)}, expected a contiguous "
-                             f"{(B, H, W, self.num_classes)}")
+        check_incoming_grad("SegmentationSubNet.backward: d_seg", d_seg, (B, H, W, self.num_classes))
         need_dec, need_skip = need_dx
         grads = {}
         out = self.output_layer
         dx, go = out.backward(tape["out_in"], d_seg)
-        _name_grads(grads, out, go)
+        out.name_grads(go, grads)
         d_cat = self._towers_backward(units, tape, [dx], grads)[0]
         c_dec = int(dec_input.shape[-1])
         d_dec = ops.resize_bilinear_ac_grad(d_cat, dec_input.shape[1], dec_input.shape[2], C=c_dec, dy_coff=0) if need_dec else None
@@ -385,9 +370,9 @@ class SegmentationSubNet(Layer, _TowerMixin):
         d_s = torch.empty((B, H, W, self.num_skip_features), dtype=torch.float32, device=d_cat.device)
         ops.gather_channels(d_cat, c_dec, d_s)
         d_s, gg = self.skip_gn.backward(tape["skip_out"], d_s, fuse_relu=True, inplace=True)
-        _name_grads(grads, self.skip_gn, gg)
+        self.skip_gn.name_grads(gg, grads)
         d_skip, gs = self.skip_conv.backward(skip_in, d_s, need_dx=bool(need_skip))
-        _name_grads(grads, self.skip_conv, gs)
+        self.skip_conv.name_grads(gs, grads)
         return (d_dec, d_skip), grads
 
     def get_config(self):

@@ -693,14 +693,9 @@ class TrainerModel(K.Layer):
             out.update(g.device_params())
         return out
 
-    def repack(self):
-        """After the head parameters stepped: every packing under the head groups up to its master, in ONE launch."""
-        from . import ops
-        if getattr(self, "_repack_table", None) is None:
-            self._repack_table, self._repack_kept = ops.RepackTable(), (None, None)
-        if self._repack_kept[0] != ops.forms_epoch():              # kept while no packing or form was made anywhere
-            self._repack_kept = (ops.forms_epoch(), [j for g in self.head_groups() for j in g.repack_jobs()])
-        ops.repack_weights(self._repack_kept[1], self._repack_table)
+    def _repack_job_source(self):
+        """repack() after the head parameters stepped: every packing under the head groups, not the frozen layers'."""
+        return [j for g in self.head_groups() for j in g.repack_jobs()]
 
     # ---- forward (reference :233-391)
     def _named_inputs(self, inputs):
@@ -727,6 +722,11 @@ class TrainerModel(K.Layer):
     def call(self, inputs, **kwargs):
         return self._forward(inputs, None)
 
+    def _check_upstream(self, what, upstream):
+        unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
+        if unknown:
+            raise ValueError(f"TrainerModel.{what}: upstream names {unknown} are not losses ({sorted(self.GRAD_OF)})")
+
     def loss_and_gradients(self, inputs, upstream=None, wrt="predictions"):
         """The forward of `call`, metrics included, with every loss layer run as `call_with_grad` -> (outputs, grads):
         the outputs of `call` bit for bit, and grads = {"cls_pred", "loc_pred", "roi_masks", "seg_pred"} (those whose head
@@ -737,9 +737,7 @@ class TrainerModel(K.Layer):
         linear).  train_on_batch carries them on: through the heads' `backward`s into an optimizer's step and `repack()`.  Also kept in last_forward["grads"]."""
         if wrt not in ("predictions", "pre_activation"):
             raise ValueError(f"TrainerModel.loss_and_gradients: wrt must be 'predictions' or 'pre_activation', got {wrt!r}")
-        unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
-        if unknown:
-            raise ValueError(f"TrainerModel.loss_and_gradients: upstream names {unknown} are not losses ({sorted(self.GRAD_OF)})")
+        self._check_upstream("loss_and_gradients", upstream)
         grads = {}
         outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=wrt == "pre_activation", grads=grads))
         self.last_forward["grads"] = grads
@@ -805,9 +803,7 @@ class TrainerModel(K.Layer):
         NotImplementedError before anything runs; a refused step changes no weight."""
         params = self.device_params()                         # raises by name for what cannot be trained
         names = self._trainable_names(trainable, params)
-        unknown = sorted(set(upstream or {}) - set(self.GRAD_OF))
-        if unknown:
-            raise ValueError(f"TrainerModel.train_on_batch: upstream names {unknown} are not losses ({sorted(self.GRAD_OF)})")
+        self._check_upstream("train_on_batch", upstream)
         grads, tapes = {}, {}
         outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=True, grads=grads, tapes=tapes))
         wg = {}

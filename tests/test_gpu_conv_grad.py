@@ -29,7 +29,7 @@ from backbone_cases import _need_gpu, dev, host    # noqa: F401  (_need_gpu: aut
 import conv_grad_ref as R
 import dirty_memory as DM
 import optimizer_ref as OR
-from test_gpu_resample_grad import _bits, _everything
+from test_gpu_resample_grad import _bits, _everything, _kernels
 
 
 def _dc(w, bias=None):
@@ -288,8 +288,10 @@ def test_tower_backward(kind):
     assert want[2] >= KINK, f"a pre-activation lies {want[2]:.3g} from the ReLU's kink: choose another seed"
     net.load_weights(weights, torch.device("cuda:0"))
     xs = [dev(a) for a in inputs]
-    pred, tape = net.call_with_tape(xs)
-    _bits(pred, net.call(xs), f"{kind}: call_with_tape's prediction against call's")
+    (pred, tape), taped = _kernels(lambda: net.call_with_tape(xs))
+    call, called = _kernels(lambda: net.call(xs))
+    _bits(pred, call, f"{kind}: call_with_tape's prediction against call's")
+    assert called and taped == called, f"{kind}: call_with_tape's launches are not call's"
     # the prediction's PRE-activation is what the restatement computes: the sigmoid of the class head is the loss's
     pre = host(pred) if kind == "loc" else None
     if pre is not None:

@@ -28,7 +28,7 @@ import conv_grad_ref as CR
 import groupnorm_grad_ref as GR
 import mask_tail_grad_ref as TR
 import optimizer_ref as OR
-from test_gpu_resample_grad import _bits, _everything
+from test_gpu_resample_grad import _bits, _everything, _kernels
 
 NB, CLASSES, DEPTH, NF, GROUPS = 2, 3, 1, 128, 16
 N_L, CROP = (2, 1), (2, 3)
@@ -118,8 +118,12 @@ def test_call_with_tape_is_call():
     net = _loaded()
     weights, inputs, d_masks, want, f32 = head_reference()
     xs = [dev(a) for a in inputs]
-    masks, tape = net.call_with_tape(xs)
-    _bits(masks, net.call(xs), "MaskSubNet.call_with_tape's roi_masks against call's")
+    (masks, tape), taped = _kernels(lambda: net.call_with_tape(xs))
+    call, called = _kernels(lambda: net.call(xs))
+    _bits(masks, call, "MaskSubNet.call_with_tape's roi_masks against call's")
+    # the same launches but the tail's, which also stores T
+    assert called.count("deconv2x2_out1x1") == 1 and "deconv2x2_out1x1_tape" not in called
+    assert taped == ["deconv2x2_out1x1_tape" if k == "deconv2x2_out1x1" else k for k in called]
     for x, a in zip(xs, inputs):
         np.testing.assert_array_equal(host(x), a)
     assert np.abs(host(masks) - 1.0 / (1.0 + np.exp(-want[3]))).max() <= 1e-5

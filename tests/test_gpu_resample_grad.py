@@ -28,6 +28,17 @@ def _bits(a, b, what):
     DM.assert_same_bits(DM.snapshot(a), DM.snapshot(b), what)
 
 
+def _kernels(fn):
+    """-> (fn(), the launcher names it recorded in ops.PROFILE, in launch order)"""
+    from masklab_hip import ops
+    ops.PROFILE = []
+    try:
+        out = fn()
+        return out, [r["kernel"] for r in ops.PROFILE]
+    finally:
+        ops.PROFILE = None
+
+
 def _everything(run, inputs, what):
     """What every op holds: -> the first launch's snapshot, after two launches gave the same bits, stale and zeroed outputs
     and workspace gave those bits too, and the inputs (device tensor, host array) are what they were"""

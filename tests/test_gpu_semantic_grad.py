@@ -29,7 +29,7 @@ import dwconv_grad_ref as DR
 import groupnorm_grad_ref as GR
 import optimizer_ref as OR
 import resample_grad_ref as RR
-from test_gpu_resample_grad import _bits, _everything
+from test_gpu_resample_grad import _bits, _everything, _kernels
 
 NF, GROUPS, RATES, SKIP, CLASSES, DEPTH = 32, 8, (1, 2, 6), 16, 3, 2
 ASPP_IN, SKIP_IN = (2, 6, 7, 64), (2, 11, 13, 32)
@@ -157,10 +157,14 @@ def test_call_with_tape_is_call():
     aspp, seg = _loaded()
     weights, x, skip, d_seg, want, f32 = head_reference()
     xd, sd = dev(x), dev(skip)
-    a_out, a_tape = aspp.call_with_tape(xd)
-    _bits(a_out, aspp.call(xd), "ASPPNetwork.call_with_tape's output against call's")
-    pred, s_tape = seg.call_with_tape([a_out, sd])
-    _bits(pred, seg.call([a_out, sd]), "SegmentationSubNet.call_with_tape's output against call's")
+    (a_out, a_tape), a_taped = _kernels(lambda: aspp.call_with_tape(xd))
+    a_call, a_called = _kernels(lambda: aspp.call(xd))
+    _bits(a_out, a_call, "ASPPNetwork.call_with_tape's output against call's")
+    assert a_called and a_taped == a_called, "ASPPNetwork: call_with_tape's launches are not call's"
+    (pred, s_tape), s_taped = _kernels(lambda: seg.call_with_tape([a_out, sd]))
+    s_call, s_called = _kernels(lambda: seg.call([a_out, sd]))
+    _bits(pred, s_call, "SegmentationSubNet.call_with_tape's output against call's")
+    assert s_called and s_taped == s_called, "SegmentationSubNet: call_with_tape's launches are not call's"
     np.testing.assert_array_equal(host(xd), x)
     assert _rel(host(a_out), want[5]) <= 1e-5
     sig = 1.0 / (1.0 + np.exp(-want[4]))
@@ -233,8 +237,10 @@ def test_atrous_branch_backward_alone_is_the_aspp_s():
     weights, x, skip, d_seg, want, f32 = head_reference()
     xd = dev(x)
     br = aspp.aspp_branches[2]
-    out, tape = br.call_with_tape(xd)
-    _bits(out, br.call(xd), "AtrousSeparableConv2D.call_with_tape's output against call's")
+    (out, tape), taped = _kernels(lambda: br.call_with_tape(xd))
+    call, called = _kernels(lambda: br.call(xd))
+    _bits(out, call, "AtrousSeparableConv2D.call_with_tape's output against call's")
+    assert called and taped == called, "AtrousSeparableConv2D: call_with_tape's launches are not call's"
     dy_h = np.random.default_rng(53).normal(0, 1, tuple(out.shape)).astype(np.float32)
     dx, grads = br.backward(tape, dev(dy_h))
     assert sorted(grads) == sorted(n for n in weights if n.startswith("aspp_6_"))
