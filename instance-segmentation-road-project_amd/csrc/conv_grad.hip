@@ -321,15 +321,16 @@ extern "C" int ml_conv2d_wgrad_multi_f32(const ml_conv2d_wgrad_desc *descs, int3
         ML_REQUIRE((((uintptr_t)d.out | (uintptr_t)g.dkernel | (uintptr_t)g.dbias | (uintptr_t)g.add_kernel |
                      (uintptr_t)g.add_bias) & 3) == 0, "%s: problem %d: 4-byte alignment", what, i);
         const long long x_bytes = (long long)d.B * d.H * d.W * d.in_cstride * 4;
+        // dy's resource extent (what the hardware clamps): whole channel strides from d.out on, past the view's last element
         const long long dy_bytes = (((long long)d.B - 1) * pl.dy_bs + (long long)d.Ho * d.Wo * d.out_cstride) * 4;
         const long long dk_bytes = pl.tcc * 4, db_bytes = (long long)d.cout * 4;
-        ML_REQUIRE(!ml_ranges_overlap(g.dkernel, dk_bytes, d.in, x_bytes) &&
-                   !ml_ranges_overlap(g.dkernel, dk_bytes, d.out, dy_bytes), "%s: problem %d: dkernel may not overlap x or dy", what, i);
+        // what can alias: x from its buffer's base, dy from the view's first element to its last
+        const ml_range r_x = {d.in, x_bytes}, r_dk = {g.dkernel, dk_bytes}, r_db = {g.dbias, db_bytes};
+        const ml_range r_dy = {d.out + d.out_coff, ml_view_elems(d.B, pl.dy_bs, (long long)d.Ho * d.Wo, d.out_cstride, d.cout) * 4};
+        ML_REQUIRE(!ml_any_overlap({r_dk}, {r_x, r_dy}), "%s: problem %d: dkernel may not overlap x or dy", what, i);
         ML_REQUIRE(ml_add_or_disjoint(g.dkernel, g.add_kernel, dk_bytes), "%s: problem %d: dkernel may be add itself, not a shifted "
                    "view of it", what, i);
-        ML_REQUIRE(!ml_ranges_overlap(g.dbias, db_bytes, d.in, x_bytes) && !ml_ranges_overlap(g.dbias, db_bytes, d.out, dy_bytes) &&
-                   !ml_ranges_overlap(g.dbias, db_bytes, g.dkernel, dk_bytes), "%s: problem %d: dbias may not overlap x, dy or "
-                   "dkernel", what, i);
+        ML_REQUIRE(!ml_any_overlap({r_db}, {r_x, r_dy, r_dk}), "%s: problem %d: dbias may not overlap x, dy or dkernel", what, i);
         ML_REQUIRE(ml_add_or_disjoint(g.dbias, g.add_bias, db_bytes), "%s: problem %d: dbias may be add itself, not a shifted view "
                    "of it", what, i);
         WgProblem &p = A.p[i];
@@ -368,8 +369,7 @@ extern "C" int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t
     const long long bs = dy_bstride ? dy_bstride : (long long)HW * dy_cstride;
     const long long total = (long long)B * HW * cp;
     ML_REQUIRE((long long)B * HW < (1ll << 31) && total < (1ll << 31) * WG_TPB, "%s: too many pixels", what);
-    ML_REQUIRE(!ml_ranges_overlap(out, total * 4, dy, (((long long)B - 1) * bs + (long long)HW * dy_cstride) * 4),
-               "%s: out may not overlap dy", what);
+    ML_REQUIRE(!ml_ranges_overlap(out, total * 4, dy, ml_view_elems(B, bs, HW, dy_cstride, cout) * 4), "%s: out may not overlap dy", what);
     hipLaunchKernelGGL(gather_dy_kernel, dim3((unsigned)((total + WG_TPB - 1) / WG_TPB)), dim3(WG_TPB), 0, (hipStream_t)stream, dy,
                        out, HW, cout, cp, dy_cstride, bs, total);
     ML_CHECK_LAUNCH(what);

@@ -15,6 +15,7 @@
 // Numerics: exact fp32 products; the 1x1 conv sums its channels in the order (t, e, lane half), not 0 .. C_mid-1
 // (~1e-7 relative).
 #include "gfx_mem.h"
+#include "ranges.h"
 
 namespace {
 
@@ -378,13 +379,10 @@ static int deconv_out_entry(const ml_deconv_out_problem *probs, int32_t nprob, i
             ML_REQUIRE(tapes[i] && ml_aligned16(tapes[i]), "deconv2x2_out1x1_tape: problem %d: the tape must be a 16-byte aligned "
                        "[M, 4, C_mid] tensor", i);
             ML_REQUIRE(!q.live, "deconv2x2_out1x1_tape: the fixed-capacity form (`live`) keeps no tape");
-            for (int j = 0; j < i; ++j) {
-                const uintptr_t a = (uintptr_t)tapes[i], b = (uintptr_t)tapes[j];
-                ML_REQUIRE(a + (uintptr_t)t_bytes <= b || b + (uintptr_t)(probs[j].M * 4 * c_mid * 4) <= a,
+            for (int j = 0; j < i; ++j)
+                ML_REQUIRE(!ml_ranges_overlap(tapes[i], t_bytes, tapes[j], probs[j].M * 4 * c_mid * 4),
                            "deconv2x2_out1x1_tape: problems %d and %d write the same tape", j, i);
-            }
-            const uintptr_t a = (uintptr_t)tapes[i], x = (uintptr_t)q.x;
-            ML_REQUIRE(a + (uintptr_t)t_bytes <= x || x + (uintptr_t)(q.M * K * 4) <= a, "deconv2x2_out1x1_tape: problem %d: the tape "
+            ML_REQUIRE(!ml_ranges_overlap(tapes[i], t_bytes, q.x, q.M * K * 4), "deconv2x2_out1x1_tape: problem %d: the tape "
                        "overlaps x", i);
             A.tape[i] = tapes[i];
         }

@@ -263,8 +263,7 @@ extern "C" int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *pr
     ML_REQUIRE(workspace && (((uintptr_t)workspace) & 255) == 0, "%s: needs a 256-byte aligned workspace", what);
     TgArgs A;
     long long used = 0, blocks = 0, fblocks = 0;
-    struct Range { const void *p; long long bytes; };
-    Range writes[TG_MAX_PROB][3];
+    ml_range writes[TG_MAX_PROB][3];
     for (int i = 0; i < nprob; ++i) {
         const ml_deconv_out_grad_problem &d = probs[i];
         TgPlan pl;
@@ -281,25 +280,15 @@ extern "C" int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *pr
         const long long dy_bytes = ((images - 1) * d.dy_image_stride + (long long)d.rois_per_image * 4 * d.hw * ncls) * 4;
         ML_REQUIRE(ml_add_or_disjoint(d.out, d.t, t_bytes), "%s: problem %d: out may be T itself, not a shifted "
                    "view of it", what, i);
-        ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, dy_lo, dy_bytes) && !ml_ranges_overlap(d.out, t_bytes, d.wo, dk_bytes),
-                   "%s: problem %d: out may not overlap dy or the 1x1 kernel", what, i);
+        const ml_range r_t = {d.t, t_bytes}, r_dy = {dy_lo, dy_bytes}, r_wo = {d.wo, dk_bytes}, r_ws = {workspace, workspace_bytes};
         writes[i][0] = {d.out, t_bytes}; writes[i][1] = {d.dkernel, dk_bytes}; writes[i][2] = {d.dbias, db_bytes};
-        for (int a = 1; a < 3; ++a)
-            ML_REQUIRE(!ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.t, t_bytes) &&
-                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, dy_lo, dy_bytes) &&
-                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.wo, dk_bytes) &&
-                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, d.out, t_bytes) &&
-                       !ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, workspace, workspace_bytes),
-                       "%s: problem %d: dkernel / dbias may not overlap T, dy, the 1x1 kernel, out or the workspace", what, i);
+        ML_REQUIRE(!ml_any_overlap({writes[i][0]}, {r_dy, r_wo}), "%s: problem %d: out may not overlap dy or the 1x1 kernel", what, i);
+        ML_REQUIRE(!ml_any_overlap({writes[i][1], writes[i][2]}, {r_t, r_dy, r_wo, writes[i][0], r_ws}),
+                   "%s: problem %d: dkernel / dbias may not overlap T, dy, the 1x1 kernel, out or the workspace", what, i);
         ML_REQUIRE(!ml_ranges_overlap(d.dkernel, dk_bytes, d.dbias, db_bytes), "%s: problem %d: dkernel overlaps dbias", what, i);
-        ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, workspace, workspace_bytes) &&
-                   !ml_ranges_overlap(d.t, t_bytes, workspace, workspace_bytes),
-                   "%s: problem %d: T / out overlap the workspace", what, i);
+        ML_REQUIRE(!ml_any_overlap({writes[i][0], r_t}, {r_ws}), "%s: problem %d: T / out overlap the workspace", what, i);
         for (int j = 0; j < i; ++j)
-            for (int a = 0; a < 3; ++a)
-                for (int b = 0; b < 3; ++b)
-                    ML_REQUIRE(!ml_ranges_overlap(writes[i][a].p, writes[i][a].bytes, writes[j][b].p, writes[j][b].bytes),
-                               "%s: problems %d and %d write the same tensor", what, j, i);
+            ML_REQUIRE(!ml_any_overlap(writes[i], 3, writes[j], 3), "%s: problems %d and %d write the same tensor", what, j, i);
         for (int j = 0; j < nprob; ++j)
             if (j != i)
                 ML_REQUIRE(!ml_ranges_overlap(d.out, t_bytes, probs[j].t, probs[j].M * 4 * probs[j].c_mid * 4),
@@ -341,8 +330,7 @@ extern "C" int ml_deconv2x2_grad_relayout_f32(const float *dk1x1, const float *d
     ML_REQUIRE((db4 == nullptr) == (dbias == nullptr), "%s: give both bias tensors or neither", what);
     const long long nk = (long long)cin * 4 * c_mid, n = nk + c_mid;
     ML_REQUIRE(n < (1ll << 31), "%s: too large", what);
-    ML_REQUIRE(!ml_ranges_overlap(dkernel, nk * 4, dk1x1, nk * 4) && !ml_ranges_overlap(dbias, c_mid * 4ll, db4, c_mid * 16ll) &&
-               !ml_ranges_overlap(dkernel, nk * 4, db4, c_mid * 16ll) && !ml_ranges_overlap(dbias, c_mid * 4ll, dk1x1, nk * 4) &&
+    ML_REQUIRE(!ml_any_overlap({{dkernel, nk * 4}, {dbias, c_mid * 4ll}}, {{dk1x1, nk * 4}, {db4, c_mid * 16ll}}) &&
                !ml_ranges_overlap(dkernel, nk * 4, dbias, c_mid * 4ll), "%s: the tensors may not overlap", what);
     hipLaunchKernelGGL(deconv_grad_relayout_kernel, dim3((unsigned)((n + TG_TPB - 1) / TG_TPB)), dim3(TG_TPB), 0, (hipStream_t)stream,
                        dk1x1, db4, dkernel, dbias, cin, 4 * c_mid);

@@ -262,8 +262,7 @@ extern "C" int ml_dwconv3x3_wgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs,
                    "%s: problem %d: 4-byte alignment", what, i);
         const long long x_bytes = (long long)d.B * d.H * d.W * d.in_cstride * 4, dy_bytes = pl.P * d.dy_cstride * 4;
         const long long dk_bytes = 9ll * d.C * 4, db_bytes = (long long)d.C * 4;
-        ML_REQUIRE(!ml_ranges_overlap(d.dkernel, dk_bytes, d.x, x_bytes) && !ml_ranges_overlap(d.dkernel, dk_bytes, d.dy, dy_bytes) &&
-                   !ml_ranges_overlap(d.dbias, db_bytes, d.x, x_bytes) && !ml_ranges_overlap(d.dbias, db_bytes, d.dy, dy_bytes) &&
+        ML_REQUIRE(!ml_any_overlap({{d.dkernel, dk_bytes}, {d.dbias, db_bytes}}, {{d.x, x_bytes}, {d.dy, dy_bytes}}) &&
                    !ml_ranges_overlap(d.dbias, db_bytes, d.dkernel, dk_bytes), "%s: problem %d: the outputs may not overlap x, dy or "
                    "each other", what, i);
         ML_REQUIRE(ml_add_or_disjoint(d.dkernel, d.add_kernel, dk_bytes),
@@ -301,8 +300,8 @@ extern "C" int ml_dwconv3x3_dgrad_multi_f32(const ml_dwconv3x3_grad_desc *descs,
         ML_REQUIRE(ml_aligned16(d.dy) && ml_aligned16(d.wgt) && ml_aligned16(d.dx) && ml_aligned16(d.add_x),
                    "%s: problem %d: pointers must be 16-byte aligned", what, i);
         const long long dx_bytes = (long long)d.B * d.H * d.W * d.C * 4;
-        ML_REQUIRE(!ml_ranges_overlap(d.dx, dx_bytes, d.dy, (long long)d.B * d.Ho * d.Wo * d.dy_cstride * 4) &&
-                   !ml_ranges_overlap(d.dx, dx_bytes, d.wgt, 9ll * d.C * 4), "%s: problem %d: dx may not overlap dy or the kernel", what, i);
+        ML_REQUIRE(!ml_any_overlap({{d.dx, dx_bytes}}, {{d.dy, (long long)d.B * d.Ho * d.Wo * d.dy_cstride * 4}, {d.wgt, 9ll * d.C * 4}}),
+                   "%s: problem %d: dx may not overlap dy or the kernel", what, i);
         ML_REQUIRE(ml_add_or_disjoint(d.dx, d.add_x, dx_bytes),
                    "%s: problem %d: dx may be add itself, not a shifted view of it", what, i);
         for (int j = 0; j < i; ++j)

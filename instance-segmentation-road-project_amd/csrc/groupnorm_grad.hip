@@ -18,7 +18,7 @@
 // forward's own code (gn_common.h) over the forward's slices, so they have the bits of ml_groupnorm_chunk_stats_f32 and of the
 // sliced forward, and the mask is decided by the forward's gn_y().
 #include "gn_common.h"
-#include "slice_sum.h"
+#include "ranges.h"
 
 namespace {
 
@@ -405,7 +405,7 @@ static int gg_run(const ml_gn_grad_desc *descs, int32_t n, const char *what, voi
         ML_REQUIRE(d.dy && d.dx, "%s: null pointer", what);
         const long long bytes = (long long)d.N * d.HWC * (long long)sizeof(float);
         ML_REQUIRE(!ml_ranges_overlap(d.x, bytes, d.dx, bytes), "%s: dx may not alias x (the layer's input is needed as it was)", what);
-        ML_REQUIRE(d.dx == d.dy || !ml_ranges_overlap(d.dy, bytes, d.dx, bytes), "%s: dx may be dy itself, not a shifted view of it", what);
+        ML_REQUIRE(ml_add_or_disjoint(d.dx, d.dy, bytes), "%s: dx may be dy itself, not a shifted view of it", what);
         const long long L = d.HWC / d.G;
         const int cg = d.C / d.G;
         GgProb P;

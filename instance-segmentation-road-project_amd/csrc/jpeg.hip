@@ -26,6 +26,7 @@
 //   7 scatter        header, the bytes with 0x00 after every 0xFF, EOI, the image's length
 // The per-thread bodies are __host__ __device__ functions of a thread index, so they can be run on a CPU in a loop.
 #include "common.h"
+#include "ranges.h"
 #include <string.h>
 #include <initializer_list>
 
@@ -451,12 +452,6 @@ void make_header(int H, int W, const QuantTables &qt, Header &h) {
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void *a, long long na, const void *b, long long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 }  // namespace
 
 extern "C" int64_t ml_jpeg_encode_capacity(int32_t H, int32_t W) {
@@ -487,10 +482,9 @@ extern "C" int ml_jpeg_encode_u8(const uint8_t *images, int32_t B, int32_t H, in
     ML_REQUIRE(ml_aligned16(workspace), "jpeg_encode: workspace must be 16-byte aligned");
     const long long in_bytes = (long long)B * H * W * 3, out_bytes = (long long)B * capacity;
     const long long ws_bytes = ml_jpeg_encode_workspace_bytes(B, H, W);
-    ML_REQUIRE(!overlap(out, out_bytes, images, in_bytes), "jpeg_encode: out overlaps images");
-    ML_REQUIRE(!overlap(workspace, ws_bytes, images, in_bytes) && !overlap(workspace, ws_bytes, out, out_bytes) &&
-               !overlap(lengths, 4ll * B, out, out_bytes) && !overlap(lengths, 4ll * B, workspace, ws_bytes) &&
-               !overlap(lengths, 4ll * B, images, in_bytes),
+    ML_REQUIRE(!ml_ranges_overlap(out, out_bytes, images, in_bytes), "jpeg_encode: out overlaps images");
+    ML_REQUIRE(!ml_any_overlap({{workspace, ws_bytes}, {lengths, 4ll * B}}, {{images, in_bytes}, {out, out_bytes}}) &&
+               !ml_ranges_overlap(workspace, ws_bytes, lengths, 4ll * B),
                "jpeg_encode: workspace or lengths overlaps another buffer");
 
     const unsigned lens_stride = (unsigned)(round16(g.nblk * 4ll) / 4);

@@ -17,7 +17,8 @@
 // A block finds its unit's job by bisection over the table's first_unit, as the optimizer's apply kernel finds a chunk's tensor.
 // No atomics, no workspace, plain vector stores.  Compiled with FP contraction off (Makefile): w - hi(w) of the split form and
 // the fp64 sums of G g G^T are the operations written here, one rounding each.
-#include "slice_sum.h"
+#include "common.h"
+#include "ranges.h"
 
 #include <algorithm>
 #include <vector>

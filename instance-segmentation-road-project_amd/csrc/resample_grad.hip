@@ -12,7 +12,8 @@
 // no bit-equal coordinates between forward and backward; the test decides.  This file is compiled without FP contraction and
 // with correctly rounded division (Makefile): a coordinate is the float32 value of its expression, one rounding per
 // operation in the order written, whatever the compiler would have fused.
-#include "slice_sum.h"
+#include "common.h"
+#include "ranges.h"
 
 namespace {
 

@@ -16,6 +16,7 @@
 //      out may be c3 itself (every element is read and written by one thread).
 // No atomics: eager launches, graph replay and image k of a batch against image k alone give the same bits.
 #include "common.h"
+#include "ranges.h"
 
 namespace {
 
@@ -234,13 +235,6 @@ int64_t sb_pool_chunk(int32_t HW, int32_t C) {
 }
 int64_t sb_npool(int32_t HW, int32_t C) { return ((int64_t)HW + sb_pool_chunk(HW, C) - 1) / sb_pool_chunk(HW, C); }
 
-// [a, a + bytes) and [b, b + bytes) intersect without being the same range
-bool sb_partial_overlap(const void *a, const void *b, int64_t bytes) {
-    if (!a || !b || a == b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
-}
-
 template <class T>
 int se_bottleneck_launch(const char *what, const ml_se_bottleneck_desc *d, void *workspace, int64_t workspace_bytes,
                          void *stream) {
@@ -266,10 +260,9 @@ int se_bottleneck_launch(const char *what, const ml_se_bottleneck_desc *d, void 
                (long long)need);
     // out may be the very buffer of c3 or of residual (each element is read and written by one thread), nothing else
     const int64_t bytes = (int64_t)d->B * d->HW * d->C * (int64_t)sizeof(T);
-    ML_REQUIRE(!sb_partial_overlap(d->out, d->c3, bytes) && !sb_partial_overlap(d->out, d->residual, bytes),
+    ML_REQUIRE(ml_add_or_disjoint(d->out, d->c3, bytes) && ml_add_or_disjoint(d->out, d->residual, bytes),
                "%s: out partially overlaps an input", what);
-    const uintptr_t ws = (uintptr_t)workspace, o = (uintptr_t)d->out;
-    ML_REQUIRE(ws + (uintptr_t)need <= o || o + (uintptr_t)bytes <= ws, "%s: the workspace overlaps out", what);
+    ML_REQUIRE(!ml_ranges_overlap(workspace, need, d->out, bytes), "%s: the workspace overlaps out", what);
     SbArgs A;
     A.c3 = d->c3;
     A.residual = d->residual;

@@ -17,6 +17,7 @@
 // No atomics: every sum has one fixed order that depends on neither the batch size nor scheduling, so eager launches,
 // graph replay and image k of a batch against image k alone give the same bits.
 #include "common.h"
+#include "ranges.h"
 
 namespace {
 
@@ -156,13 +157,6 @@ int64_t sr_pool_chunk(int32_t HW, int32_t C) {
 }
 int64_t sr_npool(int32_t HW, int32_t C) { return ((int64_t)HW + sr_pool_chunk(HW, C) - 1) / sr_pool_chunk(HW, C); }
 
-// [a, a + bytes) and [b, b + bytes) intersect without being the same range
-bool sr_partial_overlap(const void *a, const void *b, int64_t bytes) {
-    if (!a || !b || a == b) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)bytes && y < x + (uintptr_t)bytes;
-}
-
 }  // namespace
 
 extern "C" int64_t ml_se_residual_workspace_bytes(int32_t B, int32_t HW, int32_t C) {
@@ -205,8 +199,8 @@ extern "C" int ml_se_residual_f32(const ml_se_residual_desc *d, void *workspace,
     const void *outs[2] = {d->out_act, d->out_y};
     for (const void *o : outs)
         for (const void *i : ins)
-            ML_REQUIRE(!sr_partial_overlap(o, i, bytes), "%s: an output partially overlaps an input", what);
-    ML_REQUIRE(d->out_act != d->out_y && !sr_partial_overlap(d->out_act, d->out_y, bytes),
+            ML_REQUIRE(ml_add_or_disjoint(o, i, bytes), "%s: an output partially overlaps an input", what);
+    ML_REQUIRE(d->out_act != d->out_y && !ml_ranges_overlap(d->out_act, bytes, d->out_y, bytes),
                "%s: out_act and out_y overlap", what);
     SrArgs A;
     A.x = d->x;

@@ -1,5 +1,5 @@
 // The parts of the slice-sum scheme that the weight gradients share (conv_grad.hip, dwconv_grad.hip, deconv_out_grad.hip;
-// "One definition: slice sums"), and the range tests every gradient launcher makes.
+// "One definition: slice sums").  Their launchers' range tests come with it from ranges.h.
 //
 // The scheme: the pixel axis of a problem is cut into slices that are a function of its geometry alone; a block writes the
 // fp32 partial of its slice into the launch's workspace (no float atomics); a finish kernel adds an element's partials in
@@ -7,18 +7,7 @@
 // per-launch checks stay in the files: only what was the same text in each of them lives here.  Plain functions, no state.
 #pragma once
 #include "common.h"
-
-// null-safe: no range, no overlap
-inline bool ml_ranges_overlap(const void *a, long long abytes, const void *b, long long bbytes) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return a && b && pa < pb + (uintptr_t)bbytes && pb < pa + (uintptr_t)abytes;
-}
-
-// out = add + gradient is safe: there is no `add`, or it is `out` itself (an element is read before it is written), or the
-// two are apart.  A shifted view is refused.
-inline bool ml_add_or_disjoint(const void *out, const void *add, long long bytes) {
-    return add == out || !ml_ranges_overlap(out, bytes, add, bytes);
-}
+#include "ranges.h"
 
 inline long long ml_align256(long long v) { return (v + 255) & ~255ll; }
 

@@ -9,6 +9,7 @@
 // is the same bytes.
 #include "common.h"
 #include "paste.h"
+#include "ranges.h"
 #pragma clang fp contract(off)
 
 namespace {
@@ -325,12 +326,6 @@ using VisKernels = VisTable<0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 
 inline unsigned grid_for(long long n) { return (unsigned)((n + TPB - 1) / TPB); }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void *a, long long na, const void *b, long long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
-
 int make_palette(const float *colors, int32_t K, float alpha, Palette &p, const char *what) {
     ML_REQUIRE(colors, "%s: null colour table", what);
     ML_REQUIRE(K >= 1 && K <= KMAX, "%s: %d colours, 1 <= K <= %d", what, K, KMAX);
@@ -348,8 +343,8 @@ extern "C" int ml_draw_boxes_u8(const uint8_t *images, const int32_t *det, uint8
     ML_REQUIRE(images && det && out, "draw_boxes: null pointer");
     ML_REQUIRE(B > 0 && B < 65536 && n >= 0 && H > 0 && W > 0, "draw_boxes: bad dims");
     const long long bytes = (long long)B * H * W * 3;
-    ML_REQUIRE(out == images || !overlap(out, bytes, images, bytes), "draw_boxes: out overlaps images (only out == images is allowed)");
-    ML_REQUIRE(!overlap(out, bytes, det, (long long)B * n * 24), "draw_boxes: out overlaps det");
+    ML_REQUIRE(ml_add_or_disjoint(out, images, bytes), "draw_boxes: out overlaps images (only out == images is allowed)");
+    ML_REQUIRE(!ml_ranges_overlap(out, bytes, det, (long long)B * n * 24), "draw_boxes: out overlaps det");
     hipStream_t s = (hipStream_t)stream;
     if (out != images)
         ML_REQUIRE(hipMemcpyAsync(out, images, (size_t)bytes, hipMemcpyDeviceToDevice, s) == hipSuccess, "draw_boxes: copy failed");
@@ -367,8 +362,8 @@ extern "C" int ml_draw_instance_u8(const uint8_t *images, const int32_t *det, co
     const int e = make_palette(colors, K, alpha, pal, "draw_instance");
     if (e != ML_OK) return e;
     const long long px = (long long)B * H * W;
-    ML_REQUIRE(out == images || !overlap(out, px * 3, images, px * 3), "draw_instance: out overlaps images (only out == images is allowed)");
-    ML_REQUIRE(!overlap(out, px * 3, det, (long long)B * n * 24) && !overlap(out, px * 3, masks, px * n * 4),
+    ML_REQUIRE(ml_add_or_disjoint(out, images, px * 3), "draw_instance: out overlaps images (only out == images is allowed)");
+    ML_REQUIRE(!ml_any_overlap({{out, px * 3}}, {{det, (long long)B * n * 24}, {masks, px * n * 4}}),
                "draw_instance: out overlaps det or masks");
     ML_REQUIRE(grid_for(px) < (1u << 31), "draw_instance: frame too large for one launch");
     hipLaunchKernelGGL(draw_instance_kernel, dim3(grid_for(px)), dim3(TPB), 0, (hipStream_t)stream, images, det, masks, out,
@@ -386,8 +381,8 @@ extern "C" int ml_draw_segmentation_u8(const uint8_t *images, const void *maps, 
     const int e = make_palette(colors, K, alpha, pal, "draw_segmentation");
     if (e != ML_OK) return e;
     const long long px = (long long)B * H * W;
-    ML_REQUIRE(out == images || !overlap(out, px * 3, images, px * 3), "draw_segmentation: out overlaps images (only out == images is allowed)");
-    ML_REQUIRE(!overlap(out, px * 3, maps, px * K * 4), "draw_segmentation: out overlaps maps");
+    ML_REQUIRE(ml_add_or_disjoint(out, images, px * 3), "draw_segmentation: out overlaps images (only out == images is allowed)");
+    ML_REQUIRE(!ml_ranges_overlap(out, px * 3, maps, px * K * 4), "draw_segmentation: out overlaps maps");
     ML_REQUIRE(grid_for(px) < (1u << 31), "draw_segmentation: frame too large for one launch");
     hipStream_t s = (hipStream_t)stream;
     if (maps_are_f32)
@@ -411,12 +406,11 @@ extern "C" int ml_serving_visualize_u8(const uint8_t *images, const int32_t *det
     e = make_palette(semantic_colors, Ks, semantic_alpha, ps, "serving_visualize");
     if (e != ML_OK) return e;
     const long long px = (long long)B * H * W;
-    ML_REQUIRE(out == images || !overlap(out, px * 3, images, px * 3), "serving_visualize: out overlaps images (only out == images is allowed)");
-    ML_REQUIRE(!overlap(out, px * 3, det, (long long)B * n * 24) && !overlap(out, px * 3, ins, (long long)B * n * mh * mw * 4) &&
-               !overlap(out, px * 3, seg, px * Ks * 4) && !overlap(out, px * 3, threshold_ws, 4),
+    ML_REQUIRE(ml_add_or_disjoint(out, images, px * 3), "serving_visualize: out overlaps images (only out == images is allowed)");
+    const ml_range r_det = {det, (long long)B * n * 24}, r_ins = {ins, (long long)B * n * mh * mw * 4}, r_seg = {seg, px * Ks * 4};
+    ML_REQUIRE(!ml_any_overlap({{out, px * 3}}, {r_det, r_ins, r_seg, {threshold_ws, 4}}),
                "serving_visualize: out overlaps an input or the threshold workspace");
-    ML_REQUIRE(!overlap(threshold_ws, 4, images, px * 3) && !overlap(threshold_ws, 4, det, (long long)B * n * 24) &&
-               !overlap(threshold_ws, 4, ins, (long long)B * n * mh * mw * 4) && !overlap(threshold_ws, 4, seg, px * Ks * 4),
+    ML_REQUIRE(!ml_any_overlap({{threshold_ws, 4}}, {{images, px * 3}, r_det, r_ins, r_seg}),
                "serving_visualize: threshold_ws overlaps an input");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(conf_threshold_kernel, dim3(1), dim3(256), 0, s, det, B * n, threshold_ws);
