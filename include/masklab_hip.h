@@ -79,7 +79,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             _wgrad_plan, ml_dwconv3x3_dgrad_multi_f32, ml_relu_grad_f32;
                                             (additive, same version) ml_deconv2x2_out1x1_tape_f32, ml_deconv_out_grad_problem,
                                             ml_deconv2x2_out1x1_grad_f32 / _grad_plan, ml_deconv2x2_grad_relayout_f32;
-                                            (additive, same version) ml_repack_job, ml_repack_plan, ml_repack_f32 */
+                                            (additive, same version) ml_repack_job, ml_repack_plan, ml_repack_f32;
+                                            (additive, same version) ml_batchnorm_train_f32 / _infer_f32 / _grad_f32 /
+                                            _workspace_bytes / _plan */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -553,6 +555,46 @@ typedef struct ml_gn_grad_desc {
 } ml_gn_grad_desc;
 int ml_groupnorm_grad_multi_f32(const ml_gn_grad_desc *descs, int32_t n, void *workspace, int64_t workspace_bytes,
                                 void *stream);
+
+/* ---------------------------------------------------------------- BatchNormalization, training (fp32 only; csrc/batchnorm.hip)
+ * tf.keras.layers.BatchNormalization in training mode on NHWC tensors, axis = -1: every sum runs over all N = B*H*W pixels
+ * of a channel c.  The moving-statistics rule is tf.keras's fused path as remembered from the 1.x releases; parity with
+ * TensorFlow is UNPINNED (README).
+ *   mean_b = sum x / N,   var_b = sum (x - mean_b)^2 / N   (biased)
+ *   r = 1/sqrt(var_b + eps),   scale = gamma * r,   shift = beta - mean_b * scale      (fp64, each rounded once to float32)
+ *   y = x * scale + shift [+ residual],   then max(., 0) when relu
+ *   var_u = var_b * N / (N - 1);   batch_mean = f32(mean_b),  batch_var = f32(var_u)    (rounded once from fp64)
+ *   moving <- moving - (moving - batch_stat) * f32(1 - momentum)                         three float32 operations, each
+ *                                                                                        rounded, no fused multiply-add
+ * Backward, with the forward's saved (mean_b, r) in fp64:
+ *   g = dy * [y > 0] when relu (strict, as tf.nn.relu's; decided on the forward's own y), else g = dy
+ *   xhat = (x - mean_b) * r,   dbeta = sum g,   dgamma = sum g * xhat
+ *   dx = scale * (g - dbeta/N - xhat * dgamma/N),   d_residual = g
+ * Inference: scale = gamma / sqrt(moving_var + eps), shift = beta - moving_mean * scale (fp64, rounded once), the same y.
+ * gamma == NULL: ones (scale=False).  beta == NULL: zeros (center=False).  residual == NULL: none.
+ * Sums are fp64 in a fixed order (thread, block rows in order, slices in ascending order), no atomics, no host read: two
+ * launches give the same bits whatever outputs and workspace held; the launches can be captured in a graph.
+ * Refused (ML_E_BADARG, the message names the argument): C no multiple of 4 (lanes run along the channels with 16-byte
+ * accesses), N < 2 in training (var_u divides by N - 1), maps that are not 16-byte aligned, a workspace smaller than
+ * ml_batchnorm_workspace_bytes(N, C), and every aliasing but: y may be x itself; dx may be dy itself; d_residual may be dy
+ * itself when dx is not.
+ * saved: [C][2] doubles (mean_b, r), written by _train, read by _grad.  batch_mean / batch_var: [C] floats.
+ * moving_mean / moving_var: [C], updated in place; both NULL: no update.  d_residual, dgamma, dbeta: NULL = not wanted.
+ * y of _grad is read only when relu.  Nothing in the workspace needs initialising. */
+int64_t ml_batchnorm_workspace_bytes(int64_t N, int32_t C);        /* -1: refused, ml_last_error() says why */
+/* host only: the slice plan, a function of (N, C) alone -- slices of the pixel axis, pixels per slice (the last one may be
+ * shorter), workspace bytes.  Any of the three pointers may be NULL. */
+int ml_batchnorm_plan(int64_t N, int32_t C, int32_t *slices, int64_t *pixels_per_slice, int64_t *bytes);
+int ml_batchnorm_train_f32(const float *x, const float *residual, float *y, const float *gamma, const float *beta,
+                           float *moving_mean, float *moving_var, double *saved, float *batch_mean, float *batch_var,
+                           int64_t N, int32_t C, float eps, double momentum, int32_t relu,
+                           void *workspace, int64_t workspace_bytes, void *stream);
+int ml_batchnorm_infer_f32(const float *x, const float *residual, float *y, const float *gamma, const float *beta,
+                           const float *moving_mean, const float *moving_var, int64_t N, int32_t C, float eps,
+                           int32_t relu, void *workspace, int64_t workspace_bytes, void *stream);
+int ml_batchnorm_grad_f32(const float *x, const float *dy, const float *y, const double *saved, const float *gamma,
+                          float *dx, float *d_residual, float *dgamma, float *dbeta, int64_t N, int32_t C,
+                          int32_t relu, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------- resampling / reductions
  * tf.compat.v1.image.resize_bilinear(align_corners=True) (engine/layers/misc.py:306), with the

@@ -212,6 +212,11 @@ SIGNATURES = {
     "ml_groupnorm_chunk_grad_f32": (C.c_int, [_vp] * 8 + [_i32, _i64, _i32, _i32, _f32, _i32, _i32, _vp, _vp]),
     "ml_groupnorm_chunk_stats_f32": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp]),
     "ml_groupnorm_grad_multi_f32": (C.c_int, [C.POINTER(GnGradDesc), _i32, _vp, _i64, _vp]),
+    "ml_batchnorm_workspace_bytes": (_i64, [_i64, _i32]),
+    "ml_batchnorm_plan": (C.c_int, [_i64, _i32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ml_batchnorm_train_f32": (C.c_int, [_vp] * 10 + [_i64, _i32, _f32, _f64, _i32, _vp, _i64, _vp]),
+    "ml_batchnorm_infer_f32": (C.c_int, [_vp] * 7 + [_i64, _i32, _f32, _i32, _vp, _i64, _vp]),
+    "ml_batchnorm_grad_f32": (C.c_int, [_vp] * 9 + [_i64, _i32, _i32, _vp, _i64, _vp]),
     "ml_resize_bilinear_ac_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 12 + [_vp]),
     "ml_resize_bilinear_ac_grad_workspace_bytes": (_i64, [_i32] * 6),
     "ml_resize_bilinear_ac_grad_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 8 + [_vp, _i64, _vp]),

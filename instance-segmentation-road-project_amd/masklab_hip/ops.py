@@ -1169,6 +1169,148 @@ def groupnorm_chunk_grad_multi(problems):
     return outs
 
 
+def batchnorm_plan(pixels, channels):
+    """The slice plan of the BatchNormalization kernels (ml_batchnorm_plan), host only, a function of the geometry alone:
+    pixels = B*H*W values per channel.  -> {"slices", "pixels_per_slice", "bytes"} (bytes: the workspace)."""
+    slices, per, nbytes = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    lib = _lib.load()
+    if lib.ml_batchnorm_plan(int(pixels), int(channels), C.byref(slices), C.byref(per), C.byref(nbytes)) != 0:
+        raise ValueError(lib.ml_last_error().decode())
+    return {"slices": slices.value, "pixels_per_slice": per.value, "bytes": nbytes.value}
+
+
+def _bn_problem(what, maps, vectors, training=True, out=None, out_may_be=(), also=None):
+    """The argument checks the three BatchNormalization ops share (shapes and dtypes first: they need no device), with the
+    exception types of _gn_grad_problem.  maps: {name: tensor or None} of x's shape, x first; vectors: {name: tensor or
+    None} of [C].  out: None or a float32 tensor of x's shape, which may be one of the maps named in out_may_be.  also(C):
+    the op's own host checks, run before the first check that needs a device.
+    -> (pixels, C)"""
+    x = maps["x"]
+    for name, t in maps.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() < 2:
+            raise ValueError(f"{what}: `{name}` must be a tensor [..., C]")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: `{name}` is {t.dtype}; BatchNormalization's training kernels are float32 only")
+        if tuple(t.shape) != tuple(x.shape):
+            raise ValueError(f"{what}: `{name}` {tuple(t.shape)} must have x's shape {tuple(x.shape)}")
+    Cc = x.shape[-1]
+    N = x.numel() // max(Cc, 1)
+    if Cc < 1 or Cc % 4:
+        raise ValueError(f"{what}: C ({Cc}) must be a multiple of 4: lanes run along the channels with 16-byte accesses")
+    if N < (2 if training else 1):
+        raise ValueError(f"{what}: N ({N} pixels per channel) must be at least 2: the moving variance takes var_b*N/(N-1)")
+    for name, t in vectors.items():
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (Cc,)):
+            raise ValueError(f"{what}: `{name}` must be a float32 tensor [{Cc}]")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape)):
+        raise ValueError(f"{what}: `out` must be a float32 tensor of x's shape")
+    if also is not None:
+        also(Cc)
+    for name, t in list(maps.items()) + list(vectors.items()) + [("out", out)]:
+        if t is not None:
+            _require_dev(t, name)
+    if out is not None:
+        for name, t in maps.items():
+            if t is not None and name not in out_may_be and out.data_ptr() == t.data_ptr():
+                allowed = " or ".join(out_may_be)
+                raise ValueError(f"{what}: `out` may be {allowed}, not {name}")
+    return N, Cc
+
+
+def _bn_forward_bytes(x, residual):
+    """algorithmic: x (and the residual) read once, y written once"""
+    return x.element_size() * x.numel() * (2 + (residual is not None))
+
+
+def batchnorm_train(x, gamma, beta, moving_mean, moving_var, momentum, eps, relu=False, residual=None, out=None,
+                    update_moving=True):
+    """BatchNormalization in Keras's training mode (csrc/batchnorm.hip; include/masklab_hip.h has the arithmetic), float32
+    NHWC: normalises with the statistics of the batch, y = x*scale + shift [+ residual] [ReLU], and moves moving_mean /
+    moving_var toward the batch's (in place; update_moving=False: they are not touched and may be None).
+    gamma / beta = None: scale=False / center=False.  out: None, or x itself (in place: then x is gone, no backward).
+    -> (y, saved, batch_mean, batch_var): saved = float64 [C, 2] (mean_b, r) for batchnorm_grad; batch_var is the
+    Bessel-corrected variance, as TF returns it."""
+    what = "batchnorm_train"
+
+    def also(Cc):
+        if update_moving and (moving_mean is None or moving_var is None):
+            raise ValueError(f"{what}: `moving_mean` and `moving_var` are needed with update_moving")
+        if not 0.0 <= float(momentum) <= 1.0:
+            raise ValueError(f"{what}: `momentum` ({momentum}) must be in [0, 1]")
+
+    N, Cc = _bn_problem(what, {"x": x, "residual": residual}, {"gamma": gamma, "beta": beta, "moving_mean": moving_mean,
+                                                               "moving_var": moving_var}, out=out, out_may_be=("x",), also=also)
+    lib = _lib.load()
+    y = torch.empty_like(x) if out is None else out
+    saved = torch.empty((Cc, 2), dtype=torch.float64, device=x.device)
+    batch_mean = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    batch_var = torch.empty(Cc, dtype=torch.float32, device=x.device)
+    ws = workspace(lib.ml_batchnorm_workspace_bytes(N, Cc), x.device, "gn")        # the normalisation layers' scratch
+    mm, mv = (moving_mean, moving_var) if update_moving else (None, None)
+    with _Prof("batchnorm_train", 0, _bn_forward_bytes(x, residual), f"N={N} C={Cc}"):
+        _lib.check(lib.ml_batchnorm_train_f32(_ptr(x), _ptr(residual), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(mm), _ptr(mv),
+                                              _ptr(saved), _ptr(batch_mean), _ptr(batch_var), N, Cc, float(eps),
+                                              float(momentum), int(relu), _ptr(ws), ws.numel(), _stream()),
+                   "ml_batchnorm_train_f32")
+    return y, saved, batch_mean, batch_var
+
+
+def batchnorm_infer(x, gamma, beta, moving_mean, moving_var, eps, relu=False, residual=None, out=None):
+    """BatchNormalization's inference arithmetic on device-resident moving statistics (no host copy of them, no fold into a
+    conv): y = x*scale + shift [+ residual] [ReLU], scale = gamma/sqrt(moving_var + eps), shift = beta - moving_mean*scale.
+    out: None, or x itself."""
+    what = "batchnorm_infer"
+
+    def also(Cc):
+        if moving_mean is None or moving_var is None:
+            raise ValueError(f"{what}: `moving_mean` and `moving_var` are needed")
+
+    N, Cc = _bn_problem(what, {"x": x, "residual": residual}, {"gamma": gamma, "beta": beta, "moving_mean": moving_mean,
+                                                               "moving_var": moving_var}, training=False, out=out,
+                        out_may_be=("x",), also=also)
+    lib = _lib.load()
+    y = torch.empty_like(x) if out is None else out
+    ws = workspace(lib.ml_batchnorm_workspace_bytes(N, Cc), x.device, "gn")        # the normalisation layers' scratch
+    with _Prof("batchnorm_infer", 0, _bn_forward_bytes(x, residual), f"N={N} C={Cc}"):
+        _lib.check(lib.ml_batchnorm_infer_f32(_ptr(x), _ptr(residual), _ptr(y), _ptr(gamma), _ptr(beta), _ptr(moving_mean),
+                                              _ptr(moving_var), N, Cc, float(eps), int(relu), _ptr(ws), ws.numel(), _stream()),
+                   "ml_batchnorm_infer_f32")
+    return y
+
+
+def batchnorm_grad(x, dy, saved, gamma, y=None, relu=False, out=None, want_residual_grad=False, want_param_grads=True):
+    """Backward of batchnorm_train: x its input, dy the gradient at its output, saved its second result, gamma as given to it.
+    relu: the forward fused a ReLU; y, the forward's output, is then needed (the mask is decided on it; with a residual it
+    cannot be recomputed from x).  out: None, or dy (in place on the gradient buffer).  want_residual_grad: the gradient of
+    the forward's residual (= g), a tensor of its own.
+    -> (dx, d_residual | None, dgamma | None, dbeta | None)"""
+    what = "batchnorm_grad"
+    if relu and y is None:
+        raise ValueError(f"{what}: `y` (the forward's output) is needed with relu: the mask is decided on it")
+
+    def also(Cc):
+        if not isinstance(saved, torch.Tensor) or saved.dtype != torch.float64 or tuple(saved.shape) != (Cc, 2):
+            raise ValueError(f"{what}: `saved` must be float64 [{Cc}, 2] (batchnorm_train's second result)")
+
+    N, Cc = _bn_problem(what, {"x": x, "dy": dy, "y": y if relu else None}, {"gamma": gamma}, out=out, out_may_be=("dy",),
+                        also=also)
+    _require_dev(saved, "saved")
+    lib = _lib.load()
+    dx = torch.empty_like(x) if out is None else out
+    dres = torch.empty_like(x) if want_residual_grad else None
+    dgamma = torch.empty(Cc, dtype=torch.float32, device=x.device) if want_param_grads else None
+    dbeta = torch.empty(Cc, dtype=torch.float32, device=x.device) if want_param_grads else None
+    ws = workspace(lib.ml_batchnorm_workspace_bytes(N, Cc), x.device, "gn")        # the normalisation layers' scratch
+    nbytes = x.element_size() * x.numel() * (3 + int(relu) + int(want_residual_grad))
+    with _Prof("batchnorm_grad", 0, nbytes, f"N={N} C={Cc}"):
+        _lib.check(lib.ml_batchnorm_grad_f32(_ptr(x), _ptr(dy), _ptr(y if relu else None), _ptr(saved), _ptr(gamma), _ptr(dx),
+                                             _ptr(dres), _ptr(dgamma), _ptr(dbeta), N, Cc, int(relu), _ptr(ws), ws.numel(),
+                                             _stream()), "ml_batchnorm_grad_f32")
+    return dx, dres, dgamma, dbeta
+
+
 def resize_bilinear_ac(x, oh, ow, add=None, out=None, out_coff=0):
     lib = _lib.load()
     _require_dev(x, "x")
