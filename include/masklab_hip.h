@@ -20,6 +20,10 @@
  *     (hipFuncSetAttribute is a per-device setting; racing threads set the same value), and
  *     a per-device cache of the compute-unit count (sizes the persistent kernels' grids;
  *     never changes what is computed).
+ *
+ * masklab_hip/_lib.py binds this file by hand and tests/test_abi_cpu.py holds that binding to it: every prototype,
+ * struct and ML_* constant, parsed from here.  A new entry point needs its declaration here and a row in
+ * _lib.SIGNATURES (a new struct: a mirror in _lib.STRUCTS), and nothing in any test file.
  */
 #ifndef MASKLAB_HIP_H
 #define MASKLAB_HIP_H
@@ -81,7 +85,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             ml_deconv2x2_out1x1_grad_f32 / _grad_plan, ml_deconv2x2_grad_relayout_f32;
                                             (additive, same version) ml_repack_job, ml_repack_plan, ml_repack_f32;
                                             (additive, same version) ml_batchnorm_train_f32 / _infer_f32 / _grad_f32 /
-                                            _workspace_bytes / _plan */
+                                            _workspace_bytes / _plan;
+                                            (additive, same version) ML_DECONV_OUT_MAX_PROBLEMS, ML_JPEG_DECODE_MAX_BATCH:
+                                            names for limits the entry points already had */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -378,7 +384,8 @@ int ml_stem7x7s2_pool_x3(const float *image, const void *wgt_x3, const float *bi
 /* ---------------------------------------------------------------- fused mask-head tail
  * Conv2DTranspose(C_mid, (2,2), (2,2)) + bias + act_mid followed by Conv2D(ncls, (1,1)) + bias + act_out in one
  * kernel (reference engine/layers/instance.py:196-201 constructs the pair, :226-233 calls it; replaces the
- * tf.nn.conv2d_transpose -> tf.nn.conv2d pair).  Up to 4 problems (RoI levels, each with its own weights) per launch.
+ * tf.nn.conv2d_transpose -> tf.nn.conv2d pair).  Up to ML_DECONV_OUT_MAX_PROBLEMS problems (RoI levels, each with its own
+ * weights) per launch.
  *   x        [M, K] fp32, M = rois * hw input pixels (whole h x w maps, RoIs grouped per image: rois = B * rois_per_image)
  *   wd       [4][C_mid][K]: position q = dy*2+dx major, k contiguous (the ml_conv2d_desc packing of the transposed conv)
  *   bd       [C_mid] or NULL;   bo [ncls] or NULL
@@ -388,6 +395,7 @@ int ml_stem7x7s2_pool_x3(const float *image, const void *wgt_x3, const float *bi
  *   out      element (img, j, 2y+dy, 2x+dx, c) of RoI j of image img at
  *            out[img * out_image_stride + out_base + j * (4 hw ncls) + ((2y+dy) * 2w + 2x+dx) * ncls + c]
  * K % 32 == 0, C_mid in {128, 256}, ncls <= 32, M < 2^24 per problem. */
+#define ML_DECONV_OUT_MAX_PROBLEMS 4   /* problems per launch of the tail, forward and backward */
 typedef struct ml_deconv_out_problem {
     const float *x, *wd, *bd, *wo_table, *bo;
     float *out;
@@ -419,9 +427,9 @@ int ml_deconv2x2_out1x1_tape_f32(const ml_deconv_out_problem *probs, float *cons
  *   out[m,q,c]   = t[m,q,c] > 0 ? sum_k dy[pixel(m,q), k] * wo[c,k] : 0     ([M, 4, C_mid]; out may be t itself)
  *   dkernel[c,k] = sum over (m,q) of t[m,q,c] * dy[pixel(m,q), k]           ([1,1,C_mid,ncls], the Keras layout)
  *   dbias[k]     = sum over (m,q) of dy[pixel(m,q), k]
- * in ONE pass over t (read once; out written once; dy read once).  wo is the 1x1 kernel itself, [C_mid, ncls].  Up to 4
- * problems per launch.  C_mid % 4 == 0, C_mid <= 256, ncls <= 32, M < 2^24.  A row whose dy is all zero loads no t and
- * stores zeros (the same bits for every finite t).
+ * in ONE pass over t (read once; out written once; dy read once).  wo is the 1x1 kernel itself, [C_mid, ncls].  Up to
+ * ML_DECONV_OUT_MAX_PROBLEMS problems per launch.  C_mid % 4 == 0, C_mid <= 256, ncls <= 32, M < 2^24.  A row whose dy is all
+ * zero loads no t and stores zeros (the same bits for every finite t).
  * No float atomics: the pixels are cut into slices of ceil(M / 512) pixels rounded up to a multiple of 32, at least 128 -- a
  * function of the problem's pixel count alone (ml_deconv2x2_out1x1_grad_plan); a block sums a slice in a fixed order (dkernel
  * in fp32, the dy sums of dbias in fp64), the finish kernel adds an element's partials in ascending slice order in fp64 and
@@ -996,6 +1004,7 @@ int ml_jpeg_encode_u8(const uint8_t *images, int32_t B, int32_t H, int32_t W, in
  * ------------------------------------------------------------------------------------------- */
 enum { ML_JPEG_GRAY = 0, ML_JPEG_444 = 1, ML_JPEG_420 = 2 };
 #define ML_JPEG_UNSUPPORTED 1
+#define ML_JPEG_DECODE_MAX_BATCH 32    /* streams per call of the device entries below (decode and entropy) */
 /* Host.  info int32[4] = { H, W, mode, blocks }.  ML_OK: the device path takes the stream; ML_JPEG_UNSUPPORTED: it does
  * not (ml_last_error says why; also for a header that cannot be read) -- decode it elsewhere.                */
 int ml_jpeg_decode_info(const uint8_t *data, int64_t n, int32_t *info);
@@ -1007,7 +1016,7 @@ int64_t ml_jpeg_decode_packed_bytes(const uint8_t *data, int64_t n);
  * its table, a run past coefficient 63, a DC category above 11 or an AC size above 10, a wrong or missing RSTn, a
  * missing EOI, a full buffer.  Never reads beyond data[n) or writes beyond packed[capacity).                 */
 int64_t ml_jpeg_decode_entropy(const uint8_t *data, int64_t n, void *packed, int64_t capacity);
-/* Device.  Planar uint8 Y, Cb, Cr of B images (1 <= B <= 32) between the two launches.                       */
+/* Device.  Planar uint8 Y, Cb, Cr of B images (1 <= B <= ML_JPEG_DECODE_MAX_BATCH) between the two launches. */
 int64_t ml_jpeg_decode_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t mode);
 /* Device.  `packed`: B packed images of the same H, W and mode in one device buffer, image b at byte offsets[b]
  * (host array of B + 1, offsets[B] = the end; 16-byte aligned) -> out uint8 [B,H,W,3] (4-byte aligned, below 2^31
@@ -1065,7 +1074,8 @@ int ml_jpeg_entropy_geometry(int32_t *geometry);
  * host decoder's reason for a stream that is not taken, truncated before SOS or without one of its tables.    */
 int64_t ml_jpeg_entropy_plan_bytes(void);
 int ml_jpeg_entropy_plan(const uint8_t *data, int64_t n, void *plan);
-/* Host.  Workspace of a call over B streams (1 <= B <= 32), stream b being file_offsets[b + 1] - file_offsets[b] bytes. */
+/* Host.  Workspace of a call over B streams (1 <= B <= ML_JPEG_DECODE_MAX_BATCH), stream b being
+ * file_offsets[b + 1] - file_offsets[b] bytes. */
 int64_t ml_jpeg_entropy_workspace_bytes(const int64_t *file_offsets, int32_t B);
 /* Device.  files: the raw files in one device buffer, stream b at byte file_offsets[b] (host array of B + 1);
  * plans: B plans, ml_jpeg_entropy_plan_bytes() apart; packed: stream b's packed form goes to byte packed_offsets[b]

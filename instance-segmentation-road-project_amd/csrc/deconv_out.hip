@@ -21,7 +21,6 @@ namespace {
 
 constexpr int TM = 128;                            // input pixels per block
 constexpr int ROWB = 128;                          // bytes of K per staged row and chunk (32 floats)
-constexpr int DO_MAX_PROB = 4;
 
 struct DoProb {
     const void *x, *wd;          // fp32, or IEEE half when the launch is the fp16-storage one (HALF)
@@ -34,10 +33,10 @@ struct DoProb {
     long long img_stride, base;  // out elements: between images / of this level's first RoI in image 0
 };
 struct DoArgs {
-    DoProb p[DO_MAX_PROB];
+    DoProb p[ML_DECONV_OUT_MAX_PROBLEMS];
     int nprob, K, ncls, cp, tiles, out_sigmoid;
     float mid_lo, mid_hi, out_lo, out_hi;      // activations as clamps (the output one unless out_sigmoid)
-    float *tape[DO_MAX_PROB];                  // TAPE launches: per problem T [M][4][C_mid], the transposed conv's output
+    float *tape[ML_DECONV_OUT_MAX_PROBLEMS];   // TAPE launches: per problem T [M][4][C_mid], the transposed conv's output
 };
 
 // n / d for 0 <= n < 2^24 (exact in float), d >= 1: one multiply and a two-sided correction
@@ -341,7 +340,7 @@ int launch_do(const DoArgs &A, hipStream_t s) {
 static int deconv_out_entry(const ml_deconv_out_problem *probs, int32_t nprob, int32_t K, int32_t c_mid, int32_t ncls,
                             int32_t cp, int32_t act_mid, int32_t act_out, void *stream, bool half, float *const *tapes = nullptr) {
     const int es = half ? 2 : 4, kc = half ? 64 : 32;
-    ML_REQUIRE(probs && nprob >= 1 && nprob <= DO_MAX_PROB, "deconv2x2_out1x1: 1..%d problems per launch", DO_MAX_PROB);
+    ML_REQUIRE(probs && nprob >= 1 && nprob <= ML_DECONV_OUT_MAX_PROBLEMS, "deconv2x2_out1x1: 1..%d problems per launch", ML_DECONV_OUT_MAX_PROBLEMS);
     ML_REQUIRE(K >= kc && K % kc == 0, "deconv2x2_out1x1: input channels (%d) must be a multiple of %d", K, kc);
     ML_REQUIRE(c_mid == 128 || c_mid == 256, "deconv2x2_out1x1: transposed-conv filters must be 128 or 256 (got %d)", c_mid);
     ML_REQUIRE(ncls >= 1 && ncls <= 32 && cp >= ncls && cp <= 32 && (cp & (cp - 1)) == 0,
@@ -387,7 +386,7 @@ static int deconv_out_entry(const ml_deconv_out_problem *probs, int32_t nprob, i
             A.tape[i] = tapes[i];
         }
     }
-    for (int i = nprob; i < DO_MAX_PROB; ++i) { A.p[i] = A.p[0]; A.tape[i] = A.tape[0]; }
+    for (int i = nprob; i < ML_DECONV_OUT_MAX_PROBLEMS; ++i) { A.p[i] = A.p[0]; A.tape[i] = A.tape[0]; }
     A.tiles = tiles;
     if (tapes) return c_mid == 128 ? launch_do<4, false, true>(A, (hipStream_t)stream) : launch_do<8, false, true>(A, (hipStream_t)stream);
     if (half) return c_mid == 128 ? launch_do<4, true>(A, (hipStream_t)stream) : launch_do<8, true>(A, (hipStream_t)stream);

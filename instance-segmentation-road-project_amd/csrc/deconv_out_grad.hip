@@ -36,7 +36,6 @@
 namespace {
 
 constexpr int TG_TPB = 256;
-constexpr int TG_MAX_PROB = 4;
 constexpr int TG_ROUND = 32;           // slice lengths are multiples of this
 constexpr int TG_SLICE_MIN = 128;
 constexpr int TG_SLICE_DIV = 512;      // at most this many slices per problem
@@ -50,7 +49,7 @@ struct TgProb {
     int cl_shift, sp, slices, first_block, first_fblock;
 };
 struct TgArgs {
-    TgProb p[TG_MAX_PROB];
+    TgProb p[ML_DECONV_OUT_MAX_PROBLEMS];
     int n, ncls;
 };
 
@@ -259,11 +258,11 @@ extern "C" int ml_deconv2x2_out1x1_grad_plan(const ml_deconv_out_grad_problem *p
 extern "C" int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *probs, int32_t nprob, int32_t ncls, void *workspace,
                                             int64_t workspace_bytes, void *stream) {
     const char *what = "deconv2x2_out1x1_grad";
-    ML_REQUIRE(probs && nprob >= 1 && nprob <= TG_MAX_PROB, "%s: 1..%d problems per launch", what, TG_MAX_PROB);
+    ML_REQUIRE(probs && nprob >= 1 && nprob <= ML_DECONV_OUT_MAX_PROBLEMS, "%s: 1..%d problems per launch", what, ML_DECONV_OUT_MAX_PROBLEMS);
     ML_REQUIRE(workspace && (((uintptr_t)workspace) & 255) == 0, "%s: needs a 256-byte aligned workspace", what);
     TgArgs A;
     long long used = 0, blocks = 0, fblocks = 0;
-    ml_range writes[TG_MAX_PROB][3];
+    ml_range writes[ML_DECONV_OUT_MAX_PROBLEMS][3];
     for (int i = 0; i < nprob; ++i) {
         const ml_deconv_out_grad_problem &d = probs[i];
         TgPlan pl;
@@ -305,7 +304,7 @@ extern "C" int ml_deconv2x2_out1x1_grad_f32(const ml_deconv_out_grad_problem *pr
         blocks += pl.slices;
         fblocks += ((long long)d.c_mid * ncls + ncls + TG_TPB - 1) / TG_TPB;
     }
-    for (int i = nprob; i < TG_MAX_PROB; ++i) A.p[i] = A.p[0];
+    for (int i = nprob; i < ML_DECONV_OUT_MAX_PROBLEMS; ++i) A.p[i] = A.p[0];
     A.n = nprob; A.ncls = ncls;
     hipStream_t s = (hipStream_t)stream;
     int cp = 1;

@@ -32,7 +32,7 @@ constexpr int LANES = 8;                                           // lanes per 
 constexpr int BLOCKS_PER_WG = TPB / LANES;
 constexpr int PITCH = 9, BLOCK_INTS = 72;                          // LDS: row pitch 9, 72 = 8 (mod 64): both passes hit 64 banks
 constexpr uint32_t MAGIC = 0x4B50444Au;                            // "JDPK"
-constexpr int MAX_SIDE = 16384, MAX_BATCH = 32;
+constexpr int MAX_SIDE = 16384;
 constexpr int MAX_COMPONENTS = 3;
 
 struct PackedHeader {
@@ -52,7 +52,7 @@ struct Geometry {
 };
 
 struct Offsets {
-    long long at[MAX_BATCH];                                       // byte offset of image b in the packed upload
+    long long at[ML_JPEG_DECODE_MAX_BATCH];                        // byte offset of image b in the packed upload
 };
 
 long long round16(long long n) { return (n + 15) / 16 * 16; }
@@ -694,7 +694,7 @@ extern "C" int64_t ml_jpeg_decode_workspace_bytes(int32_t B, int32_t H, int32_t 
     Geometry g;
     const int e = geometry(H, W, mode, g, "jpeg_decode_workspace_bytes");
     if (e != ML_OK) return e;
-    ML_REQUIRE(B > 0 && B <= MAX_BATCH, "jpeg_decode_workspace_bytes: bad dims (B %d; 1 .. %d)", B, MAX_BATCH);
+    ML_REQUIRE(B > 0 && B <= ML_JPEG_DECODE_MAX_BATCH, "jpeg_decode_workspace_bytes: bad dims (B %d; 1 .. %d)", B, ML_JPEG_DECODE_MAX_BATCH);
     return (long long)B * (g.y_bytes + 2 * g.c_bytes);
 }
 
@@ -702,7 +702,7 @@ namespace {
 int check_call(const char *what, const void *packed, const int64_t *offsets, int32_t B, int32_t H, int32_t W, int32_t mode,
                const uint8_t *out, const void *workspace, Geometry &g, Offsets &o) {
     ML_REQUIRE(packed && offsets && out && workspace, "%s: null pointer", what);
-    ML_REQUIRE(B > 0 && B <= MAX_BATCH, "%s: bad dims (B %d; 1 .. %d)", what, B, MAX_BATCH);
+    ML_REQUIRE(B > 0 && B <= ML_JPEG_DECODE_MAX_BATCH, "%s: bad dims (B %d; 1 .. %d)", what, B, ML_JPEG_DECODE_MAX_BATCH);
     const int e = geometry(H, W, mode, g, what);
     if (e != ML_OK) return e;
     ML_REQUIRE((long long)B * H * W * 3 < (1ll << 31), "%s: the frames of a call must stay below 2^31 bytes (B %d, H %d, W %d)", what, B, H, W);
@@ -715,7 +715,7 @@ int check_call(const char *what, const void *packed, const int64_t *offsets, int
                    (long long)offsets[b], b + 1, (long long)offsets[b + 1], least);
         o.at[b] = offsets[b];
     }
-    for (int b = B; b < MAX_BATCH; ++b) o.at[b] = 0;
+    for (int b = B; b < ML_JPEG_DECODE_MAX_BATCH; ++b) o.at[b] = 0;
     return ML_OK;
 }
 }  // namespace
@@ -887,8 +887,8 @@ __host__ __device__ inline Region region_of(uint8_t *ws, uint32_t sub_cap, uint3
 }
 
 struct Streams {                                                   // kernel argument: where stream b's buffers are
-    long long file_at[MAX_BATCH], packed_at[MAX_BATCH], ws_at[MAX_BATCH];
-    uint32_t file_n[MAX_BATCH], capacity[MAX_BATCH];
+    long long file_at[ML_JPEG_DECODE_MAX_BATCH], packed_at[ML_JPEG_DECODE_MAX_BATCH], ws_at[ML_JPEG_DECODE_MAX_BATCH];
+    uint32_t file_n[ML_JPEG_DECODE_MAX_BATCH], capacity[ML_JPEG_DECODE_MAX_BATCH];
 };
 
 // The host decoder's BitReader over the raw file, every read below n.  ff: bit j set if the j-th last byte taken was an
@@ -1510,7 +1510,7 @@ extern "C" int ml_jpeg_entropy_plan(const uint8_t *data, int64_t n, void *plan) 
 namespace {
 int entropy_streams(const char *what, const int64_t *file_offsets, int32_t B, Streams &st, long long &ws_total, uint32_t &max_wg) {
     ML_REQUIRE(file_offsets, "%s: null pointer", what);
-    ML_REQUIRE(B > 0 && B <= MAX_BATCH, "%s: bad dims (B %d; 1 .. %d)", what, B, MAX_BATCH);
+    ML_REQUIRE(B > 0 && B <= ML_JPEG_DECODE_MAX_BATCH, "%s: bad dims (B %d; 1 .. %d)", what, B, ML_JPEG_DECODE_MAX_BATCH);
     memset(&st, 0, sizeof(st));
     ws_total = 0;
     max_wg = 0;
@@ -1558,7 +1558,7 @@ extern "C" int ml_jpeg_entropy_device(const uint8_t *files, const int64_t *file_
     uint32_t max_cap = 0;
     for (int b = 0; b < B; ++b) max_cap = st.capacity[b] > max_cap ? st.capacity[b] : max_cap;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(jpeg_entropy_clear_kernel, dim3(1), dim3(MAX_BATCH), 0, s, (uint8_t *)workspace, st, B);
+    hipLaunchKernelGGL(jpeg_entropy_clear_kernel, dim3(1), dim3(ML_JPEG_DECODE_MAX_BATCH), 0, s, (uint8_t *)workspace, st, B);
     for (int launch = 0; launch < SYNC_LAUNCHES; ++launch)
         hipLaunchKernelGGL(jpeg_entropy_sync_kernel, dim3(max_wg, B), dim3(SYNC_TPB), 0, s, files, (const uint8_t *)plans,
                            (uint8_t *)workspace, st, launch);

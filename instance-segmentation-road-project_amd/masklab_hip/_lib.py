@@ -1,5 +1,8 @@
 """ctypes binding of libmasklab_hip.so (the C ABI declared in include/masklab_hip.h).
 
+Hand-written and checked: tests/test_abi_cpu.py parses the header and holds every row of SIGNATURES, every mirror of
+STRUCTS and every upper-case integer below (`X` here is `ML_X` there) to it, type by type.
+
 The product path has NO CPU fallback: if the shared library is missing or a kernel
 call fails, a RuntimeError is raised.
 """
@@ -12,8 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # resolved path into its JSON line.
 LIB_PATH = os.path.join(_HERE, "libmasklab_hip.so")
 
-ABI_VERSION = 7          # ML_ABI_VERSION of include/masklab_hip.h
+ABI_VERSION = 7
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SIGMOID = 0, 1, 2, 3
+MATH_F32, MATH_F16, MATH_F16S, MATH_F32X3 = 0, 1, 2, 3
 ACT_BY_NAME = {None: ACT_NONE, "linear": ACT_NONE, "relu": ACT_RELU, "relu6": ACT_RELU6,
                "sigmoid": ACT_SIGMOID}
 
@@ -147,16 +151,26 @@ class RepackJob(C.Structure):
                 ("cp", C.c_int32), ("nb", C.c_int32), ("cb", C.c_int32), ("bias_n", C.c_int32), ("first_unit", C.c_int64)]
 
 
+# C struct -> its mirror; every struct of the header
+STRUCTS = {
+    "ml_conv2d_desc": ConvDesc, "ml_conv2d_wgrad_desc": ConvWgradDesc, "ml_dwconv3x3_grad_desc": DwGradDesc,
+    "ml_gn_desc": GnDesc, "ml_gn_grad_desc": GnGradDesc, "ml_roi_grad_level": RoiGradLevel,
+    "ml_deconv_out_problem": DeconvOutProblem, "ml_deconv_out_grad_problem": DeconvOutGradProblem,
+    "ml_se_desc": SeDesc, "ml_se_residual_desc": SeResidualDesc, "ml_se_bottleneck_desc": SeBottleneckDesc,
+    "ml_opt_tensor": OptTensor, "ml_opt_state": OptState, "ml_opt_scalars": OptScalars, "ml_repack_job": RepackJob,
+}
+
 SE_RES_GATE, SE_RES_BN_RELU = 0, 1
+CONV_MAX_PROBLEMS = 12
 GN_MAX_PROBLEMS = 8
-CONV_WGRAD_MAX_PROBLEMS = 8                                          # ML_CONV_WGRAD_MAX_PROBLEMS
-DWCONV_GRAD_MAX_PROBLEMS = 8                                         # ML_DWCONV_GRAD_MAX_PROBLEMS
+CONV_WGRAD_MAX_PROBLEMS = 8
+DWCONV_GRAD_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
-RESAMPLE_MAX_LEVELS = 8                                             # ML_RESAMPLE_MAX_LEVELS
+RESAMPLE_MAX_LEVELS = 8
 DECONV_OUT_MAX_PROBLEMS = 4
 _i32, _i64, _f32, _f64, _vp = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_void_p
 
-# name -> (restype, argtypes); every symbol include/masklab_hip.h declares
+# name -> (restype, argtypes); every prototype of the header
 SIGNATURES = {
     "ml_version": (C.c_int, []),
     "ml_last_error": (C.c_char_p, []),
@@ -301,25 +315,26 @@ SIGNATURES = {
     "ml_polygon_instance_masks": (C.c_int, [_vp, _i64, _vp, _vp] + [_i32] * 4 + [_vp, _vp]),
     "ml_polygon_semantic_maps": (C.c_int, [_vp, _i64, _vp, _i32, _vp] + [_i32] * 4 + [_vp, _vp]),
     "ml_polygon_reference_host": (C.c_int, [_i32, _vp, _i64, _vp, _i32, _vp, _vp] + [_i32] * 4 + [_vp]),
-    "ml_optimizer_plan": (_i64, [_vp, _i32]),
-    "ml_optimizer_scalars": (C.c_int, [_i32, _vp, _vp] + [_f64] * 6 + [_vp]),
-    "ml_optimizer_apply_f32": (C.c_int, [_i32, _vp, _i32, _i64, _vp, _vp]),
-    "ml_repack_plan": (_i64, [_vp, _i32]),
-    "ml_repack_f32": (C.c_int, [_vp, _i32, _i64, _vp]),
+    "ml_optimizer_plan": (_i64, [C.POINTER(OptTensor), _i32]),
+    "ml_optimizer_scalars": (C.c_int, [_i32, C.POINTER(OptState), C.POINTER(OptScalars)] + [_f64] * 6 + [_vp]),
+    "ml_optimizer_apply_f32": (C.c_int, [_i32, C.POINTER(OptTensor), _i32, _i64, C.POINTER(OptScalars), _vp]),
+    "ml_repack_plan": (_i64, [C.POINTER(RepackJob), _i32]),
+    "ml_repack_f32": (C.c_int, [C.POINTER(RepackJob), _i32, _i64, _vp]),
 }
-REPACK_CONV, REPACK_TABLE = 0, 1                                    # ML_REPACK_*
-OPT_RADAM, OPT_ADAMW = 0, 1                                         # ML_OPT_*
-OPT_CHUNK = 4096                                                    # ML_OPT_CHUNK
-POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1                           # ML_POLYGON_*
-CV_RESIZE_U8, CV_RESIZE_ROUND_U8, CV_RESIZE_ROUND_F32 = 0, 1, 2     # ML_CV_RESIZE_*
-TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1                    # ML_TRAIN_MASK_*
-TRAIN_MAX_BLOCKS = 512                                  # ML_TRAIN_MAX_BLOCKS
-EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3     # ML_EVAL_*
-EVAL_MAX_CLASSES = 16                                  # ML_EVAL_MAX_CLASSES
-JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2     # ML_JPEG_*
-JPEG_UNSUPPORTED = 1                        # ML_JPEG_UNSUPPORTED
+REPACK_CONV, REPACK_TABLE = 0, 1
+OPT_RADAM, OPT_ADAMW = 0, 1
+OPT_CHUNK = 4096
+POLYGON_INSTANCE, POLYGON_SEMANTIC = 0, 1
+CV_RESIZE_U8, CV_RESIZE_ROUND_U8, CV_RESIZE_ROUND_F32 = 0, 1, 2
+TRAIN_MASK_I8, TRAIN_MASK_U8 = 0, 1
+TRAIN_MAX_BLOCKS = 512
+EVAL_F32, EVAL_F16, EVAL_I32, EVAL_U8 = 0, 1, 2, 3
+EVAL_MAX_CLASSES = 16
+JPEG_GRAY, JPEG_444, JPEG_420 = 0, 1, 2
+JPEG_UNSUPPORTED = 1
 JPEG_DECODE_MAX_BATCH = 32
-DRAW_MAX_CLASSES = 16    # ML_DRAW_MAX_CLASSES
+JPEG_ENTROPY_OK, JPEG_ENTROPY_ASK_HOST, JPEG_ENTROPY_NOT_SYNCED = 0, 10, 11
+DRAW_MAX_CLASSES = 16
 
 _lib = None
 

@@ -74,7 +74,8 @@ class _Prof:
 # on maps of >= 4 096 pixels run on the persistent pipelined kernel, every other conv on the generic one.
 # Process-wide switch, read when a conv is launched; set it through set_conv_math().
 CONV_MATH = "f32"
-_MATH_CODE = {"f32": 0, "f16": 1, "f16s": 1, "f32x3": 3}   # per-launch code of fp32-tensor convs; half tensors select ML_MATH_F16S
+# per-launch code of fp32-tensor convs; half tensors select ML_MATH_F16S
+_MATH_CODE = {"f32": _lib.MATH_F32, "f16": _lib.MATH_F16, "f16s": _lib.MATH_F16, "f32x3": _lib.MATH_F32X3}
 
 
 def set_conv_math(mode):
@@ -97,6 +98,11 @@ def _stream():
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _ptr_as(t, struct):
+    """The address of tensor `t`, which holds `struct` records (a table or a state in device memory); None -> NULL."""
+    return C.cast(t.data_ptr(), C.POINTER(struct)) if t is not None else None
 
 
 def half_storage():
@@ -424,10 +430,10 @@ def _conv_desc(x, dc, stride=1, padding="same", dilation=1, act=_lib.ACT_NONE, r
         _require_dev(lv, "live")
         d.live, d.live_period = lv.data_ptr(), int(period)
     if half_in:
-        d.math, d.out_f16 = 2, int(odt == torch.float16)          # ML_MATH_F16S
+        d.math, d.out_f16 = _lib.MATH_F16S, int(odt == torch.float16)
     else:
         d.math, d.out_f16 = _MATH_CODE[CONV_MATH], int(odt == torch.float16)
-        if d.out_f16 and d.math != 1:
+        if d.out_f16 and d.math != _lib.MATH_F16:
             raise ValueError("conv2d: a half output from fp32 input needs the fp16 MFMA mode (set_conv_math('f16s'))")
     M = B * Ho * Wo
     real_cin = p.span if p.cpp_shift == 30 else 3
@@ -574,8 +580,8 @@ def conv2d_multi(problems):
     n = len(problems)
     if n == 0:
         return []
-    if n > 12:
-        return conv2d_multi(problems[:12]) + conv2d_multi(problems[12:])
+    if n > _lib.CONV_MAX_PROBLEMS:
+        return conv2d_multi(problems[:_lib.CONV_MAX_PROBLEMS]) + conv2d_multi(problems[_lib.CONV_MAX_PROBLEMS:])
     arr = (_lib.ConvDesc * n)()
     rets, flops, nbytes, shapes = [], 0.0, 0.0, []
     for i, pr in enumerate(problems):
@@ -1461,7 +1467,7 @@ def conv2d_wgrad_geometry(x_shape, p, stride=1, padding="same", dilation=1, in_c
     d.KH, d.KW, d.stride, d.dil, d.pad_t, d.pad_l = p.KH, p.KW, stride, dilation, pt, pl
     d.cout, d.n_pad = p.cout, p.n_pad
     d.out_cstride, d.out_coff, d.out_bstride = (p.cout if dy_cstride is None else int(dy_cstride)), 0, int(dy_bstride)
-    d.group_cin_step, d.shuffle2x2, d.math = p.group_cin_step, p.shuffle2x2, 0
+    d.group_cin_step, d.shuffle2x2, d.math = p.group_cin_step, p.shuffle2x2, _lib.MATH_F32
     return g
 
 
@@ -3446,7 +3452,7 @@ class OptimizerTable:
             arr = (_lib.OptTensor * n).from_address(host.data_ptr())
             for e, (p, g, m, v, numel) in zip(arr, key):
                 e.p, e.g, e.m, e.v, e.n, e.first_chunk = p, g, m, v, numel, 0
-            chunks = int(lib.ml_optimizer_plan(C.c_void_p(host.data_ptr()), n))
+            chunks = int(lib.ml_optimizer_plan(arr, n))
             if chunks < 0:
                 _lib.check(chunks, "ml_optimizer_plan")
             if self.table is None or self.table.numel() < nbytes or self.table.device != device:
@@ -3503,10 +3509,12 @@ def optimizer_step(kind, tensors, table, state, scalars, beta_1, beta_2, epsilon
         table.update(key, state.device)
         nelem = sum(k[4] for k in key)
         with _Prof("optimizer_step", 12 * nelem, 28 * nelem, f"{kind} x{len(key)}"):
-            _lib.check(lib.ml_optimizer_scalars(code, _ptr(state), _ptr(scalars), float(beta_1), float(beta_2), float(epsilon),
-                                                float(decay), float(weight_decay), float(init_lr), _stream()), "ml_optimizer_scalars")
-            _lib.check(lib.ml_optimizer_apply_f32(code, _ptr(table.table), table.n, table.chunks, _ptr(scalars), _stream()),
-                       "ml_optimizer_apply_f32")
+            dev_scalars = _ptr_as(scalars, _lib.OptScalars)
+            _lib.check(lib.ml_optimizer_scalars(code, _ptr_as(state, _lib.OptState), dev_scalars, float(beta_1), float(beta_2),
+                                                float(epsilon), float(decay), float(weight_decay), float(init_lr), _stream()),
+                       "ml_optimizer_scalars")
+            _lib.check(lib.ml_optimizer_apply_f32(code, _ptr_as(table.table, _lib.OptTensor), table.n, table.chunks, dev_scalars,
+                                                  _stream()), "ml_optimizer_apply_f32")
 
 
 # ----------------------------------------------------------------------------- re-packing stepped weights (csrc/repack.hip)
@@ -3647,7 +3655,7 @@ class RepackTable:
                                "uploaded while a graph is captured: take one eager call with these jobs first")
         units = 0
         if n:
-            units = int(_lib.load().ml_repack_plan(C.cast(arr, C.c_void_p), n))
+            units = int(_lib.load().ml_repack_plan(arr, n))
             if units < 0:
                 _lib.check(units, "ml_repack_plan")
             nbytes = n * C.sizeof(_lib.RepackJob)
@@ -3675,7 +3683,7 @@ def repack_plan(jobs):
     device = None
     for i, job in enumerate(jobs):
         device, _ = _repack_fill(arr[i], i, job, device, on_gpu=False)
-    units = int(_lib.load().ml_repack_plan(C.cast(arr, C.c_void_p), n)) if n else 0
+    units = int(_lib.load().ml_repack_plan(arr, n)) if n else 0
     if units < 0:
         _lib.check(units, "ml_repack_plan")
     return units, [(arr[i].nb, arr[i].cb, arr[i].first_unit) for i in range(n)]
@@ -3694,4 +3702,5 @@ def repack_weights(jobs, table=None):
     device = table.update(jobs)
     with torch.cuda.device(device):
         with _Prof("repack_weights", 0, table.nbytes, f"x{table.n} ({table.units} units)"):
-            _lib.check(_lib.load().ml_repack_f32(_ptr(table.table), table.n, table.units, _stream()), "ml_repack_f32")
+            _lib.check(_lib.load().ml_repack_f32(_ptr_as(table.table, _lib.RepackJob), table.n, table.units, _stream()),
+                       "ml_repack_f32")

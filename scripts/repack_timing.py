@@ -100,7 +100,7 @@ def main():
 
     def launch(k):                                          # the launch alone, its table as the call above left it
         t = sets[k][1]
-        lib.ml_repack_f32(ops._ptr(t.table), t.n, t.units, ops._stream())
+        lib.ml_repack_f32(ops._ptr_as(t.table, _lib.RepackJob), t.n, t.units, ops._stream())
 
     lms, lenq = time_launch(launch, copies, args.steps, args.inner, args.warmup)
     half = nbytes // 2 // 16 * 16

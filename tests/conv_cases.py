@@ -44,9 +44,10 @@ from dataclasses import dataclass, replace
 
 import numpy as np
 
+from masklab_hip import _lib
 from oracle import tfops as T
 
-MATH_CODE = {"f32": 0, "f16": 1, "f16s": 2, "f32x3": 3}          # ML_MATH_* (include/masklab_hip.h)
+MATH_CODE = {"f32": _lib.MATH_F32, "f16": _lib.MATH_F16, "f16s": _lib.MATH_F16S, "f32x3": _lib.MATH_F32X3}
 SUFFIX = {"f32": "", "f16": "_f16", "f16s": "_h", "f32x3": "_x3"}  # of the profile name conv_mfma_<BM>x<BN><suffix>
 ACT = {None: lambda v: v, "relu": T.relu, "relu6": T.relu6, "sigmoid": T.sigmoid}
 STEM_PAD = ((3, 3), (3, 3))
@@ -245,7 +246,6 @@ def dest_layout(prob):
 def _host_desc(p, in_shape, math, stride, padding, dil, act, hout, res, dest, gn):
     """The ml_conv2d_desc ops._conv_desc builds for this problem, with aligned fake addresses: the planning entries
     dereference nothing on the host."""
-    from masklab_hip import _lib
     from masklab_hip.packing import resolve_padding
     B, H, W, cbuf = in_shape
     hs = math == "f16s"

@@ -40,7 +40,9 @@ from dataclasses import dataclass
 
 import numpy as np
 
-ACT_CODE = {None: 0, "relu": 1, "relu6": 2}          # ML_ACT_* (include/masklab_hip.h)
+from masklab_hip import _lib
+
+ACT_CODE = {None: _lib.ACT_NONE, "relu": _lib.ACT_RELU, "relu6": _lib.ACT_RELU6}
 P11 = ((1, 1), (1, 1))
 P01 = ((0, 1), (0, 1))
 BODY = {("f32", 4): "mfma4", ("f32", 8): "mfma4", ("f32", 16): "gconv16",
@@ -157,7 +159,6 @@ assert len(BY_NAME) == len(ROWS)
 def plan(row, B=None):
     """-> (rc, [tile_h, tile_w, tiles_x, tiles_y, run, blocks]) of ml_gconv3x3_launch_plan for `row` (or its images alone)."""
     import ctypes as C
-    from masklab_hip import _lib
     Bn, H, W = row.shape
     Ho, Wo, _, _ = out_hw(row)
     out = (C.c_int32 * 6)()

@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 
 import jpeg_decode_ref as D
 import jpeg_entropy_streams as S
+from masklab_hip import _lib
 
 DEVICE = "cuda:0"
-OK, NOT_SYNCED = 0, 11
+OK, NOT_SYNCED = _lib.JPEG_ENTROPY_OK, _lib.JPEG_ENTROPY_NOT_SYNCED
 
 
 @pytest.fixture(scope="module", autouse=True)

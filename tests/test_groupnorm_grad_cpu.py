@@ -1,9 +1,7 @@
 """CPU tests of GroupNormalization's backward: the closed form the kernels implement (include/masklab_hip.h) against torch
 autograd over the float64 restatement of the reference layer, the index rule, the argument checks of the ops, and the
-C ABI's new symbols."""
+workspace size."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ torch = pytest.importorskip("torch")
 
 import groupnorm_grad_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = [(False, False), (False, True), (True, False), (True, True)]
 
 
@@ -79,22 +76,9 @@ def test_argument_checks_raise_on_the_host():
         ops.groupnorm_chunk_stats(x, 4)
 
 
-def test_new_symbols_are_declared_and_bound_with_matching_arity():
+def test_grad_workspace_holds_the_partial_sums_of_every_block():
     from masklab_hip import _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "masklab_hip.h")).read(), flags=re.S)
     lib = _lib.load()
-    for name in ("ml_groupnorm_grad_workspace_bytes", "ml_groupnorm_chunk_grad_f32", "ml_groupnorm_chunk_stats_f32",
-                 "ml_groupnorm_grad_multi_f32"):
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-        assert decl is not None, f"{name} is not declared in masklab_hip.h"
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == len(decl.group(1).split(",")), name
-    # the descriptor: 8 pointers, one int64, 5 int32, one float, padded to 8
-    fields = re.search(r"typedef struct ml_gn_grad_desc \{(.*?)\} ml_gn_grad_desc;", header, flags=re.S).group(1)
-    names = [n.strip(" *") for decl in fields.split(";") if decl.strip() for n in decl.split(",")]
-    names = [n.split()[-1].lstrip("*") for n in names]
-    assert names == [f[0] for f in _lib.GnGradDesc._fields_], names
-    assert ctypes.sizeof(_lib.GnGradDesc) == 8 * 8 + 8 + 5 * 4 + 4 and _lib.GnGradDesc.HWC.offset == 64
     assert lib.ml_groupnorm_grad_workspace_bytes(8, 16, 256) >= 8 * 64 * 2 * (16 + 256) * 8
 
 

@@ -4,7 +4,6 @@ malformed input -- and the per-thread code of the two kernels run in CPU loops (
 import ctypes as C
 import io
 import os
-import re
 import sys
 
 import numpy as np
@@ -13,9 +12,6 @@ import pytest
 import jpeg_decode_ref as D
 import jpeg_ref as J
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("ml_jpeg_decode_info", "ml_jpeg_decode_packed_bytes", "ml_jpeg_decode_entropy", "ml_jpeg_decode_workspace_bytes",
-       "ml_jpeg_decode_u8", "ml_jpeg_decode_reference_host")
 MODES = {"gray": D.GRAY, "444": D.S444, "420": D.S420}
 
 
@@ -114,16 +110,10 @@ def test_reference_restart_parser_is_strict(cases):
 
 
 # ----------------------------------------------------------------------------- the C ABI
-def test_new_entry_points_are_declared_exported_and_bound(lib):
+def test_mode_codes_are_the_reference_decoders(lib):
     from masklab_hip import _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "masklab_hip.h")).read(), flags=re.S)
-    for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", header), name
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
     assert lib.ml_version() == _lib.ABI_VERSION == 7
     assert (_lib.JPEG_GRAY, _lib.JPEG_444, _lib.JPEG_420) == (D.GRAY, D.S444, D.S420)
-    for name in ("ML_JPEG_GRAY = 0", "ML_JPEG_444 = 1", "ML_JPEG_420 = 2", "ML_JPEG_UNSUPPORTED 1"):
-        assert name in header
 
 
 def test_device_entry_point_validates_its_arguments(lib):

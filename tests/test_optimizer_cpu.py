@@ -1,10 +1,7 @@
 """CPU tests of the optimizers: the float64 restatement (tests/optimizer_ref.py) against torch's own optimizers as
 independent witnesses, the step at which RectifiedAdam starts to rectify, CyclicLR against hand-computed values, the
-argument checks of the ops on host tensors, and the C ABI's new symbols."""
-import ctypes
+argument checks of the ops on host tensors, and the host half of the C entry points."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +10,6 @@ torch = pytest.importorskip("torch")
 
 import optimizer_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, STEPS = 1000, 12
 
 
@@ -196,23 +192,9 @@ def test_argument_checks_raise_on_the_host():
     assert opt.get_weights()[1:] == [] and opt.iterations == 0
 
 
-def test_new_symbols_are_declared_and_bound_with_matching_arity():
+def test_scalars_fields_are_the_restatements_and_the_plan_is_a_chunk_prefix_sum():
     from masklab_hip import _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "masklab_hip.h")).read(), flags=re.S)
     lib = _lib.load()
-    for name in ("ml_optimizer_plan", "ml_optimizer_scalars", "ml_optimizer_apply_f32"):
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-        assert decl is not None, f"{name} is not declared in masklab_hip.h"
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == len(decl.group(1).split(",")), name
-    for struct, mirror, size in (("ml_opt_tensor", _lib.OptTensor, 48), ("ml_opt_state", _lib.OptState, 16),
-                                 ("ml_opt_scalars", _lib.OptScalars, 48)):
-        fields = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct + ";", header, flags=re.S).group(1)
-        names = [n.strip().split()[-1].lstrip("*") for decl in fields.split(";") if decl.strip() for n in decl.split(",")]
-        assert names == [f[0] for f in mirror._fields_], (struct, names)
-        assert ctypes.sizeof(mirror) == size, struct
-    assert _lib.OptTensor.n.offset == 32 and _lib.OptState.lr.offset == 8 and _lib.OptScalars.rectified.offset == 40
-    assert re.search(r"#define ML_OPT_CHUNK (\d+)", header).group(1) == str(_lib.OPT_CHUNK)
     assert set(R.FLOAT_FIELDS) | {"rectified", "decays"} == {f[0] for f in _lib.OptScalars._fields_}
     # the host half of the ABI: the chunk prefix sum, tensors without elements included
     sizes = [0, 1, _lib.OPT_CHUNK, _lib.OPT_CHUNK + 1, 0, 3 * _lib.OPT_CHUNK + 7, 0]

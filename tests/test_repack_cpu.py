@@ -1,8 +1,6 @@
-"""CPU tests of the re-pack's host half: the ABI's declaration and binding, ml_repack_plan's unit counts and refusals, and the
-bookkeeping of DeviceConv.bind_master on packings that live on the CPU (no kernel runs here; tests/test_gpu_repack.py holds
-the device's bits to the host's)."""
-import ctypes
-import os
+"""CPU tests of the re-pack's host half: ml_repack_plan's unit counts and refusals, and the bookkeeping of
+DeviceConv.bind_master on packings that live on the CPU (no kernel runs here; tests/test_gpu_repack.py holds the device's bits
+to the host's)."""
 import re
 
 import numpy as np
@@ -13,28 +11,13 @@ torch = pytest.importorskip("torch")
 import repack_cases as RC
 from masklab_hip import _lib, ops, packing
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 def _bound(name, seed=0, dgrad=True):
     return RC.bound_conv(*RC.conv_case(name, np.random.default_rng(seed)), "cpu", dgrad)
 
 
-def test_symbols_are_declared_and_bound_and_the_struct_mirrors_the_header():
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "masklab_hip.h")).read(), flags=re.S)
-    lib = _lib.load()
-    for name in ("ml_repack_plan", "ml_repack_f32"):
-        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", header)
-        assert decl is not None, f"{name} is not declared in masklab_hip.h"
-        assert name in _lib.SIGNATURES and hasattr(lib, name), name
-        assert len(_lib.SIGNATURES[name][1]) == len(decl.group(1).split(",")), name
-    fields = re.search(r"typedef struct ml_repack_job \{(.*?)\} ml_repack_job;", header, flags=re.S).group(1)
-    names = [n.strip().split()[-1].lstrip("*") for decl in fields.split(";") if decl.strip() for n in decl.split(",")]
-    assert names == [f[0] for f in _lib.RepackJob._fields_]
-    assert ctypes.sizeof(_lib.RepackJob) == 208 and _lib.RepackJob.first_unit.offset == 200 and _lib.RepackJob.kind.offset == 40
-    kinds = re.search(r"enum \{ ML_REPACK_CONV = (\d+), ML_REPACK_TABLE = (\d+) \}", header).groups()
-    assert kinds == (str(_lib.REPACK_CONV), str(_lib.REPACK_TABLE))
-    assert lib.ml_repack_plan(None, 0) == 0
+def test_plan_of_no_jobs_is_no_units():
+    assert _lib.load().ml_repack_plan(None, 0) == 0
 
 
 # tiles along n x tiles along c (+ 1 for a bias), worked out by hand from the padded extents of every form of the case:

@@ -1,5 +1,5 @@
-"""Fused SqueezeExcite and half skip-add without a GPU: the entry points are bound, every bad argument is refused with
-ML_E_BADARG and a message before anything is launched, the workspace rule, and which mask heads run at capacity."""
+"""Fused SqueezeExcite and half skip-add without a GPU: every bad argument is refused with ML_E_BADARG and a message before
+anything is launched, the workspace rule, and which mask heads run at capacity."""
 import ctypes as C
 
 import numpy as np
@@ -25,12 +25,9 @@ def _desc(**kw):
     return d
 
 
-def test_entry_points_are_bound():
-    _l, lib = _lib()
-    for name in ("ml_squeeze_excite_f32", "ml_squeeze_excite_f16", "ml_squeeze_excite_workspace_bytes", "ml_add_f16"):
-        assert name in _l.SIGNATURES and hasattr(lib, name)
+def test_a_launch_takes_up_to_eight_problems():
+    _l, _ = _lib()
     assert _l.SE_MAX_PROBLEMS == 8
-    assert C.sizeof(_l.SeDesc) == 4 * 8 + 4 * 4 + 8 + 2 * 4 + 8 and _l.SeDesc.ws_offset.offset == 64
 
 
 def test_workspace_grows_with_samples_and_chunks():

@@ -271,17 +271,9 @@ def test_new_layers_refuse_cpu_tensors():
         losses.MaskLoss()([z(1, 2, 4, 4, dtype=torch.int32), z(1, 2, 4, 4, 5)])
 
 
-def test_library_exports_the_trainer_kernels():
-    import os
+def test_trainer_workspace_size_and_refusals_without_a_device():
     from masklab_hip import _lib
     lib = _lib.load()
-    names = ["ml_train_workspace_bytes", "ml_train_calculate_iou_f32", "ml_train_best_prior_f32", "ml_train_assign_boxes_f32",
-             "ml_train_class_loss_f32", "ml_train_box_loss_f32", "ml_train_assign_masks", "ml_train_mask_loss_f32",
-             "ml_train_assign_seg", "ml_train_seg_loss_f32"]
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    header = open(os.path.join(root, "include", "masklab_hip.h")).read()
-    for name in names:
-        assert name in _lib.SIGNATURES and getattr(lib, name) is not None and f" {name}(" in header
     assert lib.ml_train_workspace_bytes(8, 5) >= 8 * 8 * 5 * 2 and lib.ml_train_workspace_bytes(0, 5) == 0
     # argument checks run before anything is launched: refused without a device
     assert lib.ml_train_best_prior_f32(None, None, 1, 1, 1, None, None, None) != 0 and b"null pointer" in lib.ml_last_error()
