@@ -87,7 +87,9 @@ enum { ML_MATH_F32 = 0, ML_MATH_F16 = 1, ML_MATH_F16S = 2, ML_MATH_F32X3 = 3 };
                                             (additive, same version) ml_batchnorm_train_f32 / _infer_f32 / _grad_f32 /
                                             _workspace_bytes / _plan;
                                             (additive, same version) ML_DECONV_OUT_MAX_PROBLEMS, ML_JPEG_DECODE_MAX_BATCH:
-                                            names for limits the entry points already had */
+                                            names for limits the entry points already had;
+                                            (additive, same version) ml_conv2d_dgrad_s2_f32 / _classes,
+                                            ML_CONV_DGRAD_S2_MAX_TAPS */
 int ml_version(void);                 /* returns ML_ABI_VERSION of the library that was built */
 const char *ml_last_error(void);      /* text of the last failure on the calling thread   */
 int ml_device_check(void);            /* ML_OK iff device 0.. current is gfx950           */
@@ -269,6 +271,37 @@ int ml_conv2d_wgrad_plan(const ml_conv2d_wgrad_desc *desc, int32_t *slices, int3
  * weights (packing.pack_dense_transposed) -- reads.  Every element of `out` is written. */
 int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t B, int32_t HW, int32_t cout, int32_t dy_cstride,
                                  int64_t dy_bstride, void *stream);
+
+/* Data gradient of a dense STRIDE-2 ml_conv2d_desc problem (csrc/conv_grad.hip), float32.  For the forward
+ *   y[b,oy,ox,co] = sum of x[b, 2 oy + ky*dil - pad_t, 2 ox + kx*dil - pad_l, ci] * w[ky,kx,ci,co]:
+ *   dx[b,iy,ix,ci] = (add[b,iy,ix,ci] +) sum over the taps (ky,kx) with iy + pad_t - ky*dil and ix + pad_l - kx*dil both even
+ *                    and oy = (iy + pad_t - ky*dil) / 2 in [0,Ho), ox likewise in [0,Wo), of sum_co dy[b,oy,ox,co] * w[ky,kx,ci,co]
+ * The parity of (iy, ix) fixes the live taps: the input pixels fall into four classes, class = 2 (iy & 1) + (ix & 1), and
+ * inside a class the gradient is a stride-1 walk over dy -- pixel (iy, ix) reads dy at ((iy >> 1) + off_y, (ix >> 1) + off_x),
+ * one offset pair per live tap (3x3: 2x2, 2x1, 1x2 and 1x1 taps; 1x1: one class with one tap, three with none).  Per class
+ * a GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products): a block holds 128 pixels of ONE class by up to 128 input
+ * channels; no MFMA is issued for a dead tap and no zero-inserted dy exists, so the MACs are the forward's
+ * (B*Ho*Wo*KH*KW*cin*cout).
+ * `desc` is the FORWARD problem: span = cin (% 4 == 0; any multiple), cout % 4 == 0, KH x KW up to 5 x 5, any dilation,
+ * stride exactly 2, pad_t / pad_l as the forward resolved them (TF `same` on even maps: 0), B, H, W the input's and Ho, Wo
+ * the output's dims.  `out` (out_cstride = cout, out_coff = 0, out_bstride 0 or dense) is dy, a DENSE [B,Ho,Wo,cout] tensor
+ * that is only read; `wgt` is the KERAS-LAYOUT kernel [KH,KW,cin,cout] as it stands (the master a training step updates:
+ * no packed form, no re-pack).  in, bias, residual, act, n_pad, span_pad, tile, live and gn_partials are ignored.  dx: a
+ * dense [B,H,W,cin]; add: NULL, or like dx -- dx = add + gradient with one fp32 addition, and dx may be add itself (no
+ * block reads what another writes).  (dx and add are parameters, not descriptor fields: the structs of ABI 7 are a
+ * closed set.)  All four tensors 16-byte aligned; dy and the kernel smaller than 2 GiB each.
+ * Refused by name: half tensors (math = ML_MATH_F16S or out_f16), grouped / depthwise (group_cin_step), row-span
+ * (cpp_shift != 30) and shuffle2x2 problems, a stride other than 2, cin % 4 or cout % 4, kernels above 5 x 5, a map the
+ * kernel does not fit (Ho or Wo < 1, or a last window that starts beyond the map), a dy view.
+ * fp32 accumulation in a fixed order -- live taps ascending (ky, then kx), cout ascending -- no atomics, no split along K:
+ * the same bits run to run, whatever dx held.  Every element of dx is written by the launch; a pixel no tap reaches
+ * (a class without live taps, the last row or column under `valid`) gets add bit for bit, or +0.0. */
+#define ML_CONV_DGRAD_S2_MAX_TAPS 25
+int ml_conv2d_dgrad_s2_f32(const ml_conv2d_desc *desc, float *dx, const float *add, void *stream);
+/* Host only: the four classes of that problem (checked as the launch checks it; tensor pointers may be NULL).
+ * pixels[4]: input pixels of class c = 2 (iy & 1) + (ix & 1) over the batch (they sum to B*H*W); ntaps[4]: its live taps;
+ * taps[4][ML_CONV_DGRAD_S2_MAX_TAPS][4]: per live tap, ascending, (ky, kx, off_y, off_x). */
+int ml_conv2d_dgrad_s2_classes(const ml_conv2d_desc *desc, int64_t *pixels, int32_t *ntaps, int32_t *taps);
 
 /* ---------------------------------------------------------------- depthwise 3x3, backward (csrc/dwconv_grad.hip), fp32
  * For y = ml_dwconv3x3_f32(x, w) (+ b) with stride 1 or 2, any dilation and leading pads (pad_t, pad_l); dy is the gradient

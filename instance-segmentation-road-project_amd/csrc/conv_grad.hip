@@ -1,6 +1,7 @@
-// Backward of the dense convolutions, fp32: the weight and bias gradient (this file's GEMM kernel) and the small gather
-// that brings a `dy` view into the form the data gradient reads.  The data gradient itself is the FORWARD kernels on
-// transposed weights (masklab_hip/packing.py pack_dense_transposed, ops.conv2d_dgrad): nothing of it lives here.
+// Backward of the dense convolutions, fp32: the weight and bias gradient (this file's GEMM kernel), the small gather
+// that brings a `dy` view into the form the stride-1 data gradient reads, and the STRIDE-2 data gradient (second half of the
+// file).  The stride-1 data gradient is the FORWARD kernels on transposed weights (masklab_hip/packing.py
+// pack_dense_transposed, ops.conv2d_dgrad): nothing of it lives here.
 //
 //   dW[kh,kw,ci,co] = sum over (b,oy,ox) of x[b, oy*s + kh*d - pad_t, ox*s + kw*d - pad_l, ci] * dy[b,oy,ox,co]
 //   db[co]          = sum over (b,oy,ox) of dy[b,oy,ox,co]
@@ -372,6 +373,297 @@ extern "C" int ml_conv2d_grad_gather_dy_f32(const float *dy, float *out, int32_t
     ML_REQUIRE(!ml_ranges_overlap(out, total * 4, dy, ml_view_elems(B, bs, HW, dy_cstride, cout) * 4), "%s: out may not overlap dy", what);
     hipLaunchKernelGGL(gather_dy_kernel, dim3((unsigned)((total + WG_TPB - 1) / WG_TPB)), dim3(WG_TPB), 0, (hipStream_t)stream, dy,
                        out, HW, cout, cp, dy_cstride, bs, total);
+    ML_CHECK_LAUNCH(what);
+    return ML_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- stride-2 data gradient
+//   dx[b,iy,ix,ci] = (add +) sum over the taps (ky,kx) with iy + pad_t - ky*d and ix + pad_l - kx*d both even and
+//                    oy = (iy + pad_t - ky*d) / 2 in [0,Ho), ox likewise in [0,Wo), of sum_co dy[b,oy,ox,co] * w[ky,kx,ci,co]
+// The parity of (iy, ix) fixes which taps are live, so the input pixels fall into four CLASSES (class = 2 (iy & 1) + (ix & 1));
+// inside a class the gradient is a stride-1 walk over dy: pixel (2 cy + py, 2 cx + px) reads dy at (cy + off_y, cx + off_x)
+// with one offset pair per live tap.  Per class a GEMM with M = cin, N = the class's pixels (b, cy, cx ascending) and
+// K = live taps x cout on v_mfma_f32_32x32x2_f32 -- the weights as operand A, so a lane's four accumulator registers of a
+// row group are four consecutive cin of ONE pixel and dx is stored as float4 straight from registers.  No zero-inserted dy,
+// no MFMA for a dead tap: the MACs are the forward's.
+//
+// A block: DG_BM = 128 pixels of one class (4 waves x 32) by NT x 32 input channels (NT = 1 .. 4: the instantiation is picked
+// by cin), its K loop over (live tap ascending, cout ascending in chunks of DG_KC = 32).  Per chunk dy [128 pixels][32 co] and
+// w [NT x 32 ci][32 co] -- the Keras kernel as it stands, co contiguous -- arrive by LDS-DMA (gfx_mem.h) into one of two
+// staging buffers; window positions outside [0,Ho) x [0,Wo), pixels past the class, channels past cin / cout are requested
+// beyond the resource's extent and land as zeros.  A row is 8 granules of 16 bytes; granule j of row r sits at position
+// j ^ ((r >> 1) & 7), so the ds_read_b128 of a lane's (row, j) is conflict-free in every 16-lane group (two rows share a
+// 256-byte bank row; the rows of a group take 16 different slots).  Both lane halves read the granule and take
+// co = 4j + h and 4j + 2 + h of it: an accumulator sees co ascending.  No atomics, no split along K, nothing read from
+// another block's output: the same bits run to run, and `out` may be `add`.  Every dx element is written by the launch: a
+// class without live taps, or a pixel whose taps all fall outside dy, gets add (bit for bit) or +0.0.
+namespace {
+
+constexpr int DG_TPB = 256;
+constexpr int DG_BM = 128;           // pixels per block: 4 waves x 32
+constexpr int DG_KC = 32;            // cout per staged chunk
+constexpr int DG_MAXK = 5;           // kernel extent per axis
+
+struct DgAxis {                      // the live taps of one parity along one axis, ascending: output index = (input index >> 1) + off
+    int n;
+    int k[DG_MAXK], off[DG_MAXK];
+};
+struct DgArgs {
+    const float *dy, *w, *add;
+    float *dx;
+    int B, H, W, Ho, Wo, cin, cout, KW;
+    int dy_bytes, w_bytes;
+    int ntn;                         // N (cin) tiles
+    int first_tile[5];               // pixel tiles before class c; [4] = all
+    int Hc[2], Wc[2];                // rows / columns of each parity
+    DgAxis ay[2], ax[2];
+};
+
+template <int NT>
+__global__ void __launch_bounds__(DG_TPB, 2) conv_dgrad_s2_kernel(const DgArgs A) {
+    __shared__ __align__(16) float sy[2][DG_BM * DG_KC];
+    __shared__ __align__(16) float sw[2][NT * 32 * DG_KC];
+    const int nt = blockIdx.x % A.ntn;
+    int mt = blockIdx.x / A.ntn;
+    int cls = 0;
+    while (cls < 3 && mt >= A.first_tile[cls + 1]) ++cls;
+    mt -= A.first_tile[cls];
+    const int py = cls >> 1, px = cls & 1;
+    const DgAxis &ay = A.ay[py], &ax = A.ax[px];
+    const int ny = ay.n, nx = ax.n;
+    if (ny * nx == 0 && A.add == A.dx) return;               // in place, no live tap: the class already holds add
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const int H = A.H, W = A.W, Ho = A.Ho, Wo = A.Wo, cin = A.cin, cout = A.cout;
+    const int Wc = A.Wc[px], HcWc = A.Hc[py] * Wc, Mc = A.B * HcWc;
+    const int m0 = mt * DG_BM, n0 = nt * NT * 32;
+
+    // staging: one DMA of the block brings 32 rows (8 per wave, 8 granules each); a lane's row within its wave's 8 and its
+    // granule position are the same for every DMA, and so is the granule it fetches (the swizzle repeats every 16 rows)
+    const int g_row = lane >> 3;
+    const int g_j = (lane & 7) ^ ((4 * (wave & 1) + (g_row >> 1)) & 7);
+    int y_base[4], y_cy[4], y_cx[4];                         // per dy DMA: the row's image base in dy pixels (-1: past the class)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + (i * 4 + wave) * 8 + g_row;
+        const int b = m / HcWc, rem = m - b * HcWc;
+        y_cy[i] = rem / Wc;
+        y_cx[i] = rem - y_cy[i] * Wc;
+        y_base[i] = m < Mc ? b * Ho * Wo : -1;
+    }
+    const __amdgpu_buffer_rsrc_t rsrc_y = rsrc_bytes(A.dy, A.dy_bytes);
+    const __amdgpu_buffer_rsrc_t rsrc_w = rsrc_bytes(A.w, A.w_bytes);
+
+    // requests chunk (live tap ty, tx; channels c0 ..) into buffer `buf`
+    auto issue = [&](int buf, int ty, int tx, int c0) {
+        const int oyo = ay.off[ty], oxo = ax.off[tx];
+        const int tap = ay.k[ty] * A.KW + ax.k[tx];
+        const int c = c0 + 4 * g_j;
+        const bool cok = c < cout;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int oy = y_cy[i] + oyo, ox = y_cx[i] + oxo;
+            const bool ok = cok && y_base[i] >= 0 && (unsigned)oy < (unsigned)Ho && (unsigned)ox < (unsigned)Wo;
+            const int off = ((y_base[i] + oy * Wo + ox) * cout + c) * 4;
+            lds_dma16(rsrc_y, (char *)(&sy[buf][0] + (i * 4 + wave) * 8 * DG_KC), ok ? off : WG_OOB, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            const int ci = n0 + (i * 4 + wave) * 8 + g_row;
+            const bool ok = cok && ci < cin;
+            const int off = ((tap * cin + ci) * cout + c) * 4;
+            lds_dma16(rsrc_w, (char *)(&sw[buf][0] + (i * 4 + wave) * 8 * DG_KC), ok ? off : WG_OOB, 0);
+        }
+    };
+
+    f32x16 acc[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[n][e] = 0.f;
+
+    const int kchunks = (cout + DG_KC - 1) / DG_KC;
+    const int chunks = ny * nx * kchunks;
+    int ty = 0, tx = 0, kc = 0;                              // the next chunk to request
+    auto advance = [&]() {
+        if (++kc == kchunks) {
+            kc = 0;
+            if (++tx == nx) { tx = 0; ++ty; }
+        }
+    };
+    if (chunks > 0) {
+        issue(0, ty, tx, kc * DG_KC);
+        advance();
+    }
+    const int rd = (wave * 32 + r) * DG_KC, sz = (r >> 1) & 7;   // this lane's dy row; rows 32 apart share the swizzle
+    int buf = 0;
+    for (int it = 0; it < chunks; ++it) {
+        // this chunk has landed (every wave waits for its own requests, then for the others), and every wave is past its
+        // reads of the other buffer
+        wait_vmcnt<0>();
+        __syncthreads();
+        if (it + 1 < chunks) {
+            issue(buf ^ 1, ty, tx, kc * DG_KC);
+            advance();
+        }
+        const float *cy = &sy[buf][0] + rd;
+        const float *cw = &sw[buf][0] + r * DG_KC;
+#pragma unroll
+        for (int j = 0; j < DG_KC / 4; ++j) {
+            const int g = (j ^ sz) * 4;
+            const f32x4 yv = *(const f32x4 *)(cy + g);
+            const float b0 = h ? yv[1] : yv[0], b1 = h ? yv[3] : yv[2];
+            float a0[NT], a1[NT];
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const f32x4 wv = *(const f32x4 *)(cw + n * 32 * DG_KC + g);
+                a0[n] = h ? wv[1] : wv[0];
+                a1[n] = h ? wv[3] : wv[2];
+            }
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[n], b0, acc[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[n], b1, acc[n], 0, 0, 0);
+        }
+        buf ^= 1;
+    }
+
+    // ---- dx.  C/D layout: col = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (cin): float4 per reg >> 2
+    const int m = m0 + wave * 32 + r;
+    if (m >= Mc) return;
+    const int b = m / HcWc, rem = m - b * HcWc;
+    const int cyy = rem / Wc, cxx = rem - cyy * Wc;
+    const long long pix = ((long long)b * H + 2 * cyy + py) * W + 2 * cxx + px;
+    float *dst = A.dx + pix * cin;
+    const float *add = A.add ? A.add + pix * cin : nullptr;
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int ci = n0 + n * 32 + 8 * q + 4 * h;
+            if (ci >= cin) continue;
+            f32x4 v = {acc[n][4 * q], acc[n][4 * q + 1], acc[n][4 * q + 2], acc[n][4 * q + 3]};
+            if (add) {
+                const f32x4 a = *(const f32x4 *)(add + ci);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) v[t] = v[t] == 0.f ? a[t] : a[t] + v[t];   // an exact zero leaves add's bits
+            }
+            *(f32x4 *)(dst + ci) = v;
+        }
+}
+
+struct DgPlan {
+    DgAxis ay[2], ax[2];
+    int Hc[2], Wc[2];
+    long long pixels[4];
+};
+
+DgAxis dg_axis(int parity, int pad, int K, int dil) {
+    DgAxis a = {};
+    for (int k = 0; k < K; ++k) {
+        const int t = parity + pad - k * dil;
+        if (t & 1) continue;
+        a.k[a.n] = k;
+        a.off[a.n] = t >> 1;         // t is even: exact for a negative t too
+        ++a.n;
+    }
+    return a;
+}
+
+// the checks of one problem and its classes: geometry only
+int dg_plan(const ml_conv2d_desc &d, DgPlan &pl) {
+    const char *what = "conv2d_dgrad_s2";
+    ML_REQUIRE(d.math != ML_MATH_F16S && !d.out_f16, "%s: half tensors are refused (the backward is float32 only)", what);
+    ML_REQUIRE(!d.group_cin_step, "%s: grouped / depthwise problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(d.cpp_shift == 30, "%s: row-span (image input) problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(!d.shuffle2x2, "%s: shuffle2x2 (Conv2DTranspose) problems are refused (dense convolutions only)", what);
+    ML_REQUIRE(d.stride == 2, "%s: stride %d: stride 2 only (stride 1 is the forward kernels on transposed weights)", what, d.stride);
+    ML_REQUIRE(d.KH >= 1 && d.KH <= DG_MAXK && d.KW >= 1 && d.KW <= DG_MAXK, "%s: kernel %d x %d: at most 5 x 5", what, d.KH, d.KW);
+    ML_REQUIRE(d.dil >= 1, "%s: bad dilation", what);
+    ML_REQUIRE(d.span > 0 && d.span % 4 == 0, "%s: cin (%d) must be a multiple of 4", what, d.span);
+    ML_REQUIRE(d.cout > 0 && d.cout % 4 == 0, "%s: cout (%d) must be a multiple of 4", what, d.cout);
+    ML_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0, "%s: bad dims", what);
+    ML_REQUIRE(d.pad_t >= 0 && d.pad_l >= 0 && d.pad_t <= (d.KH - 1) * d.dil && d.pad_l <= (d.KW - 1) * d.dil,
+               "%s: leading pads (%d, %d) outside the kernel's extent", what, d.pad_t, d.pad_l);
+    // the last window starts inside the padded map
+    ML_REQUIRE(d.Ho >= 1 && d.Wo >= 1 && 2 * (d.Ho - 1) - d.pad_t < d.H && 2 * (d.Wo - 1) - d.pad_l < d.W,
+               "%s: the kernel does not fit the map: %d x %d outputs from a %d x %d input", what, d.Ho, d.Wo, d.H, d.W);
+    ML_REQUIRE((long long)d.B * d.H * d.W < (1ll << 31) - DG_BM, "%s: too many pixels", what);
+    ML_REQUIRE((long long)d.B * d.Ho * d.Wo * d.cout * 4 < (1ll << 31), "%s: dy must be smaller than 2 GiB", what);
+    ML_REQUIRE((long long)d.KH * d.KW * d.span * d.cout * 4 < (1ll << 31), "%s: the kernel must be smaller than 2 GiB", what);
+    for (int p = 0; p < 2; ++p) {
+        pl.ay[p] = dg_axis(p, d.pad_t, d.KH, d.dil);
+        pl.ax[p] = dg_axis(p, d.pad_l, d.KW, d.dil);
+        pl.Hc[p] = (d.H + 1 - p) / 2;
+        pl.Wc[p] = (d.W + 1 - p) / 2;
+    }
+    for (int c = 0; c < 4; ++c) pl.pixels[c] = (long long)d.B * pl.Hc[c >> 1] * pl.Wc[c & 1];
+    return ML_OK;
+}
+
+}  // namespace
+
+extern "C" int ml_conv2d_dgrad_s2_classes(const ml_conv2d_desc *desc, int64_t *pixels, int32_t *ntaps, int32_t *taps) {
+    ML_REQUIRE(desc && pixels && ntaps && taps, "conv2d_dgrad_s2_classes: null argument");
+    DgPlan pl;
+    const int rc = dg_plan(*desc, pl);
+    if (rc != ML_OK) return rc;
+    for (int c = 0; c < 4; ++c) {
+        const DgAxis &ay = pl.ay[c >> 1], &ax = pl.ax[c & 1];
+        pixels[c] = pl.pixels[c];
+        ntaps[c] = ay.n * ax.n;
+        int32_t *t = taps + c * ML_CONV_DGRAD_S2_MAX_TAPS * 4;
+        for (int i = 0; i < ay.n; ++i)
+            for (int j = 0; j < ax.n; ++j, t += 4) {
+                t[0] = ay.k[i]; t[1] = ax.k[j]; t[2] = ay.off[i]; t[3] = ax.off[j];
+            }
+    }
+    return ML_OK;
+}
+
+extern "C" int ml_conv2d_dgrad_s2_f32(const ml_conv2d_desc *desc, float *dx, const float *add, void *stream) {
+    const char *what = "conv2d_dgrad_s2";
+    ML_REQUIRE(desc, "%s: null descriptor", what);
+    const ml_conv2d_desc &d = *desc;
+    DgPlan pl;
+    const int rc = dg_plan(d, pl);
+    if (rc != ML_OK) return rc;
+    ML_REQUIRE(d.out && d.wgt && dx, "%s: null pointer", what);
+    ML_REQUIRE(d.out_cstride == d.cout && d.out_coff == 0 && (d.out_bstride == 0 || d.out_bstride == (long long)d.Ho * d.Wo * d.cout),
+               "%s: dy must be a dense [B,Ho,Wo,cout] tensor, not a view", what);
+    ML_REQUIRE(ml_aligned16(d.out) && ml_aligned16(d.wgt) && ml_aligned16(dx) && ml_aligned16(add),
+               "%s: dy, the kernel, dx and add must be 16-byte aligned", what);
+    const long long dy_bytes = (long long)d.B * d.Ho * d.Wo * d.cout * 4, w_bytes = (long long)d.KH * d.KW * d.span * d.cout * 4;
+    const long long dx_bytes = (long long)d.B * d.H * d.W * d.span * 4;
+    const ml_range r_dy = {d.out, dy_bytes}, r_w = {d.wgt, w_bytes}, r_dx = {dx, dx_bytes};
+    ML_REQUIRE(!ml_any_overlap({r_dx}, {r_dy, r_w}), "%s: dx may not overlap dy or the kernel", what);
+    ML_REQUIRE(ml_add_or_disjoint(dx, add, dx_bytes), "%s: dx may be add itself, not a shifted view of it", what);
+    DgArgs A;
+    A.dy = d.out; A.w = d.wgt; A.add = add; A.dx = dx;
+    A.B = d.B; A.H = d.H; A.W = d.W; A.Ho = d.Ho; A.Wo = d.Wo; A.cin = d.span; A.cout = d.cout; A.KW = d.KW;
+    A.dy_bytes = (int)dy_bytes; A.w_bytes = (int)w_bytes;
+    const int nsub = (d.span + 31) / 32, NT = nsub < 4 ? nsub : 4;
+    A.ntn = (nsub + NT - 1) / NT;
+    long long tiles = 0;
+    for (int c = 0; c < 4; ++c) {
+        A.first_tile[c] = (int)tiles;
+        tiles += (pl.pixels[c] + DG_BM - 1) / DG_BM;
+    }
+    A.first_tile[4] = (int)tiles;
+    ML_REQUIRE(tiles * A.ntn < (1ll << 31), "%s: grid too large", what);
+    for (int p = 0; p < 2; ++p) {
+        A.Hc[p] = pl.Hc[p]; A.Wc[p] = pl.Wc[p]; A.ay[p] = pl.ay[p]; A.ax[p] = pl.ax[p];
+    }
+    const dim3 grid((unsigned)(tiles * A.ntn)), block(DG_TPB);
+    hipStream_t s = (hipStream_t)stream;
+    switch (NT) {
+    case 1: hipLaunchKernelGGL(conv_dgrad_s2_kernel<1>, grid, block, 0, s, A); break;
+    case 2: hipLaunchKernelGGL(conv_dgrad_s2_kernel<2>, grid, block, 0, s, A); break;
+    case 3: hipLaunchKernelGGL(conv_dgrad_s2_kernel<3>, grid, block, 0, s, A); break;
+    default: hipLaunchKernelGGL(conv_dgrad_s2_kernel<4>, grid, block, 0, s, A); break;
+    }
     ML_CHECK_LAUNCH(what);
     return ML_OK;
 }

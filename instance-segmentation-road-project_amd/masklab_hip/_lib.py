@@ -164,6 +164,7 @@ SE_RES_GATE, SE_RES_BN_RELU = 0, 1
 CONV_MAX_PROBLEMS = 12
 GN_MAX_PROBLEMS = 8
 CONV_WGRAD_MAX_PROBLEMS = 8
+CONV_DGRAD_S2_MAX_TAPS = 25
 DWCONV_GRAD_MAX_PROBLEMS = 8
 SE_MAX_PROBLEMS = 8
 RESAMPLE_MAX_LEVELS = 8
@@ -189,6 +190,8 @@ SIGNATURES = {
     "ml_conv2d_wgrad_multi_f32": (C.c_int, [C.POINTER(ConvWgradDesc), _i32, _vp, _i64, _vp]),
     "ml_conv2d_wgrad_plan": (C.c_int, [C.POINTER(ConvWgradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ml_conv2d_grad_gather_dy_f32": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "ml_conv2d_dgrad_s2_f32": (C.c_int, [C.POINTER(ConvDesc), _vp, _vp, _vp]),
+    "ml_conv2d_dgrad_s2_classes": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ml_dwconv3x3_wgrad_multi_f32": (C.c_int, [C.POINTER(DwGradDesc), _i32, _vp, _i64, _vp]),
     "ml_dwconv3x3_wgrad_plan": (C.c_int, [C.POINTER(DwGradDesc), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ml_dwconv3x3_dgrad_multi_f32": (C.c_int, [C.POINTER(DwGradDesc), _i32, _vp]),

@@ -159,13 +159,55 @@ class BackboneModel(Layer):
             self.preprocess.extra_affine = input_affine(weights, eps)
 
     def call(self, images, **kwargs):
+        return self._forward(images, kwargs.get("fork_stream"))
+
+    def call_with_tape(self, images):
+        """`call` without fork_stream (the same launches on one stream: the same bits; the body as in `call`, frozen and
+        folded) and what backward_extra_levels needs.  -> (feats, tape): tape = {"c5": the last C tap, "p6": P6_conv's
+        post-ReLU output, "g6": P6_norm's output, "p7": P7_conv's post-ReLU output}."""
+        tape = {}
+        return self._forward(images, None, tape), tape
+
+    def extra_level_layers(self):
+        """The layers behind the last C tap: what a head-tune step trains of the backbone, asked for their device_params()
+        one by one (BackboneModel.device_params() keeps raising for the folded body)."""
+        return [self.p6_conv, self.p6_norm, self.p7_conv]
+
+    def backward_extra_levels(self, tape, d_p6, d_p7, need_dx=False):
+        """Backward of the two extra levels.  tape: call_with_tape's; d_p6 / d_p7: the gradients at the exported P6 (PRE-norm,
+        post-ReLU) and P7, float32, or None for a level nobody reads.  In this order: relu_grad at p7; P7_conv's weight
+        gradient and its stride-2 data gradient (ops.conv2d_dgrad_s2); P6_norm.backward; its result plus d_p6, through p6's
+        ReLU; P6_conv's weight gradient and, with need_dx, its stride-2 data gradient.
+        -> (the gradient at the last C tap or None unless need_dx, {full weight name: gradient}).  d_p7 None leaves P7_conv
+        and P6_norm without a gradient; both None returns (None, {})."""
+        from ..keras_like import check_incoming_grad
+        grads = {}
+        p6, g6, p7 = tape["p6"], tape["g6"], tape["p7"]
+        total = None
+        if d_p7 is not None:
+            check_incoming_grad("BackboneModel.backward_extra_levels: d_p7", d_p7, p7.shape)
+            dz7 = ops.relu_grad(p7, d_p7)
+            d_g6, g = self.p7_conv.backward(g6, dz7, strided_dx=True)
+            self.p7_conv.name_grads(g, grads)
+            total, g = self.p6_norm.backward(p6, d_g6, inplace=True)
+            self.p6_norm.name_grads(g, grads)
+        if d_p6 is not None:
+            check_incoming_grad("BackboneModel.backward_extra_levels: d_p6", d_p6, p6.shape)
+            total = ops.add_(total, d_p6) if total is not None else d_p6
+        if total is None:
+            return None, grads
+        dz6 = ops.relu_grad(p6, total, out=total if d_p7 is not None else None)      # never over the caller's d_p6
+        d_c5, g = self.p6_conv.backward(tape["c5"], dz6, need_dx=need_dx, strided_dx=True)
+        self.p6_conv.name_grads(g, grads)
+        return d_c5, grads
+
+    def _forward(self, images, fork, tape=None):
         x = self.preprocess(images)
         taps = self.body(x, wanted=self.taps)
         feats = [self.identities[k](taps[k]) for k in self.taps]
         # The extra levels are three small launches (16- and 4-tile convs, a 64-block GroupNorm: ~0.14 ms during which
         # most of the chip idles).  A caller that has other work for the main stream (the FPN chain) passes
         # `fork_stream` and joins `self.pending_stream` before it consumes P6 / P7.
-        fork = kwargs.get("fork_stream")
         aux = fork("_extra_level_stream") if fork is not None else None
         self.pending_stream = aux
         import contextlib
@@ -174,6 +216,8 @@ class BackboneModel(Layer):
             p6 = self.p6_conv(feats[-1])
             g6 = self.p6_norm(p6)                              # new tensor: P6 itself stays intact
             p7 = self.p7_conv(g6)
+        if tape is not None:
+            tape.update(c5=feats[-1], p6=p6, g6=g6, p7=p7)
         if 'P6' in self.backbone_outputs:
             feats.append(p6)                                   # exported P6 is PRE-norm (:308-309)
         if 'P7' in self.backbone_outputs:

@@ -369,18 +369,28 @@ class Conv2D(Layer):
     def _grad_args(self):
         return dict(dc=self.dev, stride=self.strides[0], padding=self.padding, dilation=self.dilation_rate[0])
 
-    def backward(self, x, dy, need_dx=True, dy_view=None, add=None):
-        """The layer's backward (ops.conv2d_wgrad / ops.conv2d_dgrad), float32 only.
+    def backward(self, x, dy, need_dx=True, dy_view=None, add=None, strided_dx=False):
+        """The layer's backward (ops.conv2d_wgrad / ops.conv2d_dgrad / ops.conv2d_dgrad_s2), float32 only.
         x: what the layer was called on.  dy: the gradient at the layer's PRE-activation output (or dy_view, the forward's
         out_view, with dy=None): the activation's own derivative is the caller's -- a ReLU's mask comes from
         GroupNormalization.backward(input_relu=True) on the layer above, a sigmoid's from
         loss_and_gradients(wrt="pre_activation").  add: dx = add + gradient.
-        -> (dx [B,H,W,cin] or None unless need_dx, {"kernel": ..., "bias": ...} with the weights the layer has).  Stride 2
-        has no dx (NotImplementedError); its weight gradient exists."""
+        -> (dx [B,H,W,cin] or None unless need_dx, {"kernel": ..., "bias": ...} with the weights the layer has).  A stride-2
+        layer's dx is refused (NotImplementedError) unless strided_dx=True asks for the stride-2 data-gradient kernel
+        (ops.conv2d_dgrad_s2: a dense dy, no dy_view; `add` may be the tensor the result replaces); its weight gradient
+        exists either way."""
         self._check_backward()
         args = self._grad_args()
         grads = pair_grads(self, ops.conv2d_wgrad(x, dy, dy_view=dy_view, want_bias=self.use_bias, **args))
-        dx = ops.conv2d_dgrad(dy, in_hw=(x.shape[1], x.shape[2]), dy_view=dy_view, add=add, **args) if need_dx else None
+        if not need_dx:
+            return None, grads
+        if strided_dx and self.strides[0] == 2:
+            if dy_view is not None:
+                raise ValueError(f"Conv2D.backward ('{self.name}'): the stride-2 data gradient takes a dense dy, not a dy_view")
+            dx = ops.conv2d_dgrad_s2(dy, self.dev, in_hw=(x.shape[1], x.shape[2]), padding=self.padding,
+                                     dilation=self.dilation_rate[0], add=add)
+        else:
+            dx = ops.conv2d_dgrad(dy, in_hw=(x.shape[1], x.shape[2]), dy_view=dy_view, add=add, **args)
         return dx, grads
 
     def get_config(self):

@@ -39,10 +39,18 @@ class FeaturePyramid(Layer):
         return [l for b in self.blocks for l in b]
 
     def call(self, inputs, **kwargs):
+        return self._forward(inputs, kwargs.get("fork_stream"))
+
+    def call_with_tape(self, inputs):
+        """`call` without fork_stream (the same launches on one stream: the same bits) and what `backward` needs.
+        -> (outputs, tape): tape["inputs"] the C taps and tape["merged"] the merged maps the 3x3 convs read, finest first."""
+        tape = {"inputs": list(inputs)}
+        return self._forward(inputs, None, tape), tape
+
+    def _forward(self, inputs, fork, tape=None):
         # The top-down chain (lateral -> resize + add -> next lateral ...) is serial, but the 3x3 output conv of a
         # coarse level only reads its own merged map and is a 64- / 256-tile launch: with `fork_stream` those run on an
         # auxiliary stream beside the chain; the finest level's conv (1024 tiles) closes the chain on the main stream.
-        fork = kwargs.get("fork_stream")
         aux = fork("_fpn_stream") if fork is not None and len(inputs) > 1 else None
         main = torch.cuda.current_stream() if aux is not None else None
         prev = None
@@ -55,6 +63,8 @@ class FeaturePyramid(Layer):
                 # ResizeLike(prev -> lateral size) + Add, in place into `lateral` (reference :58-60)
                 ops.resize_bilinear_ac(prev, lateral.shape[1], lateral.shape[2], add=lateral, out=lateral)
             prev = lateral
+            if tape is not None:
+                tape.setdefault("merged", []).insert(0, lateral)
             if aux is not None and idx != last:
                 aux.wait_stream(main)
                 lateral.record_stream(aux)
@@ -76,6 +86,40 @@ class FeaturePyramid(Layer):
         for fine, coarse in zip(d_merged[:-1], d_merged[1:]):
             ops.resize_bilinear_ac_grad(fine, coarse.shape[1], coarse.shape[2], add=coarse, out=coarse)
         return list(d_merged)
+
+    def backward(self, tape, d_outputs, need_dx=False):
+        """The layer's backward.  tape: call_with_tape's; d_outputs: the gradients at the outputs, finest first, float32
+        [B,h,w,num_features] each (the 3x3 `P{k}` convs are linear: these are their pre-activation gradients).
+        In this order: one conv2d_wgrad_multi and one conv2d_dgrad_multi over the 3x3 convs; backward_top_down in place on
+        the result; one conv2d_wgrad_multi over the laterals; with need_dx their conv2d_dgrad_multi.
+        -> (the gradients at the C taps, finest first, or None unless need_dx; {full weight name: gradient})"""
+        n = len(tape["inputs"])
+        if len(d_outputs) != n or len(tape["merged"]) != n:
+            raise ValueError(f"FeaturePyramid.backward: {len(d_outputs)} gradients for {n} levels")
+        blocks = self.blocks[:n][::-1]                           # finest first, like the tensors
+        for l, (dy, m) in enumerate(zip(d_outputs, tape["merged"])):
+            check_incoming_grad(f"FeaturePyramid.backward: d_outputs[{l}]", dy, m.shape)
+        grads = {}
+
+        def weight_grads(convs, xs, dys):
+            for c in convs:
+                c._check_backward()
+            pairs = ops.conv2d_wgrad_multi([dict(x=x, dy=dy, want_bias=c.use_bias, **c._grad_args())
+                                            for c, x, dy in zip(convs, xs, dys)])
+            for c, pair in zip(convs, pairs):
+                c.name_grads(pair_grads(c, pair), grads)
+
+        def data_grads(convs, xs, dys):
+            return ops.conv2d_dgrad_multi([dict(dy=dy, in_hw=(x.shape[1], x.shape[2]), **c._grad_args())
+                                           for c, x, dy in zip(convs, xs, dys)])
+
+        outs = [b[1] for b in blocks]
+        weight_grads(outs, tape["merged"], d_outputs)
+        d_lateral = self.backward_top_down(data_grads(outs, tape["merged"], d_outputs))
+        laterals = [b[0] for b in blocks]
+        weight_grads(laterals, tape["inputs"], d_lateral)
+        d_inputs = data_grads(laterals, tape["inputs"], d_lateral) if need_dx else None
+        return d_inputs, grads
 
     def get_config(self):
         config = super().get_config()

@@ -157,6 +157,7 @@ class DeviceConv:
         self._wgt_wino = None
         self._wgt_stem_h = None
         self._dgrad = None
+        self._keras_kernel = None   # keras_kernel: the uploaded [kh,kw,cin,cout] copy of a packing that follows no master
         self._master = None         # bind_master: the device tensors this packing follows
         self._tr_of = None          # a data-gradient packing: the DeviceConv it is the `dgrad` of
 
@@ -173,6 +174,21 @@ class DeviceConv:
                 self._dgrad = DeviceConv(pack_dense_transposed(unpack_dense(self.p)), self.wgt.device)
                 self._dgrad._tr_of = self
         return self._dgrad
+
+    @property
+    def keras_kernel(self):
+        """The dense conv's kernel in the Keras layout [kh,kw,cin,cout] on the device -- what the stride-2 data gradient reads
+        (conv2d_dgrad_s2): the bound master itself where the packing follows one (a stepped kernel is seen at once: no packed
+        form, no re-pack job), else a copy uploaded on first use from the host weights and kept (dropped by bind_master)."""
+        m = self._master
+        if m is not None:
+            if m["offset"] or tuple(m["kernel"].shape) != (m["KH"], m["KW"], m["C"], m["N"]):
+                raise NotImplementedError("DeviceConv.keras_kernel: the packing follows a cin slice or a transposed-conv master; "
+                                          "the stride-2 data gradient reads a whole [kh,kw,cin,cout] kernel")
+            return m["kernel"]
+        if self._keras_kernel is None:
+            self._keras_kernel = torch.from_numpy(unpack_dense(self.p)).to(self.wgt.device)
+        return self._keras_kernel
 
     @property
     def wgt_wino(self):
@@ -290,6 +306,7 @@ class DeviceConv:
         if bias is not None and (bias_reps < 1 or bias.numel() * bias_reps != self.bias.numel()):
             raise ValueError(f"{what}: a bias of {bias.numel()} elements x {bias_reps} is not the packing's {self.bias.numel()}")
         self._master = dict(kernel=kernel, bias=bias, bias_reps=int(bias_reps), **geom)
+        self._keras_kernel = None
         _forms_epoch[0] += 1
         self.p = dataclasses.replace(p, wgt=None, bias=None)
         if self._dgrad is not None:
@@ -1580,6 +1597,73 @@ def conv2d_dgrad(dy, dc, in_hw, stride=1, padding="same", dilation=1, dy_view=No
 def conv2d_dgrad_multi(problems):
     """Several data-gradient problems as ONE conv2d_multi launch.  problems: list of dicts with conv2d_dgrad's arguments."""
     return conv2d_multi([_dgrad_problem(**pr) for pr in problems])
+
+
+def _dgrad_s2_desc(what, p, in_hw, padding="same", dilation=1, B_default=1):
+    """The ml_conv2d_desc of a stride-2 data-gradient problem without its tensors: the FORWARD problem's geometry."""
+    _dense_only(what, p)
+    B, H, W = _in_hw(what, in_hw, B_default)
+    Ho, Wo, pt, pl = resolve_padding(H, W, p.kh_real, p.kw_real, 2, dilation, padding)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"{what}: the kernel does not fit the {H} x {W} input")
+    d = _lib.ConvDesc()
+    d.B, d.H, d.W, d.in_cstride, d.in_coff = B, H, W, p.span, 0
+    d.span, d.span_pad, d.cpp_shift = p.span, p.span_pad, p.cpp_shift
+    d.Ho, d.Wo = Ho, Wo
+    d.KH, d.KW, d.stride, d.dil, d.pad_t, d.pad_l = p.KH, p.KW, 2, dilation, pt, pl
+    d.cout, d.n_pad = p.cout, p.n_pad
+    d.out_cstride, d.out_coff, d.out_bstride = p.cout, 0, 0
+    d.group_cin_step, d.shuffle2x2, d.math = p.group_cin_step, p.shuffle2x2, _lib.MATH_F32
+    return d
+
+
+def conv2d_dgrad_s2_classes(p, in_hw, padding="same", dilation=1):
+    """The four parity classes of a stride-2 data-gradient problem (ml_conv2d_dgrad_s2_classes, host only).  p: the forward's
+    PackedConv; in_hw = (H, W) (one image) or (B, H, W[, C]).  -> list over class c = 2 (iy & 1) + (ix & 1) of
+    (pixels, [(ky, kx, off_y, off_x) per live tap, ascending]): input pixel (iy, ix) of the class reads dy at
+    ((iy >> 1) + off_y, (ix >> 1) + off_x) for that tap."""
+    d = _dgrad_s2_desc("conv2d_dgrad_s2", p, in_hw, padding, dilation)
+    pixels, ntaps = (C.c_int64 * 4)(), (C.c_int32 * 4)()
+    taps = (C.c_int32 * (4 * _lib.CONV_DGRAD_S2_MAX_TAPS * 4))()
+    _lib.check(_lib.load().ml_conv2d_dgrad_s2_classes(C.byref(d), pixels, ntaps, taps), "ml_conv2d_dgrad_s2_classes")
+    out = []
+    for c in range(4):
+        base = c * _lib.CONV_DGRAD_S2_MAX_TAPS * 4
+        out.append((int(pixels[c]), [tuple(taps[base + 4 * t: base + 4 * t + 4]) for t in range(ntaps[c])]))
+    return out
+
+
+def conv2d_dgrad_s2(dy, dc, in_hw, padding="same", dilation=1, add=None, out=None):
+    """Data gradient of the dense conv `dc` at STRIDE 2 (csrc/conv_grad.hip, ml_conv2d_dgrad_s2_f32), float32: dy [B,Ho,Wo,cout]
+    dense, at the conv's PRE-activation output; in_hw = (H, W) of the conv's input or its shape (B, H, W[, C]).  Reads the
+    Keras-layout kernel dc.keras_kernel (the bound master where there is one).  add / out: out = add + gradient with one
+    float32 addition; `out` may be `add` (in place).  -> dx [B,H,W,cin]; every element written by the launch, pixels no tap
+    reaches get add or +0.0.  Exact fp32 products whatever set_conv_math says; a fixed summation order (live taps ascending,
+    cout ascending): two launches give the same bits."""
+    what = "conv2d_dgrad_s2"
+    p = dc.p
+    _grad_tensor(what, "dy", dy)
+    if dy.dim() != 4:
+        raise ValueError(f"{what}: `dy` must be [B, Ho, Wo, cout], got {tuple(dy.shape)}")
+    d = _dgrad_s2_desc(what, p, in_hw, padding, dilation, B_default=int(dy.shape[0]))
+    _grad_tensor(what, "dy", dy, (d.B, d.Ho, d.Wo, p.cout))
+    if not dy.is_contiguous():
+        raise ValueError(f"{what}: `dy` must be contiguous (a dense tensor, not a view)")
+    if p.span % 4 or p.cout % 4:
+        raise ValueError(f"{what}: cin ({p.span}) and cout ({p.cout}) must each be a multiple of 4 (16-byte accesses)")
+    dx = _grad_out(what, (d.B, d.H, d.W, p.span), dy.device, add, out)
+    if not dx.is_contiguous() or (add is not None and not add.is_contiguous()):
+        raise ValueError(f"{what}: `out` and `add` must be contiguous")
+    _require_dev(dy, "dy")
+    w = dc.keras_kernel
+    d.out, d.wgt = dy.data_ptr(), w.data_ptr()
+    M = d.B * d.Ho * d.Wo
+    flops = 2.0 * M * p.KH * p.KW * p.span * p.cout
+    nbytes = 4 * (dy.numel() + w.numel() + dx.numel() * (2 if add is not None else 1))
+    with _Prof("conv_dgrad_s2", flops, nbytes, f"M={p.span} N={d.B * d.H * d.W} K={p.KH * p.KW * p.cout} k{p.KH}x{p.KW} s2 "
+               f"d{dilation} HxW={d.H}x{d.W}"):
+        _lib.check(_lib.load().ml_conv2d_dgrad_s2_f32(C.byref(d), _ptr(dx), _ptr(add), _stream()), "ml_conv2d_dgrad_s2_f32")
+    return dx
 
 
 # ------------------------------------------------------------------ depthwise 3x3, backward (csrc/dwconv_grad.hip)

@@ -15,6 +15,7 @@ import torch
 
 from . import backbone
 from . import keras_like as K
+from . import ops
 from .config import ModelConfiguration
 from .layers import (ASPPNetwork, AssignBoxes, AssignMasks, AssignSeg, BoxRegressionSubNet, ClassificationSubNet, CropAndPadMask,
                      DetectionProposal,
@@ -570,7 +571,7 @@ class TrainerModel(K.Layer):
     """The Keras functional `Model([images, gt_boxes, gt_boxes_exist, gt_masks, gt_seg, gt_seg_exist] -> losses and metrics)`
     of reference :223-395, executed eagerly (no hipGraph, no fixed-capacity stage 2): what
     `fit_generator(validation_data=...)` evaluates to report a checkpoint's validation losses.  `loss_and_gradients` adds the
-    gradients of the compiled scalar at the four head outputs; `train_on_batch` carries them through the head groups' `backward`s into an optimizer's step and one re-pack (the FPN and the backbone are frozen).  The backbone and head layers
+    gradients of the compiled scalar at the four head outputs; `train_on_batch` carries them through the head groups' `backward`s into an optimizer's step and one re-pack (the FPN and the backbone are frozen; trainable="head_tune" also trains the FPN and the two extra levels behind C5).  The backbone and head layers
     are the OBJECTS the inference model holds, as in the reference; the assignment, loss and metric layers are the model's
     own.  Every output is float32 [B]; the lists shrink like the reference's when a head group is None.
     `last_forward` keeps the intermediate tensors of the last call."""
@@ -682,20 +683,48 @@ class TrainerModel(K.Layer):
             out += list(self.semantic_networks)
         return out
 
-    def device_params(self):
-        """{full weight name: float32 device tensor} of every head group present (Layer.device_params): what an optimizer's
-        apply_gradients steps.  The FPN and the backbone are not in it: their layers cannot be trained yet (stride-2 data
-        gradient, folded BatchNormalization) and say so when asked."""
+    STAGES = ("heads", "head_tune")
+
+    def _stage_layers(self, what, stage):
+        """The layers a stage trains.  "heads": the head groups present.  "head_tune" (the reference's train_head_tune,
+        freeze_depth="C5"): those, the FeaturePyramid and the backbone's extra levels (P6_conv, P6_norm, P7_conv)."""
+        if stage not in self.STAGES:
+            raise ValueError(f"TrainerModel.{what}: stage must be one of {self.STAGES}, got {stage!r}")
+        layers = self.head_groups()
+        if stage == "head_tune":
+            if self.detection_networks is None:
+                raise ValueError(f"TrainerModel.{what}: the 'head_tune' stage trains the FeaturePyramid: it needs the detection "
+                                 f"networks")
+            layers = layers + [self.detection_networks[1]] + self.backbone_network.extra_level_layers()
+        return layers
+
+    def device_params(self, stage="heads"):
+        """{full weight name: float32 device tensor} of every layer the stage trains (Layer.device_params): what an
+        optimizer's apply_gradients steps.  "heads": the head groups present; the FPN and the backbone are not in it, and
+        nothing of them is bound or uploaded.  "head_tune": also the FPN's and the extra levels' (P6_conv, P6_norm, P7_conv)
+        parameters.  The backbone's body is in neither: its BatchNormalization is folded into its weights."""
         if self.device is None:
             raise RuntimeError("TrainerModel: call load_weights(weights, device) first")
         out = {}
-        for g in self.head_groups():
+        for g in self._stage_layers("device_params", stage):
             out.update(g.device_params())
         return out
 
     def _repack_job_source(self):
         """repack() after the head parameters stepped: every packing under the head groups, not the frozen layers'."""
         return [j for g in self.head_groups() for j in g.repack_jobs()]
+
+    def repack(self, stage="heads"):
+        """Layer.repack over the stage's layers: one launch.  "head_tune" keeps a job list and a table of its own, so a
+        "heads" step's stay what they were."""
+        layers = self._stage_layers("repack", stage)
+        if stage == "heads":
+            return super().repack()
+        if getattr(self, "_tune_repack", None) is None:
+            self._tune_repack = [ops.RepackTable(), (None, None)]
+        if self._tune_repack[1][0] != ops.forms_epoch():
+            self._tune_repack[1] = (ops.forms_epoch(), [j for g in layers for j in g.repack_jobs()])
+        ops.repack_weights(self._tune_repack[1][1], self._tune_repack[0])
 
     # ---- forward (reference :233-391)
     def _named_inputs(self, inputs):
@@ -767,9 +796,9 @@ class TrainerModel(K.Layer):
         """The names of `params` a step updates.  "heads": all of them; a set of names or a predicate narrows it.  A name under
         the FPN or the backbone raises NotImplementedError, any other unknown name ValueError."""
         if isinstance(trainable, str):
-            if trainable != "heads":
-                raise ValueError(f"TrainerModel.train_on_batch: trainable must be 'heads', a set of weight names or a predicate, "
-                                 f"got {trainable!r}")
+            if trainable not in self.STAGES:
+                raise ValueError(f"TrainerModel.train_on_batch: trainable must be 'heads', 'head_tune', a set of weight names or "
+                                 f"a predicate, got {trainable!r}")
             return set(params)
         frozen_specs = dict(self.backbone_network.weight_specs())
         if self.detection_networks is not None:
@@ -784,9 +813,10 @@ class TrainerModel(K.Layer):
                 raise ValueError(f"TrainerModel.train_on_batch: {unknown[:5]} are not trainable weights of this model")
             frozen = sorted(names & set(frozen_specs))
         if frozen:
-            raise NotImplementedError(f"TrainerModel.train_on_batch: {list(frozen)[:5]} lie under the FPN or the backbone, which "
-                                      f"cannot be trained yet: the FPN's backward and the stride-2 data gradient of its P6 / P7 "
-                                      f"convs are missing, and the backbone's BatchNormalization is folded into its weights")
+            raise NotImplementedError(f"TrainerModel.train_on_batch: {list(frozen)[:5]} lie under the FPN or the backbone, which a "
+                                      f"set of names or a predicate cannot select: trainable=\"head_tune\" trains the FPN and the "
+                                      f"P6 / P7 levels (the whole stage), and the backbone's body cannot be trained yet -- its "
+                                      f"BatchNormalization is folded into its weights")
         return names
 
     def train_on_batch(self, inputs, optimizer, trainable="heads", upstream=None):
@@ -799,15 +829,24 @@ class TrainerModel(K.Layer):
         optimizer.apply_gradients(device_params(), grads, trainable=names), then ONE repack_weights brings every packing of
         the head groups up to its master.  trainable: "heads" (every weight of the head groups present), a set of names or a
         predicate; a name under the FPN or the backbone raises NotImplementedError, a name the model does not have
-        ValueError.  Head groups with SqueezeExcite or separable towers, half tensors and set_conv_math("f16") raise
+        ValueError.  trainable="head_tune" is the reference's first training stage (train_head_tune: everything behind the C5
+        tap): the backbone and the FPN run as call_with_tape (the same bits), MaskSubNet.backward(need_dx=True), and per
+        pyramid level the class tower's, the box tower's and PyramidRoiAlign.backward's gradients are summed in that order
+        (_head_tune_backward), then BackboneModel.backward_extra_levels and FeaturePyramid.backward; the merged dict goes to
+        ONE apply_gradients over device_params("head_tune") and one re-pack launch.  The semantic head's input gradients are
+        still dropped (its inputs are backbone taps), and the backbone's body stays frozen.  Head groups with SqueezeExcite or separable towers, half tensors and set_conv_math("f16") raise
         NotImplementedError before anything runs; a refused step changes no weight."""
-        params = self.device_params()                         # raises by name for what cannot be trained
+        tune = isinstance(trainable, str) and trainable == "head_tune"
+        params = self.device_params("head_tune" if tune else "heads")     # raises by name for what cannot be trained
         names = self._trainable_names(trainable, params)
         self._check_upstream("train_on_batch", upstream)
         grads, tapes = {}, {}
-        outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=True, grads=grads, tapes=tapes))
+        outputs = self._forward(inputs, dict(upstream=dict(upstream or {}), through_sigmoid=True, grads=grads, tapes=tapes,
+                                             head_tune=tune))
         wg = {}
-        if self.detection_networks is not None:
+        if self.detection_networks is not None and tune:
+            self._head_tune_backward(tapes, grads, wg)
+        elif self.detection_networks is not None:
             _, _, cls_subnet, loc_subnet = self.detection_networks
             wg.update(cls_subnet.backward(tapes[cls_subnet.name], grads["cls_pred"])[1])
             wg.update(loc_subnet.backward(tapes[loc_subnet.name], grads["loc_pred"])[1])
@@ -822,8 +861,32 @@ class TrainerModel(K.Layer):
         self.last_forward["grads"] = grads
         self.last_forward["weight_grads"] = wg
         optimizer.apply_gradients(params, wg, trainable=names)
-        self.repack()
+        self.repack("head_tune" if tune else "heads")
         return outputs
+
+    def _head_tune_backward(self, tapes, grads, wg):
+        """The detection side of a "head_tune" step: the towers' and the mask head's backward with their input gradients kept,
+        summed per pyramid level in the fixed order class tower, box tower, RoI align (in place on the class tower's
+        tensors), then the extra levels' and the FPN's backward.  Fills `wg`."""
+        _, fpn_subnet, cls_subnet, loc_subnet = self.detection_networks
+        bb = self.backbone_network
+        d_feat, g = cls_subnet.backward(tapes[cls_subnet.name], grads["cls_pred"])
+        wg.update(g)
+        d_loc, g = loc_subnet.backward(tapes[loc_subnet.name], grads["loc_pred"])
+        wg.update(g)
+        d_feat = [ops.add_(a, b) for a, b in zip(d_feat, d_loc)]
+        if self.instance_networks is not None:
+            pyramid_roi_align, mask_subnet = self.instance_networks[2:4]
+            d_rois, g = mask_subnet.backward(tapes[mask_subnet.name], grads["roi_masks"], need_dx=True)
+            wg.update(g)
+            t = tapes[pyramid_roi_align.name]
+            n = len(t["fmap_shapes"])
+            pyramid_roi_align.backward(d_rois, t["fmap_shapes"], t["rows"], t["image_hw"], t["slots"], t["lcounts"],
+                                       add=d_feat[:n], out=d_feat[:n])
+        n_fpn = len(tapes[fpn_subnet.name]["inputs"])
+        extra = dict(zip(tapes["feature_names"][n_fpn:], d_feat[n_fpn:]))       # gradients at other backbone taps are dropped
+        wg.update(bb.backward_extra_levels(tapes[bb.name], extra.get("P6"), extra.get("P7"), need_dx=False)[1])
+        wg.update(fpn_subnet.backward(tapes[fpn_subnet.name], d_feat[:n_fpn], need_dx=False)[1])
 
     def _forward(self, inputs, want):
         if self.device is None:
@@ -832,7 +895,12 @@ class TrainerModel(K.Layer):
         x = self._named_inputs(inputs)
         images = self._dev(x['images'])
         bb = self.backbone_network
-        by_name = dict(zip(bb.output_names, bb(images)))
+        tune = want is not None and want.get("head_tune")
+        if tune:
+            feats, want["tapes"][bb.name] = bb.call_with_tape(images)
+        else:
+            feats = bb(images)
+        by_name = dict(zip(bb.output_names, feats))
         fw, outputs = {}, []
         if self.detection_networks is not None:
             det_config = cfg.detection
@@ -840,7 +908,13 @@ class TrainerModel(K.Layer):
             pr_boxes = prior_subnet(images)
             fpn_inputs = [by_name[n] for n in bb.output_names if n in det_config.feature_pyramid_inputs]
             without_fpn = [by_name[n] for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
-            feature_outputs = fpn_subnet(fpn_inputs) + without_fpn
+            if tune:
+                fpn_outputs, want["tapes"][fpn_subnet.name] = fpn_subnet.call_with_tape(fpn_inputs)
+                want["tapes"]["feature_names"] = [n for n in bb.output_names if n in det_config.feature_pyramid_inputs] + \
+                    [n for n in bb.output_names if n not in det_config.feature_pyramid_inputs]
+            else:
+                fpn_outputs = fpn_subnet(fpn_inputs)
+            feature_outputs = fpn_outputs + without_fpn
             cls_pred = self._head(cls_subnet, feature_outputs, want)
             loc_pred = self._head(loc_subnet, feature_outputs, want)
             gt_boxes = self._dev(x['gt_boxes'], torch.float32)
@@ -863,7 +937,16 @@ class TrainerModel(K.Layer):
                 # wherever it is (csrc/detect.hip), and the crops are taken from the per-level slot lists it writes
                 chosen_boxes = torch.cat([gt_boxes, proposed_loss], dim=1)              # Concatenate(axis=1)
                 dist_boxes = distribute_layer(chosen_boxes)
-                roi_fmaps, roi_boxes = pyramid_roi_align([feature_outputs[:cfg.instance.max_k + 1], dist_boxes, images])
+                if tune:
+                    # PyramidRoiAlign.call taken apart, so that its backward gets the tables this forward used
+                    fmaps, rows = feature_outputs[:cfg.instance.max_k + 1], dist_boxes.contiguous()
+                    image_hw = (int(images.shape[1]), int(images.shape[2]))
+                    slots, lcounts, lmax = pyramid_roi_align.distribute(len(fmaps), rows, True)
+                    roi_fmaps, roi_boxes = pyramid_roi_align.crop_distributed(fmaps, rows, image_hw, slots, lcounts, lmax)
+                    want["tapes"][pyramid_roi_align.name] = dict(rows=rows, slots=slots, lcounts=lcounts, image_hw=image_hw,
+                                                                 fmap_shapes=[tuple(f.shape) for f in fmaps])
+                else:
+                    roi_fmaps, roi_boxes = pyramid_roi_align([feature_outputs[:cfg.instance.max_k + 1], dist_boxes, images])
                 roi_masks = self._head(mask_subnet, roi_fmaps, want)
                 gt_masks = self._dev(x['gt_masks'])
                 match_gt_masks = self.assign_masks([roi_boxes, roi_masks, gt_boxes, gt_masks])
@@ -892,7 +975,7 @@ class TrainerModel(K.Layer):
 
 def construct_trainer_network(configuration: ModelConfiguration, backbone_network, detection_networks=None,
                               semantic_networks=None, instance_networks=None):
-    """Same signature as reference :223-227; the returned model trains its head groups (train_on_batch); the FPN and the backbone are frozen."""
+    """Same signature as reference :223-227; the returned model trains its head groups (train_on_batch) and, as the "head_tune" stage, the FPN and P6 / P7; the backbone's body is frozen."""
     return TrainerModel(configuration, backbone_network, detection_networks=detection_networks,
                         semantic_networks=semantic_networks, instance_networks=instance_networks)
 

@@ -32,20 +32,11 @@ def group_of(kernel):
     return "other forward (resize, RoI align, detection, pooling)"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--batch", type=int, default=8)
-    ap.add_argument("--size", type=int, default=1024)
-    args = ap.parse_args()
+def build(B, S):
+    """-> (the default configuration's trainer with init_weights(seed=2) loaded, a batch of B images of S x S on the device)"""
     import numpy as np
     import torch
-    from masklab_hip import ModelConfiguration, ops, retinamasklab as R
-    from masklab_hip.optimizers import RectifiedAdam
-    if not torch.cuda.is_available():
-        raise SystemExit("train_step_timing: no GPU -- nothing is measured without one")
-    B, S = args.batch, args.size
+    from masklab_hip import ModelConfiguration, retinamasklab as R
     trainer, _ = R.construct_masklab_networks(ModelConfiguration(), with_trainer=True)
     trainer.load_weights(trainer.init_weights(seed=2), "cuda:0")
     rng = np.random.default_rng(3)
@@ -63,6 +54,23 @@ def main():
                  gt_boxes_exist=np.ones((B, 5), np.float32), gt_masks=gt_masks,
                  gt_seg=(rng.random((B, S, S, 3)) < 0.5).astype(np.uint8), gt_seg_exist=np.ones((B, 3), np.float32))
     batch = {k: torch.as_tensor(v).to("cuda:0") for k, v in batch.items()}      # on the device once: a generator's job
+    return trainer, batch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--size", type=int, default=1024)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    from masklab_hip import ops
+    from masklab_hip.optimizers import RectifiedAdam
+    if not torch.cuda.is_available():
+        raise SystemExit("train_step_timing: no GPU -- nothing is measured without one")
+    trainer, batch = build(args.batch, args.size)
     opt = RectifiedAdam(1e-4)
     for _ in range(args.warmup):
         trainer.train_on_batch(batch, opt)
@@ -90,7 +98,7 @@ def main():
         print(json.dumps({"group": g, "ms_per_step": round(ms / args.steps, 4), "launchers_per_step": launches[g] // args.steps,
                           "share_of_launches": round(ms / args.steps / total, 4)}))
     print(json.dumps({"step_ms_median": round(float(np.median(whole)), 3), "step_ms_min": round(min(whole), 3),
-                      "step_ms_max": round(max(whole), 3), "recorded_launch_ms": round(total, 3), "batch": B, "size": S,
+                      "step_ms_max": round(max(whole), 3), "recorded_launch_ms": round(total, 3), "batch": args.batch, "size": args.size,
                       "head_weights": len(trainer.device_params())}))
 
 
